@@ -443,7 +443,7 @@ def test_bench_line_contract(gpu_ctx):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--n", "4096",
-                        "--cpu-baseline", "none"], capture_output=True, text=True, timeout=600, env=env)
+                        "--full", "--cpu-baseline", "none"], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -465,6 +465,46 @@ def test_bench_line_contract(gpu_ctx):
     assert sum(rec["stages"]["ms"].values()) <= 1.05 * rec["ms_per_step"]
 
 
+def test_bench_plain_line_and_dumped_outputs(gpu_ctx, tmp_path):
+    """A plain run prints the headline only (no roofline, stages, reference check or CPU baseline) and ``--dump-outputs`` writes
+    the last timed step's loss and parameter gradients: the same values an in-process evaluation of the same inputs gives."""
+    import json
+    import subprocess
+    import sys
+
+    import bench
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out_dir = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--n", "4096",
+                        "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600, env=env)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    rec = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert key in rec, key
+    assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["dtype"] == "f64" and rec["higher_is_better"] is True
+    assert abs(rec["value"] - 1e3 / rec["ms_per_step"]) <= 1e-6 * rec["value"]
+    assert not {"roofline", "stages", "cpu_baseline"} & set(rec) and "loss_ref" not in rec["config"]
+
+    from gpplus_amd.models import GP_Plus
+
+    X, y = bench.make_c2_data(4096)
+    m = GP_Plus(X, y, dtype=torch.float64, device="cuda:0")
+    bench.set_theta1(m)
+    loss, grads = _loss_and_grads(m)
+    dumped_loss = np.load(out_dir / "loss.npy")
+    assert dumped_loss.dtype == np.float64 and float(dumped_loss) == rec["config"]["loss"]
+    np.testing.assert_allclose(dumped_loss, loss, rtol=1e-10)
+    assert grads
+    for name, g in grads.items():
+        d = np.load(out_dir / f"grad_{name.replace('.', '_')}.npy")
+        assert d.dtype == np.float64 and d.shape == g.shape, name
+        np.testing.assert_allclose(d, g, rtol=1e-9, atol=1e-12 * max(np.abs(g).max(), 1.0), err_msg=name)
+
+
 @pytest.mark.gpu
 def test_bench_two_ranks_through_both_legs_on_one_gpu():
     """``bench.py --gpus 2 --share-gpu`` (test mode: both ranks on cuda:0 over gloo, small sizes): the N > 1 code path of the
@@ -477,7 +517,7 @@ def test_bench_two_ranks_through_both_legs_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "2", "--warmup", "1",
-                        "--n", "4096", "--sharded-n", "3000", "--nb", "256", "--sharded-steps", "1", "--sharded-warmup", "1",
+                        "--full", "--n", "4096", "--sharded-n", "3000", "--nb", "256", "--sharded-steps", "1", "--sharded-warmup", "1",
                         "--sharded-timeout", "300"], capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

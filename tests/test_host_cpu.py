@@ -210,8 +210,17 @@ def test_bench_self_launches_its_ranks_dry_run():
     assert p.returncode != 0 and "GPU" in p.stderr
 
 
+def test_bench_refuses_a_run_without_timed_steps():
+    """``--steps`` is the number of timed steps and ``ms_per_step`` is divided by it: zero is refused before any work starts."""
+    import subprocess
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 2 and "--steps" in p.stderr, p.stderr[-2000:]
+
+
 def test_bench_watchdog_ends_a_hung_second_leg_on_every_rank():
-    """``--dry-run --fake-hang``: rank 1 never returns from the (fake) sharded leg.  After ``--sharded-timeout`` seconds rank 0 prints
+    """``--dry-run --full --fake-hang``: rank 1 never returns from the (fake) sharded leg.  After ``--sharded-timeout`` seconds rank 0 prints
     the line with the failure recorded, EVERY rank leaves with a non-zero status, and the self-launcher still returns 0 because
     the line was relayed — within seconds, not after a process-group timeout."""
     import json
@@ -222,7 +231,8 @@ def test_bench_watchdog_ends_a_hung_second_leg_on_every_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     t0 = time.time()
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--dry-run", "--fake-hang", "--sharded-timeout", "5"], capture_output=True, text=True, timeout=300, env=env)
+                        "--dry-run", "--full", "--fake-hang", "--sharded-timeout", "5"], capture_output=True, text=True, timeout=300,
+                       env=env)
     took = time.time() - t0
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]

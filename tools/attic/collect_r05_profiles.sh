@@ -7,8 +7,8 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 python3 -c "import sys; sys.path.insert(0,'.'); from gpplus_amd import _lib; print(_lib.load().gpp_version().decode())" > $OUT/lib_version.txt
 # 1) the bench command itself: plain, and under kernel trace + stats
-timeout 600 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_line.json 2> $OUT/bench_line.err
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_stats -o b -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_profiled.json 2> $OUT/bench_profiled.err
+timeout 600 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_line.json 2> $OUT/bench_line.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_stats -o b -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_profiled.json 2> $OUT/bench_profiled.err
 find $OUT/bench_stats -name "*kernel_stats.csv" -exec cp {} $OUT/bench_kernel_stats.csv \;
 # Counter collection SERIALISES dispatches; the DAG executor's launches wait for the panel stream's launches through device
 # counters and cannot run one at a time.  Every --pmc pass therefore runs the SAME ticket list with the SAME kernel as a sequence of

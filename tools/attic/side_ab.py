@@ -6,7 +6,7 @@ import gpplus_amd.linalg as L
 import bench
 for side_min in (6144, 10**9, 6144, 10**9):
     L.SIDE_STREAM_MIN_N = side_min
-    sys.argv = ["bench.py", "--steps", "10", "--warmup", "2", "--no-cpu-baseline"]
+    sys.argv = ["bench.py", "--full", "--steps", "10", "--warmup", "2", "--no-cpu-baseline"]
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         bench.main()

@@ -26,11 +26,11 @@ for d in pmcA pmcB pmcF_ALL pmcW_ALL pmcF_P pmcW_P; do python3 tools/pmc_summary
 # the phased form's own timing (how far the profiled form is from the timed one)
 timeout 300 python3 tools/bench_stages.py 20000 8 3 > $OUT/stages_20000_phased.txt 2>&1
 unset GPP_DAG_PHASED
-# 1) the bench command itself, AFTER the counter passes so that its roofline.traffic reads this build's records: the default run
-#    (with the CPU baseline, minutes of host time), and under kernel trace + stats
+# 1) the bench command itself, AFTER the counter passes so that its roofline.traffic reads this build's records: the full run
+#    (--full: roofline, stages and the CPU baseline, minutes of host time), and under kernel trace + stats
 cp $OUT/r06_potrf_pmc.json $OUT/r06_trtri_pmc.json $OUT/r06_lauum_pmc.json profiles/
-timeout 900 python3 bench.py > $OUT/bench_line.json 2> $OUT/bench_line.err
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_stats -o b -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_profiled.json 2> $OUT/bench_profiled.err
+timeout 900 python3 bench.py --full > $OUT/bench_line.json 2> $OUT/bench_line.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_stats -o b -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_profiled.json 2> $OUT/bench_profiled.err
 find $OUT/bench_stats -name "*kernel_stats.csv" -exec cp {} $OUT/bench_kernel_stats.csv \;
 # 4) timelines: per-task traces of the executor at the C2 / C3 / C4 sizes, kernel timeline at N = 10000
 TRACE=1 CHECK=0 timeout 300 python3 tools/dag_check.py 10000 > $OUT/dag_trace_10000.txt 2>&1
