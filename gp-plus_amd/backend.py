@@ -22,7 +22,7 @@ from ._lib import GppError, check
 KIND_RBF, KIND_MATERN32, KIND_MATERN52 = 0, 1, 2
 UPLO_FULL, UPLO_LOWER, UPLO_UPPER = 0, 1, 2
 OPT_COOP_PANEL, OPT_PANEL_FAULT, OPT_PANEL_TIMEOUT_MS, OPT_EXEC_SCHED, OPT_DAG_SCHED = 1, 2, 3, 4, 5  # gpp_set_option (include/gpp.h)
-OP_MLL_EVAL, OP_PREDICT = 0, 1
+OP_MLL_EVAL, OP_PREDICT, OP_PREDICT_GRAD = 0, 1, 2
 #: the tile kernels stage at most this many feature columns (manifold + quantitative) per point in LDS (gpp_build.hip DMAX)
 MAX_FEATURES = 64
 
@@ -417,6 +417,32 @@ class GppContext:
         check(self.lib.gpp_predict_tn(self.h, Linv.data_ptr(), _ld(Linv), Linv.shape[0], z.data_ptr(), Kns.data_ptr(), _ld(Kns),
                                       Kns.shape[1], kss.data_ptr(), V.data_ptr(), _ld(V), mean_out.data_ptr(), var_out.data_ptr()),
               "gpp_predict_tn")
+
+    @_on_own_device
+    def cross_grad(self, Ua, Ub, w, sf2, gmean, alpha, gvar, B, g_Ua, g_Ub, g_w, g_sf2, *, kind=KIND_RBF, d_split=0):
+        """Backward of a prediction from the test / training features Ua (M x D) and Ub (N x D): with G = gmean alpha^T +
+        diag(gvar) B and K = sf2 k(Ua, Ub; w), g_Ua = G dK/dUa (M x dA), g_Ub = G^T dK/dUb (N x dB), g_w, g_sf2 (gpp_cross_grad).
+        Either input pair may be None, and so may every output (dA / dB are the outputs' widths)."""
+        M, D = Ua.shape
+        N = Ub.shape[0]
+        _check_features(D)
+        for t, n in ((Ua, "Ua"), (Ub, "Ub"), (w, "w"), (sf2, "sf2")):
+            _need(t, torch.float64, n)
+        if not (Ua.is_contiguous() and Ub.is_contiguous()):
+            raise GppError("Ua/Ub must be contiguous")
+        for t, n in ((gmean, "gmean"), (alpha, "alpha"), (gvar, "gvar"), (g_w, "g_w"), (g_sf2, "g_sf2")):
+            if t is not None:
+                _need(t, torch.float64, n)
+        dA = 0 if g_Ua is None else g_Ua.shape[1]
+        dB = 0 if g_Ub is None else g_Ub.shape[1]
+        for t, rows, n in ((g_Ua, M, "g_Ua"), (g_Ub, N, "g_Ub")):
+            if t is not None and (t.dtype != torch.float64 or not t.is_contiguous() or t.shape[0] != rows):
+                raise GppError(f"{n} must be a contiguous float64 ({rows} x d) matrix")
+        self.ensure_workspace(OP_PREDICT_GRAD, N, M, D, dB)
+        self._stream()
+        check(self.lib.gpp_cross_grad(self.h, Ua.data_ptr(), M, Ub.data_ptr(), N, D, w.data_ptr(), sf2.data_ptr(), kind, d_split,
+                                      _ptr(gmean), _ptr(alpha), _ptr(gvar), _ptr(B), 0 if B is None else _ld(B), _ptr(g_Ua), dA,
+                                      _ptr(g_Ub), dB, _ptr(g_w), _ptr(g_sf2)), "gpp_cross_grad")
 
     @_on_own_device
     def gemm(self, transA, transB, M, N, K, alpha, A, B, beta, C, *, a_mask=0, b_mask=0, klo_mode=0, khi_mode=0,

@@ -1278,11 +1278,11 @@ int gpp_shard_back_list(gpp_handle_t h, int64_t N, int64_t nb, int rank, int nra
 
 size_t gpp_workspace_bytes(gpp_handle_t h, int op, int64_t N, int64_t M, int D, int S) {
   (void)h;
-  (void)M;
   if (op == GPP_OP_MLL_EVAL) {
     return std::max(gpp_grad_ws_bytes(N, D, S, D), gpp_trmv_t_ws_bytes(N)) + 256;
   }
   if (op == GPP_OP_PREDICT) return 256;
+  if (op == GPP_OP_PREDICT_GRAD) return gpp_pgrad_ws_bytes(M, N, D, D, S) + 256;
   return 0;
 }
 
@@ -1695,6 +1695,30 @@ int gpp_predict_tn(gpp_handle_t h, const double* Linv, int64_t ldi, int64_t N, c
   GPP_TRY(gpp_launch_gemm(h->stream, 2, g, 1));
   // mean_a = sum_j V[a][j] z_j (= K_*N alpha, alpha = L^-T z), var_a = kss_a - sum_j V[a][j]^2: one pass over V
   GPP_TRY(gpp_launch_predict_reduce(h->stream, V, ldv, V, ldv, M, N, z, kss, mean_out, var_out));
+  return 0;
+}
+
+int gpp_cross_grad(gpp_handle_t h, const double* Ua, int64_t M, const double* Ub, int64_t N, int D, const double* w,
+                   const double* sf2, int kind, int d_split, const double* gmean, const double* alpha, const double* gvar,
+                   const double* B, int64_t ldb, double* g_Ua, int dA, double* g_Ub, int dB, double* g_w, double* g_sf2) {
+  if (!h) return -1;
+  if (M < 0) return -3;
+  if (!Ua && M > 0) return -2;
+  if (N < 0) return -5;
+  if (!Ub && N > 0) return -4;
+  if (D < 1 || D > 64) return -6;
+  if (!w) return -7;
+  if (!sf2) return -8;
+  if (kind < 0 || kind > 2) return -9;
+  if (d_split < 0 || d_split > D) return -10;
+  if ((gmean == nullptr) != (alpha == nullptr)) return -11;
+  if ((gvar == nullptr) != (B == nullptr)) return -13;
+  if (B && (!aligned16(B) || (ldb & 1) || ldb < N)) return -15;
+  if (dA < 0 || dA > D || (dA > 0 && !g_Ua)) return -17;
+  if (dB < 0 || dB > D || (dB > 0 && !g_Ub)) return -19;
+  if (!h->ws || h->ws_bytes < gpp_pgrad_ws_bytes(M, N, D, dA, dB)) return -1;
+  GPP_TRY(gpp_launch_cross_grad(h->stream, Ua, M, Ub, N, D, w, sf2, kind, d_split, gmean, alpha, gvar, B, ldb, g_Ua, dA, g_Ub, dB,
+                                g_w, g_sf2, h->ws, h->ws_bytes));
   return 0;
 }
 

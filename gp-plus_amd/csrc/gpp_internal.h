@@ -314,6 +314,12 @@ size_t gpp_trmv_t_ws_bytes(int64_t N);  // scratch of the trans = 1 form (partia
 //  g_U + b*N*dU; the workspace holds batch * gpp_grad_ws_bytes)
 // dst[c][r] = src[r][c] for r < rows, c < cols (64 x 64 tiles through LDS)
 hipError_t gpp_launch_transpose(hipStream_t s, const double* src, int64_t lds, int64_t rows, int64_t cols, double* dst, int64_t ldd);
+// gradient of predictions (gpp_cross_grad in gpp.h): scratch of gpp_pgrad_ws_bytes
+size_t gpp_pgrad_ws_bytes(int64_t M, int64_t N, int D, int dA, int dB);
+hipError_t gpp_launch_cross_grad(hipStream_t s, const double* Ua, int64_t M, const double* Ub, int64_t N, int D, const double* w,
+                                 const double* sf2, int kind, int d_split, const double* gmean, const double* alpha,
+                                 const double* gvar, const double* B, int64_t ldb, double* g_Ua, int dA, double* g_Ub, int dB,
+                                 double* g_w, double* g_sf2, void* ws, size_t ws_bytes);
 hipError_t gpp_launch_predict_reduce(hipStream_t s, const double* Ksn, int64_t lds, const double* V, int64_t ldv,
                                      int64_t M, int64_t N, const double* alpha, const double* kss, double* mean_out,
                                      double* var_out);

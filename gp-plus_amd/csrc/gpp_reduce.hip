@@ -8,6 +8,8 @@
 // Every matrix is streamed exactly once; all reductions are two-stage and deterministic (no float atomics).
 #include "gpp_internal.h"
 
+#include <algorithm>
+
 typedef double v2d __attribute__((ext_vector_type(2)));
 
 namespace {
@@ -494,6 +496,248 @@ __global__ __launch_bounds__(256) void gpp_gU_finish(const double* __restrict__ 
   g_U[e] = s;
 }
 
+// ------------------------------------------------------------------------------------------------
+// gradient of predictions (gpp_cross_grad).  With G_aj = gmean_a alpha_j + gvar_a B_aj (never materialised) and
+// K_aj = sf2 k(u_a, u_j) recomputed in registers from the staged features:
+//    g_Ua[a,d] += G_aj dK_aj/du_ad = (-2 w_d) G_aj sf2 k'_aj (u_ad-u_jd)      (d < dA)
+//    g_Ub[j,d] += G_aj dK_aj/du_jd = ( 2 w_d) G_aj sf2 k'_aj (u_ad-u_jd)      (d < dB)
+//    g_w[d]    += G_aj dK_aj/dw_d  = -G_aj sf2 k'_aj (u_ad-u_jd)^2            g_sf2 += G_aj k_aj
+// (k' = k for the RBF dims, the Matern factor's derivative for d >= d_split, as in gpp_grad_tiles).
+// Work-group (c, t): row tile t (64 test rows, staged once) against the column tiles c, c + CN, c + 2 CN, ... of the
+// training points, so both M and N are split over the grid (M = 1 against N = 20000: 313 work-groups; M = 8192: 128 x 16).
+// Thread (ty, tx): rows 4 ty .. 4 ty + 3 and the column pairs {2 tx, 2 tx + 1}, {32 + 2 tx, 33 + 2 tx} of the tile (16-byte LDS
+// reads covering every bank once, see gpp_grad_tiles).  Deterministic: the row sums of a tile are reduced over the 16 lanes that
+// share a row and added, in column-tile order, to an LDS accumulator with one owner per entry, written once per work-group to
+// slot [c][a]; column sums go to slot [t][j] (every slot written exactly once); scalar sums to one record per work-group.
+// The finish kernels add the slots in a fixed order.  B (M x N) is the only M x N operand, read once.
+constexpr int PG_WGS = 2048;
+
+struct PgradShape {
+  int64_t MT, NT;
+  int CN;
+};
+
+static PgradShape pgrad_shape(int64_t M, int64_t N) {
+  PgradShape s;
+  s.MT = (M + GT - 1) / GT;
+  s.NT = (N + GT - 1) / GT;
+  const int64_t want = (PG_WGS + s.MT - 1) / (s.MT > 0 ? s.MT : 1);
+  s.CN = (int)std::max<int64_t>(1, std::min<int64_t>(s.NT, want));
+  return s;
+}
+
+template <int DT, bool MAT>
+__global__ __launch_bounds__(256) void gpp_pgrad_tiles(const double* __restrict__ Ua, int64_t M, const double* __restrict__ Ub,
+                                                       int64_t N, int D, const double* __restrict__ w,
+                                                       const double* __restrict__ sf2p, int kind, int d_split,
+                                                       const double* __restrict__ gmean, const double* __restrict__ alpha,
+                                                       const double* __restrict__ gvar, const double* __restrict__ B, int64_t ldb,
+                                                       int dA, int dB, int want_w, int CN,
+                                                       double* __restrict__ rec /* [MT * CN][D+1] */,
+                                                       double* __restrict__ gApart /* [CN][M][dA] */,
+                                                       double* __restrict__ gBpart /* [MT][N][dB] */) {
+  __shared__ __attribute__((aligned(16))) double sa[DT * GT];  // test rows of tile t, [d][r]
+  __shared__ __attribute__((aligned(16))) double sb[DT * GT];  // training rows of the current column tile, [d][r]
+  __shared__ double accA[DT * GT];                              // g_Ua of tile t over this work-group's column tiles, [d][r]
+  __shared__ double s_gm[GT], s_gv[GT], s_al[GT];
+  __shared__ double sw[DT];
+  __shared__ double wacc[4 * DT];
+  __shared__ double colred[4 * GT];
+  __shared__ double red[256];
+  const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15, wave = tid >> 6, lane = tid & 63;
+  const int c = blockIdx.x;
+  const int64_t t = blockIdx.y, i0 = t * GT;
+  const double sf2 = *sf2p;
+  const GppExpConsts ec = gpp_exp_consts();
+  const int dsp = MAT ? d_split : DT;
+  if (tid < DT) sw[tid] = (tid < D) ? w[tid] : 0.0;
+  for (int e = tid; e < DT * GT; e += 256) {
+    const int d = e / GT, r = e - d * GT;
+    sa[e] = (d < D && i0 + r < M) ? Ua[(i0 + r) * D + d] : 0.0;
+    accA[e] = 0.0;
+  }
+  for (int e = tid; e < 4 * DT; e += 256) wacc[e] = 0.0;
+  if (tid < GT) {
+    const bool ok = i0 + tid < M;
+    s_gm[tid] = (ok && gmean) ? gmean[i0 + tid] : 0.0;
+    s_gv[tid] = (ok && gvar) ? gvar[i0 + tid] : 0.0;
+  }
+  double my_sf2 = 0.0;
+  const int64_t NT = (N + GT - 1) / GT;
+  typedef double v2d __attribute__((ext_vector_type(2)));
+  for (int64_t ct = c; ct < NT; ct += CN) {
+    const int64_t j0 = ct * GT;
+    __syncthreads();
+    for (int e = tid; e < DT * GT; e += 256) {
+      const int d = e / GT, r = e - d * GT;
+      sb[e] = (d < D && j0 + r < N) ? Ub[(j0 + r) * D + d] : 0.0;
+    }
+    if (tid < GT) s_al[tid] = (alpha && j0 + tid < N) ? alpha[j0 + tid] : 0.0;
+    __syncthreads();
+
+    // this thread's 4 x 4 entries of B, two 16-byte loads per row issued before the arithmetic
+    double bv[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) bv[a][b] = 0.0;
+    if (B) {
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        const int64_t i = i0 + 4 * ty + a, jb = j0 + 2 * tx;
+        const double* src = B + (i < M ? i : M - 1) * ldb + jb;
+        if (jb + 34 <= ldb) {
+          const v2d p0 = *reinterpret_cast<const v2d*>(src), p1 = *reinterpret_cast<const v2d*>(src + 32);
+          bv[a][0] = p0.x; bv[a][1] = p0.y; bv[a][2] = p1.x; bv[a][3] = p1.y;
+        } else {
+#pragma unroll
+          for (int b = 0; b < 4; ++b) bv[a][b] = (jb + (b & 1) + ((b >> 1) << 5) < N) ? src[(b & 1) + ((b >> 1) << 5)] : 0.0;
+        }
+      }
+    }
+
+    double r2[4][4], r2m[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) r2[a][b] = r2m[a][b] = 0.0;
+#pragma unroll 4
+    for (int d = 0; d < DT; ++d) {
+      const v2d u01 = *reinterpret_cast<const v2d*>(sa + d * GT + 4 * ty), u23 = *reinterpret_cast<const v2d*>(sa + d * GT + 4 * ty + 2);
+      const v2d b01 = *reinterpret_cast<const v2d*>(sb + d * GT + 2 * tx), b23 = *reinterpret_cast<const v2d*>(sb + d * GT + 32 + 2 * tx);
+      const double ua[4] = {u01.x, u01.y, u23.x, u23.y}, ub[4] = {b01.x, b01.y, b23.x, b23.y};
+      const double wd = sw[d];
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const double df = ua[a] - ub[b];
+          if (!MAT || d < dsp) r2[a][b] = fma(wd * df, df, r2[a][b]);
+          else r2m[a][b] = fma(wd * df, df, r2m[a][b]);
+        }
+    }
+    // compiler barrier: the feature pass below reads the same LDS addresses again instead of keeping them live (gpp_grad_tiles)
+    __asm__ volatile("" ::: "memory");
+    // g = G sf2 k (the RBF dims' factor of dK/d(-r2)), gm = G sf2 dm/d(-r2_mat) for the Matern dims (as in gpp_grad_tiles)
+    double g[4][4], gm[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const int64_t i = i0 + 4 * ty + a;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const int cb = 2 * tx + (b & 1) + ((b >> 1) << 5);
+        double gg = 0.0, gmm = 0.0;
+        if (i < M && j0 + cb < N) {
+          const double er = gpp_exp_nonpos(-r2[a][b], ec);
+          double kv = er, kd = 0.0;
+          if (MAT && kind == 1) {
+            const double aa = sqrt(6.0 * r2m[a][b]), ea = gpp_exp_nonpos(-aa, ec);
+            kv = er * (1.0 + aa) * ea;
+            kd = er * 3.0 * ea;
+          } else if (MAT && kind == 2) {
+            const double aa = sqrt(10.0 * r2m[a][b]), ea = gpp_exp_nonpos(-aa, ec);
+            kv = er * (1.0 + aa + aa * aa * (1.0 / 3.0)) * ea;
+            kd = er * (5.0 / 3.0) * (1.0 + aa) * ea;
+          }
+          const double G = fma(s_gm[4 * ty + a], s_al[cb], s_gv[4 * ty + a] * bv[a][b]);
+          my_sf2 = fma(G, kv, my_sf2);
+          gg = G * sf2 * kv;
+          gmm = G * sf2 * kd;
+        }
+        g[a][b] = gg;
+        gm[a][b] = gmm;
+      }
+    }
+    // feature pass: per feature, the g_w sum (wave-reduced into one LDS accumulator per wave), the row sums (reduced over the
+    // 16 lanes of a row) and the column sums (reduced over the wave, then over the four waves through LDS)
+#pragma unroll 2
+    for (int d = 0; d < D; ++d) {
+      const v2d u01 = *reinterpret_cast<const v2d*>(sa + d * GT + 4 * ty), u23 = *reinterpret_cast<const v2d*>(sa + d * GT + 4 * ty + 2);
+      const v2d b01 = *reinterpret_cast<const v2d*>(sb + d * GT + 2 * tx), b23 = *reinterpret_cast<const v2d*>(sb + d * GT + 32 + 2 * tx);
+      const double ua[4] = {u01.x, u01.y, u23.x, u23.y}, ub[4] = {b01.x, b01.y, b23.x, b23.y};
+      const double wd = sw[d];
+      const bool rbf_dim = !MAT || d < dsp;
+      double rs[4] = {0.0, 0.0, 0.0, 0.0}, cs[4] = {0.0, 0.0, 0.0, 0.0}, sw2 = 0.0;
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const double df = ua[a] - ub[b];
+          const double gs = rbf_dim ? g[a][b] : gm[a][b];
+          const double gd = gs * df;
+          rs[a] += gd;
+          cs[b] += gd;
+          sw2 = fma(-gd, df, sw2);
+        }
+      if (want_w) {
+        const double s = wave_sum(sw2);
+        if (lane == 0) wacc[wave * DT + d] += s;
+      }
+      if (d < dA) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+          double v = rs[a];
+#pragma unroll
+          for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o);
+          if (tx == 0) accA[d * GT + 4 * ty + a] += -2.0 * wd * v;
+        }
+      }
+      if (d < dB) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          double v = cs[b];
+          v += __shfl_xor(v, 16);
+          v += __shfl_xor(v, 32);
+          if (lane < 16) colred[wave * GT + 2 * tx + (b & 1) + ((b >> 1) << 5)] = v;
+        }
+        __syncthreads();
+        if (tid < GT && j0 + tid < N)
+          gBpart[((int64_t)t * N + j0 + tid) * dB + d] =
+              2.0 * wd * ((colred[tid] + colred[GT + tid]) + (colred[2 * GT + tid] + colred[3 * GT + tid]));
+        __syncthreads();
+      }
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < dA * GT; e += 256) {
+    const int d = e / GT, r = e - d * GT;
+    if (i0 + r < M) gApart[((int64_t)c * M + i0 + r) * dA + d] = accA[e];
+  }
+  const int nrec = D + 1;
+  const int64_t wg = t * CN + c;
+  for (int q = 0; q < nrec; ++q) {
+    double v = my_sf2;
+    if (q < D) v = (lane == 0) ? wacc[wave * DT + q] : 0.0;
+    __syncthreads();
+    red[tid] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if (tid < o) red[tid] += red[tid + o];
+      __syncthreads();
+    }
+    if (tid == 0) rec[wg * nrec + q] = red[0];
+  }
+}
+
+// q < D: g_w[q]; q == D: g_sf2 — each only when asked for
+__global__ __launch_bounds__(256) void gpp_pgrad_finish(const double* __restrict__ rec, int nwg, int D, double* __restrict__ g_w,
+                                                        double* __restrict__ g_sf2) {
+  __shared__ double red[256];
+  const int q = blockIdx.x, nrec = D + 1, tid = threadIdx.x;
+  double v = 0.0;
+  for (int b = tid; b < nwg; b += 256) v += rec[(int64_t)b * nrec + q];
+  red[tid] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    if (q < D && g_w) g_w[q] = red[0];
+    else if (q == D && g_sf2) g_sf2[0] = red[0];
+  }
+}
+
 // mean_a = sum_j Ksn[a][j] alpha_j ; var_a = kss_a - sum_j V[a][j]^2 : one wave per test row.
 __global__ __launch_bounds__(256) void gpp_predict_rows(const double* __restrict__ Ksn, int64_t lds, const double* __restrict__ V,
                                                         int64_t ldv, int64_t M, int64_t N, const double* __restrict__ alpha,
@@ -605,6 +849,52 @@ hipError_t gpp_launch_grad_reduce(hipStream_t s, const double* U, int64_t N, int
   if (dU > 0)
     hipLaunchKernelGGL(gpp_gU_finish, dim3((unsigned)((N * dU + 255) / 256), batch), dim3(256), 0, s, gUpart, N, dU, T, g_U,
                        ws_stride);
+  return hipGetLastError();
+}
+
+size_t gpp_pgrad_ws_bytes(int64_t M, int64_t N, int D, int dA, int dB) {
+  const PgradShape p = pgrad_shape(M, N);
+  const int64_t nwg = p.MT * p.CN;
+  return ((size_t)nwg * (D + 1) + (size_t)p.CN * M * std::max(dA, 0) + (size_t)p.MT * N * std::max(dB, 0)) * sizeof(double);
+}
+
+hipError_t gpp_launch_cross_grad(hipStream_t s, const double* Ua, int64_t M, const double* Ub, int64_t N, int D, const double* w,
+                                 const double* sf2, int kind, int d_split, const double* gmean, const double* alpha,
+                                 const double* gvar, const double* B, int64_t ldb, double* g_Ua, int dA, double* g_Ub, int dB,
+                                 double* g_w, double* g_sf2, void* ws, size_t ws_bytes) {
+  if (kind < 0 || kind > 2 || D < 1 || D > GD_MAX) return hipErrorInvalidValue;
+  if (M <= 0 || N <= 0) {  // empty sums
+    if (g_w) if (hipError_t e = hipMemsetAsync(g_w, 0, (size_t)D * sizeof(double), s); e != hipSuccess) return e;
+    if (g_sf2) if (hipError_t e = hipMemsetAsync(g_sf2, 0, sizeof(double), s); e != hipSuccess) return e;
+    if (dA > 0 && M > 0) if (hipError_t e = hipMemsetAsync(g_Ua, 0, (size_t)M * dA * sizeof(double), s); e != hipSuccess) return e;
+    if (dB > 0 && N > 0) if (hipError_t e = hipMemsetAsync(g_Ub, 0, (size_t)N * dB * sizeof(double), s); e != hipSuccess) return e;
+    return hipSuccess;
+  }
+  const PgradShape p = pgrad_shape(M, N);
+  if (p.MT > 65535) return hipErrorInvalidValue;
+  if (ws_bytes < gpp_pgrad_ws_bytes(M, N, D, dA, dB)) return hipErrorInvalidValue;
+  const int nwg = (int)(p.MT * p.CN);
+  double* rec = reinterpret_cast<double*>(ws);
+  double* gApart = rec + (size_t)nwg * (D + 1);
+  double* gBpart = gApart + (size_t)p.CN * M * std::max(dA, 0);
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.CN, (unsigned)p.MT), dim3(256), 0, s, Ua, M, Ub, N, D, w, sf2, kind, d_split, gmean,
+                       alpha, gvar, B, ldb, dA, dB, g_w ? 1 : 0, p.CN, rec, gApart, gBpart);
+  };
+  const bool mat = kind != 0;
+#define GPP_PG(DT) (mat ? launch(gpp_pgrad_tiles<DT, true>) : launch(gpp_pgrad_tiles<DT, false>))
+  if (D <= 8) GPP_PG(8);
+  else if (D <= 16) GPP_PG(16);
+  else if (D <= 32) GPP_PG(32);
+  else GPP_PG(64);
+#undef GPP_PG
+  if (g_w || g_sf2) hipLaunchKernelGGL(gpp_pgrad_finish, dim3(D + 1), dim3(256), 0, s, rec, nwg, D, g_w, g_sf2);
+  if (dA > 0)
+    hipLaunchKernelGGL(gpp_gU_finish, dim3((unsigned)((M * dA + 255) / 256), 1), dim3(256), 0, s, gApart, M, dA, p.CN, g_Ua,
+                       (int64_t)0);
+  if (dB > 0)
+    hipLaunchKernelGGL(gpp_gU_finish, dim3((unsigned)((N * dB + 255) / 256), 1), dim3(256), 0, s, gBpart, N, dB, (int)p.MT, g_Ub,
+                       (int64_t)0);
   return hipGetLastError();
 }
 

@@ -7,6 +7,7 @@ import warnings
 
 import torch
 
+from .. import settings
 from .distributions import DenseCovariance, MultivariateNormal
 from .kernels import LazyKernelMatrix
 from .module import Module
@@ -118,6 +119,9 @@ class ExactGP(GP):
             out = self._graphed_prior_call(inputs, kwargs)
             return out if out is not None else Module.__call__(self, *inputs, **kwargs)
         # ---- posterior mode -----------------------------------------------------------------------
+        if settings.differentiable_predictions.value() and torch.is_grad_enabled() and (
+                any(torch.is_tensor(a) and a.requires_grad for a in inputs) or any(p.requires_grad for p in self.parameters())):
+            return self._differentiable_posterior(inputs, kwargs)
         from ..linalg import factorize, predict_from_cache, cross_kernel
 
         with torch.no_grad():
@@ -150,3 +154,40 @@ class ExactGP(GP):
                 return Kss
 
             return MultivariateNormal(pred_mean, DenseCovariance(lambda: var_and_v()[0], full_cov, n=Us.shape[0]))
+
+    def _differentiable_posterior(self, inputs, kwargs):
+        """The eval-mode call under ``settings.differentiable_predictions``: the same factor cache and the same numbers as the
+        no-grad path, with the test features and test mean (and, when a latent map makes them depend on parameters, the training
+        features) built under autograd.  The mean and the variance diagonal are autograd-connected (linalg.predict_mean /
+        predict_var); the joint covariance is not offered."""
+        from ..linalg import predict_mean, predict_var
+
+        with torch.no_grad():
+            cache = self._ensure_prediction_cache(**kwargs)
+        test_out = Module.__call__(self, *inputs, **kwargs)
+        tcov = test_out.lazy_covariance_matrix
+        if not isinstance(tcov, LazyKernelMatrix):
+            raise RuntimeError("exact prediction needs the model's forward to return a lazy kernel covariance")
+        Us, spec = tcov.U1.to(torch.float64), tcov.spec
+        Utr, dB = None, 0
+        # (n_grad_dims == 0: no feature column depends on a parameter — no latent map — and the training features are constants)
+        if tcov.n_grad_dims != 0 and any(p.requires_grad for p in self.parameters()):
+            trcov = Module.__call__(self, *self.train_inputs, **kwargs).lazy_covariance_matrix
+            if trcov.U1.requires_grad:
+                dB = trcov.n_grad_dims if trcov.n_grad_dims is not None else trcov.U1.shape[1]
+                if dB > 0:
+                    Utr = trcov.U1.to(torch.float64)
+        pred_mean = test_out.mean.to(torch.float64) + predict_mean(cache, Us, Utr, spec.w, spec.sf2, dB)
+        lazy = {}
+
+        def var():
+            if "var" not in lazy:
+                lazy["var"] = predict_var(cache, Us, Utr, spec.w, spec.sf2, dB)
+            return lazy["var"]
+
+        def full_cov():
+            raise NotImplementedError("the joint predictive covariance of a differentiable prediction is not available "
+                                      "(only its mean and variance carry gradients); predict without "
+                                      "settings.differentiable_predictions for covariance_matrix")
+
+        return MultivariateNormal(pred_mean, DenseCovariance(var, full_cov, n=Us.shape[0]))

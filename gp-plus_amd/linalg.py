@@ -27,7 +27,7 @@ from .errors import NanError, NotPSDError
 from . import settings
 
 __all__ = ["KernelSpec", "exact_mll", "ExactMLLFunction", "EvalWorkspace", "dense_kernel", "cross_kernel",
-           "FactorCache", "factorize", "dense_log_prob"]
+           "FactorCache", "factorize", "dense_log_prob", "predict_mean", "predict_var"]
 
 
 @dataclass
@@ -396,6 +396,106 @@ def predict_from_cache(cache: FactorCache, Us: torch.Tensor, need_var: bool = Tr
     var = torch.empty(M, dtype=torch.float64, device=dev)
     gctx.predict_tn(cache.Linv, cache.z, Kns, kss, V, mean, var)
     return mean, var, V
+
+
+# ---------------------------------------------------------------------------------------------------
+# differentiable prediction (settings.differentiable_predictions): gpytorch's exact prediction strategy under autograd with its
+# default detach_test_caches — alpha = Ky^-1 (y - m) and Ky are constants; the test-train covariance, the prior variance sf2 and
+# (through Utr) the training features stay differentiable.  Both backwards end in gpp_cross_grad, which recomputes K_*N in
+# registers: G = gmean alpha^T (mean) or -2 diag(gvar) B with B = K_*N Ky^-1 = V Linv (variance).
+# ---------------------------------------------------------------------------------------------------
+def _cross_backward(ctx, gmean, alpha, gvar, B):
+    """Gradients (Us, Utr, w, sf2) of sum_aj G_aj K_aj from one gpp_cross_grad call, each in the dtype of its input."""
+    cache, dB = ctx.cache, ctx.dB
+    Us, Utr, w, sf2 = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    dev = cache.U.device
+    Ua = _as_f64(Us.detach(), dev)
+    Ub = cache.U if Utr is None else _as_f64(Utr.detach(), dev)
+    M, D = Ua.shape
+    N = Ub.shape[0]
+    f64 = dict(dtype=torch.float64, device=dev)
+    g_Ua = torch.empty(M, D, **f64) if need[0] else None
+    g_Ub = torch.empty(N, dB, **f64) if need[1] and dB > 0 else None
+    g_w = torch.empty(D, **f64) if need[2] else None
+    g_s = torch.empty(1, **f64) if need[3] else None
+    if g_Ua is not None or g_Ub is not None or g_w is not None or g_s is not None:
+        cache.gctx.cross_grad(Ua, Ub, _as_f64(w.detach(), dev), _as_f64(sf2.detach().reshape(1), dev), gmean, alpha, gvar, B,
+                              g_Ua, g_Ub, g_w, g_s, kind=cache.spec.kind, d_split=cache.spec.d_split)
+    g_U = None
+    if need[1]:
+        g_U = torch.zeros(N, D, **f64)
+        if g_Ub is not None:
+            g_U[:, :dB] = g_Ub
+    return (None if g_Ua is None else g_Ua.to(Us.dtype), None if g_U is None else g_U.to(Utr.dtype),
+            None if g_w is None else g_w.to(w.dtype), None if g_s is None else g_s.reshape(sf2.shape).to(sf2.dtype))
+
+
+class PredictMeanFunction(torch.autograd.Function):
+    """mean_a = sum_j K(Us_a, Utr_j) alpha_j: the forward is ``predict_from_cache``'s mean-only path (the same numbers as a
+    no-grad prediction); the backward is ONE gpp_cross_grad with G = gmean alpha^T — O(M N D), no N x N operand."""
+
+    @staticmethod
+    def forward(ctx, Us, Utr, w, sf2, cache, dB):
+        dev = cache.U.device
+        with torch.cuda.device(dev):
+            mean, _, _ = predict_from_cache(cache, _as_f64(Us.detach(), dev), need_var=False)
+        ctx.cache, ctx.dB = cache, dB
+        ctx.save_for_backward(Us, Utr, w, sf2)
+        return mean
+
+    @staticmethod
+    def backward(ctx, gmean):
+        with torch.cuda.device(ctx.cache.U.device):
+            grads = _cross_backward(ctx, gmean.to(torch.float64).contiguous(), ctx.cache.alpha, None, None)
+        return grads + (None, None)
+
+
+class PredictVarFunction(torch.autograd.Function):
+    """var_a = sf2 - k_a^T Ky^-1 k_a: the forward is ``predict_from_cache``'s variance path (V = K_*N Linv^T, kept for the
+    backward); the backward forms B = V Linv (one M N^2 GEMM) and runs gpp_cross_grad with gvar = -2 dL/dvar."""
+
+    @staticmethod
+    def forward(ctx, Us, Utr, w, sf2, cache, dB):
+        dev = cache.U.device
+        with torch.cuda.device(dev):
+            # another model of the same size may have factored into the shared workspace since the cache was made
+            cache.refresh()
+            _, var, V = predict_from_cache(cache, _as_f64(Us.detach(), dev), need_var=True, need_V=True)
+        ctx.cache, ctx.dB, ctx.V = cache, dB, V
+        ctx.save_for_backward(Us, Utr, w, sf2)
+        return var
+
+    @staticmethod
+    def backward(ctx, gvar):
+        cache, V = ctx.cache, ctx.V
+        with torch.cuda.device(cache.U.device):
+            cache.refresh()  # Linv of this cache's own factor (the same bits: same inputs, same jitter schedule)
+            M, N = V.shape
+            B = torch.empty((M, V.stride(0)), dtype=torch.float64, device=V.device)[:, :N]
+            # B = V Linv against the lower triangle of the Linv buffer (its upper triangle holds the mirror; keep k >= n), as the
+            # row-contiguous TN product from V^T: the NN form of the same product measured 95 ms against 55 for the forward's TN
+            # product at M = 8192, N = 20000 (the k-contiguous variant, gpp_predict_tn); the transpose costs 2 M N doubles of traffic
+            Vt = torch.empty((N, max(16, (M + 15) // 16 * 16)), dtype=torch.float64, device=V.device)[:, :M]
+            cache.gctx.transpose(V, Vt)
+            cache.gctx.gemm(1, 0, M, N, N, 1.0, Vt, cache.Linv, 0.0, B, b_mask=2, klo_mode=2)
+            del Vt
+            gv = gvar.to(torch.float64).contiguous()
+            g_Us, g_Utr, g_w, g_s = _cross_backward(ctx, None, None, -2.0 * gv, B)
+            if g_s is not None:
+                g_s = g_s + gv.sum().reshape(g_s.shape).to(g_s.dtype)  # k(u, u) = sf2 for every stationary kind
+        return g_Us, g_Utr, g_w, g_s, None, None
+
+
+def predict_mean(cache: FactorCache, Us, Utr, w, sf2, dB: int = 0) -> torch.Tensor:
+    """K_*N alpha, differentiable w.r.t. the test features Us, the training features Utr[:, :dB] (None: the cache's, constant),
+    the kernel weights w and the outputscale sf2."""
+    return PredictMeanFunction.apply(Us, Utr, w, sf2, cache, int(dB))
+
+
+def predict_var(cache: FactorCache, Us, Utr, w, sf2, dB: int = 0) -> torch.Tensor:
+    """sf2 - diag(K_*N Ky^-1 K_N*), differentiable like :func:`predict_mean`."""
+    return PredictVarFunction.apply(Us, Utr, w, sf2, cache, int(dB))
 
 
 @torch.no_grad()

@@ -10,7 +10,8 @@ What runs differently from the reference, by design:
     gp_plus.py:532-534) become one cached integer index + gather;
   * the model is placed on ``device`` at construction (the reference moves it in ``fit``, gp_plus.py:562).
 Out of scope (raise ``NotImplementedError``): probabilistic embedding / calibration (stochastic multi-pass
-ensembles), neural-network and polynomial mean functions, plotting, Sobol indices, botorch glue.
+ensembles), neural-network and polynomial mean functions, plotting, Sobol indices, botorch glue, and gradients through the
+joint predictive covariance (``predict_with_grad`` differentiates the mean and the variance diagonal).
 """
 import math
 import warnings
@@ -352,7 +353,14 @@ class GP_Plus(GPR):
             return super().predict(Xtest.to(self.tkwargs['device']), return_std=return_std, include_noise=include_noise)
 
     def predict_with_grad(self, Xtest, return_std=True, include_noise=True):
-        raise NotImplementedError("gradients of predictions (BO glue, gp_plus.py:626-628) are outside this build's scope")
+        """gp_plus.py:626-628: ``predict`` without ``torch.no_grad()``.  The mean and std are autograd-connected to Xtest's
+        quantitative columns (categorical columns get zero gradient, as the reference's index lookup gives) and to the model's
+        parameters, with gpytorch's default detach_test_caches (Ky and alpha constant); backward by gpp_cross_grad."""
+        from .. import settings as gpp_settings
+
+        Xtest = data_type_check(Xtest)
+        with gpp_settings.differentiable_predictions(True):
+            return super().predict(Xtest.to(self.tkwargs['device']), return_std=return_std, include_noise=include_noise)
 
     def noise_value(self):
         return self.likelihood.noise_covar.noise.detach() * self.y_std ** 2

@@ -68,6 +68,14 @@ reference_fp32_theta = _Value(False)
 sharded_evaluation = _Value(None)
 
 
+# Differentiable predictions (GP_Plus.predict_with_grad, reference models/gp_plus.py:626-628): inside
+# ``with settings.differentiable_predictions(True):``, with grad mode on and some input or parameter requiring grad, the eval-mode call
+# of a model builds its test features, test mean and (for a latent map) training features under autograd, and the mean and the
+# variance diagonal of the returned MultivariateNormal are autograd-connected (linalg.predict_mean / predict_var, backward by
+# gpp_cross_grad).  Off by default: predictions then carry no graph, as they always have (callers call ``.numpy()`` on them).
+differentiable_predictions = _Value(False)
+
+
 @contextmanager
 def fast_computations(covar_root_decomposition=True, log_prob=True, solves=True):
     yield

@@ -48,6 +48,7 @@ typedef struct gpp_handle_s* gpp_handle_t;
 /* operation ids for gpp_workspace_bytes */
 #define GPP_OP_MLL_EVAL 0   /* potrf + trtri + lauum + mll_reduce + grad_reduce for an N-point model */
 #define GPP_OP_PREDICT  1   /* gpp_predict with M test points */
+#define GPP_OP_PREDICT_GRAD 2 /* gpp_cross_grad with M test points, N training points, D features; S carries dB (0..D) */
 
 const char* gpp_version(void);
 
@@ -342,6 +343,18 @@ int gpp_predict(gpp_handle_t h, const double* Linv, int64_t ldi, int64_t N, cons
  * is ~1.7x faster than gpp_predict's); for the mean alone gpp_predict with V = NULL is O(M N).  (models/gpregression.py:122-149) */
 int gpp_predict_tn(gpp_handle_t h, const double* Linv, int64_t ldi, int64_t N, const double* z, const double* Kns, int64_t ldk,
                    int64_t M, const double* kss, double* V, int64_t ldv, double* mean_out, double* var_out);
+
+/* Backward of a prediction (models/gp_plus.py predict_with_grad): with G = gmean (x) alpha + diag(gvar) B (never formed) and
+ * K = sf2 k(Ua, Ub; w) recomputed in registers (kind / d_split as in gpp_cross_kernel),
+ *   g_Ua[a,d] = sum_j G_aj dK_aj/dUa_ad  (d < dA),   g_Ub[j,d] = sum_a G_aj dK_aj/dUb_jd  (d < dB),
+ *   g_w[d] = sum_aj G_aj dK_aj/dw_d,   g_sf2 = sum_aj G_aj K_aj / sf2.
+ * Ua: M x D, Ub: N x D row-major; gmean (M) and alpha (N) may both be NULL, and so may gvar (M) and B (M x N, ldb >= N even,
+ * 16-byte aligned).  Every output may be NULL (g_Ua / g_Ub with dA / dB = 0).  Deterministic: per-work-group partial sums in
+ * the handle workspace (gpp_workspace_bytes(GPP_OP_PREDICT_GRAD, N, M, D, dB)), added in a fixed order; no atomics.
+ * For the variance the caller passes gvar = -2 dL/dvar and B = K_*N Ky^-1, and adds sum(dL/dvar) to g_sf2 itself. */
+int gpp_cross_grad(gpp_handle_t h, const double* Ua, int64_t M, const double* Ub, int64_t N, int D, const double* w,
+                   const double* sf2, int kind, int d_split, const double* gmean, const double* alpha, const double* gvar,
+                   const double* B, int64_t ldb, double* g_Ua, int dA, double* g_Ub, int dB, double* g_w, double* g_sf2);
 
 /*
  * The fp64 MFMA GEMM behind all of the above, exported for the parity tests:
