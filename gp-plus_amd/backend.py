@@ -244,6 +244,26 @@ class GppContext:
         check(self.lib.gpp_lauum(self.h, Linv.data_ptr(), Linv.shape[0], _ld(Linv), Kinv.data_ptr(), _ld(Kinv)), "gpp_lauum")
 
     @_on_own_device
+    def post_cov_train(self, Kinv, tau, grp, d, out, *, jitter=0.0):
+        """out(upper) = diag(tau[grp] + d + jitter) - T Kinv T with T = diag(tau[grp]), from the lower triangle of Kinv
+        (gpp_post_cov_train): the posterior covariance at the training inputs.  ``out`` may be ``Kinv`` itself."""
+        N = Kinv.shape[0]
+        for t, n in ((Kinv, "Kinv"), (tau, "tau"), (out, "A")):
+            _need(t, torch.float64, n)
+        if d is not None:
+            _need(d, torch.float64, "d")
+            if d.numel() != N or not d.is_contiguous():
+                raise GppError(f"d must be a contiguous vector of {N} doubles")
+        if grp is not None:
+            self._check_groups(grp, N, tau.numel())
+        if out.shape[0] != N or out.shape[1] != N:
+            raise GppError("post_cov_train: shapes do not match")
+        self._stream()
+        check(self.lib.gpp_post_cov_train(self.h, Kinv.data_ptr(), N, _ld(Kinv), tau.data_ptr(), _ptr(grp), tau.numel(), _ptr(d),
+                                          float(jitter), out.data_ptr(), _ld(out)), "gpp_post_cov_train")
+        return out
+
+    @_on_own_device
     def syrk_rows(self, Urow, C, nb, first_block, rank, nranks):
         """C(upper) -= Urow^T Urow on the block rows (height nb) of C this rank owns (block-cyclic), one launch."""
         self._stream()

@@ -1432,6 +1432,19 @@ int gpp_lauum(gpp_handle_t h, const double* Linv, int64_t N, int64_t ldi, double
   return 0;
 }
 
+int gpp_post_cov_train(gpp_handle_t h, const double* Kinv, int64_t N, int64_t ldk, const double* tau, const int32_t* grp, int S,
+                       const double* d, double jitter, double* A, int64_t lda) {
+  if (!h) return -1;
+  if (N < 0) return -3;
+  if (int r = check_mat(Kinv, ldk, N, 2)) return r;
+  if (!tau) return -5;
+  if (S < 1) return -7;
+  if (int r = check_mat(A, lda, N, 10)) return r;
+  if (A == Kinv && lda != ldk) return -11;  // in place: the same layout
+  GPP_TRY(gpp_launch_post_cov_train(h->stream, Kinv, ldk, N, tau, grp, d, jitter, A, lda));
+  return 0;
+}
+
 int gpp_lauum_rows(gpp_handle_t h, const double* Linv, int64_t N, int64_t ldi, double* Kinv, int64_t ldk, int rank, int nranks) {
   if (!h) return -1;
   if (N < 0) return -3;

@@ -210,3 +210,97 @@ hipError_t gpp_launch_cross_kernel(hipStream_t s, const double* Ua, int64_t Ma, 
                      tiles_n, (int64_t)0, (int64_t)0, (int64_t)0, 0);
   return hipGetLastError();
 }
+
+// ---- posterior covariance at the training inputs (gpp_post_cov_train in gpp.h) -------------------------------------------
+// With Ky = K + T (T = diag(tau[grp])) the predictive covariance of the latent function at the training inputs,
+// K - K Ky^-1 K, is exactly T - T Ky^-1 T: one scaling of Ky^-1 (gpp_lauum's lower triangle), no cancellation of O(sf2) terms.
+//   A[i,j] = -tau_i Kinv[j,i] tau_j + (i == j)(tau_i + d_i + jitter)        j >= i
+// One work-group per 128 x 128 tile of the upper triangle, in four 64 x 64 quarters staged through LDS: the quarter of
+// Kinv's lower triangle (rows j, columns i) is read with 16-byte loads along its rows and written transposed with 16-byte
+// stores along the rows of A.  HBM-bound: one read and one write of N^2/2 doubles.
+// In place (A == Kinv) is allowed: a work-group reads only the lower tile (tj, ti) and writes only the upper tile
+// (ti, tj), so two work-groups never share an element; inside a diagonal tile a quarter's reads all precede the barrier
+// in front of its writes, and the only elements both read and written there are the diagonal ones.
+namespace {
+
+constexpr int PC_T = 128;  // output tile
+constexpr int PC_Q = 64;   // LDS quarter
+
+__global__ __launch_bounds__(256) void gpp_post_cov_tile(const double* Kinv, int64_t ldk, int64_t N, const double* __restrict__ tau,
+                                                         const int32_t* __restrict__ grp, const double* __restrict__ d,
+                                                         double jitter, double* A, int64_t lda) {
+  __shared__ double s[PC_Q][PC_Q + 1];  // s[i][j] = Kinv[j][i]; padded against bank conflicts of the transposed writes
+  typedef double v2d __attribute__((ext_vector_type(2)));
+  int64_t ti, tj;  // upper-triangle tile ti <= tj: the row-major enumeration of the lower triangle, mirrored
+  {
+    const int64_t t = blockIdx.x;
+    int64_t r = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while ((r + 1) * (r + 2) / 2 <= t) ++r;
+    while (r * (r + 1) / 2 > t) --r;
+    tj = r;
+    ti = t - r * (r + 1) / 2;
+  }
+  const int tid = threadIdx.x;
+  const int lc = (tid & 31) * 2, lr = tid >> 5;  // a column pair, and rows lr + 8 k
+  for (int q = 0; q < 4; ++q) {
+    const int qa = q >> 1, qb = q & 1;
+    if (ti == tj && qa > qb) continue;  // the lower quarter of a diagonal tile (uniform in the work-group)
+    const int64_t i0 = ti * PC_T + qa * PC_Q, j0 = tj * PC_T + qb * PC_Q;
+    if (i0 >= N || j0 >= N) continue;
+    __syncthreads();  // the previous quarter's LDS reads are done
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {  // rows j of Kinv, columns i: the lower triangle only (j >= i)
+      const int jr = lr + 8 * k;
+      const int64_t j = j0 + jr, i = i0 + lc;
+      double x0 = 0.0, x1 = 0.0;
+      if (j < N) {
+        const double* p = Kinv + j * ldk + i;
+        if (i + 1 < N && i + 1 <= j) {
+          const v2d v = *reinterpret_cast<const v2d*>(p);
+          x0 = v.x;
+          x1 = v.y;
+        } else {
+          if (i < N && i <= j) x0 = p[0];
+          if (i + 1 < N && i + 1 <= j) x1 = p[1];
+        }
+      }
+      s[lc][jr] = x0;
+      s[lc + 1][jr] = x1;
+    }
+    __syncthreads();
+    const int64_t j = j0 + lc;
+    const double tj0 = j < N ? tau[grp ? grp[j] : 0] : 0.0;
+    const double tj1 = j + 1 < N ? tau[grp ? grp[j + 1] : 0] : 0.0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {  // rows i of A, columns j: the upper triangle only (j >= i)
+      const int ir = lr + 8 * k;
+      const int64_t i = i0 + ir;
+      if (i >= N) continue;
+      const double tv = tau[grp ? grp[i] : 0];
+      double v0 = -tv * s[ir][lc] * tj0, v1 = -tv * s[ir][lc + 1] * tj1;
+      const double dg = tv + (d ? d[i] : 0.0) + jitter;
+      if (i == j) v0 += dg;
+      if (i == j + 1) v1 += dg;
+      double* o = A + i * lda + j;
+      const bool w0 = j < N && j >= i, w1 = j + 1 < N && j + 1 >= i;
+      if (w0 && w1) {
+        const v2d v = {v0, v1};
+        *reinterpret_cast<v2d*>(o) = v;
+      } else {
+        if (w0) o[0] = v0;
+        if (w1) o[1] = v1;
+      }
+    }
+  }
+}
+
+}  // namespace
+
+hipError_t gpp_launch_post_cov_train(hipStream_t s, const double* Kinv, int64_t ldk, int64_t N, const double* tau, const int32_t* grp,
+                                     const double* d, double jitter, double* A, int64_t lda) {
+  if (N <= 0) return hipSuccess;
+  const int64_t nt = (N + PC_T - 1) / PC_T;
+  hipLaunchKernelGGL(gpp_post_cov_tile, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, s, Kinv, ldk, N, tau, grp, d, jitter, A,
+                     lda);
+  return hipGetLastError();
+}

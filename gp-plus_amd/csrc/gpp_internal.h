@@ -287,6 +287,9 @@ hipError_t gpp_launch_kernel_build(hipStream_t s, const double* U, int64_t N, in
                                    int64_t sU = 0, int64_t sK = 0);
 hipError_t gpp_launch_cross_kernel(hipStream_t s, const double* Ua, int64_t Ma, const double* Ub, int64_t Nb, int D,
                                    const double* w, const double* sf2, int kind, int d_split, double* Kab, int64_t ld);
+// A(upper) = diag(tau[grp] + d + jitter) - T Kinv T from Kinv's lower triangle (gpp_post_cov_train; A may be Kinv)
+hipError_t gpp_launch_post_cov_train(hipStream_t s, const double* Kinv, int64_t ldk, int64_t N, const double* tau, const int32_t* grp,
+                                     const double* d, double jitter, double* A, int64_t lda);
 
 // ---- reductions (gpp_reduce.hip) --------------------------------------------------------------
 // batch > 1 (all reductions): matrices at + b*sT, vectors at + b*sv (sv even, >= N), out3 at + 3*b

@@ -17,6 +17,19 @@ class GP(Module):
     pass
 
 
+def _same_inputs(inputs, train_inputs) -> bool:
+    """True when the eval-mode inputs are the training inputs: the same tensors, or equal ones (``torch.equal`` waits for the
+    GPU, so it is asked only when a draw needs the answer)."""
+    if train_inputs is None or len(inputs) != len(train_inputs):
+        return False
+    for x, t in zip(inputs, train_inputs):
+        if x is t:
+            continue
+        if not (torch.is_tensor(x) and x.shape == t.shape and x.dtype == t.dtype and x.device == t.device and torch.equal(x, t)):
+            return False
+    return True
+
+
 class ExactGP(GP):
     def __init__(self, train_inputs, train_targets, likelihood):
         if train_inputs is not None and torch.is_tensor(train_inputs):
@@ -153,7 +166,19 @@ class ExactGP(GP):
                 gctx.gemm(0, 1, M, M, V.shape[1], -1.0, V, V, 1.0, Kss)
                 return Kss
 
-            return MultivariateNormal(pred_mean, DenseCovariance(lambda: var_and_v()[0], full_cov, n=Us.shape[0]))
+            train_inputs = self.train_inputs
+
+            def cov_upper(A, added, jitter, Us=Us, spec=cache.spec, cache=cache):
+                # what rsample factors: at the training inputs Sigma = T - T Ky^-1 T (+ the likelihood's diagonal), which does
+                # not lose the O(tau) result to a difference of O(sf2) terms and needs no V; elsewhere Kss - V V^T
+                from ..linalg import predictive_cov_upper, train_post_cov_upper
+
+                if not kwargs and _same_inputs(inputs, train_inputs):
+                    return train_post_cov_upper(cache, added, jitter, out=A)
+                return predictive_cov_upper(Us, spec, var_and_v()[1], added, jitter, out=A)
+
+            return MultivariateNormal(pred_mean, DenseCovariance(lambda: var_and_v()[0], full_cov, n=Us.shape[0],
+                                                                 upper_builder=cov_upper))
 
     def _differentiable_posterior(self, inputs, kwargs):
         """The eval-mode call under ``settings.differentiable_predictions``: the same factor cache and the same numbers as the
@@ -190,4 +215,8 @@ class ExactGP(GP):
                                       "(only its mean and variance carry gradients); predict without "
                                       "settings.differentiable_predictions for covariance_matrix")
 
-        return MultivariateNormal(pred_mean, DenseCovariance(var, full_cov, n=Us.shape[0]))
+        def no_draws(A, added, jitter):
+            raise NotImplementedError("sampling from a differentiable prediction is not available (only its mean and variance "
+                                      "carry gradients); sample without settings.differentiable_predictions")
+
+        return MultivariateNormal(pred_mean, DenseCovariance(var, full_cov, n=Us.shape[0], upper_builder=no_draws))

@@ -27,7 +27,8 @@ from .errors import NanError, NotPSDError
 from . import settings
 
 __all__ = ["KernelSpec", "exact_mll", "ExactMLLFunction", "EvalWorkspace", "dense_kernel", "cross_kernel",
-           "FactorCache", "factorize", "dense_log_prob", "predict_mean", "predict_var"]
+           "FactorCache", "factorize", "dense_log_prob", "predict_mean", "predict_var", "predictive_cov_upper",
+           "train_post_cov_upper", "mvn_root", "mvn_draw"]
 
 
 @dataclass
@@ -531,3 +532,96 @@ def dense_log_prob(cov: torch.Tensor, diff: torch.Tensor) -> torch.Tensor:
     out3 = torch.empty(3, dtype=torch.float64, device=dev)
     gctx.mll_reduce(A, Li, _as_f64(diff, dev), z, out3)
     return out3[2].clone()
+
+
+# ---------------------------------------------------------------------------------------------------
+# sampling (MultivariateNormal.rsample, GP_Plus.sample_y — models/gp_plus.py:985-998): a covariance built straight into the upper
+# triangle of a square buffer, its Cholesky factor U (Sigma = U^T U) with the jitter schedule of ``dense_log_prob``, and draws
+# loc + Z U.  No autograd: gradients through draws are not offered.
+# ---------------------------------------------------------------------------------------------------
+@torch.no_grad()
+def predictive_cov_upper(Us: torch.Tensor, spec: KernelSpec, V: torch.Tensor, d: Optional[torch.Tensor] = None,
+                         jitter: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K(Us, Us) + diag(d) + jitter I - V V^T (V = K_*N L^-T from ``predict_from_cache``) in the UPPER triangle of ``out``: the
+    kernel build writes the upper tiles only and the MFMA GEMM subtracts V V^T on the upper triangle only (c_tri = 2), half the
+    flops of the full square that ``covariance_matrix`` forms."""
+    dev = Us.device
+    gctx = get_context(dev)
+    M = Us.shape[0]
+    A = square_buffer(M, dev) if out is None else out
+    tau = grp = None
+    if d is not None:  # the added diagonal as M noise groups of one point each
+        tau = _as_f64(d.reshape(-1), dev)
+        grp = torch.arange(M, dtype=torch.int32, device=dev)
+    with _stage("pred_cov_build"):
+        gctx.kernel_build(_as_f64(Us, dev), _as_f64(spec.w, dev), _as_f64(spec.sf2.reshape(1), dev), tau, grp, A, jitter=jitter,
+                          kind=spec.kind, d_split=spec.d_split, uplo=UPLO_UPPER)
+    with _stage("pred_cov_vvt"):
+        gctx.gemm(0, 1, M, M, V.shape[1], -1.0, V, V, 1.0, A, c_tri=2)
+    return A
+
+
+@torch.no_grad()
+def train_post_cov_upper(cache: FactorCache, d: Optional[torch.Tensor] = None, jitter: float = 0.0,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The same covariance when the test points ARE the training points: Sigma = T - T Ky^-1 T (+ diag(d) + jitter I), T the
+    training noise (plus the cache's own jitter, so that it equals the general route's K - K (Ky + jI)^-1 K).  Ky^-1 is one LAUUM of
+    the cached inverse factor into ``out``, which gpp_post_cov_train then overwrites in place; cache.L / cache.Linv stay as they are."""
+    cache.refresh()
+    gctx = cache.gctx
+    dev = cache.U.device
+    N = cache.U.shape[0]
+    A = square_buffer(N, dev) if out is None else out
+    tau, grp, _ = cache._refactor
+    if cache.jitter:
+        tau = tau + cache.jitter
+    with _stage("sample_lauum"):
+        gctx.lauum(cache.Linv, A)
+    with _stage("post_cov_train"):
+        gctx.post_cov_train(A, tau, grp, None if d is None else _as_f64(d.reshape(-1), dev), A, jitter=jitter)
+    return A
+
+
+@torch.no_grad()
+def mvn_root(build_upper, n: int, device) -> Tuple[torch.Tensor, float]:
+    """Upper Cholesky factor U of a covariance that ``build_upper(A, jitter)`` writes into the upper triangle of the n x n buffer A
+    (with ``jitter`` added to its diagonal), under the jitter schedule of ``dense_log_prob``: 0, then cholesky_jitter * 10^i, then
+    ``NotPSDError``; a panel time-out repeats the attempt.  Returns (U, jitter); U's strict lower triangle is not part of it."""
+    dev = torch.device(device)
+    gctx = get_context(dev)
+    A, Li, T = square_buffer(n, dev), square_buffer(n, dev), square_buffer(n, dev)
+    info = torch.zeros(1, dtype=torch.int32, device=dev)
+    jitters = [0.0] + [settings.cholesky_jitter.value() * (10 ** i) for i in range(settings.cholesky_max_tries.value())]
+    prev, attempts = 0.0, list(jitters)
+    while attempts:
+        jit = attempts.pop(0)
+        build_upper(A, jit)
+        with _stage("sample_potrf"):
+            gctx.potrf(A, Li, info, T)
+        status = int(info.item())
+        if panel_timed_out(gctx, status):
+            attempts.insert(0, jit)  # the same attempt again, without the cooperative panel
+            continue
+        if status == 0:
+            if jit > 0:
+                warnings.warn(f"A not p.d., added jitter of {jit:.1e} to the diagonal", RuntimeWarning)
+            return A, jit
+        prev = jit
+    raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {prev:.1e}.")
+
+
+@torch.no_grad()
+def mvn_draw(U: torch.Tensor, loc: torch.Tensor, Z: torch.Tensor) -> torch.Tensor:
+    """loc + Z U for Z (S x M, fp64) and the upper factor U of ``mvn_root``: S draws of N(loc, U^T U), one NN GEMM against U's upper
+    triangle (b_mask = 1, K range cut at each column tile's end)."""
+    dev = U.device
+    gctx = get_context(dev)
+    S, M = Z.shape
+    ld = max(16, (M + 15) // 16 * 16)
+    Zp = torch.empty((S, ld), dtype=torch.float64, device=dev)[:, :M]
+    Zp.copy_(Z)
+    out = torch.empty((S, ld), dtype=torch.float64, device=dev)[:, :M]
+    out.copy_(_as_f64(loc, dev).expand(S, M))
+    if S > 0 and M > 0:
+        gctx.gemm(0, 0, S, M, M, 1.0, Zp, U, 1.0, out, b_mask=1, khi_mode=2)
+    return out

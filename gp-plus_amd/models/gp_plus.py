@@ -10,8 +10,9 @@ What runs differently from the reference, by design:
     gp_plus.py:532-534) become one cached integer index + gather;
   * the model is placed on ``device`` at construction (the reference moves it in ``fit``, gp_plus.py:562).
 Out of scope (raise ``NotImplementedError``): probabilistic embedding / calibration (stochastic multi-pass
-ensembles), neural-network and polynomial mean functions, plotting, Sobol indices, botorch glue, and gradients through the
-joint predictive covariance (``predict_with_grad`` differentiates the mean and the variance diagonal).
+ensembles), neural-network and polynomial mean functions, plotting (``visualize_latent``, ``sample_y(plot=True)``), Sobol
+indices, botorch glue, gradients through the joint predictive covariance (``predict_with_grad`` differentiates the mean and
+the variance diagonal) and gradients through posterior draws (``sample_y`` returns draws without an autograd graph).
 """
 import math
 import warnings
@@ -429,6 +430,26 @@ class GP_Plus(GPR):
                     key = n
         print(params[key])
         return params[key]
+
+    def sample_y(self, size=1, X=None, plot=False):
+        """gp_plus.py:985-998: ``size`` draws of ``likelihood(self(X))`` in eval mode, shape (size, len(X)), in the scaled
+        target space (no un-scaling), at the training inputs by default.  At the training inputs the covariance is built as
+        T - T Ky^-1 T + diag(noise) from the cached factor (gpp_post_cov_train); elsewhere as Kss + diag(noise) - V V^T."""
+        if plot:
+            raise NotImplementedError("plotting (visual/) is out of scope of this build; plot the returned draws instead")
+        X = self.train_inputs[0] if X is None else data_type_check(X).to(self.tkwargs['device'])
+        self.eval()
+        lik = self.likelihood
+        swap = hasattr(lik, 'fidel_indices')
+        if swap:
+            saved, lik.fidel_indices = lik.fidel_indices, X[:, -1]  # the points' own sources, as evaluation() does
+        try:
+            with torch.no_grad():
+                out = lik(self(X))
+                return out.sample(sample_shape=torch.Size([size]))
+        finally:
+            if swap:
+                lik.fidel_indices = saved
 
     def get_latent_space(self):
         if len(self.qual_dict_list) > 0:

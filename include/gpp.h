@@ -136,6 +136,17 @@ int gpp_trtri(gpp_handle_t h, const double* U, int64_t N, int64_t ld, double* Li
 /* Kinv(lower) = Linv^T Linv.  With gpp_trtri this is K7's "K_y^-1" (ATen cholesky_backward, optim/mll_torch.py:117). */
 int gpp_lauum(gpp_handle_t h, const double* Linv, int64_t N, int64_t ldi, double* Kinv, int64_t ldk);
 
+/* Posterior covariance at the TRAINING inputs (models/gp_plus.py:985-998 sample_y: likelihood(self(train_x)).sample()), built into
+ * the upper triangle of A in the layout gpp_potrf_ws factors:
+ *   A[i,j] = -tau[grp[i]] Kinv[j,i] tau[grp[j]] + (i == j)(tau[grp[i]] + d[i] + jitter)      j >= i
+ * from Kinv = Ky^-1 (LOWER triangle, as gpp_lauum leaves it; Ky = K + diag(tau[grp])): with that T = diag(tau[grp]),
+ * K - K Ky^-1 K = T - T Ky^-1 T, and the likelihood's diagonal d on top (d = tau[grp]: 2T - T Ky^-1 T, eigenvalues in
+ * [min tau, 2 max tau)).  tau: S doubles; grp: N int32 or NULL (group 0); d: N doubles or NULL (none).  Only the upper
+ * triangle of A is written.  A may be Kinv itself (same ld): a tile of the upper triangle is written from the mirrored tile
+ * of the lower one, and the diagonal is read before it is written, so the strict lower triangle of Kinv survives. */
+int gpp_post_cov_train(gpp_handle_t h, const double* Kinv, int64_t N, int64_t ldk, const double* tau, const int32_t* grp, int S,
+                       const double* d, double jitter, double* A, int64_t lda);
+
 /* Trailing update of a block-row-cyclic sharded factorisation, one launch per rank and step:
  *   C(upper triangle of Nt x Nt) -= Urow^T Urow   on the block rows (height nb, a multiple of 128) this rank owns,
  * block row i of C (0-based) being global block row first_block + i, owned when (first_block + i) % nranks == rank.
