@@ -16,7 +16,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, settings
 from ._lib import GppError, check
 
 KIND_RBF, KIND_MATERN32, KIND_MATERN52 = 0, 1, 2
@@ -133,8 +133,8 @@ class GppContext:
         with torch.cuda.device(self.index):
             check(self.lib.gpp_create(ctypes.byref(h), self.index), "gpp_create")
         self.h = h
-        self.coop_panel = os.environ.get("GPP_COOP_PANEL", "1") != "0"  # mirrors the handle's GPP_OPT_COOP_PANEL
-        self.dag_sched = os.environ.get("GPP_DAG_SCHED", "1") != "0"
+        self.coop_panel = settings.ENV_COOP_PANEL  # mirrors the handle's GPP_OPT_COOP_PANEL
+        self.dag_sched = settings.ENV_DAG_SCHED
         # kernels that wait for each other across launches cannot run when dispatches are serialised: they would only time out
         if any(os.environ.get(v, "0") not in ("", "0") for v in ("HIP_LAUNCH_BLOCKING", "AMD_SERIALIZE_KERNEL", "CUDA_LAUNCH_BLOCKING")):
             self.set_option(OPT_DAG_SCHED, 0)

@@ -25,6 +25,28 @@
 #include <cstring>
 #include <new>
 
+const GppEnv& gpp_env() {
+  static const GppEnv env = [] {
+    auto num = [](const char* name, long long unset) { const char* v = getenv(name); return v ? atoll(v) : unset; };
+    GppEnv e;
+    e.coop_panel = num("GPP_COOP_PANEL", 1) != 0;
+    e.dag_sched = num("GPP_DAG_SCHED", 1) != 0;
+    e.dag_phased = num("GPP_DAG_PHASED", 0) != 0;
+    e.shard_list = num("GPP_SHARD_LIST", 1) != 0;
+    e.shard_workers = (int)num("GPP_SHARD_WORKERS", 0);
+    e.shard_fill = (int)num("GPP_SHARD_FILL", -1);
+    e.shard_timeout_ms = num("GPP_SHARD_TIMEOUT_MS", 60000);
+    const int64_t cols = num("GPP_SHARD_PIECE_COLS", 8192);
+    e.shard_piece_cols = cols <= 0 ? (int64_t)0 : std::max<int64_t>(GPP_TILE, cols / GPP_TILE * GPP_TILE);
+    e.sharded_force_collectives = num("GPP_SHARDED_FORCE_COLLECTIVES", 0) != 0;
+    e.exec_verbose = getenv("GPP_EXEC_VERBOSE") != nullptr;
+    e.dag_dump = (int)num("GPP_DAG_DUMP", 0);
+    e.dag_check_verbose = getenv("GPP_DAG_CHECK_VERBOSE") != nullptr;
+    return e;
+  }();
+  return env;
+}
+
 namespace {
 
 constexpr int NBLK = GPP_TILE;
@@ -103,8 +125,7 @@ hipError_t potrf_blk(const Ctx& c, int64_t o, int64_t n) {
     if (e != hipSuccess) return e;
     GemmArgs u = mk(Bp, c.ld, Bp, c.ld, c.A + (oo + nb) * c.ld + (oo + nb), c.ld, rem, rem, nb, -1.0, 1.0);
     u.c_lower = 2;
-    static const int ut = getenv("GPP_BLK_UPD_TILE") ? atoi(getenv("GPP_BLK_UPD_TILE")) : 32;  // K = 128: small tiles win (measured)
-    e = gpp_launch_gemm(c.s, 2, u, 1, ut, ut);
+    e = gpp_launch_gemm(c.s, 2, u, 1, 32, 32);  // K = 128: small tiles win (measured)
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
@@ -138,8 +159,7 @@ hipError_t potrf_rec(const Ctx& c, int64_t o, int64_t n) {
   if (n <= 0) return hipSuccess;
   if (n <= NBLK)
     return gpp_launch_leaf(c.s, c.A + o * c.ld + o, c.ld, c.Li + o * c.ldi + o, c.ldi, (int)n, c.info, (int)o);
-  static const int64_t blk_max = getenv("GPP_BLK_MAX") ? atol(getenv("GPP_BLK_MAX")) : BLK_MAX;  // experiment knob
-  if (n <= blk_max) return potrf_blk(c, o, n);
+  if (n <= BLK_MAX) return potrf_blk(c, o, n);
   const int64_t n1 = split(n), n2 = n - n1;
   hipError_t e = potrf_rec(c, o, n1);
   if (e != hipSuccess) return e;
@@ -155,15 +175,11 @@ hipError_t potrf_rec(const Ctx& c, int64_t o, int64_t n) {
 }
 
 // Cooperative panel (gpp_leaf.hip): the block [o, o+n) factored AND inverted by one launch — used for the look-ahead's diagonal
-// blocks and for a whole small matrix.  GPP_COOP_PANEL=0 restores the chain of leaf-step launches + pair merges (experiment knob).
+// blocks and for a whole small matrix.  GPP_COOP_PANEL=0 (or GPP_OPT_COOP_PANEL = 0) restores the chain of leaf-step launches + pair
+// merges: the reference path of the tests.
 constexpr int64_t PANEL_MAX_N = 2048;
-inline bool panel_enabled() {
-  static const bool on = !(getenv("GPP_COOP_PANEL") && atoi(getenv("GPP_COOP_PANEL")) == 0);
-  return on;
-}
 inline bool panel_fits(const gpp_handle_s* h, int64_t n) {
-  static const int64_t nmax = getenv("GPP_PANEL_MAX_N") ? atol(getenv("GPP_PANEL_MAX_N")) : PANEL_MAX_N;  // experiment knob
-  return h->coop_panel && h->panel_flags && h->ncu >= 2 && n > 2 * NBLK && n <= nmax && (n + NBLK - 1) / NBLK <= gpp_panel_max_leaves();
+  return h->coop_panel && h->panel_flags && h->ncu >= 2 && n > 2 * NBLK && n <= PANEL_MAX_N && (n + NBLK - 1) / NBLK <= gpp_panel_max_leaves();
 }
 // The cooperative panel of an n x n diagonal block whose own addresses are c.A / c.Li (o: its first row, for the status word).
 hipError_t launch_panel_at(gpp_handle_s* h, const Ctx& c, int64_t o, int64_t n, int max_wgs) {
@@ -207,8 +223,7 @@ hipError_t trtri_level(hipStream_t st, const double* U, int64_t ld, double* Linv
     g1.b_mask = 2; g1.klo_mode = 2; g1.col_major = 1;  // K range depends on the column tile: keep columns together
     g1.sA = pstride_U; g1.sB = pstride_I; g1.sC = pstride_T;
     g1.batch2 = mbatch; g1.zA = msU; g1.zB = msLi; g1.zC = msT;  // independent matrices (batched evaluation)
-    static const bool bf = !(getenv("GPP_BATCH_FAST") && atoi(getenv("GPP_BATCH_FAST")) == 0);  // experiment knob
-    g1.batch_fast = bf;  // the pairs' tiles of equal K run together: the launch ends on every pair's short tiles
+    g1.batch_fast = 1;  // the pairs' tiles of equal K run together: the launch ends on every pair's short tiles
     hipError_t e = gpp_launch_gemm(st, 2, g1, batch, g1_tile, g1_tile);
     if (e != hipSuccess) return e;
     if (before_g2) {  // W22 comes from another stream (the look-ahead's bordering: the first product does not need it)
@@ -222,7 +237,7 @@ hipError_t trtri_level(hipStream_t st, const double* U, int64_t ld, double* Linv
     g2.sA = pstride_I; g2.sB = pstride_T; g2.sC = pstride_I;
     g2.C2 = Linv + o * ldi + (o + s); g2.ldc2 = ldi; g2.sC2 = pstride_I;
     g2.batch2 = mbatch; g2.zA = msLi; g2.zB = msT; g2.zC = msLi; g2.zC2 = msLi;
-    g2.batch_fast = bf;
+    g2.batch_fast = 1;
     return gpp_launch_gemm(st, 2, g2, batch);
   };
   // full pairs: batched over maximal runs of pairs that still need merging
@@ -252,9 +267,15 @@ hipError_t trtri_level(hipStream_t st, const double* U, int64_t ld, double* Linv
 // Stream priorities alone do not help: the leaf needs a CU to itself (its register allocation does not fit beside a GEMM
 // work-group), so while an update saturates every CU it is not placed until the update drains (measured: 5.8 ms).  The
 // two streams therefore get DISJOINT CU sets through CU masks (see the comment at the mask below for what that costs).
-constexpr int PANEL_CUS_DEFAULT = 32;
+constexpr int PANEL_CUS = 32;
 constexpr int64_t BORDER_MAX_N = 11264;  // largest N whose inverse is built by bordering inside the look-ahead
 constexpr int64_t BORDER_MIN_N = 3840;   // with bordering the look-ahead already wins from here (4.16 vs 4.32 ms per evaluation; 3712: 4.10 vs 4.03)
+constexpr int64_t BORDER_FULL_MIN_N = 9216;  // from here the bordering products run on the stream without a CU mask (potrf_lookahead)
+// entries of the trailing update's upper triangle that run on the CU-masked stream beside the next diagonal block (4.5e7 .. 9e7
+// equal before the panel kernel; 2e8 loses the gain, 1.5e7 half of it.  Round 3, with the panel kernel — that block now takes 0.6
+// instead of ~1 ms — 3e7 against 6e7, twice each: potrf 15.28 vs 15.76 ms at N = 12288, 51.2-51.5 vs 51.5-51.8 at 20000, 154.0-154.5
+// vs 156.0-157.6 at 30000, 1139 vs 1144-1147 at 60000)
+constexpr int64_t SPLIT_ELEMS = 30000000;
 hipError_t ensure_streams(gpp_handle_s* h) {
   if (h->cu_split < 0) {
     hipDeviceProp_t prop;
@@ -262,12 +283,10 @@ hipError_t ensure_streams(gpp_handle_s* h) {
     if (e != hipSuccess) return e;
     const int ncu = prop.multiProcessorCount;
     h->cu_split = 0;
-    int PANEL_CUS = PANEL_CUS_DEFAULT;
-    if (const char* e = getenv("GPP_PANEL_CUS")) PANEL_CUS = atoi(e);  // experiment knob
-    if (ncu >= 4 * PANEL_CUS && ncu <= 1024 && PANEL_CUS > 0 && !getenv("GPP_NO_CU_SPLIT")) {
+    if (ncu >= 4 * PANEL_CUS && ncu <= 1024) {
       uint32_t mp[32] = {0}, mu[32] = {0};
       const int words = (ncu + 31) / 32;
-      // The FIRST mask bits.  Measured (tools/attic/gemm_update_probe.py with GPP_GEMM_ON_UPD=1): a K = 1024 trailing update runs
+      // The FIRST mask bits.  Measured (a K = 1024 product on the CU-masked update stream): a K = 1024 trailing update runs
       // at 62.3 TFLOP/s on all 256 CUs and at 54.3 / 54.8 / 54.7 with 2 / 16 / 32 CUs masked out — the loss is a step of
       // 12.5 %, not proportional.  Consecutive mask bits fall in different XCDs and then in different shader engines of an
       // XCD; work-groups are dealt round-robin to XCDs and to their 4 shader engines regardless of the CUs each has left, so
@@ -297,7 +316,7 @@ hipError_t ensure_streams(gpp_handle_s* h) {
       // NOT silent: without disjoint CU sets a leaf waits for a CU until the co-running update drains (measured: 5.8 ms per
       // diagonal block, 90 instead of ~55 ms per factorisation at N = 20000)
       static bool warned = false;
-      if (!warned && !getenv("GPP_NO_CU_SPLIT")) {
+      if (!warned) {
         warned = true;
         fprintf(stderr, "libgpp_hip: hipExtStreamCreateWithCUMask unavailable on device %d (%d CUs): the look-ahead factorisation "
                         "falls back to priority streams and will be markedly slower\n", h->device, ncu);
@@ -314,22 +333,10 @@ hipError_t ensure_streams(gpp_handle_s* h) {
     }
   }
   if (!h->full_stream) {
-    // Experiment knob GPP_FULL_PRIO=1: LOWEST priority for the stream without a CU mask.  The bulk of a trailing update overlaps
-    // the start of the panel after next, and its work-groups also run on the panel's CUs; with equal priorities the panel's small
-    // launches queue for slots behind the bulk's thousands of tiles (traced: a 28-work-group panel solve took 1.57 ms).  Measured
-    // A/B, twice each: potrf 52.26 / 52.07 -> 51.73 / 51.48 ms at N = 20000; no change at 30000.  NOT the default: with the
-    // priority stream `rocprofv3 --kernel-trace --stats -- python3 bench.py` never returned on this stack (ROCm 7.2.0; the plain
-    // run is fine) — a 0.4 % gain is not worth a benchmark that cannot be profiled.
-    static const int prio = getenv("GPP_FULL_PRIO") ? atoi(getenv("GPP_FULL_PRIO")) : 0;
-    hipError_t e;
-    if (prio) {
-      int lo = 0, hi = 0;
-      e = hipDeviceGetStreamPriorityRange(&lo, &hi);
-      if (e != hipSuccess) return e;
-      e = hipStreamCreateWithPriority(&h->full_stream, hipStreamNonBlocking, lo);
-    } else {
-      e = hipStreamCreateWithFlags(&h->full_stream, hipStreamNonBlocking);
-    }
+    // Default priority.  (LOWEST priority for this stream, so that the panel's small launches do not queue behind the bulk's tiles,
+    // measured 0.4 % faster at N = 20000 and even at 30000 — and `rocprofv3 --kernel-trace` of the benchmark never returned with it
+    // on ROCm 7.2.0: not worth a benchmark that cannot be profiled.  profiles/EXPERIMENTS.md.)
+    hipError_t e = hipStreamCreateWithFlags(&h->full_stream, hipStreamNonBlocking);
     if (e != hipSuccess) return e;
   }
   while (h->n_events < 16) {
@@ -363,86 +370,51 @@ hipError_t potrf_lookahead(gpp_handle_s* h, const Ctx& cm, int64_t N, int64_t NB
   Ctx cp = cm, cu = cm;
   cp.s = h->panel_stream;
   cu.s = h->upd_stream;
-  const char* env_nb = getenv("GPP_LOOKAHEAD_NB");  // experiment knob: "big,small,threshold"
-  static const int64_t border_max_x = getenv("GPP_BORDER_MAX") ? atol(getenv("GPP_BORDER_MAX")) : BORDER_MAX_N;
   hipEvent_t ev = next_event(h);
   HIP_TRY(hipEventRecord(ev, cm.s));  // inputs (kernel build) are ready
   HIP_TRY(hipStreamWaitEvent(cp.s, ev, 0));
   HIP_TRY(hipStreamWaitEvent(cu.s, ev, 0));
-  const int64_t o_begin = 0;
-  // Round 1 measured 1024 above / 512 below 6144 remaining rows best (70.6 vs 71.7 ms for 1024 flat at N = 20000); with the panel
-  // kernel a 1024-row block costs 0.58 ms where two 512-row blocks cost 2 x (0.29 + 0.07 ms hand-off), and 1024 flat wins (means
-  // of 3: potrf 15.50 -> 15.22 ms at N = 12288, 25.27 -> 24.87 at 15000, 51.84 -> 51.46 at 20000, 155.3 -> 155.3 at 30000).
-  // (The bordering range chooses its own height below.)
-  long nb_big = NB, nb_small = NB, nb_thresh = 0;
-  if (env_nb) sscanf(env_nb, "%ld,%ld,%ld", &nb_big, &nb_small, &nb_thresh);
   // bordering pays while the factorisation is bound by its chain of diagonal blocks (measured: 9.6 -> 7.8 ms per
   // evaluation at N = 6144, 16.3 -> 14.0 at 8192, 26.5 -> 24.4 at 10000, a tie at 12288, 147 -> 156 at 20000 where the
   // throughput CUs have no idle time to give and the long-K bordering products are slower than batched pair merges)
-  const int64_t border_max = border_max_x;  // knob GPP_BORDER_MAX
-  const bool border = T != nullptr && N <= border_max;
-  // the first product of a bordering step needs neither this block's factor nor its inverse: it is issued before them
-  // and only the second waits for D (measured: 4.54 -> 4.44 ms per evaluation at 4096, 13.7 -> 13.4 at 8192, even above)
-  static const bool border_early = !(getenv("GPP_BORDER_EARLY") && atoi(getenv("GPP_BORDER_EARLY")) == 0);  // experiment knob
-  // (measured: potrf 58.2 -> 56.4 ms at N = 20000, 28.4 -> 27.3 at 15000, 17.0 -> 16.4 at 10000)
-  static const bool merge_upd_on = !(getenv("GPP_MERGE_UPD") && atoi(getenv("GPP_MERGE_UPD")) == 0);  // experiment knob
-  static const bool split_chain = !(getenv("GPP_SPLIT_CHAIN") && atoi(getenv("GPP_SPLIT_CHAIN")) == 0);  // experiment knob
+  const bool border = T != nullptr && N <= BORDER_MAX_N;
   // Round 4: from N = 9216 the inverse's bordering products run on the stream WITHOUT a CU mask, i.e. also on the panel's 32 CUs
   // while those idle (60 % of the time at N = 10 000, profiles/r04_timeline_n10000.txt).  Measured A/B on one box, potrf + inverse:
   // 16.08 -> 15.68 ms at N = 10 000, 21.03 -> 20.54 at 11 264, even at 8192, a LOSS at 6144 (4.99 -> 5.23: the chain matters more
-  // there and a long bordering tile on a panel CU holds the next diagonal block up).  GPP_BORDER_FULL_MIN moves the threshold.
-  static const int64_t border_full_min = getenv("GPP_BORDER_FULL_MIN") ? atol(getenv("GPP_BORDER_FULL_MIN")) : 9216;
-  hipStream_t cf = (T != nullptr && N <= border_max_x && N >= border_full_min) ? h->full_stream : h->fill_stream;
-  static const int64_t border_t128 = getenv("GPP_BORDER_T128") ? atol(getenv("GPP_BORDER_T128")) : 640;  // experiment knob
+  // there and a long bordering tile on a panel CU holds the next diagonal block up).
+  hipStream_t cf = (border && N >= BORDER_FULL_MIN_N) ? h->full_stream : h->fill_stream;
   hipEvent_t R_prev = nullptr;  // row solves of the steps before the current one are complete
   // The CU mask costs the throughput stream 12.5 % (see ensure_streams) although the panel needs its CUs only while it
   // factors the next diagonal block (~1 ms of a 6.7 ms step at N = 20000).  The trailing update is therefore split: the
   // first rows run on the masked stream beside the panel, the bulk waits for the panel (event D) and runs on a stream
-  // WITHOUT a mask.  Measured: potrf 56.6 -> 55.5 ms at N = 20000, 173.3 -> 165 ms at 30000; the masked part is sized in
-  // entries of the upper triangle (4.5e7 .. 9e7 equal; 2e8 loses the gain, 1.5e7 half of it).
-  static const bool split_upd_on = !(getenv("GPP_SPLIT_UPD") && atoi(getenv("GPP_SPLIT_UPD")) == 0);  // experiment knob
-  // (round 3, with the panel kernel — the next diagonal block now takes 0.6 instead of ~1 ms: 3e7 against 6e7 entries, twice each:
-  //  potrf 15.28 vs 15.76 ms at N = 12288, 51.2-51.5 vs 51.5-51.8 at 20000, 154.0-154.5 vs 156.0-157.6 at 30000, 1139 vs 1144-1147 at 60000)
-  static const int64_t split_elems = getenv("GPP_SPLIT_ELEMS") ? atol(getenv("GPP_SPLIT_ELEMS")) : 30000000;
-  const bool split_upd = split_upd_on && !border && h->cu_split == 1;
+  // WITHOUT a mask.  Measured: potrf 56.6 -> 55.5 ms at N = 20000, 173.3 -> 165 ms at 30000.
+  const bool split_upd = !border && h->cu_split == 1;
   hipStream_t cx = h->full_stream;
   struct { bool on; GemmArgs g; hipEvent_t rows_ready; int64_t rows_masked; } pend{false, GemmArgs{}, nullptr, 0};
   hipEvent_t be_wait = nullptr;  // end of the previous step's unmasked part, not yet waited for by the throughput stream
-  // (measured: potrf 55.3 -> 54.0 ms at N = 20000, 162.8 -> 161.1 at 30000)
-  static const bool defer_be = !(getenv("GPP_DEFER_BE") && atoi(getenv("GPP_DEFER_BE")) == 0);  // experiment knob
-  // with bordering the block height matters little; one height per N measured best (512 up to ~7000 rows: 7.5 vs 8.3 ms per
-  // evaluation at 6144; 1024 above: 23.3 vs 24.2 ms at 10000)
-  if (border && !env_nb) {
-    nb_small = NB / 2;
-    nb_thresh = (N <= 7168) ? N + 1 : 0;
-  }
-  for (int64_t o = o_begin, nb = 0; o < N; o += nb) {
-    // tall block rows while the trailing update is long enough to hide their diagonal factorisation, shorter after
-    const int64_t want = (N - o >= nb_thresh) ? nb_big : nb_small;
-    nb = std::min(want, N - o);
+  // Block rows of NB = 1024 (with the panel kernel a 1024-row block costs 0.58 ms where two 512-row blocks cost 2 x (0.29 + 0.07 ms
+  // hand-off): means of 3, potrf 15.50 -> 15.22 ms at N = 12288, 25.27 -> 24.87 at 15000, 51.84 -> 51.46 at 20000).  With bordering
+  // the height matters little; one height per N measured best (512 up to ~7000 rows: 7.5 vs 8.3 ms per evaluation at 6144; 1024
+  // above: 23.3 vs 24.2 ms at 10000)
+  const int64_t bh = (border && N <= 7168) ? NB / 2 : NB;
+  for (int64_t o = 0, nb = 0; o < N; o += nb) {
+    nb = std::min(bh, N - o);
     const int64_t rem = N - o - nb;
     const bool coop = T != nullptr && panel_fits(h, nb);
     if (coop) {
       // factor + complete inverse of the diagonal block in ONE cooperative launch on the panel's CUs
       HIP_TRY(launch_panel(h, cp, o, nb, h->cu_split == 1 ? h->panel_cus : std::min(64, h->ncu)));
-      if (h->inv_nblocks < 128) {
-        h->inv_o[h->inv_nblocks] = o;
-        h->inv_n[h->inv_nblocks] = nb;
-        ++h->inv_nblocks;
-      }
     } else {
       HIP_TRY(potrf_rec(cp, o, nb));
-    }
-    if (T && !coop) {
       // complete inverse of this diagonal block, still on the panel stream (hidden behind the trailing update): it turns
       // the wide trsm below into ONE GEMM and is exactly the low levels of gpp_trtri, which will skip them
-      for (int64_t s = NBLK; s < nb; s *= 2)
+      for (int64_t s = NBLK; T && s < nb; s *= 2)
         HIP_TRY(trtri_level(cp.s, cm.A, cm.ld, cm.Li, cm.ldi, T, ldt, o, nb, s, [](int64_t) { return false; }));
-      if (h->inv_nblocks < 128) {
-        h->inv_o[h->inv_nblocks] = o;
-        h->inv_n[h->inv_nblocks] = nb;
-        ++h->inv_nblocks;
-      }
+    }
+    if (T && h->inv_nblocks < 128) {
+      h->inv_o[h->inv_nblocks] = o;
+      h->inv_n[h->inv_nblocks] = nb;
+      ++h->inv_nblocks;
     }
     hipEvent_t D = next_event(h);
     HIP_TRY(hipEventRecord(D, cp.s));
@@ -458,58 +430,27 @@ hipError_t potrf_lookahead(gpp_handle_s* h, const Ctx& cm, int64_t N, int64_t NB
       pend.on = false;
       // This step's chain (next diagonal block's columns and update) and row solve touch only rows the MASKED part of that
       // update produced, when it was tall enough: then they run beside the bulk, and only this step's own trailing update
-      // waits for it.
-      if (defer_be && pend.rows_masked >= nb + std::min<int64_t>((rem >= nb_thresh) ? nb_big : nb_small, rem)) be_wait = BE;
+      // waits for it (measured: potrf 55.3 -> 54.0 ms at N = 20000, 162.8 -> 161.1 at 30000).
+      if (pend.rows_masked >= nb + std::min(bh, rem)) be_wait = BE;
       else HIP_TRY(hipStreamWaitEvent(cu.s, BE, 0));
     }
-    auto border_step = [&]() -> hipError_t {
+    if (border && o > 0) {
       // bordering step of the inverse: Linv[o.., 0..o) = -W_oo^T (U[0..o, o..)^T Linv[0..o, 0..o)) — the ragged pair merge
       // of [0, o) with [o, o+nb).  Needs block rows < o of U (row solves of the earlier steps: event R) and this block's
       // inverse (D).  Its work grows as the trailing update shrinks, so the two together keep the throughput CUs busy.
-      if (!border_early) HIP_TRY(hipStreamWaitEvent(cf, D, 0));
+      // The first product needs neither this block's factor nor its inverse: it is issued here and only the second waits for D
+      // (measured: 4.54 -> 4.44 ms per evaluation at 4096, 13.7 -> 13.4 at 8192, even above).
       HIP_TRY(hipStreamWaitEvent(cf, R_prev, 0));
       // few, long tiles (K up to o): 64-wide tiles balance better until there are several waves of 128-wide ones
       const int64_t t128 = ((nb + 127) / 128) * ((o + 127) / 128);
-      return trtri_level(cf, cm.A, cm.ld, cm.Li, cm.ldi, T, ldt, 0, o + nb, o, [](int64_t) { return false; }, 1, 0, 0, 0,
-                         t128 < border_t128 ? 64 : 0, border_early ? D : nullptr);
-    };
-    // Experiment knob GPP_BORDER_RL=1 (round 4, measured and NOT adopted): the bordered inverse RIGHT-looking, as rank-nb updates
-    // of running sums kept in the scratch T (what the sharded forward sweep does, gp-plus_amd/sharded.py): with X = L^-1, step k
-    //   A(k): X[k, :k) = -X_kk S_k                 S_k = T[o:o+nb, 0:o): sum over j < k of L[k, j] X[j, :]   (K <= nb, + mirror)
-    //   B(k): S_m += L[m, k] X[k, :k+1), m > k     ONE product with K = nb over (N - o - nb) x (o + nb) entries
-    // instead of the left-looking X[k, :k) = -X_kk (U[:k, k]^T X[:k, :k)) whose K grows to N and whose few long tiles run
-    // 64 wide.  Correct (the kernel tests pass with it) and no faster: potrf + inverse 16.46 vs 16.10 ms at N = 10 000, 9.45 vs 9.21
-    // at 8192, 5.28 vs 5.07 at 6144, 20.7 vs 21.1 at 11 264 — at these sizes the throughput CUs are the shared bottleneck of the
-    // factor's updates and the inverse's products whatever the products' shape (profiles/EXPERIMENTS.md, round 4).
-    static const bool border_rl = getenv("GPP_BORDER_RL") && atoi(getenv("GPP_BORDER_RL")) != 0;
-    auto border_A = [&]() -> hipError_t {
-      HIP_TRY(hipStreamWaitEvent(cf, D, 0));  // this block's inverse (its sums are complete in stream order: B(k-1))
-      GemmArgs g2 = mk(cm.Li + o * cm.ldi + o, cm.ldi, T + o * ldt, ldt, cm.Li + o * cm.ldi, cm.ldi, nb, o, nb, -1.0, 0.0);
-      g2.a_mask = 1; g2.khi_mode = 1; g2.row_reverse = 1;
-      g2.C2 = cm.Li + o; g2.ldc2 = cm.ldi;
-      return gpp_launch_gemm(cf, 2, g2, 1);
-    };
-    auto border_B = [&](hipEvent_t row_solved) -> hipError_t {
-      HIP_TRY(hipStreamWaitEvent(cf, row_solved, 0));  // block row o of U is final
-      const int64_t o1 = o + nb, M = N - o1;
-      if (o > 0) {  // the columns left of this block: X[k, :k) from A(k) above
-        GemmArgs b1 = mk(cm.A + o * cm.ld + o1, cm.ld, cm.Li + o * cm.ldi, cm.ldi, T + o1 * ldt, ldt, M, o, nb, 1.0, 1.0);
-        HIP_TRY(gpp_launch_gemm(cf, 2, b1, 1));
-      }
-      // this block's own columns start the sums (beta = 0: the scratch is never cleared): X_kk, lower triangular
-      GemmArgs b2 = mk(cm.A + o * cm.ld + o1, cm.ld, cm.Li + o * cm.ldi + o, cm.ldi, T + o1 * ldt + o, ldt, M, nb, nb, 1.0, 0.0);
-      b2.b_mask = 2; b2.klo_mode = 2;
-      return gpp_launch_gemm(cf, 2, b2, 1);
-    };
-    if (border && border_rl && o > 0) HIP_TRY(border_A());
-    if (border && !border_rl && o > 0 && border_early) HIP_TRY(border_step());
+      HIP_TRY(trtri_level(cf, cm.A, cm.ld, cm.Li, cm.ldi, T, ldt, 0, o + nb, o, [](int64_t) { return false; }, 1, 0, 0, 0,
+                          t128 < 640 ? 64 : 0, D));
+    }
     if (rem == 0) {
-      if (border && !border_rl && o > 0 && !border_early) HIP_TRY(border_step());
       if (be_wait) HIP_TRY(hipStreamWaitEvent(cu.s, be_wait, 0));
       break;
     }
-    const int64_t want2 = (rem >= nb_thresh) ? nb_big : nb_small;
-    const int64_t nb2 = std::min(want2, rem), rest = rem - nb2;
+    const int64_t nb2 = std::min(bh, rem), rest = rem - nb2;
     // U[o.., c0..c0+nc) = W_oo^T A[o.., c0..c0+nc) : one TN GEMM (W_oo = mirror of the block's inverse, keep i <= k) into
     // the scratch, then copied over A (a GEMM with several row tiles cannot run in place)
     auto row_solve = [&](int64_t c0, int64_t nc) -> hipError_t {
@@ -523,35 +464,29 @@ hipError_t potrf_lookahead(gpp_handle_s* h, const Ctx& cm, int64_t N, int64_t NB
                               nc * sizeof(double), nb, hipMemcpyDeviceToDevice, cu.s);
     };
     const double* Urow = cm.A + o * cm.ld;  // block row o: U[o.., :]
-    const bool merge_upd = merge_upd_on && split_chain && nb2 % NBLK == 0;
     // the chain first: the columns of the NEXT diagonal block, its update, and the panel stream may go on (event S)
-    HIP_TRY(row_solve(o + nb, split_chain ? nb2 : rem));
+    // (measured: potrf 58.2 -> 56.4 ms at N = 20000, 28.4 -> 27.3 at 15000, 17.0 -> 16.4 at 10000)
+    HIP_TRY(row_solve(o + nb, nb2));
     GemmArgs g = mk(Urow + (o + nb), cm.ld, Urow + (o + nb), cm.ld, cm.A + (o + nb) * cm.ld + (o + nb), cm.ld, nb2, nb2, nb,
                     -1.0, 1.0);
     g.c_lower = 2;
     HIP_TRY(gpp_launch_gemm(cu.s, 2, g, 1));
     hipEvent_t S = next_event(h);
-    if (split_chain) {
-      HIP_TRY(hipEventRecord(S, cu.s));
-      if (rest > 0) HIP_TRY(row_solve(o + nb + nb2, rest));
-    }
+    HIP_TRY(hipEventRecord(S, cu.s));
+    if (rest > 0) HIP_TRY(row_solve(o + nb + nb2, rest));
     hipEvent_t R = nullptr;
     if (border) {
       R = next_event(h);
       HIP_TRY(hipEventRecord(R, cu.s));
-      if (border_rl) HIP_TRY(border_B(R));
     }
+    // the trailing update (minus the next diagonal block, done above) goes out as ONE launch when that block ends on a tile edge
+    const bool merge_upd = nb2 % NBLK == 0;
     if (rest > 0 && !merge_upd) {  // the part of the next block row to the right of its diagonal block
       GemmArgs g2 = mk(Urow + (o + nb), cm.ld, Urow + (o + nb + nb2), cm.ld, cm.A + (o + nb) * cm.ld + (o + nb + nb2), cm.ld,
                        nb2, rest, nb, -1.0, 1.0);
       HIP_TRY(gpp_launch_gemm(cu.s, 2, g2, 1));
     }
-    if (!split_chain) HIP_TRY(hipEventRecord(S, cu.s));
     HIP_TRY(hipStreamWaitEvent(cp.s, S, 0));  // the next diagonal block may be factored
-    if (border && !border_rl && o > 0 && !border_early) {
-      HIP_TRY(hipStreamWaitEvent(cf, S, 0));  // behind the strip: the chain's own launches get the CUs first
-      HIP_TRY(border_step());
-    }
     if (be_wait) {
       HIP_TRY(hipStreamWaitEvent(cu.s, be_wait, 0));
       be_wait = nullptr;
@@ -564,8 +499,8 @@ hipError_t potrf_lookahead(gpp_handle_s* h, const Ctx& cm, int64_t N, int64_t NB
       g3.c_lower = 2;
       g3.skip_lead = (int)nb2;
       // rows [0, rA) of the trailing matrix run beside the next diagonal block on the CU-masked stream; rA is sized so
-      // that this takes about as long as that block (split_elems entries of the upper triangle), the rest follows unmasked
-      int64_t rA = ((split_elems / rem + NBLK - 1) / NBLK) * NBLK;
+      // that this takes about as long as that block (SPLIT_ELEMS entries of the upper triangle), the rest follows unmasked
+      int64_t rA = ((SPLIT_ELEMS / rem + NBLK - 1) / NBLK) * NBLK;
       rA = std::max(rA, nb2);
       if (split_upd && rem - rA >= 2048) {
         pend.rows_ready = next_event(h);
@@ -575,19 +510,14 @@ hipError_t potrf_lookahead(gpp_handle_s* h, const Ctx& cm, int64_t N, int64_t NB
         HIP_TRY(gpp_launch_gemm(cu.s, 2, a2, 1, NBLK, NBLK));
         GemmArgs a1 = g3;  // upper triangle of the leading rA x rA block (minus the next diagonal block): a few hundred
         a1.M = a1.N = (int)rA;  // tiles, issued last so that they run beside the unmasked part instead of on an emptying chip
-        // (measured A/B twice: potrf 26.8 -> 25.9 ms at N = 15000, 52.9 -> 52.3 at 20000, 16.2 -> 16.0 at 12288, even at 30000)
-        static const bool a1_fill = !(getenv("GPP_A1_FILL") && atoi(getenv("GPP_A1_FILL")) == 0);  // experiment knob
-        if (a1_fill) {
-          // on the second masked stream, beside the rectangle above: the two launches share ONE ragged last wave of work-groups
-          // instead of each ending on its own (a K = 1024 tile runs ~240 us; 990 tiles on 448 slots are 2.2 waves)
-          HIP_TRY(hipStreamWaitEvent(cf, pend.rows_ready, 0));
-          HIP_TRY(gpp_launch_gemm(cf, 2, a1, 1, NBLK, NBLK));
-          hipEvent_t A1 = next_event(h);
-          HIP_TRY(hipEventRecord(A1, cf));
-          HIP_TRY(hipStreamWaitEvent(cu.s, A1, 0));
-        } else {
-          HIP_TRY(gpp_launch_gemm(cu.s, 2, a1, 1, NBLK, NBLK));
-        }
+        // on the second masked stream, beside the rectangle above: the two launches share ONE ragged last wave of work-groups
+        // instead of each ending on its own (a K = 1024 tile runs ~240 us; 990 tiles on 448 slots are 2.2 waves; measured A/B
+        // twice: potrf 26.8 -> 25.9 ms at N = 15000, 52.9 -> 52.3 at 20000, 16.2 -> 16.0 at 12288, even at 30000)
+        HIP_TRY(hipStreamWaitEvent(cf, pend.rows_ready, 0));
+        HIP_TRY(gpp_launch_gemm(cf, 2, a1, 1, NBLK, NBLK));
+        hipEvent_t A1 = next_event(h);
+        HIP_TRY(hipEventRecord(A1, cf));
+        HIP_TRY(hipStreamWaitEvent(cu.s, A1, 0));
         pend.g = mk(Urow + (o + nb + rA), cm.ld, Urow + (o + nb + rA), cm.ld, cm.A + (o + nb + rA) * cm.ld + (o + nb + rA),
                     cm.ld, rem - rA, rem - rA, nb, -1.0, 1.0);
         pend.g.c_lower = 2;
@@ -620,7 +550,7 @@ hipError_t potrf_lookahead(gpp_handle_s* h, const Ctx& cm, int64_t N, int64_t NB
 }
 
 // ---- DAG executor (round 5, gpp_dag.hip / gpp_dag_f64) ---------------------------------------------------------------------------
-// The factorisation — and for N <= GPP_DAG_INV_MAX the whole inverse beside it, right-looking — as ONE ticket list of tile tasks on
+// The factorisation — and for N <= DAG_INV_MAX_N the whole inverse beside it, right-looking — as ONE ticket list of tile tasks on
 // the throughput CUs, the diagonal blocks as cooperative panel launches on the panel CUs behind one-wave gate kernels.  Replaces
 // the launch-per-product look-ahead with bordering in 3840 <= N <= 11264, where the factorisation is bound by its chain of
 // diagonal blocks: there every launch boundary (head solve -> diagonal update -> rest solve -> trailing update, in stream order)
@@ -654,83 +584,99 @@ hipError_t dag_abort(gpp_handle_s* h, const DagPlan* P) {
   return hipStreamSynchronize(h->full_stream);  // (an error path: the host may wait for one store)
 }
 
-hipError_t potrf_dag(gpp_handle_s* h, const Ctx& cm, int64_t N, double* T, int64_t ldt, bool* used) {
-  *used = false;
-  static const bool dag_env = !(getenv("GPP_DAG_SCHED") && atoi(getenv("GPP_DAG_SCHED")) == 0);
-  // Measured on one box, potrf + inverse (tools/attic/sweep_dag.sh, profiles/r05_dag_sweep.txt): launches win below ~6900 rows, where the
-  // chain of diagonal blocks is all there is (4.99 vs 5.39 ms at 6144), the ticket list from there (6.35 vs 6.82 at 7168, 8.05 vs
-  // 9.16 at 8192, 13.45 vs 15.68 at 10 000, 18.14 vs 20.46 at 11 264).  With the inverse inside the list up to ~19 000 rows (22.64 vs
-  // 24.73 at 12 288, 40.19 vs 41.97 at 15 000); above, the inverse's K = 1024 tiles on 503 slots lose to gpp_trtri's long-K launches on
-  // 256 CUs and only the factorisation (+ the leading block of the inverse) runs here (88.23 vs 89.51 at 20 000 with the round-4
-  // executor, 284.8 vs 287.1 at 30 000; with the fused steps 86.3 and 278.2).
-  static const int64_t dag_min = getenv("GPP_DAG_MIN_N") ? atol(getenv("GPP_DAG_MIN_N")) : 6912;  // (6656: 5.98 vs 5.78 ms for launches; 7168: 6.32 vs 6.82)
-  // (up to 65 536 rows since the fused steps: 645.9 vs 663.3 ms at 40 000, 1253 vs 1286 at 50 000, 2165 vs 2213 at 60 000 against
-  //  the launch path; without them the list lost at 60 000.  Planning a 60 000-row list takes ~1.2 s of host time, once per size.)
-  static const int64_t dag_max = getenv("GPP_DAG_MAX_N") ? atol(getenv("GPP_DAG_MAX_N")) : 65536;
-  // (with the fused steps the whole inverse inside the list pays up to ~19 000 rows: 54.7 vs 57.0 ms at 17 000, 69.8 vs 71.5 at 18 500,
-  //  87.3 vs 86.7 at 20 000)
-  static const int64_t dag_inv_max = getenv("GPP_DAG_INV_MAX") ? atol(getenv("GPP_DAG_INV_MAX")) : 19456;
-  static const int64_t dag_nb_env = getenv("GPP_DAG_NB") ? atol(getenv("GPP_DAG_NB")) : 0;
-  static const int64_t dag_nb_small = getenv("GPP_DAG_NB_SMALL_N") ? atol(getenv("GPP_DAG_NB_SMALL_N")) : 0;
-  if (!dag_env || !h->dag_sched || !h->coop_panel || !T || N < dag_min || N > dag_max) return hipSuccess;
-  HIP_TRY(ensure_streams(h));
-  if (h->cu_split != 1) return hipSuccess;
-  const int64_t nb = dag_nb_env ? dag_nb_env : (N <= dag_nb_small ? 512 : 1024);
-  if (nb % NBLK != 0 || !panel_fits(h, nb) || !panel_fits(h, nb + 256)) return hipSuccess;
-  // Above GPP_DAG_INV_MAX only the LEADING block of the inverse is built inside the list: its low-priority tasks fill the slots the
-  // factorisation leaves idle (start-up, the dips beside each panel, the chain-bound tail), and gpp_trtri, which treats a
-  // complete leading block like the diagonal blocks it finds inverted, merges the rest around it.  The block is a power of two
-  // times 1024 rows (the pair merges' alignment), by default the largest one <= 0.42 N (8192 of 20 000).
-  static const int64_t dag_inv_lead = getenv("GPP_DAG_INV_LEAD") ? atol(getenv("GPP_DAG_INV_LEAD")) : -1;
-  int64_t inv_rows = N;
-  if (N > dag_inv_max) {
-    inv_rows = 0;
-    if (dag_inv_lead < 0) {
-      for (int64_t r = 2 * nb; r <= (int64_t)(0.42 * (double)N); r *= 2) inv_rows = r;
-    } else if (dag_inv_lead >= 2 * nb && dag_inv_lead < N && dag_inv_lead % nb == 0) {
-      inv_rows = dag_inv_lead;
-    }
-  }
-  const int flags = inv_rows > 0 ? DAG_INV : 0;
-  // the plan: a hit in the handle's LRU, or planned now (host only) and uploaded (a few MB, once per shape)
+// fused steps (gpp_dag.hip): far tiles take 2 / 4 consecutive steps' updates in one task.  Measured, factor + inverse, same box
+// (profiles/r05_dag_sweep.txt): 26.85 -> 25.97 ms at 13 000 with 2; 40.15 -> 38.98 -> 38.75 at 15 000, 87.9 -> 86.4 -> 86.3 at
+// 20 000, 284.4 -> 278.7 -> 278.2 at 30 000 with 2 -> 4; below ~11 000 rows the longer tasks cost the chain more than the saved
+// epilogues return (8.03 -> 8.19 ms at 8192 with 2; 13.42 -> 13.58 at 10 000 with 4)
+inline int dag_fuse(int64_t N) { return N >= 14336 ? 4 : N >= 11264 ? 2 : 1; }
+
+// What distinguishes the plans of a handle's LRU.  A caller leaves the fields it does not use at the value its plans carry: the
+// single-GPU list rank 0 of 1 and workers 0; the sharded lists the inv_rows their flags imply (DAG_INV: N, else 0).
+struct PlanKey {
+  int64_t N, nb, ld, ldi, ldt;
+  int flags;
+  int64_t inv_rows;
+  int rank, nranks, workers;
+};
+// The plan of `k`: a hit in the handle's LRU (no synchronisation), or made now by make() — planned on the host and uploaded (a few
+// MB, once per shape); nullptr where make() gives up — and put in place of the least recently used one.
+template <typename Make>
+DagPlan* dag_plan_cached(gpp_handle_s* h, const PlanKey& k, Make make) {
   DagPlan* P = nullptr;
-  int slot = -1, lru = 0;
+  int lru = 0;
   for (int i = 0; i < GPP_DAG_PLANS; ++i) {
     DagPlan* q = h->dag_plans[i];
-    if (q && q->N == N && q->nb == nb && q->ld == cm.ld && q->ldi == cm.ldi && q->ldt == ldt && q->flags == flags && q->inv_rows == inv_rows) slot = i;
+    if (q && q->N == k.N && q->nb == k.nb && q->ld == k.ld && q->ldi == k.ldi && q->ldt == k.ldt && q->flags == k.flags &&
+        q->inv_rows == k.inv_rows && q->rank == k.rank && q->nranks == k.nranks && q->workers == k.workers)
+      P = q;
     if (!q) lru = i;
     else if (h->dag_plans[lru] && q->stamp < h->dag_plans[lru]->stamp) lru = i;
   }
-  if (slot >= 0) P = h->dag_plans[slot];
-  else {
-    DagTuning tune = gpp_dag_default_tuning();
-    tune.workers = 2 * (h->ncu - h->panel_cus);
-    if (tune.fill > 0) tune.fill = 2 * h->panel_cus;
-    tune.inv_rows = inv_rows;
-    // fused steps (gpp_dag.hip): far tiles take 2 / 4 consecutive steps' updates in one task.  Measured, factor + inverse, same box
-    // (profiles/r05_dag_sweep.txt): 26.85 -> 25.97 ms at 13 000 with 2; 40.15 -> 38.98 -> 38.75 at 15 000, 87.9 -> 86.4 -> 86.3 at
-    // 20 000, 284.4 -> 278.7 -> 278.2 at 30 000 with 2 -> 4; below ~11 000 rows the longer tasks cost the chain more than the saved
-    // epilogues return (8.03 -> 8.19 ms at 8192 with 2; 13.42 -> 13.58 at 10 000 with 4)
-    if (!getenv("GPP_DAG_FUSE")) tune.fuse = N >= 14336 ? 4 : N >= 11264 ? 2 : 1;
-    P = gpp_dag_plan(N, nb, cm.ld, cm.ldi, ldt, 0, flags, tune);
-    if (!P) return hipSuccess;
-    for (int b = 0; b < P->B; ++b) {
-      const int64_t rows = std::min<int64_t>((int64_t)P->tb[b + 1] * NBLK, N) - (int64_t)P->tb[b] * NBLK;
-      if (!panel_fits(h, rows)) {
-        gpp_dag_free(P);
-        return hipSuccess;
-      }
-    }
-    if (gpp_dag_upload(P) != hipSuccess) {  // no memory for the device copy: not an error of the factorisation
-      (void)hipGetLastError();
-      gpp_dag_free(P);
-      h->dag_sched = 0;
-      return hipSuccess;
-    }
+  if (!P) {
+    P = make();
+    if (!P) return nullptr;
     if (h->dag_plans[lru]) gpp_dag_free(h->dag_plans[lru]);  // (its own last launch, then hipFree: a device-wide wait, see gpp_dag_free)
     h->dag_plans[lru] = P;
   }
   P->stamp = ++h->dag_clock;
+  return P;
+}
+
+// Measured on one box, potrf + inverse (profiles/r05_dag_sweep.txt): launches win below ~6900 rows, where the chain of diagonal
+// blocks is all there is (4.99 vs 5.39 ms at 6144; 6656: 5.98 vs 5.78 ms for launches), the ticket list from there (6.32 vs 6.82
+// at 7168, 8.05 vs 9.16 at 8192, 13.45 vs 15.68 at 10 000, 18.14 vs 20.46 at 11 264).
+constexpr int64_t DAG_MIN_N = 6912;
+// (up to 65 536 rows since the fused steps: 645.9 vs 663.3 ms at 40 000, 1253 vs 1286 at 50 000, 2165 vs 2213 at 60 000 against
+//  the launch path; without them the list lost at 60 000.  Planning a 60 000-row list takes ~1.2 s of host time, once per size.)
+constexpr int64_t DAG_MAX_N = 65536;
+// With the inverse inside the list up to ~19 000 rows (22.64 vs 24.73 at 12 288, 40.19 vs 41.97 at 15 000; with the fused steps
+// 54.7 vs 57.0 ms at 17 000, 69.8 vs 71.5 at 18 500, 87.3 vs 86.7 at 20 000); above, the inverse's K = 1024 tiles on 503 slots lose
+// to gpp_trtri's long-K launches on 256 CUs and only the factorisation (+ the leading block of the inverse) runs in the list (88.23
+// vs 89.51 at 20 000 with the round-4 executor, 284.8 vs 287.1 at 30 000; with the fused steps 86.3 and 278.2).
+constexpr int64_t DAG_INV_MAX_N = 19456;
+constexpr int64_t DAG_NB = 1024;  // block-row height of the single-GPU list
+
+hipError_t potrf_dag(gpp_handle_s* h, const Ctx& cm, int64_t N, double* T, int64_t ldt, bool* used) {
+  *used = false;
+  if (!gpp_env().dag_sched || !h->dag_sched || !h->coop_panel || !T || N < DAG_MIN_N || N > DAG_MAX_N) return hipSuccess;
+  HIP_TRY(ensure_streams(h));
+  if (h->cu_split != 1) return hipSuccess;
+  const int64_t nb = DAG_NB;
+  if (!panel_fits(h, nb) || !panel_fits(h, nb + 256)) return hipSuccess;
+  // Above DAG_INV_MAX_N only the LEADING block of the inverse is built inside the list: its low-priority tasks fill the slots the
+  // factorisation leaves idle (start-up, the dips beside each panel, the chain-bound tail), and gpp_trtri, which treats a
+  // complete leading block like the diagonal blocks it finds inverted, merges the rest around it.  The block is a power of two
+  // times 1024 rows (the pair merges' alignment), the largest one <= 0.42 N (8192 of 20 000).
+  int64_t inv_rows = N;
+  if (N > DAG_INV_MAX_N) {
+    inv_rows = 0;
+    for (int64_t r = 2 * nb; r <= (int64_t)(0.42 * (double)N); r *= 2) inv_rows = r;
+  }
+  const int flags = inv_rows > 0 ? DAG_INV : 0;
+  DagPlan* P = dag_plan_cached(h, PlanKey{N, nb, cm.ld, cm.ldi, ldt, flags, inv_rows, 0, 1, 0}, [&]() -> DagPlan* {
+    DagTuning tune = gpp_dag_default_tuning();
+    tune.workers = 2 * (h->ncu - h->panel_cus);
+    tune.fill = 2 * h->panel_cus;
+    tune.inv_rows = inv_rows;
+    tune.fuse = dag_fuse(N);
+    DagPlan* Q = gpp_dag_plan(N, nb, cm.ld, cm.ldi, ldt, 0, flags, tune);
+    if (!Q) return nullptr;
+    for (int b = 0; b < Q->B; ++b) {
+      const int64_t rows = std::min<int64_t>((int64_t)Q->tb[b + 1] * NBLK, N) - (int64_t)Q->tb[b] * NBLK;
+      if (!panel_fits(h, rows)) {
+        gpp_dag_free(Q);
+        return nullptr;
+      }
+    }
+    if (gpp_dag_upload(Q) != hipSuccess) {  // no memory for the device copy: not an error of the factorisation
+      (void)hipGetLastError();
+      gpp_dag_free(Q);
+      h->dag_sched = 0;
+      return nullptr;
+    }
+    return Q;
+  });
+  if (!P) return hipSuccess;  // not applicable: the caller continues with the older paths
   Ctx cp = cm, cu = cm;
   cp.s = h->panel_stream;
   cu.s = h->upd_stream;
@@ -747,14 +693,12 @@ hipError_t potrf_dag(gpp_handle_s* h, const Ctx& cm, int64_t N, double* T, int64
   dl.counters = P->d_counters; dl.info = cm.info; dl.budget = budget;
   dl.max_tasks = 0; dl.quit_id = -1; dl.quit_val = 0; dl.ticket_limit = 0;
   dl.trace = P->d_trace; dl.tag = 0;
-  static const int dag_workers = getenv("GPP_DAG_WORKERS") ? atoi(getenv("GPP_DAG_WORKERS")) : 0;
   // GPP_DAG_PHASED=1 (profiling): the SAME ticket list executed as a sequence of launches on the caller's stream that never wait for
   // each other — panel b, then one launch of the executor's kernel that stops in front of the first task that needs panel b + 1
   // (the fillers' ticket limit, for every work-group), and so on.  Counter collection (rocprofv3 --pmc) serialises dispatches,
   // under which the concurrent form cannot run; this form runs the same kernel over the same tasks in the same order, so its
   // FETCH_SIZE / WRITE_SIZE describe the timed path's tiles (profiles/r05_potrf_pmc.json).
-  static const bool phased = getenv("GPP_DAG_PHASED") && atoi(getenv("GPP_DAG_PHASED")) != 0;
-  if (phased) {
+  if (gpp_env().dag_phased) {
     const int wgs = 2 * h->ncu;
     for (int b = 0; b < P->B; ++b) {
       const int64_t o = (int64_t)P->tb[b] * NBLK, rows = std::min<int64_t>((int64_t)P->tb[b + 1] * NBLK, N) - o;
@@ -770,7 +714,7 @@ hipError_t potrf_dag(gpp_handle_s* h, const Ctx& cm, int64_t N, double* T, int64
     *used = true;
     return hipSuccess;
   }
-  HIP_TRY(gpp_launch_dag(cu.s, dag_workers > 0 ? dag_workers : 2 * (h->ncu - h->panel_cus), dl));
+  HIP_TRY(gpp_launch_dag(cu.s, 2 * (h->ncu - h->panel_cus), dl));
   // (the executor is running from here on: a failure below raises the abort word and still joins the streams — its work-groups
   //  would otherwise spin for the whole budget behind a call that has already returned an error)
   auto enqueue_panel_stream = [&]() -> hipError_t {
@@ -934,7 +878,7 @@ int gpp_create(gpp_handle_t* out, int device) {
   h->inv_nblocks = 0;
   h->panel_flags = nullptr;
   h->panel_next = 0;
-  h->coop_panel = panel_enabled() ? 1 : 0;
+  h->coop_panel = gpp_env().coop_panel ? 1 : 0;
   h->panel_fault = 0;
   h->panel_timeout_ms = 500;
   for (int i = 0; i < GPP_DAG_PLANS; ++i) h->dag_plans[i] = nullptr;
@@ -1031,11 +975,11 @@ int gpp_internal_stream(gpp_handle_t h, int which, void** out) {
 }
 
 // ---- the sharded evaluation's factorisation + forward sweep as ONE ticket list per rank (gpp_dag.hip, DAG_SHARD) -------------------
+constexpr int64_t SHARD_LIST_MIN_N = 4096;
 static long long shard_budget(const gpp_handle_s* h) {
   // the waits of a sharded list include the other ranks' progress (and, the first time, their planning): generous by default
-  static const long long ms = getenv("GPP_SHARD_TIMEOUT_MS") ? atoll(getenv("GPP_SHARD_TIMEOUT_MS")) : 60000;
   (void)h;
-  return ms * 100000;
+  return gpp_env().shard_timeout_ms * 100000;
 }
 
 int gpp_shard_list_begin(gpp_handle_t h, int64_t N, int64_t nb, int rank, int nranks, double* A, int64_t ld, double* Kc, double* Lc,
@@ -1056,51 +1000,37 @@ int gpp_shard_list_begin(gpp_handle_t h, int64_t N, int64_t nb, int rank, int nr
   if ((ldw & 1) || ldw < N) return -15;
   if (!info) return -16;
   if (h->shard_cur) return -1;  // a list is open on this handle
-  if (workers <= 0 && getenv("GPP_SHARD_WORKERS")) workers = atoi(getenv("GPP_SHARD_WORKERS"));  // (tests: ranks sharing one GPU)
-  static const bool list_env = !(getenv("GPP_SHARD_LIST") && atoi(getenv("GPP_SHARD_LIST")) == 0);
-  static const int64_t list_min = getenv("GPP_SHARD_LIST_MIN_N") ? atol(getenv("GPP_SHARD_LIST_MIN_N")) : 4096;
-  if (!list_env || !h->dag_sched || !h->coop_panel || N < list_min || N > 65536) return 0;
+  const GppEnv& env = gpp_env();
+  if (workers <= 0 && env.shard_workers > 0) workers = env.shard_workers;  // (tests: ranks sharing one GPU)
+  if (!env.shard_list || !h->dag_sched || !h->coop_panel || N < SHARD_LIST_MIN_N || N > DAG_MAX_N) return 0;
   GPP_TRY(ensure_streams(h));
   if (h->cu_split != 1) return 0;
   if (!panel_fits(h, nb)) return 0;
   const int flags = DAG_INV | DAG_SHARD;
-  DagPlan* P = nullptr;
-  int slot = -1, lru = 0;
-  for (int i = 0; i < GPP_DAG_PLANS; ++i) {
-    DagPlan* q = h->dag_plans[i];
-    if (q && q->N == N && q->nb == nb && q->ld == ld && q->ldi == ldc && q->ldt == ldw && q->flags == flags && q->rank == rank &&
-        q->nranks == nranks && q->workers == workers)
-      slot = i;
-    if (!q) lru = i;
-    else if (h->dag_plans[lru] && q->stamp < h->dag_plans[lru]->stamp) lru = i;
-  }
   const int nworkers = workers > 0 ? workers : 2 * (h->ncu - h->panel_cus);
-  if (slot >= 0) P = h->dag_plans[slot];
-  else {
+  DagPlan* P = dag_plan_cached(h, PlanKey{N, nb, ld, ldc, ldw, flags, N, rank, nranks, workers}, [&]() -> DagPlan* {
     DagTuning tune = gpp_dag_default_tuning();
     tune.workers = nworkers;
     // filler launches on the panel's CUs between this rank's panels (as in gpp_potrf_ws); not where ranks share one GPU (tests pass
-    // `workers`): another rank's panel needs those CUs while a filler here may be waiting for that very rank's message
-    static const int fill_env = getenv("GPP_SHARD_FILL") ? atoi(getenv("GPP_SHARD_FILL")) : -1;
+    // `workers`): another rank's panel needs those CUs while a filler here may be waiting for that very rank's message.
     // With messages on the wire (nranks > 1) ONE filler work-group per panel CU: the executor's work-groups fill their CUs to the last
     // register, so the collectives' kernels, the packing copies and the gate / signal kernels live on the panel CUs — and a filler
     // that waits for a message must never be what keeps that message's kernel from being scheduled.
-    tune.fill = fill_env >= 0 ? fill_env : (workers > 0 || tune.fill <= 0) ? 0 : (nranks > 1 ? h->panel_cus : 2 * h->panel_cus);
+    tune.fill = env.shard_fill >= 0 ? env.shard_fill : workers > 0 ? 0 : (nranks > 1 ? h->panel_cus : 2 * h->panel_cus);
     tune.inv_rows = 0;
-    if (!getenv("GPP_DAG_FUSE")) tune.fuse = N >= 14336 ? 4 : N >= 11264 ? 2 : 1;
-    P = gpp_dag_plan(N, nb, ld, ldc, ldw, 0, flags, tune, rank, nranks);
-    if (!P) return 0;
-    P->workers = workers;
-    P->fill = tune.fill;
-    if (gpp_dag_upload(P) != hipSuccess) {
+    tune.fuse = dag_fuse(N);
+    DagPlan* Q = gpp_dag_plan(N, nb, ld, ldc, ldw, 0, flags, tune, rank, nranks);
+    if (!Q) return nullptr;
+    Q->workers = workers;
+    Q->fill = tune.fill;
+    if (gpp_dag_upload(Q) != hipSuccess) {
       (void)hipGetLastError();
-      gpp_dag_free(P);
-      return 0;
+      gpp_dag_free(Q);
+      return nullptr;
     }
-    if (h->dag_plans[lru]) gpp_dag_free(h->dag_plans[lru]);
-    h->dag_plans[lru] = P;
-  }
-  P->stamp = ++h->dag_clock;
+    return Q;
+  });
+  if (!P) return 0;
   hipStream_t sm = h->stream, sp = h->panel_stream, su = h->upd_stream;
   GPP_TRY(gpp_launch_fill_i32(sm, P->d_counters, P->ncounters, 0));
   DagBases bases{{reinterpret_cast<char*>(A), reinterpret_cast<char*>(Kc), reinterpret_cast<char*>(Lc), reinterpret_cast<char*>(D),
@@ -1222,43 +1152,30 @@ int gpp_shard_back_list(gpp_handle_t h, int64_t N, int64_t nb, int rank, int nra
   if ((ldc & 1) || ldc < wc) return -10;
   if (!D || !aligned16(D)) return -11;
   if (!info) return -12;
-  static const bool list_env = !(getenv("GPP_SHARD_LIST") && atoi(getenv("GPP_SHARD_LIST")) == 0) &&
-                               !(getenv("GPP_SHARD_BACK_LIST") && atoi(getenv("GPP_SHARD_BACK_LIST")) == 0);
-  static const int64_t list_min = getenv("GPP_SHARD_LIST_MIN_N") ? atol(getenv("GPP_SHARD_LIST_MIN_N")) : 4096;
-  if (!list_env || !h->dag_sched || N < list_min || N > 65536 || h->shard_cur) return 0;
-  if (workers <= 0 && getenv("GPP_SHARD_WORKERS")) workers = 2 * atoi(getenv("GPP_SHARD_WORKERS"));
+  const GppEnv& env = gpp_env();
+  if (!env.shard_list || !h->dag_sched || N < SHARD_LIST_MIN_N || N > DAG_MAX_N || h->shard_cur) return 0;
+  if (workers <= 0 && env.shard_workers > 0) workers = 2 * env.shard_workers;
   GPP_TRY(ensure_streams(h));
   const int flags = DAG_SHARD | DAG_BACK;
-  DagPlan* P = nullptr;
-  int slot = -1, lru = 0;
-  for (int i = 0; i < GPP_DAG_PLANS; ++i) {
-    DagPlan* q = h->dag_plans[i];
-    if (q && q->N == N && q->nb == nb && q->ld == ld && q->ldi == ldc && q->flags == flags && q->rank == rank && q->nranks == nranks &&
-        q->workers == workers)
-      slot = i;
-    if (!q) lru = i;
-    else if (h->dag_plans[lru] && q->stamp < h->dag_plans[lru]->stamp) lru = i;
-  }
   const int nworkers = workers > 0 ? workers : 2 * h->ncu;
-  if (slot >= 0) P = h->dag_plans[slot];
-  else {
+  // (ldt: the list has no scratch rows; it is planned with ld in their place)
+  DagPlan* P = dag_plan_cached(h, PlanKey{N, nb, ld, ldc, ld, flags, 0, rank, nranks, workers}, [&]() -> DagPlan* {
     DagTuning tune = gpp_dag_default_tuning();
     tune.workers = nworkers;
     tune.fill = 0;
     tune.inv_rows = 0;
-    if (!getenv("GPP_DAG_FUSE")) tune.fuse = N >= 14336 ? 4 : N >= 11264 ? 2 : 1;
-    P = gpp_dag_plan(N, nb, ld, ldc, ld, 0, flags, tune, rank, nranks);
-    if (!P) return 0;
-    P->workers = workers;
-    if (P->tasks.empty() || gpp_dag_upload(P) != hipSuccess) {
+    tune.fuse = dag_fuse(N);
+    DagPlan* Q = gpp_dag_plan(N, nb, ld, ldc, ld, 0, flags, tune, rank, nranks);
+    if (!Q) return nullptr;
+    Q->workers = workers;
+    if (Q->tasks.empty() || gpp_dag_upload(Q) != hipSuccess) {
       (void)hipGetLastError();
-      gpp_dag_free(P);
-      return 0;
+      gpp_dag_free(Q);
+      return nullptr;
     }
-    if (h->dag_plans[lru]) gpp_dag_free(h->dag_plans[lru]);
-    h->dag_plans[lru] = P;
-  }
-  P->stamp = ++h->dag_clock;
+    return Q;
+  });
+  if (!P) return 0;
   hipStream_t sm = h->stream;
   GPP_TRY(gpp_launch_fill_i32(sm, P->d_counters, P->ncounters, 0));
   DagBases bases{{const_cast<char*>(reinterpret_cast<const char*>(A)), reinterpret_cast<char*>(Kc), reinterpret_cast<char*>(Lc),
@@ -1347,14 +1264,13 @@ int gpp_potrf_ws(gpp_handle_t h, double* A, int64_t N, int64_t ld, double* Linv,
   Ctx c{h->stream, A, ld, Linv, ldi, info_dev};
   h->inv_N = N;
   h->inv_nblocks = 0;
-  static const int64_t la_min = getenv("GPP_LOOKAHEAD_MIN") ? atol(getenv("GPP_LOOKAHEAD_MIN")) : 6 * LOOKAHEAD_NB;  // knob
-  // (measured: the leaf-step factorisation on one stream wins up to ~6000 rows — 2.99 vs 3.46 ms at 4096, 4.25 vs 4.53 at
-  //  5120, a tie at 6144; the look-ahead wins from there: 8.6 vs 10.1 ms at 8192)
-  static const int64_t la_min_b = getenv("GPP_BORDER_MIN") ? atol(getenv("GPP_BORDER_MIN")) : BORDER_MIN_N;  // knob
+  // (measured: without a scratch the leaf-step factorisation on one stream wins up to ~6000 rows — 2.99 vs 3.46 ms at 4096, 4.25 vs
+  //  4.53 at 5120, a tie at 6144; the look-ahead wins from there: 8.6 vs 10.1 ms at 8192.  With one, i.e. with bordering: BORDER_MIN_N)
+  const int64_t la_min = T ? BORDER_MIN_N : 6 * LOOKAHEAD_NB;
   bool dag_used = false;
   GPP_TRY(potrf_dag(h, c, N, T, ldt, &dag_used));
   if (dag_used) return 0;
-  if (N >= (T ? std::min(la_min, la_min_b) : la_min)) {
+  if (N >= la_min) {
     GPP_TRY(potrf_lookahead(h, c, N, LOOKAHEAD_NB, T, ldt));
   } else if (panel_fits(h, N)) {
     // a small matrix: factor and inverse by one cooperative launch on the caller's stream; gpp_trtri finds the inverse complete
@@ -1419,16 +1335,11 @@ int gpp_lauum(gpp_handle_t h, const double* Linv, int64_t N, int64_t ldi, double
   if (int r = check_mat(Kinv, ldk, N, 5)) return r;
   GemmArgs g = mk(Linv, ldi, Linv, ldi, Kinv, ldk, N, N, N, 1.0, 0.0);
   g.a_mask = 2; g.b_mask = 2; g.klo_mode = 3; g.c_lower = 1; g.tag = 1;
-  // experiment knob: walk every tile's K range from the top (k = N) down, so that the tile rows in flight — whose ranges start at
-  // different k but all END at N — sweep the shared operand columns in lockstep
-  static const int krev = getenv("GPP_LAUUM_KREV") ? atoi(getenv("GPP_LAUUM_KREV")) : 0;
-  g.k_reverse = krev;
   // one launch of long-K triangular tiles: small tiles balance it until there are several waves of big ones (measured:
   // N = 1024 0.167 / 0.061 / 0.034 ms with 128 / 64 / 32-wide tiles, 2048 0.312 / 0.130 / 0.098, 3072 0.490 / 0.231 /
   // 0.278, 4096 0.742 / 0.502 / 0.610, 6144 1.38 / 1.55 / 1.94)
-  static const int lt = getenv("GPP_LAUUM_TILE") ? atoi(getenv("GPP_LAUUM_TILE")) : 0;  // experiment knob (0: by size)
-  const int t = lt ? lt : (N <= 2560 ? 32 : N <= 5120 ? 64 : NBLK);
-  GPP_TRY(gpp_launch_gemm(h->stream, 2, g, 1, t, t == 256 ? 128 : t));  // (256: the tall 256 x 128 tile, 8 waves — experiment)
+  const int t = N <= 2560 ? 32 : N <= 5120 ? 64 : NBLK;
+  GPP_TRY(gpp_launch_gemm(h->stream, 2, g, 1, t, t));
   return 0;
 }
 
@@ -1753,20 +1664,8 @@ int gpp_gemm(gpp_handle_t h, int transA, int transB, int64_t M, int64_t N, int64
   if (c_tri < 0 || c_tri > 2 || (c_tri && M != N)) return -19;
   GemmArgs g = mk(A, lda, B, ldb, C, ldc, M, N, K, alpha, beta);
   g.a_mask = a_mask; g.b_mask = b_mask; g.klo_mode = klo_mode; g.khi_mode = khi_mode; g.c_lower = c_tri;
-  int ftm = 0, ftn = 0;
-  if (const char* e = getenv("GPP_GEMM_TILE")) sscanf(e, "%d,%d", &ftm, &ftn);  // dev knob (tools/attic/gemm_small_probe.py)
-  if (getenv("GPP_GEMM_ON_UPD")) {  // dev knob (tools/attic/gemm_update_probe.py): run on the CU-masked update stream
-    GPP_TRY(ensure_streams(h));
-    hipEvent_t a = next_event(h), b = next_event(h);
-    GPP_TRY(hipEventRecord(a, h->stream));
-    GPP_TRY(hipStreamWaitEvent(h->upd_stream, a, 0));
-    GPP_TRY(gpp_launch_gemm(h->upd_stream, variant, g, 1, ftm, ftn));
-    GPP_TRY(hipEventRecord(b, h->upd_stream));
-    GPP_TRY(hipStreamWaitEvent(h->stream, b, 0));
-    return 0;
-  }
   if (h->cu_split == 1 && h->stream == h->panel_stream) g.cu_hint = h->panel_cus;
-  GPP_TRY(gpp_launch_gemm(h->stream, variant, g, 1, ftm, ftn));
+  GPP_TRY(gpp_launch_gemm(h->stream, variant, g, 1));
   return 0;
 }
 

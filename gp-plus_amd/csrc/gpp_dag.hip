@@ -13,7 +13,8 @@
 //   XA(m; r, j)   inverse, rows  X[m rows, j] = -X_mm T[m rows, j] (+ mirror)     j left of block m   (K <= nb, triangular)
 // (XB / XA: with S_m = sum_{k<m} L[m,k] X[k,:] accumulated in the lower-left part of T, X[m,:m) = -X_mm S_m — the sharded forward
 // sweep's recurrence; the solved block rows live in the upper-right part of T, so the two uses of the scratch never meet.)
-// (Above GPP_DAG_INV_MAX rows only the leading inv_rows x inv_rows block of X is built here, gpp_trtri merges the rest around it.)
+// (Above 19 456 rows (gpp_api.hip: DAG_INV_MAX_N) only the leading inv_rows x inv_rows block of X is built here, gpp_trtri merges
+// the rest around it.)
 // FUSED STEPS: a tile at least f + 1 block rows below an aligned group of f steps takes the group's f updates (or the sum's f
 // contributions) in ONE task at the group's last step, with K = the f blocks' rows — see generate().
 // Every dependency is a monotone counter: strip counters (all tasks of a strip done) and per-tile version counters (the k-th
@@ -1203,13 +1204,7 @@ DagPlan* emit(Planner& pl) {
 
 // Columns per piece of a block row's tail message (gpp.h).  Measured with tools/replay_rank.py at C5 on 8 virtual ranks: see
 // profiles/r06_virtual_rank.txt.  GPP_SHARD_PIECE_COLS=0: one piece, as in round 5.
-extern "C" int64_t gpp_shard_piece_cols(void) {
-  static const int64_t cols = [] {
-    const int64_t v = getenv("GPP_SHARD_PIECE_COLS") ? atol(getenv("GPP_SHARD_PIECE_COLS")) : 8192;
-    return v <= 0 ? (int64_t)0 : std::max<int64_t>(GPP_TILE, v / GPP_TILE * GPP_TILE);
-  }();
-  return cols;
-}
+extern "C" int64_t gpp_shard_piece_cols(void) { return gpp_env().shard_piece_cols; }
 
 DagTuning gpp_dag_default_tuning() {
   DagTuning t;
@@ -1217,20 +1212,20 @@ DagTuning gpp_dag_default_tuning() {
   // K = 1024 and 1035 at 4096; the 64-tile 60 us at a mean K of 576 and 105 at 1024; a strip copy 150-180 us (latency-bound beside
   // the MFMA work); a panel 620-640 us for 8 leaves.  The ORDER of the list is only as good as these: with the first guesses
   // (3.7 us per chunk, 0.75 for the 64-tile, 12 us per copy, 580 us per panel) chain tasks were taken ~70 us before they could run.
-  t.t0_big = getenv("GPP_DAG_T0") ? atof(getenv("GPP_DAG_T0")) : 14.0;
-  t.tc_big = getenv("GPP_DAG_TC") ? atof(getenv("GPP_DAG_TC")) : 3.9;
+  t.t0_big = 14.0;
+  t.tc_big = 3.9;
   t.t0_64 = 15.0; t.tc_64 = 1.4;
   t.t0_32 = 6.0; t.tc_32 = 0.55;
   t.t_copy = 160.0;
-  t.t_panel0 = getenv("GPP_DAG_TP0") ? atof(getenv("GPP_DAG_TP0")) : 20.0;
-  t.t_panel_leaf = getenv("GPP_DAG_TPL") ? atof(getenv("GPP_DAG_TPL")) : 77.0;
-  t.t_gate = getenv("GPP_DAG_TGATE") ? atof(getenv("GPP_DAG_TGATE")) : 15.0;
-  t.chain_tile = getenv("GPP_DAG_CHAIN_TILE") ? atoi(getenv("GPP_DAG_CHAIN_TILE")) : 64;
+  t.t_panel0 = 20.0;
+  t.t_panel_leaf = 77.0;
+  t.t_gate = 15.0;
+  t.chain_tile = 64;
   t.workers = 448;
   t.inv_rows = 0;
   t.piece_cols = gpp_shard_piece_cols();
-  t.fuse = getenv("GPP_DAG_FUSE") ? atoi(getenv("GPP_DAG_FUSE")) : 1;  // (potrf_dag chooses by size)
-  t.fill = getenv("GPP_DAG_FILL") ? atoi(getenv("GPP_DAG_FILL")) : 64;
+  t.fuse = 1;  // (the drivers choose by size: gpp_api.hip, dag_fuse)
+  t.fill = 64;
   return t;
 }
 
@@ -1254,11 +1249,11 @@ DagPlan* gpp_dag_plan(int64_t N, int64_t nb, int64_t ld, int64_t ldi, int64_t ld
     return nullptr;
   }
   DagPlan* P = emit(pl);
-  if (getenv("GPP_EXEC_VERBOSE"))
+  if (gpp_env().exec_verbose)
     fprintf(stderr, "libgpp_hip: dag plan N=%lld nb=%lld flags=%d: %d blocks, %zu tasks, %zu groups, %d counters; simulated %.2f ms, "
                     "%.0f %% busy on %d workers\n", (long long)N, (long long)nb, flags, P->B, P->tasks.size(), P->groups.size(), P->ncounters,
             P->sim_ms, 100.0 * P->sim_busy, tune.workers);
-  if (getenv("GPP_DAG_DUMP")) {
+  if (gpp_env().dag_dump > 0) {
     auto fam = [&](int c) {
       static char buf[64];
       if (c < 0) return (const char*)"-";
@@ -1271,7 +1266,7 @@ DagPlan* gpp_dag_plan(int64_t N, int64_t nb, int64_t ld, int64_t ldi, int64_t ld
       snprintf(buf, sizeof buf, "%s+%d", nm, c - base);
       return (const char*)buf;
     };
-    const int nd = atoi(getenv("GPP_DAG_DUMP"));
+    const int nd = gpp_env().dag_dump;
     for (int t = 0; t < nd && t < (int)P->tasks.size(); ++t) {
       const DagTask& d = P->tasks[t];
       fprintf(stderr, "  r%d ticket %d kind %d blk %d tile (%d,%d) waits", rank, t, d.kind, pl.gmeta[d.group].second, d.tm, d.tn);
@@ -1283,7 +1278,7 @@ DagPlan* gpp_dag_plan(int64_t N, int64_t nb, int64_t ld, int64_t ldi, int64_t ld
       fprintf(stderr, "\n");
     }
   }
-  if (getenv("GPP_EXEC_VERBOSE") && !pl.fill_m.empty()) {
+  if (gpp_env().exec_verbose && !pl.fill_m.empty()) {
     fprintf(stderr, "libgpp_hip: dag plan filler tasks per work-group and block:");
     for (int m : pl.fill_m) fprintf(stderr, " %d", m);
     fprintf(stderr, "\n");
@@ -1374,7 +1369,7 @@ extern "C" int gpp_debug_dag_check(int64_t N, int64_t nb, int flags, int chain_t
           const int c = t.wait_id[q];
           const int fam = c < P->c_g1d ? 0 : c < P->c_g1d + B ? 1 : 2 + (int)(((int64_t)c - (P->c_g1d + B)) / ((int64_t)B * nt));
           mutated = 10 * gi[t.group].kind + std::min(fam, 9);
-          if (getenv("GPP_DAG_CHECK_VERBOSE"))
+          if (gpp_env().dag_check_verbose)
             fprintf(stderr, "mutate: task %ld kind %d block %d tile (%d, %d) loses wait %d (counter %d >= %d, family %d)\n",
                     (long)(&t - P->tasks.data()), gi[t.group].kind, gi[t.group].k, (int)t.tm, (int)t.tn, q, c, t.wait_val[q], fam);
           t.wait_id[q] = -1;
@@ -1423,7 +1418,7 @@ extern "C" int gpp_debug_dag_check(int64_t N, int64_t nb, int flags, int chain_t
   auto try_task = [&](const DagTask& t) -> bool {
     for (int q = 0; q < 3; ++q)
       if (t.wait_id[q] >= 0 && counters[t.wait_id[q]] < t.wait_val[q]) return false;
-    if (getenv("GPP_DAG_CHECK_VERBOSE") && lazy_counter >= 0 && (&t - P->tasks.data()) == mut_task)
+    if (gpp_env().dag_check_verbose && lazy_counter >= 0 && (&t - P->tasks.data()) == mut_task)
       fprintf(stderr, "mutated task runs: lazy counter %d = %d, tasks run so far %ld\n", lazy_counter, counters[lazy_counter], (long)ran);
     const GInfo g = gi[t.group];
     const GemmArgs& a = P->groups[t.group];
@@ -1771,7 +1766,7 @@ extern "C" int gpp_debug_shard_check(int64_t N, int64_t nb, int nranks, int chai
             else if (c >= pl->c_cph - B * nt) fam = 7;  // CPD
             else fam = c < pl->c_g1d ? 0 : c < pl->c_g1d + B ? 1 : 2 + (int)std::min<int64_t>(((int64_t)c - (pl->c_g1d + B)) / ((int64_t)B * nt), 4);
             mutated = 10 * ginfo(R[r], pl->groups[t.group]).kind + fam;
-            if (getenv("GPP_DAG_CHECK_VERBOSE"))
+            if (gpp_env().dag_check_verbose)
               fprintf(stderr, "mutate: rank %d task %ld kind %d tile (%d, %d) loses wait %d (counter %d >= %d, family %d)\n", r,
                       (long)(&t - pl->tasks.data()), mutated / 10, (int)t.tm, (int)t.tn, z, c, t.wait_val[z], fam);
             t.wait_id[z] = -1;

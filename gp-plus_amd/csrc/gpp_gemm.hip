@@ -182,7 +182,8 @@ __device__ __forceinline__ void load_fast(const double* __restrict__ ubase, cons
 // product took 8-20 us); they run (64, 1): four times fewer round trips, the next chunk's loads in flight in
 // registers during the MFMAs, two barriers per chunk.  (k-contiguous operands, VAR != 2, only exist with BK = 16.)
 // WR = rows of waves in the work-group: 2 (256 threads, 2 x 2 waves: every instantiation of the evaluation) or 4 (512 threads, 4 x 2
-// waves, a 256 x 128 tile on ONE work-group per CU: the experiment of DESIGN.md section 3.5 — 25 % fewer operand bytes per flop).
+// waves, a 256 x 128 tile on ONE work-group per CU: 25 % fewer operand bytes per flop and measured slower — LAUUM at N = 20000 41.4
+// against 39.1 ms, profiles/r03_potrf_experiments.txt — so the launcher instantiates WR = 2 only).
 // One output tile (tm, tn) of the product described by ``p``: the body shared by the launch-per-product kernel (gpp_gemm_f64, p in
 // the kernel arguments) and the DAG executor (gpp_dag_f64, p in a device array read through the constant address
 // space: scalar loads, re-materialisable like kernel arguments).  A, B, C: the batch element's operands,
@@ -500,11 +501,10 @@ constexpr size_t gemm_lds_bytes(int var, int tm, int tn, int bk, int nbuf) {
   const int mc = bk * ldt_mc(tx, bk), kc = tx * LDK;
   return (size_t)nbuf * 2 * ((var != 2 && kc > mc) ? kc : mc) * sizeof(double);
 }
-template <int VAR, int WTM, int WTN, int TAG, int BK, int NBUF, int WR = 2>
+template <int VAR, int WTM, int WTN, int TAG, int BK, int NBUF>
 hipError_t launch_inst(hipStream_t s, dim3 grid, const GemmArgs& a) {
-  constexpr size_t bytes = (WR == 2) ? gemm_lds_bytes(VAR, 2 * WTM, 2 * WTN, BK, NBUF)
-                                     : (size_t)NBUF * BK * (ldt_mc(WR * WTM, BK) + ldt_mc(2 * WTN, BK)) * sizeof(double);
-  auto* fn = gpp_gemm_f64<VAR, WTM, WTN, TAG, BK, NBUF, WR>;
+  constexpr size_t bytes = gemm_lds_bytes(VAR, 2 * WTM, 2 * WTN, BK, NBUF);
+  auto* fn = gpp_gemm_f64<VAR, WTM, WTN, TAG, BK, NBUF>;
   if (bytes > 48 * 1024) {
     static std::atomic<bool> attr_set[64];  // per instantiation and device (function attributes are per device)
     int dev = 0;
@@ -516,7 +516,7 @@ hipError_t launch_inst(hipStream_t s, dim3 grid, const GemmArgs& a) {
       if (dev >= 0 && dev < 64) attr_set[dev] = true;
     }
   }
-  hipLaunchKernelGGL(fn, grid, dim3(128 * WR), bytes, s, a);
+  hipLaunchKernelGGL(fn, grid, dim3(256), bytes, s, a);
   return hipGetLastError();
 }
 // small tiles: wide K chunks for the row-contiguous variant, the classic staging otherwise
@@ -527,9 +527,6 @@ template <int VAR>
 hipError_t launch_var(hipStream_t s, int tm, int tn, dim3 grid, const GemmArgs& a) {
   constexpr int SBK = (VAR == 2) ? GPP_SMALL_BK : 16;
   constexpr int SNB = (VAR == 2 && GPP_SMALL_BK > 16) ? 1 : 2;
-  if constexpr (VAR == 2) {
-    if (tm == 256 && tn == 128) return launch_inst<2, 64, 64, 1, 16, 2, 4>(s, grid, a);  // (TAG 1: its own name in profiles)
-  }
   if (tm == 128 && tn == 128 && a.tag == 1 && VAR == 2) return launch_inst<2, 64, 64, 1, 16, 2>(s, grid, a);
   if (tm == 128 && tn == 128) return launch_inst<VAR, 64, 64, 0, 16, 2>(s, grid, a);
   if (tm == 64 && tn == 64) return launch_inst<VAR, 32, 32, 0, SBK, SNB>(s, grid, a);
@@ -726,8 +723,7 @@ hipError_t gpp_launch_gemm(hipStream_t s, int variant, const GemmArgs& a_in, int
   };
   if (tile_m == 0) {
     // enough 128^2 tiles to give every CU a work-group -> big tile; otherwise shrink until the chip is covered
-    static const int64_t t128 = getenv("GPP_TILE_T128") ? atol(getenv("GPP_TILE_T128")) : 256;  // experiment knobs
-    static const int64_t t64 = getenv("GPP_TILE_T64") ? atol(getenv("GPP_TILE_T64")) : 192;
+    constexpr int64_t t128 = 256, t64 = 192;
     // (a launch on the panel stream has 32 CUs to fill, not 256: the thresholds scale with the stream's CU count)
     const int64_t cus = a.cu_hint > 0 ? a.cu_hint : 256;
     if (ntiles(128) * 256 >= t128 * cus) tile_m = 128;
@@ -735,12 +731,10 @@ hipError_t gpp_launch_gemm(hipStream_t s, int variant, const GemmArgs& a_in, int
     else tile_m = 32;
     tile_n = tile_m;
   }
-  const bool tall = (tile_m == 256 && tile_n == 128);
-  if (a.c_lower && tile_m != tile_n && !(tall && a.c_lower == 1 && a.row_mod <= 1 && a.row_i1 == 0 && a.row_t1 == 0)) return hipErrorInvalidValue;
+  if (a.c_lower && tile_m != tile_n) return hipErrorInvalidValue;
   a.tiles_m = (a.M + tile_m - 1) / tile_m;
   a.tiles_n = (a.N + tile_n - 1) / tile_n;
   int64_t nt = a.c_lower ? (int64_t)a.tiles_m * (a.tiles_m + 1) / 2 : (int64_t)a.tiles_m * a.tiles_n;
-  if (tall && a.c_lower == 1) nt = (int64_t)a.tiles_m * (a.tiles_m + 1);  // row tm: column tiles 0 .. 2 tm + 1 (those past N exit)
   a.tile_base = 0;
   if (a.c_lower == 1 && (a.row_mod > 1 || a.row_i1 > 0)) {
     if (a.row_mod < 1) { a.row_mod = 1; a.row_off = 0; }

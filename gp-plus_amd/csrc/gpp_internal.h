@@ -59,6 +59,24 @@ struct gpp_handle_s {
   hipEvent_t comm_event;
 };
 extern "C" void gpp_shard_release_comm(gpp_handle_s* h);
+
+// Every environment variable the library reads (INTEGRATION.md has the table), parsed ONCE per process by gpp_env() (gpp_api.hip) on
+// first use.  The one exception is gpp_push_create, which reads GPP_SHARD_TIMEOUT_MS per channel: a test changes it inside a process.
+struct GppEnv {
+  bool coop_panel;               // GPP_COOP_PANEL (default 1): initial value of GPP_OPT_COOP_PANEL
+  bool dag_sched;                // GPP_DAG_SCHED (1): 0 keeps the single-GPU ticket list off whatever GPP_OPT_DAG_SCHED says
+  bool dag_phased;               // GPP_DAG_PHASED (0): profiling form of the ticket list (potrf_dag)
+  bool shard_list;               // GPP_SHARD_LIST (1): 0 keeps the sharded ticket lists off
+  int shard_workers;             // GPP_SHARD_WORKERS (0: by CU count): executor work-groups where ranks share one GPU (tests, bench.py)
+  int shard_fill;                // GPP_SHARD_FILL (-1: by rank count): filler work-groups per launch of a sharded list
+  long long shard_timeout_ms;    // GPP_SHARD_TIMEOUT_MS (60000): budget of a wait inside a sharded list
+  int64_t shard_piece_cols;      // GPP_SHARD_PIECE_COLS (8192): as gpp_shard_piece_cols() returns it (0 or a multiple of 128)
+  bool sharded_force_collectives;  // GPP_SHARDED_FORCE_COLLECTIVES (0): a single rank issues every collective (tests)
+  bool exec_verbose;             // GPP_EXEC_VERBOSE: print each new plan's summary
+  int dag_dump;                  // GPP_DAG_DUMP=n (0): print the first n tasks of each new plan
+  bool dag_check_verbose;        // GPP_DAG_CHECK_VERBOSE: the host-side checkers name the task they reject
+};
+const GppEnv& gpp_env();
 constexpr int GPP_PANEL_RING = 8;
 constexpr int GPP_PANEL_CAP_RING = 16;
 

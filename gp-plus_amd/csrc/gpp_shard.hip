@@ -239,7 +239,7 @@ int gpp_shard_eval(gpp_handle_t h, int64_t N, int64_t nb, const double* U, int D
       !b->info)
     return -16;
   const int P = std::max(h->comm_nranks, 1), me = h->comm_rank;
-  const bool travel = P > 1 || (h->comm.bcast && getenv("GPP_SHARDED_FORCE_COLLECTIVES") && atoi(getenv("GPP_SHARDED_FORCE_COLLECTIVES")) != 0);
+  const bool travel = P > 1 || (h->comm.bcast && gpp_env().sharded_force_collectives);
   if (P > 1 && (!h->comm.bcast || !h->comm.allreduce)) return -1;
   *info_host = 0;
   SH_HIP(hipSetDevice(h->device));

@@ -40,12 +40,7 @@ def capture_without_gc():
         if was:
             gc.enable()
 
-__all__ = ["GraphedObjective", "GraphedLossAndGrad", "GraphedSegment"]
-
-import os as _os
-
-#: capture_error_mode of every capture here (experiment knob GPP_CAPTURE_MODE: global / thread_local / relaxed)
-_CAPTURE_MODE = _os.environ.get("GPP_CAPTURE_MODE", "global")
+__all__ = ["GraphedObjective", "GraphedLossAndGrad"]
 
 
 class GraphedObjective:
@@ -93,7 +88,7 @@ class GraphedObjective:
         torch.cuda.current_stream(device).wait_stream(side)
         torch.cuda.synchronize(device)
         self.graph = torch.cuda.CUDAGraph()
-        with capture_without_gc(), torch.cuda.graph(self.graph, capture_error_mode=_CAPTURE_MODE):
+        with capture_without_gc(), torch.cuda.graph(self.graph):
             self.out = body()
         self._lib_scratch = self.gctx._ws  # (same reason: the library's scratch buffer is replaced when a larger one is needed)
         self.last_status = 0
@@ -159,7 +154,7 @@ class GraphedLossAndGrad:
         torch.cuda.current_stream(device).wait_stream(side)
         torch.cuda.synchronize(device)
         self.graph = torch.cuda.CUDAGraph()
-        with capture_without_gc(), torch.cuda.graph(self.graph, capture_error_mode=_CAPTURE_MODE):
+        with capture_without_gc(), torch.cuda.graph(self.graph):
             self.head, self.grads = body()
         self._lib_scratch = self.gctx._ws
         self.replays = self.declined = 0
@@ -181,137 +176,3 @@ class GraphedLossAndGrad:
         for p, g in zip(self.params, self.grads):
             p.grad = g
         return value
-
-
-# ---------------------------------------------------------------------------------------------------
-# The HOST segments of an evaluation as graphs (round 6; N >= 3840, where the whole evaluation cannot be one graph)
-# ---------------------------------------------------------------------------------------------------
-class GraphedSegment:
-    """A piece of the model's OWN code — ``fn()`` -> tuple of tensors, a function of ``params`` through ordinary PyTorch ops — as two
-    replayed HIP graphs: its forward, and its backward (``torch.autograd.grad`` of the outputs w.r.t. the parameters for given output
-    gradients), tied into autograd by one ``torch.autograd.Function`` node.
-
-    Why: above N = 3840 the factorisation runs on the library's internal streams and does not belong in a graph, so an evaluation
-    through the plain API (``model(*x)``, ``-mll(...)``, ``backward()``: optim/mll_torch.py:114-117) issued ~170 element-wise kernels of
-    3-4 us for the parameter transforms (models/gp_plus.py:243-295), the priors (priors/horseshoe.py:63-66, gpregression.py:84-115), the
-    manifold map and their backward, one Python call each: 0.4 ms of device time and a 0.4 ms gap in front of the next covariance build
-    at C3 (profiles/r05_hbm_probe.txt), the whole cost of an evaluation at small N.  The kernels are the same ones, on the same data,
-    in the same order — the numbers are bitwise those of the eager evaluation — but the host issues four graph launches instead.
-    The outputs live in the graph's static buffers: they are valid until the next replay (the next evaluation of the same model)."""
-
-    def __init__(self, fn: Callable[[], tuple], params: List[torch.nn.Parameter], device, module: Optional[torch.nn.Module] = None):
-        """``module`` (whose parameters ``fn`` reads; ``params`` is then ignored): the captured code runs on SHADOW leaves — copies of the
-        module's parameters swapped in for the capture (torch.nn.utils.stateless), refreshed by copies that are part of the forward
-        graph.  The real parameters then appear in ONE place only, as inputs of the segment's autograd node in the caller's own
-        graph, so their AccumulateGrad nodes are created on the caller's stream.  Without it (round 6's first form) the captured
-        autograd graph — which must stay alive — held the real parameters' AccumulateGrad nodes on the CAPTURE stream, every later
-        backward accumulated p.grad there, and a second active stream perturbs the factorisation's streams: C2 +1.9 ms."""
-        device = torch.device(device)
-        self.device = device
-        if module is not None:
-            from torch.nn.utils import stateless
-
-            named = [(n, p) for n, p in module.named_parameters() if p.requires_grad]
-            self.params = [p for _, p in named]
-            self.leaves = [p.detach().clone().requires_grad_(True) for p in self.params]
-            self.names = [n for n, _ in named]
-
-            def run():
-                with stateless._reparametrize_module(module, dict(zip(self.names, self.leaves))):
-                    return fn()
-        else:
-            self.params = [p for p in params if p.requires_grad]
-            self.leaves = self.params
-            run = fn
-
-        def grads_of(outs, gouts):
-            diff = [(o, g) for o, g in zip(outs, gouts) if g is not None]
-            if not diff or not self.leaves:
-                return [None] * len(self.leaves)
-            return list(torch.autograd.grad([o for o, _ in diff], self.leaves, [g for _, g in diff], allow_unused=True))
-
-        def refresh():
-            if self.leaves is not self.params:
-                with torch.no_grad():
-                    for leaf, p in zip(self.leaves, self.params):
-                        leaf.copy_(p)
-
-        side = torch.cuda.Stream(device=device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):
-            for _ in range(3):
-                refresh()
-                outs = run()
-                used = grads_of(outs, [torch.zeros_like(o) if o.requires_grad else None for o in outs])
-                # Only the parameters the segment really depends on are inputs of its autograd node.  (Not a nicety: with a
-                # parameter among the node's inputs that the segment does not use, the NEXT graph capture in the process — while
-                # such a node is alive — dies in hipStreamEndCapture on this stack (ROCm 7.2 / PyTorch 2.10); minimal reproducer
-                # tools/attic/dev/segment_probe.py with DISJOINT=1.)
-                keep = [g is not None for g in used]
-                shadowed = self.leaves is not self.params
-                self.params = [p for p, k in zip(self.params, keep) if k]
-                self.leaves = [p for p, k in zip(self.leaves, keep) if k] if shadowed else self.params
-                if shadowed:
-                    self.names = [n for n, k in zip(self.names, keep) if k]
-        torch.cuda.current_stream(device).wait_stream(side)
-        torch.cuda.synchronize(device)
-        self.fwd = torch.cuda.CUDAGraph()
-        # Both captures on the stream of the warm-up passes: the leaves' AccumulateGrad nodes were created there, and autograd hands a
-        # gradient to such a node on the NODE's stream — captured from another stream, the backward forks onto it (PyTorch warns:
-        # "The AccumulateGrad node's stream does not match ..."), the graph gets a second branch, and a replay then occupies a second
-        # hardware queue beside the caller's: what perturbs the factorisation's CU-masked streams (settings.graphed_segments' note).
-        cap = side if _os.environ.get("GPP_SEGMENT_CAPTURE_STREAM", "side") == "side" else None
-        with capture_without_gc(), torch.cuda.graph(self.fwd, stream=cap, capture_error_mode=_CAPTURE_MODE):
-            refresh()  # (part of the graph: the shadow leaves take the parameters' current values at every replay)
-            self.outs = tuple(run())
-        self.gouts = [torch.zeros_like(o) if o.requires_grad else None for o in self.outs]
-        self.bwd = torch.cuda.CUDAGraph()
-        with capture_without_gc(), torch.cuda.graph(self.bwd, pool=self.fwd.pool(), stream=cap, capture_error_mode=_CAPTURE_MODE):
-            self.grads = grads_of(self.outs, self.gouts)
-        # (The captured autograd graph stays alive: the backward graph replays into the activations it holds.)
-        self.replays = 0
-
-    def __call__(self) -> tuple:
-        """The outputs of this evaluation (autograd-connected to the parameters through ONE node)."""
-        return _SegmentFunction.apply(self, *self.params)
-
-
-class _SegmentFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, seg: GraphedSegment, *params):
-        seg.fwd.replay()
-        seg.replays += 1
-        ctx.seg = seg
-        outs = tuple(o.detach() for o in seg.outs)
-        ctx.mark_non_differentiable(*[o for o, g in zip(outs, seg.gouts) if g is None])
-        return outs
-
-    @staticmethod
-    def backward(ctx, *gs):
-        seg = ctx.seg
-        for static, g in zip(seg.gouts, gs):
-            if static is None:
-                continue
-            if g is None:
-                static.zero_()
-            else:
-                static.copy_(g)
-        seg.bwd.replay()
-        return (None,) + tuple(None if g is None else g.detach() for g in seg.grads)
-
-
-def segment_key(params, *tensors) -> tuple:
-    """What a captured segment depends on besides the parameters' VALUES: their storage, shape, dtype and requires_grad flags, and
-    the identity of the data tensors it reads."""
-    return (tuple((p.data_ptr(), tuple(p.shape), p.dtype, p.requires_grad) for p in params),
-            tuple((t.data_ptr(), tuple(t.shape), t.dtype) for t in tensors))
-
-
-def segments_apply(n_points: int, device) -> bool:
-    """Graphed host segments apply to evaluations the whole-evaluation graphs do not cover (N >= 3840), on a GPU, with autograd on,
-    outside any capture — when ``settings.graphed_segments`` is on (default off: measured slower, see there)."""
-    from . import settings
-
-    device = torch.device(device)
-    return (settings.graphed_segments.value() and device.type == "cuda" and n_points >= LOOKAHEAD_MIN_N and torch.is_grad_enabled()
-            and not torch.cuda.is_current_stream_capturing())

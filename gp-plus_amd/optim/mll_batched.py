@@ -28,7 +28,7 @@ from ..gpcore.mlls import ExactMarginalLogLikelihood
 
 __all__ = ["BatchedObjective", "fit_model_torch_batched", "BATCHED_MAX_N"]
 
-#: largest N the batched kernels take (gpp_api.hip: blocks up to GPP_BLK_MAX = 6144 rows are factored in leaf steps)
+#: largest N the batched kernels take (gpp_api.hip: blocks up to BLK_MAX = 6144 rows are factored in leaf steps)
 BATCHED_MAX_N = 6144
 
 

@@ -12,19 +12,19 @@ Unmeasurable on a one-GPU box: the tests run the ranks on one device (same-devic
 from __future__ import annotations
 
 import ctypes
-import os
 from ctypes import c_char, c_int, c_int64, c_void_p
 from typing import List, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
 
+from . import settings
 from ._lib import check
 from .backend import INFO_EXEC_TIMEOUT, GppContext
 
 HANDLE_BYTES = 128
 #: GPP_SHARD_PUSH=1 selects the push transport for the block rows' messages (every rank must set it alike)
-ENABLED = os.environ.get("GPP_SHARD_PUSH", "0") not in ("", "0")
+ENABLED = settings.ENV_SHARD_PUSH
 #: messages moved by push in this process (tests, bench.py's ``transport``)
 MESSAGES = 0
 

@@ -1,7 +1,18 @@
 """The handful of gpytorch.settings the path touches.  ``fast_computations`` is accepted and ignored: this back end is
 always the exact Cholesky path (the reference forces it with ``fast_computations(log_prob=False)`` at
 models/gpregression.py:127,161 and optim/mll_scipy.py:217; optim/mll_torch.py does not, SURVEY.md hazard B-2)."""
+import os as _os
 from contextlib import contextmanager
+
+# Every environment variable the Python package reads (INTEGRATION.md has the table; the library's own are in csrc/gpp_internal.h,
+# GppEnv), parsed once, when the package is imported: set them before that.
+ENV_COOP_PANEL = _os.environ.get("GPP_COOP_PANEL", "1") != "0"                          # backend.GppContext.coop_panel
+ENV_DAG_SCHED = _os.environ.get("GPP_DAG_SCHED", "1") != "0"                            # backend.GppContext.dag_sched
+ENV_SHARD_LIST = _os.environ.get("GPP_SHARD_LIST", "1") not in ("", "0")                # sharded: the per-rank ticket lists
+ENV_SHARD_WORKERS = int(_os.environ.get("GPP_SHARD_WORKERS", "0"))                      # sharded: executor work-groups (0: by CU count)
+ENV_SHARD_PUSH = _os.environ.get("GPP_SHARD_PUSH", "0") not in ("", "0")                # push.ENABLED: the one-to-all push transport
+ENV_SHARDED_FORCE_COLLECTIVES = _os.environ.get("GPP_SHARDED_FORCE_COLLECTIVES", "0") not in ("", "0")  # sharded: one rank, every collective
+ENV_SHARD_DEBUG = bool(_os.environ.get("GPP_SHARD_DEBUG"))                              # sharded: print a list's time-out status
 
 
 class _Value:
@@ -36,22 +47,6 @@ batched_restarts = _Value(True)
 # launches issued by ~2 ms of Python, ``fit_model_scipy`` captures objective + gradient once as a HIP graph and replays it per
 # evaluation (gp-plus_amd/graphed.py).  ``with settings.graphed_objective(False):`` evaluates eagerly, as the reference does.
 graphed_objective = _Value(True)
-
-
-# Above N = 3840 (where the whole evaluation cannot be one graph) the model's own host code — parameter transforms, manifold map, mean,
-# priors and their backward: 130 (C1) to 172 (C3) element-wise launches per evaluation, gpurun census of round 6 — CAN be replayed as
-# HIP graphs around the library's call (gp-plus_amd/graphed.py::GraphedSegment; gpcore/models.py, gpcore/mlls.py): same kernels, the
-# same numbers bit for bit (tests/test_gpu_graphed.py).  OFF by default, because it does not pay on this stack.  The first form lost
-# 0.2 / 1.5 / 1.9 ms at C3 / C4 / C2: the backward was captured from a stream other than the one the leaves' AccumulateGrad nodes were
-# created on, autograd forked the capture onto that stream (PyTorch's warning "The AccumulateGrad node's stream does not match ..."),
-# and a replayed graph with two branches occupies a second hardware queue — which perturbs the factorisation's CU-masked streams (the
-# effect linalg._forward documents for side streams).  Captured on the warm-up stream, on shadow copies of the parameters, the warning
-# and that loss are gone — and what remains is that a hipGraphLaunch of ~60 small nodes costs about what issuing them does: same box,
-# alternating, three times each: the mixed-input C3 model (172 launches) 20.44 -> 20.15 ms; C4 58.30 -> 58.29; C2 127.40 -> 127.57; the
-# plain 8-input model through bench.py: N = 4096 4.41 -> 5.28 ms, 6144 7.13 -> 10.2 (the launch-per-product range is the most
-# sensitive), 8192 11.85 -> 12.14, 10 000 19.79 -> 19.98, 15 000 57.1 -> 57.3, 20 000 127.5 -> 127.8 (tools/attic/dev/segments_ab*.sh).
-# ``with settings.graphed_segments(True):`` (or GPP_GRAPHED_SEGMENTS=1) switches it on.
-graphed_segments = _Value(__import__("os").environ.get("GPP_GRAPHED_SEGMENTS", "0") not in ("", "0"))
 
 
 # The reference's scipy driver casts every slice of theta to float32 before loading it into the model (optim/mll_scipy.py:32-35

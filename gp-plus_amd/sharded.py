@@ -52,7 +52,6 @@ the RCCL branch runs on a single GPU (tests/test_gpu_sharded.py).
 """
 from __future__ import annotations
 
-import os
 import warnings
 from typing import List, Optional, Tuple
 
@@ -77,7 +76,7 @@ class _Comm:
         self.direct = dist.get_backend(group) == "nccl"  # RCCL moves device memory itself
         # data travels (and is packed / unpacked around the collectives) when there is more than one rank — or always, on
         # request: the RCCL calls, their stream ordering and the buffer reuse then execute in a group of ONE rank too
-        self.travel = self.world > 1 or os.environ.get("GPP_SHARDED_FORCE_COLLECTIVES", "0") not in ("", "0")
+        self.travel = self.world > 1 or settings.ENV_SHARDED_FORCE_COLLECTIVES
         self.calls = 0  # collectives issued (tests)
         # per-collective timing (bench.py --mode sharded): (stage, bytes, start event, end event) on the stream the collective is
         # enqueued on; read out by ``comm_report`` after a synchronisation.  Off unless a log list is attached.
@@ -243,12 +242,6 @@ class _RowEvents:
             if hit is not None and hit[1] is not stream and id(hit[0]) not in seen:
                 seen.add(id(hit[0]))
                 stream.wait_event(hit[0])
-
-
-#: one step of look-ahead in the forward / backward sweeps (the small per-step products on a second stream)
-_SWEEP_LOOKAHEAD = os.environ.get("GPP_SHARD_SWEEP_LOOKAHEAD", "0") not in ("", "0")
-#: entries of the trailing matrix the CU-masked stream takes beside a running panel (the single-GPU driver's GPP_SPLIT_ELEMS)
-_EARLY_ELEMS = int(os.environ.get("GPP_SHARD_EARLY_ELEMS", "0"))
 
 
 def _factor(ctx: GppContext, comm: _Comm, ws: ShardedWorkspace, U, w, sf2, tau, grp, kind, d_split, jitter: float) -> int:
@@ -422,9 +415,7 @@ def _factor(ctx: GppContext, comm: _Comm, ws: ShardedWorkspace, U, w, sf2, tau, 
             break
         # ---- this rank's share of the trailing update A[i, i:] -= U[k, i]^T U[k, i:], i > k -------------------------------
         panel_here = (k + 1) % P == me  # the next diagonal block is factored on THIS GPU while the update runs
-        rem = N - o1
-        extra = max(0, -(-_EARLY_ELEMS // max(rem, 1)) // nb - 2) if panel_here else 0
-        e_end = min(k + 3 + extra, nblk)  # block rows [k+3, e_end) go early; [e_end, nblk) are the bulk
+        e_end = min(k + 3, nblk)  # block rows [e_end, nblk) are the bulk
         if nblk - e_end < 2:
             e_end = nblk
         diag_ready = None
@@ -458,10 +449,8 @@ def _factor(ctx: GppContext, comm: _Comm, ws: ShardedWorkspace, U, w, sf2, tau, 
     return int(info.item())
 
 
-#: GPP_SHARD_LIST=0: the launch-per-product factorisation and forward sweep of rounds 2-4 (also the library's own knob)
-_USE_LIST = os.environ.get("GPP_SHARD_LIST", "1") not in ("", "0")
-#: the factor's mirror beside the list on the copy stream or behind it (GPP_SHARD_MIRROR_BESIDE=1 / 0; default: see _mirror_beside)
-_MIRROR_ENV = os.environ.get("GPP_SHARD_MIRROR_BESIDE", "")
+#: GPP_SHARD_LIST=0: the launch-per-product factorisation and forward sweep of rounds 2-4 (also the library's own switch)
+_USE_LIST = settings.ENV_SHARD_LIST
 
 
 def _mirror_beside(world: int) -> bool:
@@ -471,14 +460,12 @@ def _mirror_beside(world: int) -> bool:
     a rank of a P = 8 run is bound by the chain of panels and messages, which lives on the 32 panel CUs — the executor's
     work-groups fill the other 224 to the last register whether they compute or wait — and the copy stream's strided
     transpositions (up to 150 MB each) landed on those same 32 CUs between the packing copies, the gates and the panel."""
-    if _MIRROR_ENV != "":
-        return _MIRROR_ENV != "0"
     return world <= 1
 #: evaluations whose factorisation + forward sweep ran as a ticket list (tests)
 LIST_EVALS = 0
 BACK_LIST_EVALS = 0
 #: work-groups of the list's executor (0 = two per throughput CU); tests in which several ranks share one GPU pass fewer
-_LIST_WORKERS = int(os.environ.get("GPP_SHARD_WORKERS", "0"))
+_LIST_WORKERS = settings.ENV_SHARD_WORKERS
 
 
 def _factor_list(ctx: GppContext, comm: _Comm, ws: ShardedWorkspace, U, w, sf2, tau, grp, kind, d_split, jitter: float) -> Optional[int]:
@@ -593,7 +580,7 @@ def _factor_list(ctx: GppContext, comm: _Comm, ws: ShardedWorkspace, U, w, sf2, 
     if st == 0:
         global LIST_EVALS
         LIST_EVALS += 1
-    elif st >= INFO_PANEL_TIMEOUT and os.environ.get("GPP_SHARD_DEBUG"):
+    elif st >= INFO_PANEL_TIMEOUT and settings.ENV_SHARD_DEBUG:
         import ctypes
         buf = (ctypes.c_int * 1024)()
         n = ctx.lib.gpp_debug_dag_counters(ctx.h, buf, 1024)
@@ -616,51 +603,29 @@ def _forward(ctx: GppContext, comm: _Comm, ws: ShardedWorkspace) -> None:
     launch per product:
         Y_j[c] = -X_jj S_j[c]                (X_jj^T = the mirror in the upper part of the diagonal block; finished rows go to ``Kc``;
                                               the own block of the step is Y_j[j] = X_jj itself)
-        S_k[c] += L[k, j] Y_j[c],  k > j     (L[k, j] = U[j, k]^T, shared by the whole batch; the sums S live in ``Lc``)
-    with one step of look-ahead: the update's first block row (k = j+1) is issued on its own, and the small product of step j+1
-    then runs on a second stream beside the rest of step j's update instead of alone on the chip."""
+        S_k[c] += L[k, j] Y_j[c],  k > j     (L[k, j] = U[j, k]^T, shared by the whole batch; the sums S live in ``Lc``)"""
     N, offs, P, me, nb = ws.N, ws.offs, comm.world, comm.rank, ws.nb
     nblk = len(offs) - 1
     A, Lc, Kc = ws.A, ws.Lc, ws.Kc
     if _first_owned(ws, comm) is None:
         return
-    main = torch.cuda.current_stream(ctx.index)
-    aux = ctx.internal_streams()[2] if _SWEEP_LOOKAHEAD else main
-    aux.wait_stream(main)
     for c in range(me, nblk - 1, P):  # the sums of the owned column blocks start from zero
         Lc[offs[c + 1]:N, ws.col(c)].zero_()
-    row_done = torch.cuda.Event()  # block row j of the sums is complete
-    row_done.record(main)
     for j in range(me, nblk):
         oj, oj1 = offs[j], offs[j + 1]
         nbj = oj1 - oj
         nleft = len(range(me, j, P))
         own = j % P == me
         Xjj = ws.dblk(j)
-        with torch.cuda.stream(aux):
-            aux.wait_event(row_done)
-            if nleft > 0:  # (the owned blocks left of j are the first nleft compact blocks, at the column spacing nb)
-                ctx.gemm_batched(1, 0, nbj, nb, nbj, -1.0, Xjj, 0, Lc[oj:oj1, 0:nb], nb, 0.0, Kc[oj:oj1, 0:nb], nb, nleft,
-                                 a_mask=1, khi_mode=1)
-            if own:  # Y_j[j] = X_jj: lower triangle, zeros above (the diagonal block's slot also holds the mirror)
-                Kc[oj:oj1, ws.col(j)].copy_(Xjj)
-                Kc[oj:oj1, ws.col(j)].tril_()
-            y_done = torch.cuda.Event()
-            y_done.record(aux)
+        if nleft > 0:  # (the owned blocks left of j are the first nleft compact blocks, at the column spacing nb)
+            ctx.gemm_batched(1, 0, nbj, nb, nbj, -1.0, Xjj, 0, Lc[oj:oj1, 0:nb], nb, 0.0, Kc[oj:oj1, 0:nb], nb, nleft,
+                             a_mask=1, khi_mode=1)
+        if own:  # Y_j[j] = X_jj: lower triangle, zeros above (the diagonal block's slot also holds the mirror)
+            Kc[oj:oj1, ws.col(j)].copy_(Xjj)
+            Kc[oj:oj1, ws.col(j)].tril_()
         nb_all = nleft + (1 if own else 0)
         if oj1 < N and nb_all > 0:
-            main.wait_event(y_done)
-            oj2 = offs[j + 2]
-            for r0, r1 in (((oj1, oj2), (oj2, N)) if _SWEEP_LOOKAHEAD else ((oj1, N),)):  # block row j+1 first: the next step's small product waits for it only
-                if r1 > r0:
-                    ctx.gemm_batched(1, 0, r1 - r0, nb, nbj, 1.0, A[oj:oj1, r0:r1], 0, Kc[oj:oj1, 0:nb], nb, 1.0,
-                                     Lc[r0:r1, 0:nb], nb, nb_all)
-                if r1 == oj2 and _SWEEP_LOOKAHEAD:
-                    row_done = torch.cuda.Event()
-                    row_done.record(main)
-        else:
-            main.wait_event(y_done)
-    main.wait_stream(aux)
+            ctx.gemm_batched(1, 0, N - oj1, nb, nbj, 1.0, A[oj:oj1, oj1:N], 0, Kc[oj:oj1, 0:nb], nb, 1.0, Lc[oj1:N, 0:nb], nb, nb_all)
 
 
 def _vectors(ctx: GppContext, comm: _Comm, ws: ShardedWorkspace, need_alpha: bool) -> None:
@@ -681,8 +646,7 @@ def _backward(ctx: GppContext, comm: _Comm, ws: ShardedWorkspace) -> int:
     one up:   Z_j = X_jj^T Y_j   (X_jj = L_jj^-1: the lower part of ``D[j]``), then the right-looking update
     Y_i -= U[i, j] Z_j of every block row c <= i < j — ONE TN GEMM per step over the lower-triangular tiles of the owned
     column blocks, its row-contiguous left operand being the factor's mirror L[j, i] in the strict lower triangle of ``A``.
-    One step of look-ahead as in ``_forward``: block row j-1 of the update first, the small products of step j-1 on a second
-    stream beside the rest.  No communication (bullet 4).  Returns 0, or the status of a ticket list that timed out
+    No communication (bullet 4).  Returns 0, or the status of a ticket list that timed out
     (agreed on by all ranks; Kc is then destroyed and the caller evaluates again)."""
     offs, P, me, nb = ws.offs, comm.world, comm.rank, ws.nb
     nblk = len(offs) - 1
@@ -707,7 +671,7 @@ def _backward(ctx: GppContext, comm: _Comm, ws: ShardedWorkspace) -> int:
         for c in range(me, nblk, P):
             Lc[offs[c]:offs[c + 1], ws.col(c)].zero_()
         used = ctx.shard_back_list(ws.N, nb, me, P, A, Kc, Lc, ws.D, ws.info[0:1], _LIST_WORKERS and 2 * _LIST_WORKERS)
-        if not used and os.environ.get("GPP_SHARD_DEBUG"):
+        if not used and settings.ENV_SHARD_DEBUG:
             print(f"[sharded rank {me}] back-substitution list: not used", flush=True)
         if used:
             # (a wait inside the list that ran out of its budget must not pass as a result — and must be EVERY rank's status: the
@@ -715,46 +679,29 @@ def _backward(ctx: GppContext, comm: _Comm, ws: ShardedWorkspace) -> int:
             #  as for the factor list; the caller then repeats the evaluation on the launch path, all ranks together.)
             mine = int(ws.info[0].item())
             st = agreed(mine)
-            if st and os.environ.get("GPP_SHARD_DEBUG"):
+            if st and settings.ENV_SHARD_DEBUG:
                 print(f"[sharded rank {me}] back-substitution list: status {st:#x} (mine {mine:#x})", flush=True)
             if st == 0:
                 global BACK_LIST_EVALS
                 BACK_LIST_EVALS += 1
             return st
     oc0 = offs[me]
-    main = torch.cuda.current_stream(ctx.index)
-    aux = ctx.internal_streams()[2] if _SWEEP_LOOKAHEAD else main
-    row_done = torch.cuda.Event()
-    row_done.record(main)
     for j in range(nblk - 1, me - 1, -1):
         oj, oj1 = offs[j], offs[j + 1]
         nbj = oj1 - oj
         nleft = len(range(me, j, P))  # owned column blocks strictly left of j
         Xjj = ws.dblk(j)
-        with torch.cuda.stream(aux):
-            aux.wait_event(row_done)
-            if nleft > 0:
-                ctx.gemm_batched(1, 0, nbj, nb, nbj, 1.0, Xjj, 0, Kc[oj:oj1, 0:nb], nb, 0.0, Lc[oj:oj1, 0:nb], nb, nleft,
-                                 a_mask=2, klo_mode=1)
-            if j % P == me:
-                # the diagonal block of Ky^-1: both operands lower triangular, only its lower part is wanted (and only the lower
-                # part of Y_j[j] is kept up to date) — the LAUUM shape; through the scratch, the product cannot run in place
-                d = ws.dscr[:nbj, :nbj]
-                ctx.gemm(1, 0, nbj, nbj, nbj, 1.0, Xjj, Kc[oj:oj1, ws.col(j)], 0.0, d, a_mask=2, b_mask=2, klo_mode=3, c_tri=1)
-                Lc[oj:oj1, ws.col(j)].copy_(d)
-            z_done = torch.cuda.Event()
-            z_done.record(aux)
-        main.wait_event(z_done)
         if nleft > 0:
-            M = oj - oc0
-            lo = max(offs[j - 1] - oc0, 0)
-            for r0, r1 in (((lo, M), (0, lo)) if _SWEEP_LOOKAHEAD else ((0, M),)):  # block row j-1 first
-                if r1 > r0:
-                    ctx.gemm_lower_cols(A[oj:oj1, oc0:oj], Lc[oj:oj1], Kc[oc0:oj], -1.0, 1.0, nb, me, me, P, r0, r1, compact=True)
-                if r0 == lo and _SWEEP_LOOKAHEAD:
-                    row_done = torch.cuda.Event()
-                    row_done.record(main)
-    main.wait_stream(aux)
+            ctx.gemm_batched(1, 0, nbj, nb, nbj, 1.0, Xjj, 0, Kc[oj:oj1, 0:nb], nb, 0.0, Lc[oj:oj1, 0:nb], nb, nleft,
+                             a_mask=2, klo_mode=1)
+        if j % P == me:
+            # the diagonal block of Ky^-1: both operands lower triangular, only its lower part is wanted (and only the lower
+            # part of Y_j[j] is kept up to date) — the LAUUM shape; through the scratch, the product cannot run in place
+            d = ws.dscr[:nbj, :nbj]
+            ctx.gemm(1, 0, nbj, nbj, nbj, 1.0, Xjj, Kc[oj:oj1, ws.col(j)], 0.0, d, a_mask=2, b_mask=2, klo_mode=3, c_tri=1)
+            Lc[oj:oj1, ws.col(j)].copy_(d)
+        if nleft > 0:
+            ctx.gemm_lower_cols(A[oj:oj1, oc0:oj], Lc[oj:oj1], Kc[oc0:oj], -1.0, 1.0, nb, me, me, P, 0, oj - oc0, compact=True)
     return agreed(0)
 
 

@@ -79,7 +79,7 @@ int gpp_internal_stream(gpp_handle_t h, int which, void** out);
 #define GPP_OPT_PANEL_FAULT 2
 #define GPP_OPT_PANEL_TIMEOUT_MS 3
 #define GPP_OPT_EXEC_SCHED 4 /* (round 4's statically scheduled executor, replaced by the DAG executor: an alias of GPP_OPT_DAG_SCHED) */
-#define GPP_OPT_DAG_SCHED 5  /* default 1 (0 with GPP_DAG_SCHED=0): factorisation (and, for 6912 <= N <= GPP_DAG_INV_MAX = 19456, the whole inverse
+#define GPP_OPT_DAG_SCHED 5  /* default 1 (0 with GPP_DAG_SCHED=0): factorisation (and, for 6912 <= N <= 19456, the whole inverse
                               * beside it) as ONE list of tile tasks in topological order that persistent work-groups take by atomic
                               * ticket (gpp_dag.hip, gpp_dag_f64) — needs no co-residency of its work-groups; the diagonal blocks still
                               * run as cooperative panel launches (GPP_OPT_COOP_PANEL) */

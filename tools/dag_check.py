@@ -1,6 +1,6 @@
 """Correctness + timing of the DAG executor's factorisation (+ inverse) against torch.linalg.cholesky, and per-task traces (dev tool).
 usage: python tools/dag_check.py N [N ...]      env: TRACE=1 per-kind task statistics of the last run, CHECK=0 timing only,
-       REPS=n timed repetitions; the knobs of gpp_api.hip / gpp_dag.hip apply (GPP_DAG_SCHED, GPP_DAG_NB, GPP_DAG_CHAIN_TILE, ...)."""
+       REPS=n timed repetitions; the library's environment variables apply (GPP_DAG_SCHED, GPP_DAG_PHASED, ...: INTEGRATION.md)."""
 import ctypes
 import os
 import sys
