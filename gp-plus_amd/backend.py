@@ -23,6 +23,8 @@ KIND_RBF, KIND_MATERN32, KIND_MATERN52 = 0, 1, 2
 UPLO_FULL, UPLO_LOWER, UPLO_UPPER = 0, 1, 2
 OPT_COOP_PANEL, OPT_PANEL_FAULT, OPT_PANEL_TIMEOUT_MS, OPT_EXEC_SCHED, OPT_DAG_SCHED = 1, 2, 3, 4, 5  # gpp_set_option (include/gpp.h)
 OP_MLL_EVAL, OP_PREDICT, OP_PREDICT_GRAD = 0, 1, 2
+NOT_SUPPORTED = 2001  # GPP_NOT_SUPPORTED: gpp_lauum_grad does not take these arguments, nothing was enqueued
+NO_WORKSPACE = 2002   # GPP_NO_WORKSPACE: gpp_lauum_grad found no (or too small a) scratch workspace on the handle
 #: the tile kernels stage at most this many feature columns (manifold + quantitative) per point in LDS (gpp_build.hip DMAX)
 MAX_FEATURES = 64
 
@@ -233,6 +235,27 @@ class GppContext:
                                         _ld(T), info.data_ptr()), "gpp_potrf_ws")
 
     @_on_own_device
+    def build_potrf(self, U, w, sf2, tau, grp, A, Linv, info, T, *, jitter=0.0, kind=KIND_RBF, d_split=0):
+        """``kernel_build(..., uplo=UPLO_UPPER)`` into ``A`` followed by ``potrf(A, Linv, info, T)`` as ONE call
+        (gpp_build_potrf_ws): the same bits; where the ticket list runs, most of Ky is built beside the first panel."""
+        N, D = U.shape
+        _check_features(D)
+        for t, n in ((U, "U"), (w, "w"), (sf2, "sf2"), (A, "A"), (Linv, "Linv"), (T, "T")):
+            _need(t, torch.float64, n)
+        _need(info, torch.int32, "info")
+        if tau is not None:
+            _need(tau, torch.float64, "tau")
+        S = 0 if tau is None else tau.numel()
+        if grp is not None:
+            self._check_groups(grp, N, S)
+        if not U.is_contiguous():
+            raise GppError("U must be contiguous")
+        self._stream()
+        check(self.lib.gpp_build_potrf_ws(self.h, U.data_ptr(), N, D, w.data_ptr(), sf2.data_ptr(), _ptr(tau), _ptr(grp), S,
+                                          float(jitter), kind, d_split, A.data_ptr(), _ld(A), Linv.data_ptr(), _ld(Linv),
+                                          T.data_ptr(), _ld(T), info.data_ptr()), "gpp_build_potrf_ws")
+
+    @_on_own_device
     def trtri(self, U, Linv, T):
         self._stream()
         check(self.lib.gpp_trtri(self.h, U.data_ptr(), U.shape[0], _ld(U), Linv.data_ptr(), _ld(Linv), T.data_ptr(), _ld(T)),
@@ -242,6 +265,31 @@ class GppContext:
     def lauum(self, Linv, Kinv):
         self._stream()
         check(self.lib.gpp_lauum(self.h, Linv.data_ptr(), Linv.shape[0], _ld(Linv), Kinv.data_ptr(), _ld(Kinv)), "gpp_lauum")
+
+    @_on_own_device
+    def lauum_grad(self, Linv, U, w, sf2, grp, S, alpha, dU, g_w, g_sf2, g_tau, *, kind=KIND_RBF) -> bool:
+        """LAUUM with the gradient reduction as its epilogue (gpp_lauum_grad): g_w, g_sf2, g_tau as ``lauum`` + ``grad_reduce``
+        define them, without Ky^-1 in memory.  False: not supported for these arguments (kind, D > 16, dU > 0) — nothing was
+        enqueued and the caller runs the pair."""
+        N, D = U.shape
+        for t, n in ((Linv, "Linv"), (U, "U"), (w, "w"), (sf2, "sf2"), (alpha, "alpha"), (g_w, "g_w"), (g_sf2, "g_sf2"),
+                     (g_tau, "g_tau")):
+            _need(t, torch.float64, n)
+        if grp is not None:
+            self._check_groups(grp, N, S)
+        if not U.is_contiguous():
+            raise GppError("U must be contiguous")
+        self.ensure_workspace(OP_MLL_EVAL, N, 0, D, S)
+        self._stream()
+        status = self.lib.gpp_lauum_grad(self.h, Linv.data_ptr(), N, _ld(Linv), U.data_ptr(), D, w.data_ptr(), sf2.data_ptr(),
+                                         _ptr(grp), S, kind, dU, alpha.data_ptr(), g_w.data_ptr(), g_sf2.data_ptr(),
+                                         g_tau.data_ptr())
+        if status == NOT_SUPPORTED:
+            return False
+        if status == NO_WORKSPACE:
+            raise GppError("gpp_lauum_grad: the handle's scratch workspace is missing or too small")
+        check(status, "gpp_lauum_grad")
+        return True
 
     @_on_own_device
     def post_cov_train(self, Kinv, tau, grp, d, out, *, jitter=0.0):

@@ -636,7 +636,21 @@ constexpr int64_t DAG_MAX_N = 65536;
 constexpr int64_t DAG_INV_MAX_N = 19456;
 constexpr int64_t DAG_NB = 1024;  // block-row height of the single-GPU list
 
-hipError_t potrf_dag(gpp_handle_s* h, const Ctx& cm, int64_t N, double* T, int64_t ldt, bool* used) {
+// `build` (gpp_build_potrf_ws; may be null): enqueues the covariance build of the columns [c0, c1) of A's upper triangle on a stream.
+// The first panel reads the leading diagonal block only: its columns are built on the caller's stream, the rest on the update
+// stream in front of the executor's launch — beside panel 0, on the CUs the panel does not use.  Every task of the list follows that
+// build in stream order except those a filler launch takes on the PANEL stream, which therefore waits for it behind panel 0.
+// Nothing is built when the list does not apply (*used = false: nothing was enqueued at all).
+struct KyBuild {
+  const double *U, *w, *sf2, *tau;
+  const int32_t* grp;
+  int D, S, kind, d_split;
+  double jitter;
+  hipError_t operator()(hipStream_t s, const Ctx& c, int64_t N, int64_t c0, int64_t c1) const {
+    return gpp_launch_kernel_build(s, U, N, D, w, sf2, tau, grp, S, jitter, kind, d_split, GPP_UPLO_UPPER, c.A, c.ld, c0, c1 - c0);
+  }
+};
+hipError_t potrf_dag(gpp_handle_s* h, const Ctx& cm, int64_t N, double* T, int64_t ldt, bool* used, const KyBuild* build = nullptr) {
   *used = false;
   if (!gpp_env().dag_sched || !h->dag_sched || !h->coop_panel || !T || N < DAG_MIN_N || N > DAG_MAX_N) return hipSuccess;
   HIP_TRY(ensure_streams(h));
@@ -683,6 +697,9 @@ hipError_t potrf_dag(gpp_handle_s* h, const Ctx& cm, int64_t N, double* T, int64
   HIP_TRY(gpp_launch_fill_i32(cm.s, P->d_counters, P->ncounters, 0));
   DagBases bases{{reinterpret_cast<char*>(cm.A), reinterpret_cast<char*>(cm.Li), reinterpret_cast<char*>(T), nullptr}};
   HIP_TRY(gpp_launch_dag_bind(cm.s, P->d_groups, P->d_groups_abs, (int)P->groups.size(), bases));
+  const int64_t lead = std::min<int64_t>((int64_t)P->tb[1] * NBLK, N);  // columns of the first diagonal block
+  const bool split_build = build && !gpp_env().dag_phased && lead < N;
+  if (build) HIP_TRY((*build)(cm.s, cm, N, 0, split_build ? lead : N));
   hipEvent_t ev = next_event(h);
   HIP_TRY(hipEventRecord(ev, cm.s));  // inputs (kernel build), cleared counters and bound groups are ready
   HIP_TRY(hipStreamWaitEvent(cp.s, ev, 0));
@@ -714,6 +731,13 @@ hipError_t potrf_dag(gpp_handle_s* h, const Ctx& cm, int64_t N, double* T, int64
     *used = true;
     return hipSuccess;
   }
+  hipEvent_t built = nullptr;
+  if (split_build) {
+    ++h->split_builds;
+    HIP_TRY((*build)(cu.s, cu, N, lead, N));
+    built = next_event(h);
+    HIP_TRY(hipEventRecord(built, cu.s));
+  }
   HIP_TRY(gpp_launch_dag(cu.s, 2 * (h->ncu - h->panel_cus), dl));
   // (the executor is running from here on: a failure below raises the abort word and still joins the streams — its work-groups
   //  would otherwise spin for the whole budget behind a call that has already returned an error)
@@ -725,6 +749,10 @@ hipError_t potrf_dag(gpp_handle_s* h, const Ctx& cm, int64_t N, double* T, int64
       } else if (op.kind == 1) {
         const int64_t rows = std::min<int64_t>((int64_t)P->tb[op.arg + 1] * NBLK, N) - o;
         HIP_TRY(launch_panel(h, cp, o, rows, h->panel_cus));
+        if (built) {  // behind panel 0: whatever this stream runs next (signal, fillers) may let a task read the rest of Ky
+          HIP_TRY(hipStreamWaitEvent(cp.s, built, 0));
+          built = nullptr;
+        }
       } else if (op.kind == 2) {
         HIP_TRY(gpp_launch_exec_signal(cp.s, P->d_counters, P->c_pd + op.arg));
       } else {
@@ -796,6 +824,8 @@ static DagPlan* dag_mru(gpp_handle_t h) {
       if (h->dag_plans[i] && (!P || h->dag_plans[i]->stamp > P->stamp)) P = h->dag_plans[i];
   return P;
 }
+// calls of gpp_build_potrf_ws on this handle that built Ky split around panel 0 (tests: the split path really ran)
+int gpp_debug_split_builds(gpp_handle_t h) { return h ? h->split_builds : -1; }
 // info[0..9]: tasks, groups, blocks, tiles per side, counters, simulated us, simulated busy per mille, flags, rows of the leading block
 // of the inverse built inside the list (N: all of it, 0: none), N
 int gpp_debug_dag_info(gpp_handle_t h, int64_t* info8) {
@@ -1196,7 +1226,7 @@ int gpp_shard_back_list(gpp_handle_t h, int64_t N, int64_t nb, int rank, int nra
 size_t gpp_workspace_bytes(gpp_handle_t h, int op, int64_t N, int64_t M, int D, int S) {
   (void)h;
   if (op == GPP_OP_MLL_EVAL) {
-    return std::max(gpp_grad_ws_bytes(N, D, S, D), gpp_trmv_t_ws_bytes(N)) + 256;
+    return std::max({gpp_grad_ws_bytes(N, D, S, D), gpp_trmv_t_ws_bytes(N), gpp_lauum_grad_ws_bytes(N, D)}) + 256;
   }
   if (op == GPP_OP_PREDICT) return 256;
   if (op == GPP_OP_PREDICT_GRAD) return gpp_pgrad_ws_bytes(M, N, D, D, S) + 256;
@@ -1250,8 +1280,8 @@ int gpp_cross_kernel(gpp_handle_t h, const double* Ua, int64_t Ma, const double*
   return 0;
 }
 
-int gpp_potrf_ws(gpp_handle_t h, double* A, int64_t N, int64_t ld, double* Linv, int64_t ldi, double* T, int64_t ldt,
-                 int32_t* info_dev) {
+static int potrf_ws_impl(gpp_handle_t h, double* A, int64_t N, int64_t ld, double* Linv, int64_t ldi, double* T, int64_t ldt,
+                         int32_t* info_dev, const KyBuild* build) {
   if (!h) return -1;
   if (N < 0) return -3;
   if (int r = check_mat(A, ld, N, 2)) return r;
@@ -1268,8 +1298,17 @@ int gpp_potrf_ws(gpp_handle_t h, double* A, int64_t N, int64_t ld, double* Linv,
   //  4.53 at 5120, a tie at 6144; the look-ahead wins from there: 8.6 vs 10.1 ms at 8192.  With one, i.e. with bordering: BORDER_MIN_N)
   const int64_t la_min = T ? BORDER_MIN_N : 6 * LOOKAHEAD_NB;
   bool dag_used = false;
-  GPP_TRY(potrf_dag(h, c, N, T, ldt, &dag_used));
-  if (dag_used) return 0;
+  // Under stream capture the call IS the two plain calls: all of Ky is built on the caller's stream FIRST, and whatever path
+  // gpp_potrf_ws takes (the ticket list included) then finds it complete, exactly as behind gpp_kernel_build.
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (build) GPP_TRY(hipStreamIsCapturing(h->stream, &cap));
+  if (build && cap != hipStreamCaptureStatusNone) {
+    GPP_TRY((*build)(h->stream, c, N, 0, N));
+    build = nullptr;
+  }
+  GPP_TRY(potrf_dag(h, c, N, T, ldt, &dag_used, build));
+  if (dag_used) return 0;  // (with `build`: Ky was built inside, split around panel 0)
+  if (build) GPP_TRY((*build)(h->stream, c, N, 0, N));  // the list does not apply: gpp_kernel_build, then the paths below
   if (N >= la_min) {
     GPP_TRY(potrf_lookahead(h, c, N, LOOKAHEAD_NB, T, ldt));
   } else if (panel_fits(h, N)) {
@@ -1297,6 +1336,34 @@ int gpp_potrf_ws(gpp_handle_t h, double* A, int64_t N, int64_t ld, double* Linv,
     GPP_TRY(potrf_rec(c, 0, N));
   }
   return 0;
+}
+
+int gpp_potrf_ws(gpp_handle_t h, double* A, int64_t N, int64_t ld, double* Linv, int64_t ldi, double* T, int64_t ldt,
+                 int32_t* info_dev) {
+  return potrf_ws_impl(h, A, N, ld, Linv, ldi, T, ldt, info_dev, nullptr);
+}
+
+int gpp_build_potrf_ws(gpp_handle_t h, const double* U, int64_t N, int D, const double* w, const double* sf2, const double* tau,
+                       const int32_t* grp, int S, double jitter, int kind, int d_split, double* A, int64_t ld, double* Linv,
+                       int64_t ldi, double* T, int64_t ldt, int32_t* info_dev) {
+  if (!h) return -1;
+  if (!U) return -2;
+  if (N < 0) return -3;
+  if (D < 1 || D > 64) return -4;
+  if (!w) return -5;
+  if (!sf2) return -6;
+  if (tau && S < 1) return -9;
+  if (kind < 0 || kind > 2) return -11;
+  if (d_split < 0 || d_split > D) return -12;
+  if (int r = check_mat(A, ld, N, 13)) return r;
+  if (int r = check_mat(Linv, ldi, N, 15)) return r;
+  if (T) {
+    if (int r = check_mat(T, ldt, N, 17)) return r;
+  }
+  if (!info_dev) return -19;
+  const KyBuild build{U, w, sf2, tau, grp, D, S, kind, d_split, jitter};
+  // (every argument potrf_ws_impl checks was checked above under THIS function's numbering: what it returns is 0 or a HIP status)
+  return potrf_ws_impl(h, A, N, ld, Linv, ldi, T, ldt, info_dev, &build);
 }
 
 int gpp_potrf(gpp_handle_t h, double* A, int64_t N, int64_t ld, double* Linv, int64_t ldi, int32_t* info_dev) {
@@ -1340,6 +1407,35 @@ int gpp_lauum(gpp_handle_t h, const double* Linv, int64_t N, int64_t ldi, double
   // 0.278, 4096 0.742 / 0.502 / 0.610, 6144 1.38 / 1.55 / 1.94)
   const int t = N <= 2560 ? 32 : N <= 5120 ? 64 : NBLK;
   GPP_TRY(gpp_launch_gemm(h->stream, 2, g, 1, t, t));
+  return 0;
+}
+
+int gpp_lauum_grad(gpp_handle_t h, const double* Linv, int64_t N, int64_t ldi, const double* U, int D, const double* w,
+                   const double* sf2, const int32_t* grp, int S, int kind, int dU, const double* alpha, double* g_w,
+                   double* g_sf2, double* g_tau) {
+  if (!h) return -1;
+  if (N < 0) return -3;
+  if (int r = check_mat(Linv, ldi, N, 2)) return r;
+  if (!U) return -5;
+  if (D < 1 || D > 64) return -6;
+  if (!w) return -7;
+  if (!sf2) return -8;
+  if (S < 1 || S > 64) return -10;
+  if (kind < 0 || kind > 2) return -11;
+  if (dU < 0 || dU > D) return -12;
+  if (!alpha) return -13;
+  if (!g_w) return -14;
+  if (!g_sf2) return -15;
+  if (!g_tau) return -16;
+  if (kind != GPP_KIND_RBF || D > 16 || dU != 0) return GPP_NOT_SUPPORTED;
+  if (!h->ws || h->ws_bytes < gpp_lauum_grad_ws_bytes(N, D)) return GPP_NO_WORKSPACE;
+  GemmArgs g = mk(Linv, ldi, Linv, ldi, nullptr, ldi, N, N, N, 1.0, 0.0);
+  g.a_mask = 2; g.b_mask = 2; g.klo_mode = 3; g.c_lower = 1;
+  const int64_t tiles = (N + NBLK - 1) / NBLK, nrec = tiles * (tiles + 1) / 2;
+  double* rec = reinterpret_cast<double*>(h->ws);
+  double* wdiag = rec + nrec * (D + 1);
+  GPP_TRY(gpp_launch_lauum_grad(h->stream, g, GradEpiArgs{U, w, sf2, alpha, rec, wdiag, D}));
+  GPP_TRY(gpp_launch_grad_finish(h->stream, rec, nrec, D, S, wdiag, grp, N, g_w, g_sf2, g_tau));
   return 0;
 }
 

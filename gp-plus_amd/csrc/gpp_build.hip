@@ -190,6 +190,15 @@ hipError_t gpp_launch_kernel_build(hipStream_t s, const double* U, int64_t N, in
   if (uplo) nt = tr1 * (tr1 + 1) / 2 - tr0 * (tr0 + 1) / 2;
   else nt = (tr1 - tr0) * tiles_n;
   // rows of the last tile row beyond row0+nrows are cut by passing Ma = row0+nrows
+  // (upper mode enumerates the mirrored tiles: [row0, row0 + nrows) is then a range of COLUMNS, every row above the diagonal of
+  //  which is written — the range must end on a tile edge or at N)
+  if (uplo == GPP_UPLO_UPPER && (row0 != 0 || nrows != N)) {
+    if (row0 % TB != 0 || ((row0 + nrows) % TB != 0 && row0 + nrows != N)) return hipErrorInvalidValue;
+    auto* fu = kind == 0 ? gpp_cov_tile<false> : gpp_cov_tile<true>;
+    hipLaunchKernelGGL(fu, dim3((unsigned)nt, (unsigned)batch), dim3(256), (size_t)2 * D * TB * sizeof(double), s, U, N, U, N, D, w, sf2, tau,
+                       grp, jitter, kind, d_split, uplo, 1, Ky, ld, (int64_t)0, tiles_n, tr0, sU, sK, S);
+    return hipGetLastError();
+  }
   // (same box, A/B twice at N = 20000: 0.496 / 0.540 ms with the RBF instantiation against 0.575 / 0.594 with the general one)
   auto* fn = kind == 0 ? gpp_cov_tile<false> : gpp_cov_tile<true>;
   hipLaunchKernelGGL(fn, dim3((unsigned)nt, (unsigned)batch), dim3(256), (size_t)2 * D * TB * sizeof(double), s, U, row0 + nrows, U, N, D, w, sf2, tau,

@@ -191,12 +191,14 @@ __device__ __forceinline__ void load_fast(const double* __restrict__ ubase, cons
 struct GemmNoHook {
   __device__ __forceinline__ void operator()() const {}
 };
+// (`epi`: anything but GemmStoreC replaces the store of C — it is handed the wave's accumulators once the main loop's LDS is free)
+struct GemmStoreC {};
 // (`before_epilogue`: called by every thread after the last MFMA and before the first access to C — the DAG executor issues its
 //  next ticket's atomic there, so that its latency runs under the epilogue)
-template <int VAR, int WTM, int WTN, int TAG, int BK, int NBUF, int WR, class P, class H = GemmNoHook>
+template <int VAR, int WTM, int WTN, int TAG, int BK, int NBUF, int WR, class P, class H = GemmNoHook, class E = GemmStoreC>
 __device__ __forceinline__ void gemm_tile(const P& p, const int tm, const int tn, const double* __restrict__ A,
                                           const double* __restrict__ B, double* __restrict__ C, double* C2,
-                                          double* __restrict__ smem, H before_epilogue = H()) {
+                                          double* __restrict__ smem, H before_epilogue = H(), const E& epi = E()) {
   static_assert(BK == 16 || VAR == 2, "wide K chunks are implemented for row-contiguous (TN) operands only");
   static_assert(BK % 16 == 0 && (NBUF == 1 || NBUF == 2), "bad staging parameters");
   static_assert(WR == 2 || (WR == 4 && VAR == 2 && BK == 16 && NBUF == 2 && WTM == 64 && WTN == 64), "the tall tile is TN only");
@@ -376,9 +378,9 @@ __device__ __forceinline__ void gemm_tile(const P& p, const int tm, const int tn
       load_fast<NVB>(ubaseB + (int64_t)kb * stepB, offb, rb);
       // raised wave priority around the MFMA phase: +2.3 % for LAUUM (TAG 1: 63.95 -> 65.4 TFLOP/s, same box), nothing
       // for gpp_trtri's masked merges, -3 % for the look-ahead factorisation's concurrent streams (both TAG 0)
-      if constexpr (TAG == 1) __builtin_amdgcn_s_setprio(1);
+      if constexpr (TAG != 0) __builtin_amdgcn_s_setprio(1);
       compute(cur);
-      if constexpr (TAG == 1) __builtin_amdgcn_s_setprio(0);
+      if constexpr (TAG != 0) __builtin_amdgcn_s_setprio(0);
       if (NBUF == 1) __syncthreads();
       store_mc<TM, BK, false, NTH>(smem + nxt * (OPA + OPB), tid, ra, 0);
       store_mc<TN, BK, false, NTH>(smem + nxt * (OPA + OPB) + OPA, tid, rb, 0);
@@ -387,6 +389,11 @@ __device__ __forceinline__ void gemm_tile(const P& p, const int tm, const int tn
   }
   for (; c < nch; ++c) general_iter(c);
   before_epilogue();
+  if constexpr (!__is_same(E, GemmStoreC)) {
+    static_assert(VAR == 2 && WTM == 64 && WTN == 64 && WR == 2, "accumulator epilogues are written for the big TN tile");
+    epi(acc4, row0, col0, p.M, smem);  // (every wave is past the barrier behind the last chunk's LDS reads)
+    return;
+  }
 
   // epilogue: slab (a,b) holds C[row0+wm+4a+(l>>4)][col0+wn+16b+(l&15)].  The beta path first issues all C loads of a
   // group of slabs (clamped addresses, no branches around loads) and only then combines and stores.
@@ -493,6 +500,152 @@ __global__ __launch_bounds__(128 * WR, ((VAR == 2 && !(BK > 16 && WTM >= 64)) ||
                                              p.C + bi * p.sC + (int64_t)blockIdx.z * p.zC,
                                              p.C2 ? p.C2 + bi * p.sC2 + (int64_t)blockIdx.z * p.zC2 : nullptr, smem);
 
+}
+
+// ---- LAUUM with the gradient reduction as its epilogue (gpp_lauum_grad in gpp.h) ---------------------------------------------
+// The accumulators of a lower-triangular 128 x 128 tile of Ky^-1 = Linv^T Linv never reach memory: each entry goes straight into
+// the sums gpp_grad_tiles (gpp_reduce.hip) defines — W_ij = 0.5 (alpha_i alpha_j - Kinv_ij), mult = 2 below the diagonal,
+//    g_w[d] += mult W_ij sf2 k_ij (-(u_id - u_jd)^2)        g_sf2 += mult W_ij k_ij        wdiag[i] = W_ii
+// with k_ij = exp(-sum_d w_d (u_id - u_jd)^2) recomputed from the tile's raw feature rows / columns, which are staged with the
+// alpha segments in the LDS the main loop has finished with.  A lane holds rows 16 a4 + 4 v + (l >> 4) and columns 16 b + (l & 15)
+// of its wave's quadrant.  The arithmetic runs in a ROLLED loop over half-slabs of 2 rows x 4 columns per lane (fully unrolled
+// over the 64 entries it is ~40 KiB of code per tile): the 16 values of slab a4 pass through lane-private LDS slots, which turns
+// the accumulator index into an address (no barrier: a lane reads back only what it wrote).
+// Deterministic: per-lane sums in a fixed order, a fixed butterfly over each wave, the four wave sums added in order, ONE record
+// of D + 1 doubles per tile (every slot written exactly once), summed by gpp_grad_finish in a fixed order.
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+template <int DT>
+struct GradEpilogue {
+  GradEpiArgs e;
+  int tile;
+  static constexpr int T = 128;
+  static constexpr int FIXED = 2 * DT * T + 2 * T + DT + 4 * (DT + 1);  // doubles in front of the slab
+  static constexpr int SLAB = (FIXED + 1) & ~1;
+  static_assert((SLAB + 16 * 256) * sizeof(double) <= 2 * 2 * BK16 * ldt_mc(T) * sizeof(double), "the epilogue lives in the main loop's LDS");
+  __device__ __forceinline__ void operator()(const v4d (&acc4)[4][4], int row0, int col0, int N, double* __restrict__ smem) const {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64, li = lane & 15, lk = lane >> 4;
+    const int D = e.D;
+    double* __restrict__ sa = smem;            // raw features of the tile's rows, [d][r]
+    double* __restrict__ sb = sa + DT * T;     // ... of its columns
+    double* __restrict__ sal_a = sb + DT * T;  // alpha of the rows / columns
+    double* __restrict__ sal_b = sal_a + T;
+    double* __restrict__ sw = sal_b + T;
+    double* __restrict__ red = sw + DT;        // [4 waves][DT + 1]
+    double* __restrict__ slab = smem + SLAB;   // [16 values][256 lanes]
+    for (int x = tid; x < DT * T; x += 256) {
+      const int d = x / T, r = x - d * T;
+      sa[x] = (d < D && row0 + r < N) ? e.U[(int64_t)(row0 + r) * D + d] : 0.0;
+      sb[x] = (d < D && col0 + r < N) ? e.U[(int64_t)(col0 + r) * D + d] : 0.0;
+    }
+    if (tid < T) {
+      sal_a[tid] = (row0 + tid < N) ? e.alpha[row0 + tid] : 0.0;
+      sal_b[tid] = (col0 + tid < N) ? e.alpha[col0 + tid] : 0.0;
+    }
+    if (tid < DT) sw[tid] = (tid < D) ? e.w[tid] : 0.0;
+    __syncthreads();
+
+    const double sf2 = *e.sf2;
+    const GppExpConsts ec = gpp_exp_consts();
+    const bool diag_tile = (row0 == col0);
+    double my_sf2 = 0.0, my_w[DT];
+#pragma unroll
+    for (int d = 0; d < DT; ++d) my_w[d] = 0.0;
+#pragma unroll
+    for (int a4 = 0; a4 < 4; ++a4) {
+#pragma unroll
+      for (int v = 0; v < 4; ++v)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) slab[(v * 4 + b) * 256 + tid] = acc4[a4][b][v];
+#pragma unroll 1
+      for (int h = 0; h < 2; ++h) {
+        const int ra = wm + 16 * a4 + 8 * h + lk;  // this half's rows inside the tile: ra and ra + 4
+        const int cb = wn + li;                    // its columns: cb + 16 b
+        double r2[2][4];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 4; ++b) r2[a][b] = 0.0;
+#pragma unroll 2
+        for (int d = 0; d < DT; ++d) {
+          const double ua[2] = {sa[d * T + ra], sa[d * T + ra + 4]};
+          const double wd = sw[d];
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            const double ub = sb[d * T + cb + 16 * b];
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+              const double df = ua[a] - ub;
+              r2[a][b] = fma(wd * df, df, r2[a][b]);
+            }
+          }
+        }
+        // compiler barrier: the second pass reads the features again instead of keeping them live across the exp section (gpp_grad_tiles)
+        __asm__ volatile("" ::: "memory");
+        double g2[2][4];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+          const int i = row0 + ra + 4 * a;
+          const double al_i = sal_a[ra + 4 * a];
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            const int j = col0 + cb + 16 * b;
+            const bool ok = (i < N) & (j <= i);  // as the store of C masks them: beyond N, above the diagonal
+            const double kv = gpp_exp_nonpos(-r2[a][b], ec);
+            const double kin = slab[((2 * h + a) * 4 + b) * 256 + tid];
+            double Wij = 0.5 * (al_i * sal_b[cb + 16 * b] - kin);
+            Wij = ok ? Wij : 0.0;  // (a select: whatever the accumulator of a masked entry holds never reaches a sum)
+            const double mult = (i == j) ? 1.0 : 2.0;
+            my_sf2 = fma(mult * Wij, kv, my_sf2);
+            g2[a][b] = mult * Wij * sf2 * kv;
+            if (diag_tile && ok && i == j) e.wdiag[i] = Wij;
+          }
+        }
+#pragma unroll
+        for (int d = 0; d < DT; ++d) {
+          const double ua[2] = {sa[d * T + ra], sa[d * T + ra + 4]};
+          double s = 0.0;
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            const double ub = sb[d * T + cb + 16 * b];
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+              const double df = ua[a] - ub;
+              s = fma(-g2[a][b] * df, df, s);
+            }
+          }
+          my_w[d] += s;
+          __builtin_amdgcn_sched_barrier(0);  // (keeps the LDS reads of later features from being hoisted: 6 registers each)
+        }
+      }
+    }
+#pragma unroll
+    for (int q = 0; q <= DT; ++q) {
+      const double v = wave_sum(q < DT ? my_w[q < DT ? q : 0] : my_sf2);
+      if (lane == 0) red[wave * (DT + 1) + q] = v;
+    }
+    __syncthreads();
+    if (tid <= D) {
+      const int q = (tid == D) ? DT : tid;
+      e.rec[(int64_t)tile * (D + 1) + tid] = ((red[q] + red[(DT + 1) + q]) + red[2 * (DT + 1) + q]) + red[3 * (DT + 1) + q];
+    }
+  }
+};
+
+// one work-group per lower-triangular tile, in gpp_gemm_f64's plain row-by-row enumeration
+template <int DT>
+__global__ __launch_bounds__(256, 2) void gpp_lauum_grad_f64(GemmArgs p, GradEpiArgs e) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int t = (int)blockIdx.x;
+  int tm = (int)((sqrtf(8.f * (float)t + 1.f) - 1.f) * 0.5f);
+  while ((tm + 1) * (tm + 2) / 2 <= t) ++tm;
+  while (tm * (tm + 1) / 2 > t) --tm;
+  const int tn = t - tm * (tm + 1) / 2;
+  gemm_tile<2, 64, 64, 2, 16, 2, 2>(p, tm, tn, p.A, p.B, nullptr, nullptr, smem, GemmNoHook(), GradEpilogue<DT>{e, t});
 }
 
 // LDS bytes of an instantiation (dynamic: the wide-chunk variants exceed the 64 KiB static limit)
@@ -779,6 +932,33 @@ hipError_t gpp_launch_gemm(hipStream_t s, int variant, const GemmArgs& a_in, int
     case 2: return launch_var<2>(s, tile_m, tile_n, grid, a);
     default: return hipErrorInvalidValue;
   }
+}
+
+// a: gpp_lauum's product (TN, both masks 2, klo_mode 3, c_lower 1; C unused).  e.rec holds one record per 128 x 128 tile.
+hipError_t gpp_launch_lauum_grad(hipStream_t s, const GemmArgs& a_in, const GradEpiArgs& e) {
+  GemmArgs a = a_in;
+  if (a.M <= 0) return hipSuccess;
+  if (a.M != a.N || a.c_lower != 1 || e.D < 1 || e.D > 16) return hipErrorInvalidValue;
+  a.tiles_m = a.tiles_n = (a.M + 127) / 128;
+  a.row_mod = 0;
+  a.swz = 0;
+  a.batch_fast = 0;
+  a.tile_base = 0;
+  const int64_t nt = (int64_t)a.tiles_m * (a.tiles_m + 1) / 2;
+  constexpr size_t bytes = gemm_lds_bytes(2, 128, 128, 16, 2);
+  auto* fn = e.D <= 8 ? gpp_lauum_grad_f64<8> : gpp_lauum_grad_f64<16>;
+  static std::atomic<bool> attr_set[2][64];  // per instantiation and device
+  int dev = 0;
+  hipError_t err = hipGetDevice(&dev);
+  if (err != hipSuccess) return err;
+  const int which = e.D <= 8 ? 0 : 1;
+  if (dev < 0 || dev >= 64 || !attr_set[which][dev]) {
+    err = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (err != hipSuccess) return err;
+    if (dev >= 0 && dev < 64) attr_set[which][dev] = true;
+  }
+  hipLaunchKernelGGL(fn, dim3((unsigned)nt), dim3(256), bytes, s, a, e);
+  return hipGetLastError();
 }
 
 hipError_t gpp_launch_dag_bind(hipStream_t s, const GemmArgs* rel, GemmArgs* abs, int n, const DagBases& bases) {

@@ -51,6 +51,7 @@ struct gpp_handle_s {
   int32_t* shard_info;
   hipEvent_t shard_ready;     // counters cleared + groups bound: what the caller's communication stream waits for before a gate / signal
   int dag_sched;             // GPP_OPT_DAG_SCHED
+  int split_builds;          // gpp_build_potrf_ws calls that built Ky split around panel 0 (gpp_debug_split_builds)
   // gpp_shard.hip: the collectives of gpp_shard_eval (the caller's callbacks, or RCCL opened at run time) and its own stream
   gpp_comm_t comm;
   int comm_rank, comm_nranks;
@@ -182,6 +183,19 @@ struct GemmArgs {
 // tile_m = 0: choose a square tile from the grid size; else force the work-group tile (128x128, 64x64, 32x32, 128x32)
 hipError_t gpp_launch_gemm(hipStream_t s, int variant, const GemmArgs& a, int batch, int tile_m = 0, int tile_n = 0);
 
+// LAUUM whose epilogue is the gradient reduction (gpp_gemm.hip; kind 0, D <= 16, no feature gradients): the tiles of Linv^T Linv
+// go into one record of D + 1 partial sums per 128 x 128 tile (rec, gpp_grad_finish's layout) and wdiag[i] = W_ii, not to memory
+struct GradEpiArgs {
+  const double* U;      // N x D features, row-major
+  const double* w;      // D weights
+  const double* sf2;
+  const double* alpha;  // N
+  double* rec;          // [tiles][D + 1]
+  double* wdiag;        // [N]
+  int D;
+};
+hipError_t gpp_launch_lauum_grad(hipStream_t s, const GemmArgs& lauum, const GradEpiArgs& e);
+
 // one-wave kernels on a stream (gpp_gemm.hip): wait until counters[id] >= target — a wait that exceeds `budget` ticks of the 100 MHz
 // clock sets the abort word counters[0] and *info = GPP_INFO_EXEC_TIMEOUT + ms —, and counters[id] += 1 behind a release fence
 hipError_t gpp_launch_exec_gate(hipStream_t s, int* counters, int id, int target, int32_t* info, long long budget);
@@ -299,6 +313,7 @@ hipError_t gpp_launch_leaf(hipStream_t s, double* A, int64_t lda, double* Linv, 
 
 // ---- covariance tiles (gpp_build.hip) ---------------------------------------------------------
 // batch > 1: independent parameter sets b: U + b*sU (sU = 0 shares the features), w + b*D, sf2 + b, tau + b*S, Ky + b*sK.
+// uplo = GPP_UPLO_UPPER with a proper sub-range: [row0, row0 + nrows) are COLUMNS (row0 a multiple of 64, the end one too or N).
 hipError_t gpp_launch_kernel_build(hipStream_t s, const double* U, int64_t N, int D, const double* w, const double* sf2,
                                    const double* tau, const int32_t* grp, int S, double jitter, int kind, int d_split,
                                    int uplo, double* Ky, int64_t ld, int64_t row0, int64_t nrows, int batch = 1,
@@ -324,6 +339,10 @@ hipError_t gpp_launch_grad_reduce(hipStream_t s, const double* U, int64_t N, int
                                   double* g_U, void* ws, size_t ws_bytes, int shard_nb = 0, int shard_rank = 0,
                                   int shard_nranks = 1, int batch = 1, int64_t sU = 0, int64_t sK = 0, int64_t sv = 0,
                                   int shard_cols = 0);
+// the finish of gpp_launch_grad_reduce alone, over `nrec` records of D + 1 sums (gpp_lauum_grad: one per 128 x 128 tile)
+size_t gpp_lauum_grad_ws_bytes(int64_t N, int D);
+hipError_t gpp_launch_grad_finish(hipStream_t s, const double* rec, int64_t nrec, int D, int S, const double* wdiag,
+                                  const int32_t* grp, int64_t N, double* g_w, double* g_sf2, double* g_tau);
 // (shard_cols = 1: the rank owns block-cyclic COLUMN blocks of Kinv's lower triangle instead of block rows; 2: and Kinv holds
 //  only those blocks, side by side: the q-th owned block in columns [q nb, (q+1) nb))
 // y = sum over the owned column blocks (width nb, block b owned when b % nranks == rank) of T(lower) x  (trans = 0), or

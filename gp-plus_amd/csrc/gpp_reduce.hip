@@ -852,6 +852,19 @@ hipError_t gpp_launch_grad_reduce(hipStream_t s, const double* U, int64_t N, int
   return hipGetLastError();
 }
 
+// gpp_lauum_grad (gpp_gemm.hip): one record per 128 x 128 tile of the lower triangle, then wdiag
+size_t gpp_lauum_grad_ws_bytes(int64_t N, int D) {
+  const int64_t T = (N + 127) / 128;
+  return (size_t)(T * (T + 1) / 2) * (D + 1) * sizeof(double) + (size_t)N * sizeof(double) + 256;
+}
+hipError_t gpp_launch_grad_finish(hipStream_t s, const double* rec, int64_t nrec, int D, int S, const double* wdiag,
+                                  const int32_t* grp, int64_t N, double* g_w, double* g_sf2, double* g_tau) {
+  if (nrec < 0 || nrec > INT32_MAX || D < 1 || D > GD_MAX || S < 1 || S > GS_MAX) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gpp_grad_finish, dim3(D + 1 + S, 1), dim3(256), 0, s, rec, (int)nrec, D, S, wdiag, grp, N, g_w, g_sf2, g_tau,
+                     (int64_t)0);
+  return hipGetLastError();
+}
+
 size_t gpp_pgrad_ws_bytes(int64_t M, int64_t N, int D, int dA, int dB) {
   const PgradShape p = pgrad_shape(M, N);
   const int64_t nwg = p.MT * p.CN;

@@ -83,6 +83,9 @@ def current_slot() -> int:
 #: smallest N for which gpp_potrf_ws (with scratch) runs its look-ahead driver on the internal streams (gpp_api.hip)
 LOOKAHEAD_MIN_N = 3840
 
+#: largest N at which gpp_lauum still runs its small tiles: the fused LAUUM + gradient reduction (128-wide tiles only) serves N above it
+FUSED_GRAD_MIN_N = 5120
+
 #: optional stage timing (bench.py): when this is a list, every stage appends (name, start_event, end_event) recorded
 #: on the stream the kernels are launched on (PyTorch's current stream).
 STAGE_EVENTS = None
@@ -153,13 +156,16 @@ def _factor(ctx: GppContext, ws: EvalWorkspace, U, w, sf2, tau, grp, kind, d_spl
         # 25.4-26.0 -> 24.3-24.8 ms.
         if ws.N >= LOOKAHEAD_MIN_N:  # (below, the factorisation is a single-stream chain and the host is the bottleneck)
             torch.cuda.current_stream(ctx.index).synchronize()
-        # (Measured and NOT adopted: building the first diagonal block's columns first and handing them to the panel stream
-        #  while the rest of Ky is written — the build is an unmasked launch that floods every CU, the panel's 32 included,
-        #  so the first leaf waits for it anyway: 53.6 ms against 0.64 + 52.4.)
+        # Build and factorisation are ONE call: where the ticket list runs (N >= 6912) only the first diagonal block's columns of
+        # Ky are built on this stream; the rest is written on the library's CU-masked update stream in front of the executor,
+        # beside the first panel on its own 32 CUs.  (As an UNMASKED launch beside the panel the same build had flooded every CU,
+        # the panel's included, and the first leaf waited for it anyway: 53.6 ms against 0.64 + 52.4, not adopted then.)
+        # The "kernel_build" stage stays as the mark of an evaluation's first launch (tools/c3_stages.py and config_stages.py
+        # measure the gap in front of it); the build's time is part of "potrf".
         with _stage("kernel_build"):
-            ctx.kernel_build(U, w, sf2, tau, grp, ws.A, jitter=jit, kind=kind, d_split=d_split, uplo=UPLO_UPPER)
+            pass
         with _stage("potrf"):
-            ctx.potrf(ws.A, ws.Li, ws.info, ws.Ki)
+            ctx.build_potrf(U, w, sf2, tau, grp, ws.A, ws.Li, ws.info, ws.Ki, jitter=jit, kind=kind, d_split=d_split)
         # the second host wait of an evaluation (the reference syncs on loss.item() too) covers the factorisation only: the
         # status goes to pinned host memory behind an event, the rest of the evaluation is enqueued, THEN the host waits
         ws.info_host.copy_(ws.info, non_blocking=True)
@@ -232,11 +238,19 @@ class ExactMLLFunction(torch.autograd.Function):
             #  137 -> 142-144 ms per evaluation at N = 20000, tools/attic/side_ab.py.)
             with _stage("alpha"):
                 gctx.alpha(ws.Li, ws.z, ws.alpha)
+            # Above FUSED_GRAD_MIN_N the gradient reduction is the EPILOGUE of the LAUUM's tiles where the library supports it (RBF,
+            # D <= 16, no feature gradients): Ky^-1 is then neither written nor read, and ws.Ki holds the inverse's scratch, not
+            # Ky^-1 (nothing reads it after a training evaluation: the prediction and sampling paths form their own).
+            fused = False
             with _stage("lauum"):
-                gctx.lauum(ws.Li, ws.Ki)
+                if N > FUSED_GRAD_MIN_N:
+                    fused = gctx.lauum_grad(ws.Li, Ud, wd, sd, grp, S, ws.alpha, dU if need_U else 0, g_w, g_s, g_t, kind=kind)
+                if not fused:
+                    gctx.lauum(ws.Li, ws.Ki)
             with _stage("grad_reduce"):
-                gctx.grad_reduce(Ud, wd, sd, grp, S, ws.alpha, ws.Ki, dU if need_U else 0, g_w, g_s, g_t, g_Ud, kind=kind,
-                                 d_split=d_split)
+                if not fused:
+                    gctx.grad_reduce(Ud, wd, sd, grp, S, ws.alpha, ws.Ki, dU if need_U else 0, g_w, g_s, g_t, g_Ud, kind=kind,
+                                     d_split=d_split)
 
         _factor(gctx, ws, Ud, wd, sd, td, grp, kind, d_split, after=rest)
         ctx.saved = (g_w, g_s, g_t, g_Ud, ws.alpha.clone() if need_grad else None, (N, D, dU))

@@ -98,6 +98,8 @@ int gpp_set_workspace(gpp_handle_t h, void* ws, size_t bytes);
  *   Ky[i,j] = sf2 * k(U_i, U_j; w) + (i==j) * (tau[grp[i]] + jitter)      for row0 <= i < row0+nrows
  * U: N x D row-major; w: D weights; sf2: 1 double (device); tau: S doubles or NULL; grp: N int32 or NULL
  * (NULL => group 0); d_split: number of leading dims that stay RBF when kind != RBF.
+ * row0 is a multiple of 64.  A proper sub-range (row0 != 0 or nrows != N) is a range of ROWS for GPP_UPLO_FULL and
+ * GPP_UPLO_LOWER; GPP_UPLO_UPPER takes only the whole matrix here (bad argument #16 otherwise).
  */
 int gpp_kernel_build(gpp_handle_t h, const double* U, int64_t N, int D, const double* w, const double* sf2,
                      const double* tau, const int32_t* grp, int S, double jitter, int kind, int d_split,
@@ -129,12 +131,38 @@ int gpp_potrf(gpp_handle_t h, double* A, int64_t N, int64_t ld, double* Linv, in
 int gpp_potrf_ws(gpp_handle_t h, double* A, int64_t N, int64_t ld, double* Linv, int64_t ldi, double* T, int64_t ldt,
                  int32_t* info_dev);
 
+/* gpp_kernel_build (uplo = GPP_UPLO_UPPER, all rows) + gpp_potrf_ws in one call: the same kernels on the same values, so A, Linv
+ * and *info_dev are bit for bit what the two calls give.  Where the ticket list applies (6912 <= N <= 65536, the options on, a
+ * scratch T) only the leading diagonal block's columns of Ky — all the first cooperative panel reads — are built on the caller's
+ * stream; the rest is built on the handle's throughput stream (CU-masked to the CUs the panel does not use) in front of the
+ * executor's launch, while the panel stream's 32 CUs already factor block 0.  The panel stream waits for that second build before
+ * its first filler launch takes tasks from the list.  Everywhere else (small N, stream capture, the list switched off or not
+ * applicable) it IS the two calls, on the caller's stream. */
+int gpp_build_potrf_ws(gpp_handle_t h, const double* U, int64_t N, int D, const double* w, const double* sf2, const double* tau,
+                       const int32_t* grp, int S, double jitter, int kind, int d_split, double* A, int64_t ld, double* Linv,
+                       int64_t ldi, double* T, int64_t ldt, int32_t* info_dev);
+
 /* Completes Linv = inv(L) (lower triangle, mirrored into the upper) from the diagonal-block inverses left by
  * gpp_potrf.  `U` is the factored matrix (upper).  T (N x N) is scratch. */
 int gpp_trtri(gpp_handle_t h, const double* U, int64_t N, int64_t ld, double* Linv, int64_t ldi, double* T, int64_t ldt);
 
 /* Kinv(lower) = Linv^T Linv.  With gpp_trtri this is K7's "K_y^-1" (ATen cholesky_backward, optim/mll_torch.py:117). */
 int gpp_lauum(gpp_handle_t h, const double* Linv, int64_t N, int64_t ldi, double* Kinv, int64_t ldk);
+
+/* gpp_lauum whose epilogue IS gpp_grad_reduce: the gradient sums of a training evaluation straight from the accumulators of
+ * Linv^T Linv, so that Ky^-1 is neither written nor read back (1.6 GB each way at N = 20000).  With W = 0.5 (alpha alpha' - Ky^-1):
+ *   g_w[d] = sum_ij W_ij dKy_ij/dw_d        g_sf2 = sum_ij W_ij K_ij / sf2        g_tau[s] = sum_{i in s} W_ii
+ * exactly as gpp_grad_reduce defines them; the sums are regrouped by 128 x 128 tiles (one record per tile in the handle's
+ * workspace, added in a fixed order: two calls agree bitwise; no atomics).  128-wide tiles at every N (the Python caller uses it
+ * above N = 5120, where gpp_lauum does too).  Supported: kind == GPP_KIND_RBF, D <= 16, dU == 0 (no feature gradients), one
+ * unsharded matrix.  Anything else returns GPP_NOT_SUPPORTED with nothing enqueued: the caller runs gpp_lauum + gpp_grad_reduce.
+ * Linv: the complete inverse factor with its mirror (gpp_trtri); U: N x D row-major; grp: N int32 or NULL; the workspace of
+ * GPP_OP_MLL_EVAL must be set (GPP_NO_WORKSPACE otherwise).  Reference counterpart: ATen cholesky_backward + the backward of the kernel ops, optim/mll_torch.py:117. */
+#define GPP_NOT_SUPPORTED 2001
+#define GPP_NO_WORKSPACE 2002 /* gpp_lauum_grad: gpp_set_workspace has not been given gpp_workspace_bytes(GPP_OP_MLL_EVAL) bytes */
+int gpp_lauum_grad(gpp_handle_t h, const double* Linv, int64_t N, int64_t ldi, const double* U, int D, const double* w,
+                   const double* sf2, const int32_t* grp, int S, int kind, int dU, const double* alpha, double* g_w,
+                   double* g_sf2, double* g_tau);
 
 /* Posterior covariance at the TRAINING inputs (models/gp_plus.py:985-998 sample_y: likelihood(self(train_x)).sample()), built into
  * the upper triangle of A in the layout gpp_potrf_ws factors:
