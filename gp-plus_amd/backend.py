@@ -443,6 +443,58 @@ class GppContext:
                                        g_sf2.data_ptr(), g_tau.data_ptr(), _ptr(g_U)), "gpp_grad_reduce")
 
     @_on_own_device
+    def loo_scalars(self, Linv, alpha, y, d, mu=None, s2=None, a=None, sqrtb=None, loo=None):
+        """Leave-one-out quantities from the inverse factor (gpp_loo_scalars): d = diag(Ky^-1) by row reductions of ``Linv``,
+        and whichever of mu = y - alpha / d, s2 = 1 / d, a = -alpha / d, sqrtb and the pseudo-likelihood ``loo`` were passed."""
+        N = Linv.shape[0]
+        _need(Linv, torch.float64, "Linv")
+        for t, n, size in ((alpha, "alpha", N), (y, "y", N), (d, "d", N), (mu, "mu", N), (s2, "s2", N), (a, "a", N),
+                           (sqrtb, "sqrtb", N), (loo, "loo", 1)):
+            if t is None:
+                continue
+            _need(t, torch.float64, n)
+            if t.numel() < size or not t.is_contiguous():
+                raise GppError(f"{n} must be a contiguous vector of {size} doubles")
+        if mu is not None and y is None:
+            raise GppError("loo_scalars: mu needs y")
+        self._stream()
+        check(self.lib.gpp_loo_scalars(self.h, Linv.data_ptr(), _ld(Linv), N, alpha.data_ptr(), _ptr(y), d.data_ptr(), _ptr(mu),
+                                       _ptr(s2), _ptr(a), _ptr(sqrtb), _ptr(loo)), "gpp_loo_scalars")
+
+    @_on_own_device
+    def sym_rowscale(self, Kinv, s, out):
+        """out[i, j] = s[i] * Kinv[max(i, j), min(i, j)]: the full row-scaled square from Kinv's lower triangle, out of place
+        (gpp_sym_rowscale)."""
+        N = Kinv.shape[0]
+        for t, n in ((Kinv, "Kinv"), (s, "s"), (out, "S")):
+            _need(t, torch.float64, n)
+        if out.shape[0] != N or out.shape[1] != N or s.numel() != N or not s.is_contiguous():
+            raise GppError("sym_rowscale: shapes do not match")
+        if out.data_ptr() == Kinv.data_ptr():
+            raise GppError("sym_rowscale works out of place")
+        self._stream()
+        check(self.lib.gpp_sym_rowscale(self.h, Kinv.data_ptr(), N, _ld(Kinv), s.data_ptr(), out.data_ptr(), _ld(out)),
+              "gpp_sym_rowscale")
+        return out
+
+    @_on_own_device
+    def loo_grad_reduce(self, U, w, sf2, grp, S, alpha, beta, C, dU, g_w, g_sf2, g_tau, g_U, *, kind=KIND_RBF, d_split=0):
+        """``grad_reduce`` with the leave-one-out weights W = -(alpha beta^T + beta alpha^T) / 2 - C (gpp_loo_grad_reduce)."""
+        N, D = U.shape
+        _check_features(D)
+        for t, n in ((alpha, "alpha"), (beta, "beta")):
+            _need(t, torch.float64, n)
+            if t.numel() != N or not t.is_contiguous():
+                raise GppError(f"{n} must be a contiguous vector of {N} doubles")
+        if grp is not None:
+            self._check_groups(grp, N, S)
+        self.ensure_workspace(OP_MLL_EVAL, N, 0, D, S)
+        self._stream()
+        check(self.lib.gpp_loo_grad_reduce(self.h, U.data_ptr(), N, D, w.data_ptr(), sf2.data_ptr(), _ptr(grp), S, kind, d_split,
+                                           alpha.data_ptr(), beta.data_ptr(), C.data_ptr(), _ld(C), dU, g_w.data_ptr(),
+                                           g_sf2.data_ptr(), g_tau.data_ptr(), _ptr(g_U)), "gpp_loo_grad_reduce")
+
+    @_on_own_device
     def grad_reduce_rows(self, U, w, sf2, grp, S, alpha, Kinv, dU, nb, rank, nranks, g_w, g_sf2, g_tau, g_U, *,
                          kind=KIND_RBF, d_split=0):
         """Partial sums over the block rows of Kinv owned by ``rank`` (block-cyclic, block height ``nb``)."""

@@ -1616,6 +1616,55 @@ int gpp_grad_reduce(gpp_handle_t h, const double* U, int64_t N, int D, const dou
   return 0;
 }
 
+int gpp_loo_scalars(gpp_handle_t h, const double* Linv, int64_t ldi, int64_t N, const double* alpha, const double* y, double* d,
+                    double* mu, double* s2, double* a, double* sqrtb, double* loo) {
+  if (!h) return -1;
+  if (N < 0) return -4;
+  if (int q = check_mat(Linv, ldi, N, 2)) return q;
+  if (!alpha) return -5;
+  if (mu && !y) return -6;
+  if (!d) return -7;
+  GPP_TRY(gpp_launch_loo_scalars(h->stream, Linv, ldi, N, alpha, y, d, mu, s2, a, sqrtb, loo));
+  return 0;
+}
+
+int gpp_sym_rowscale(gpp_handle_t h, const double* Kinv, int64_t N, int64_t ldk, const double* s, double* S, int64_t lds) {
+  if (!h) return -1;
+  if (N < 0) return -3;
+  if (int r = check_mat(Kinv, ldk, N, 2)) return r;
+  if (!s) return -5;
+  if (int r = check_mat(S, lds, N, 6)) return r;
+  if (S == Kinv) return -6;  // out of place only
+  GPP_TRY(gpp_launch_sym_rowscale(h->stream, Kinv, ldk, N, s, S, lds));
+  return 0;
+}
+
+int gpp_loo_grad_reduce(gpp_handle_t h, const double* U, int64_t N, int D, const double* w, const double* sf2,
+                        const int32_t* grp, int S, int kind, int d_split, const double* alpha, const double* beta,
+                        const double* C, int64_t ldc, int dU, double* g_w, double* g_sf2, double* g_tau, double* g_U) {
+  if (!h) return -1;
+  if (!U) return -2;
+  if (N < 0) return -3;
+  if (D < 1 || D > 64) return -4;
+  if (!w) return -5;
+  if (!sf2) return -6;
+  if (S < 1 || S > 64) return -8;
+  if (kind < 0 || kind > 2) return -9;
+  if (d_split < 0 || d_split > D) return -10;
+  if (!alpha) return -11;
+  if (!beta) return -12;
+  if (int q = check_mat(C, ldc, N, 13)) return q;
+  if (dU < 0 || dU > D) return -15;
+  if (!g_w) return -16;
+  if (!g_sf2) return -17;
+  if (!g_tau) return -18;
+  if (dU > 0 && !g_U) return -19;
+  if (!h->ws || h->ws_bytes < gpp_grad_ws_bytes(N, D, S, dU)) return -1;
+  GPP_TRY(gpp_launch_grad_reduce(h->stream, U, N, D, w, sf2, grp, S, kind, d_split, alpha, C, ldc, dU, g_w, g_sf2, g_tau, g_U,
+                                 h->ws, h->ws_bytes, 0, 0, 1, 1, 0, 0, 0, 0, beta));
+  return 0;
+}
+
 int gpp_grad_reduce_rows(gpp_handle_t h, const double* U, int64_t N, int D, const double* w, const double* sf2,
                          const int32_t* grp, int S, int kind, int d_split, const double* alpha, const double* Kinv,
                          int64_t ldk, int dU, int64_t nb, int rank, int nranks, double* g_w, double* g_sf2, double* g_tau,

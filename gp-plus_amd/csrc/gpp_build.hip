@@ -313,3 +313,89 @@ hipError_t gpp_launch_post_cov_train(hipStream_t s, const double* Kinv, int64_t 
                      lda);
   return hipGetLastError();
 }
+
+// ---- row-scaled symmetric square (gpp_sym_rowscale in gpp.h) ---------------------------------------------------------------
+// S[i,j] = s_i Kinv[max(i,j), min(i,j)] as a FULL square from Kinv's lower triangle: the operand of the leave-one-out gradient's
+// product P diag(b) P = S^T S with s = sqrt(b) (no reference counterpart: the reference names a LOOCV criterion in
+// optim/mll_noise_continuation.py:54 and never evaluates it).  One work-group per 128 x 128 tile of the LOWER triangle, in 64 x 64
+// quarters as gpp_post_cov_tile: a quarter of Kinv (rows i, columns j <= i) is read once with 16-byte loads along its rows, written
+// scaled by s_i in place (rows i of S, columns j <= i) and, through LDS, transposed and scaled by s_j into rows j of S, columns
+// i > j.  Every element of S[0..N) x [0..N) is written exactly once; nothing above Kinv's diagonal is read.  Out of place.
+// HBM-bound: N^2/2 doubles read, N^2 written.  Columns [N, lds) of S are NOT written: the TN GEMM that consumes S masks its loads
+// by the true extents (load_mc: gk < kend, gr < R, the second element of a pair by gr + 1 < R; gpp_gemm never sets pad_ok).
+namespace {
+
+__global__ __launch_bounds__(256) void gpp_sym_rowscale_tile(const double* __restrict__ Kinv, int64_t ldk, int64_t N,
+                                                             const double* __restrict__ sv, double* __restrict__ S, int64_t lds) {
+  __shared__ double t[PC_Q][PC_Q + 1];  // t[c][r] = Kinv[i0 + r][j0 + c]; padded against bank conflicts of the transposed writes
+  typedef double v2d __attribute__((ext_vector_type(2)));
+  int64_t ti, tj;  // lower-triangle tile ti >= tj, row-major enumeration
+  {
+    const int64_t tt = blockIdx.x;
+    int64_t r = (int64_t)((sqrt(8.0 * (double)tt + 1.0) - 1.0) * 0.5);
+    while ((r + 1) * (r + 2) / 2 <= tt) ++r;
+    while (r * (r + 1) / 2 > tt) --r;
+    ti = r;
+    tj = tt - r * (r + 1) / 2;
+  }
+  const int tid = threadIdx.x;
+  const int lc = (tid & 31) * 2, lr = tid >> 5;  // a column pair, and rows lr + 8 k
+  for (int q = 0; q < 4; ++q) {
+    const int qa = q >> 1, qb = q & 1;
+    if (ti == tj && qa < qb) continue;  // the upper quarter of a diagonal tile (uniform in the work-group)
+    const int64_t i0 = ti * PC_T + qa * PC_Q, j0 = tj * PC_T + qb * PC_Q;
+    if (i0 >= N || j0 >= N) continue;
+    __syncthreads();  // the previous quarter's LDS reads are done
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {  // rows i of Kinv and of S, columns j <= i
+      const int ir = lr + 8 * k;
+      const int64_t i = i0 + ir, j = j0 + lc;
+      double x0 = 0.0, x1 = 0.0;
+      if (i < N) {
+        const bool k0 = j < N && j <= i, k1 = j + 1 < N && j + 1 <= i;
+        const double* p = Kinv + i * ldk + j;
+        const double si = sv[i];
+        double* o = S + i * lds + j;
+        if (k0 && k1) {
+          const v2d v = *reinterpret_cast<const v2d*>(p);
+          x0 = v.x;
+          x1 = v.y;
+          const v2d w = {si * x0, si * x1};
+          *reinterpret_cast<v2d*>(o) = w;
+        } else if (k0) {
+          x0 = p[0];
+          o[0] = si * x0;
+        }
+      }
+      t[lc][ir] = x0;
+      t[lc + 1][ir] = x1;
+    }
+    __syncthreads();
+    const int64_t i = i0 + lc;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {  // rows j of S, columns i > j: the mirror image
+      const int jr = lr + 8 * k;
+      const int64_t j = j0 + jr;
+      if (j >= N) continue;
+      const double sj = sv[j];
+      const bool w0 = i < N && i > j, w1 = i + 1 < N && i + 1 > j;
+      double* o = S + j * lds + i;
+      if (w0 && w1) {
+        const v2d w = {sj * t[jr][lc], sj * t[jr][lc + 1]};
+        *reinterpret_cast<v2d*>(o) = w;
+      } else {
+        if (w0) o[0] = sj * t[jr][lc];
+        if (w1) o[1] = sj * t[jr][lc + 1];
+      }
+    }
+  }
+}
+
+}  // namespace
+
+hipError_t gpp_launch_sym_rowscale(hipStream_t s, const double* Kinv, int64_t ldk, int64_t N, const double* sv, double* S, int64_t lds) {
+  if (N <= 0) return hipSuccess;
+  const int64_t nt = (N + PC_T - 1) / PC_T;
+  hipLaunchKernelGGL(gpp_sym_rowscale_tile, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, s, Kinv, ldk, N, sv, S, lds);
+  return hipGetLastError();
+}

@@ -323,6 +323,8 @@ hipError_t gpp_launch_cross_kernel(hipStream_t s, const double* Ua, int64_t Ma, 
 // A(upper) = diag(tau[grp] + d + jitter) - T Kinv T from Kinv's lower triangle (gpp_post_cov_train; A may be Kinv)
 hipError_t gpp_launch_post_cov_train(hipStream_t s, const double* Kinv, int64_t ldk, int64_t N, const double* tau, const int32_t* grp,
                                      const double* d, double jitter, double* A, int64_t lda);
+// S (full square) = diag(sv) sym(Kinv) from Kinv's lower triangle, out of place (gpp_sym_rowscale)
+hipError_t gpp_launch_sym_rowscale(hipStream_t s, const double* Kinv, int64_t ldk, int64_t N, const double* sv, double* S, int64_t lds);
 
 // ---- reductions (gpp_reduce.hip) --------------------------------------------------------------
 // batch > 1 (all reductions): matrices at + b*sT, vectors at + b*sv (sv even, >= N), out3 at + 3*b
@@ -338,7 +340,12 @@ hipError_t gpp_launch_grad_reduce(hipStream_t s, const double* U, int64_t N, int
                                   const double* Kinv, int64_t ldk, int dU, double* g_w, double* g_sf2, double* g_tau,
                                   double* g_U, void* ws, size_t ws_bytes, int shard_nb = 0, int shard_rank = 0,
                                   int shard_nranks = 1, int batch = 1, int64_t sU = 0, int64_t sK = 0, int64_t sv = 0,
-                                  int shard_cols = 0);
+                                  int shard_cols = 0, const double* beta = nullptr);
+// (beta != nullptr: the leave-one-out weights W_ij = -0.5 (alpha_i beta_j + beta_i alpha_j) - Kinv_ij, `Kinv` holding
+//  C = P diag(b) P — gpp_loo_grad_reduce in gpp.h; unbatched and unsharded callers only)
+// d_i = sum_{j >= i} Linv[i][j]^2 and the leave-one-out vectors / value derived from it (gpp_loo_scalars in gpp.h; mu, s2, a, sb, loo may be null)
+hipError_t gpp_launch_loo_scalars(hipStream_t s, const double* Linv, int64_t ldi, int64_t N, const double* alpha, const double* y,
+                                  double* d, double* mu, double* s2, double* a, double* sb, double* loo);
 // the finish of gpp_launch_grad_reduce alone, over `nrec` records of D + 1 sums (gpp_lauum_grad: one per 128 x 128 tile)
 size_t gpp_lauum_grad_ws_bytes(int64_t N, int D);
 hipError_t gpp_launch_grad_finish(hipStream_t s, const double* rec, int64_t nrec, int D, int S, const double* wdiag,

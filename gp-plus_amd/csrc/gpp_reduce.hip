@@ -182,6 +182,66 @@ __global__ __launch_bounds__(1024) void gpp_mll_scalars(const double* __restrict
   }
 }
 
+// Leave-one-out quantities of an exact GP (Rasmussen & Williams, section 5.4.2; gpytorch LeaveOneOutPseudoLikelihood) from the
+// inverse factor, without Ky^-1: row i of the Linv buffer from the diagonal on is column i of L^-1 (the mirror), so
+//   d_i = (Ky^-1)_ii = sum_{j >= i} Linv[i][j]^2
+// is one contiguous row reduction — one wave per row, 16-byte loads, a lane's terms added in index order and the lanes by the
+// butterfly: a row's sum depends on N and i only, never on the grid.  Lane 0 then writes what the caller asked for:
+//   mu_i = y_i - alpha_i / d_i,  s2_i = 1 / d_i,  a_i = -alpha_i / d_i,  sb_i = sqrt(b_i),  b_i = 1 / (2 d_i) + alpha_i^2 / (2 d_i^2)
+// HBM-read-bound: 4 N^2 bytes.  (No reference counterpart: optim/mll_noise_continuation.py:54 names the criterion only.)
+__global__ __launch_bounds__(256) void gpp_loo_rows(const double* __restrict__ Linv, int64_t ldi, int64_t N,
+                                                    const double* __restrict__ alpha, const double* __restrict__ y,
+                                                    double* __restrict__ d, double* __restrict__ mu, double* __restrict__ s2,
+                                                    double* __restrict__ a, double* __restrict__ sb) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * 4 + wave;
+  if (i >= N) return;
+  const double* row = Linv + i * ldi;
+  double acc = 0.0;
+  int64_t k0 = i;
+  if (k0 & 1) {  // align the vector loop to an even column
+    if (lane == 0) acc = row[k0] * row[k0];
+    ++k0;
+  }
+  const int64_t nvec = (N - k0) >> 1;
+#pragma unroll 4
+  for (int64_t v = lane; v < nvec; v += 64) {
+    const v2d t = *reinterpret_cast<const v2d*>(row + k0 + 2 * v);
+    acc = fma(t.x, t.x, acc);
+    acc = fma(t.y, t.y, acc);
+  }
+  if (lane == 0 && ((N - k0) & 1)) acc = fma(row[N - 1], row[N - 1], acc);
+  acc = wave_sum(acc);
+  if (lane == 0) {
+    const double di = acc, al = alpha[i], inv = 1.0 / di;
+    d[i] = di;
+    if (mu) mu[i] = y[i] - al * inv;
+    if (s2) s2[i] = inv;
+    if (a) a[i] = -al * inv;
+    if (sb) sb[i] = sqrt(0.5 * inv + 0.5 * (al * inv) * (al * inv));
+  }
+}
+
+// loo = sum_i [ 0.5 log d_i - alpha_i^2 / (2 d_i) ] - (N / 2) log 2pi : one work-group, the summation order of gpp_mll_scalars
+__global__ __launch_bounds__(1024) void gpp_loo_value(const double* __restrict__ d, const double* __restrict__ alpha, int64_t N,
+                                                      double* __restrict__ out) {
+  __shared__ double sp[16];
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < N; i += 1024) {
+    const double di = d[i], al = alpha[i];
+    s += 0.5 * log(di) - 0.5 * al * al / di;
+  }
+  s = wave_sum(s);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0) sp[wave] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int w = 0; w < 16; ++w) t += sp[w];
+    out[0] = t - 0.5 * (double)N * 1.8378770664093454835606594728112;  // log(2 pi)
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // gradient reduction.  Tiles of 64x64 over the lower triangle of Kinv; 256 threads, 4x4 per thread.
 // Per tile the kernel forms G_ij = mult * W_ij * sf2*k_ij  (W = 0.5(alpha_i alpha_j - Kinv_ij), mult = 2 for the
@@ -205,7 +265,9 @@ __device__ __forceinline__ void tile_from_index(int64_t t, int64_t& ti, int64_t&
 
 // MAT = false: pure RBF product (kind 0): no Matern distance / derivative registers, two waves per SIMD
 // HASU = false: no gradient w.r.t. feature columns (dU = 0): the 4 x 4 blocks of G are never materialised
-template <int DT, bool MAT, bool HASU>
+// LOO = true: the leave-one-out pseudo-likelihood's weights W_ij = -0.5 (alpha_i beta_j + beta_i alpha_j) - C_ij (gpp_loo_grad_reduce:
+//       `Kinv` is C = P diag(b) P, `beta` = P a) in place of 0.5 (alpha_i alpha_j - Kinv_ij); everything else is shared
+template <int DT, bool MAT, bool HASU, bool LOO = false>
 __global__ __launch_bounds__(256) void gpp_grad_tiles(const double* __restrict__ U, int64_t N, int D,
                                                       const double* __restrict__ w, const double* __restrict__ sf2p,
                                                       int kind, int d_split, const double* __restrict__ alpha, const double* __restrict__ Kinv,
@@ -213,9 +275,11 @@ __global__ __launch_bounds__(256) void gpp_grad_tiles(const double* __restrict__
                                                       int shard_nranks, int shard_cols, int64_t sU, int64_t sK, int64_t sv, int64_t ws_stride,
                                                       double* __restrict__ rec /* [gridDim.x][D+1] */,
                                                       double* __restrict__ wdiag /* [N] */,
-                                                      double* __restrict__ gUpart /* [T][N][dU] */) {
+                                                      double* __restrict__ gUpart /* [T][N][dU] */,
+                                                      const double* __restrict__ beta /* [N], LOO only */) {
   {  // batch element blockIdx.y: its own parameters, matrices and slice of the workspace
     const int64_t b = blockIdx.y;
+    if constexpr (LOO) beta += b * sv;
     U += b * sU;
     w += b * D;
     sf2p += b;
@@ -228,6 +292,7 @@ __global__ __launch_bounds__(256) void gpp_grad_tiles(const double* __restrict__
   __shared__ __attribute__((aligned(16))) double sa[DT * GT];  // raw U rows of tile-row ti, [d][r]
   __shared__ __attribute__((aligned(16))) double sb[DT * GT];
   __shared__ double sal_a[GT], sal_b[GT];
+  __shared__ double sbe_a[LOO ? GT : 1], sbe_b[LOO ? GT : 1];
   __shared__ double sw[DT];
   __shared__ double red[256];
   __shared__ double rowpart[GT * 16];
@@ -267,6 +332,10 @@ __global__ __launch_bounds__(256) void gpp_grad_tiles(const double* __restrict__
     if (tid < GT) {
       sal_a[tid] = (i0 + tid < N) ? alpha[i0 + tid] : 0.0;
       sal_b[tid] = (j0 + tid < N) ? alpha[j0 + tid] : 0.0;
+      if constexpr (LOO) {
+        sbe_a[tid] = (i0 + tid < N) ? beta[i0 + tid] : 0.0;
+        sbe_b[tid] = (j0 + tid < N) ? beta[j0 + tid] : 0.0;
+      }
     }
     __syncthreads();
 
@@ -344,7 +413,13 @@ __global__ __launch_bounds__(256) void gpp_grad_tiles(const double* __restrict__
               kv = er * (1.0 + aa + aa * aa * (1.0 / 3.0)) * ea;
               kd = er * (5.0 / 3.0) * (1.0 + aa) * ea;
             }
-            const double Wij = 0.5 * (sal_a[ra + a] * sal_b[2 * tx + (b & 1) + ((b >> 1) << 5)] - kin[a][b]);
+            double Wij;
+            if constexpr (LOO) {
+              const int cb = 2 * tx + (b & 1) + ((b >> 1) << 5);
+              Wij = -0.5 * (sal_a[ra + a] * sbe_b[cb] + sbe_a[ra + a] * sal_b[cb]) - kin[a][b];
+            } else {
+              Wij = 0.5 * (sal_a[ra + a] * sal_b[2 * tx + (b & 1) + ((b >> 1) << 5)] - kin[a][b]);
+            }
             const double mult = (i == j) ? 1.0 : 2.0;
             my_sf2 = fma(mult * Wij, kv, my_sf2);
             g = mult * Wij * sf2 * kv;
@@ -802,6 +877,14 @@ hipError_t gpp_launch_mll_scalars(hipStream_t s, const double* L, int64_t ld, in
   return hipGetLastError();
 }
 
+hipError_t gpp_launch_loo_scalars(hipStream_t s, const double* Linv, int64_t ldi, int64_t N, const double* alpha, const double* y,
+                                  double* d, double* mu, double* s2, double* a, double* sb, double* loo) {
+  if (N > 0)
+    hipLaunchKernelGGL(gpp_loo_rows, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, Linv, ldi, N, alpha, y, d, mu, s2, a, sb);
+  if (loo) hipLaunchKernelGGL(gpp_loo_value, dim3(1), dim3(1024), 0, s, d, alpha, N, loo);
+  return hipGetLastError();
+}
+
 size_t gpp_grad_ws_bytes(int64_t N, int D, int S, int dU) {
   (void)S;
   const int64_t T = (N + GT - 1) / GT;
@@ -813,7 +896,7 @@ hipError_t gpp_launch_grad_reduce(hipStream_t s, const double* U, int64_t N, int
                                   const int32_t* grp, int S, int kind, int d_split, const double* alpha,
                                   const double* Kinv, int64_t ldk, int dU, double* g_w, double* g_sf2, double* g_tau,
                                   double* g_U, void* ws, size_t ws_bytes, int shard_nb, int shard_rank, int shard_nranks,
-                                  int batch, int64_t sU, int64_t sK, int64_t sv, int shard_cols) {
+                                  int batch, int64_t sU, int64_t sK, int64_t sv, int shard_cols, const double* beta) {
   if (kind < 0 || kind > 2) return hipErrorInvalidValue;
   if (batch < 1 || batch > 65535) return hipErrorInvalidValue;
   if (shard_nranks > 1 && (shard_nb < GT || shard_nb % GT != 0 || shard_rank < 0 || shard_rank >= shard_nranks))
@@ -833,17 +916,19 @@ hipError_t gpp_launch_grad_reduce(hipStream_t s, const double* U, int64_t N, int
   }
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(nwg, batch), dim3(256), 0, s, U, N, D, w, sf2, kind, d_split, alpha, Kinv, ldk, dU, ntiles,
-                       shard_nb, shard_rank, shard_nranks, shard_cols, sU, sK, sv, ws_stride, rec, wdiag, gUpart);
+                       shard_nb, shard_rank, shard_nranks, shard_cols, sU, sK, sv, ws_stride, rec, wdiag, gUpart, beta);
   };
-  const bool mat = kind != 0, hasu = dU > 0;
-#define GPP_GT(DT)                                                                                                   \
-  (mat ? (hasu ? launch(gpp_grad_tiles<DT, true, true>) : launch(gpp_grad_tiles<DT, true, false>))                   \
-       : (hasu ? launch(gpp_grad_tiles<DT, false, true>) : launch(gpp_grad_tiles<DT, false, false>)))
+  const bool mat = kind != 0, hasu = dU > 0, loo = beta != nullptr;  // beta: the leave-one-out weights (gpp_loo_grad_reduce)
+#define GPP_GT2(DT, LOO)                                                                                             \
+  (mat ? (hasu ? launch(gpp_grad_tiles<DT, true, true, LOO>) : launch(gpp_grad_tiles<DT, true, false, LOO>))         \
+       : (hasu ? launch(gpp_grad_tiles<DT, false, true, LOO>) : launch(gpp_grad_tiles<DT, false, false, LOO>)))
+#define GPP_GT(DT) (loo ? GPP_GT2(DT, true) : GPP_GT2(DT, false))
   if (D <= 8) GPP_GT(8);
   else if (D <= 16) GPP_GT(16);
   else if (D <= 32) GPP_GT(32);
   else GPP_GT(64);
 #undef GPP_GT
+#undef GPP_GT2
   hipLaunchKernelGGL(gpp_grad_finish, dim3(D + 1 + S, batch), dim3(256), 0, s, rec, nwg, D, S, wdiag, grp, N, g_w, g_sf2, g_tau,
                      ws_stride);
   if (dU > 0)

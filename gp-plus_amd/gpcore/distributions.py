@@ -171,6 +171,20 @@ class MultivariateNormal:
         dense = cov if torch.is_tensor(cov) else cov.evaluate()
         return dense_log_prob(dense, (value - self.loc).to(torch.float64))
 
+    def loo_log_prob(self, value: torch.Tensor) -> torch.Tensor:
+        """Leave-one-out log pseudo-likelihood sum_i log p(value_i | value_-i) of a (noisy) lazy kernel covariance
+        (``linalg.exact_loo``; gpytorch's LeaveOneOutPseudoLikelihood computes it from the same distribution)."""
+        cov = self._covar
+        if not isinstance(cov, LazyKernelMatrix):
+            raise NotImplementedError("loo_log_prob needs the lazy kernel covariance of a training evaluation")
+        if not cov.is_square:
+            raise RuntimeError("loo_log_prob needs a square covariance")
+        if cov.tau is None:
+            raise RuntimeError("loo_log_prob of a noise-free kernel matrix: apply the likelihood first")
+        from ..linalg import exact_loo
+
+        return exact_loo(cov.U1, cov.spec, cov.tau, self.loc, value, cov.grp, cov.n_grad_dims)
+
     # -- sampling --------------------------------------------------------------------------------
     def root_factor(self) -> torch.Tensor:
         """Upper Cholesky factor U of the covariance (U^T U = Sigma; an M x M view whose strict lower triangle is not part of

@@ -1,5 +1,7 @@
 """``ExactMarginalLogLikelihood`` (gpytorch.mlls subset; reference use: optim/mll_torch.py:17,96,116):
     (log p(y | X) + sum of prior log-densities) / N
+and ``LeaveOneOutPseudoLikelihood`` (gpytorch.mlls.LeaveOneOutPseudoLikelihood; Rasmussen & Williams 5.4.2):
+    (sum_i log p(y_i | X, y_-i) + sum of prior log-densities) / N
 """
 import torch
 
@@ -36,3 +38,19 @@ class ExactMarginalLogLikelihood(Module):
     def named_priors(self, memo=None, prefix=""):
         # priors of the model (which includes the likelihood's) — the MLL module itself has none
         yield from self.model.named_priors(memo, prefix)
+
+
+class LeaveOneOutPseudoLikelihood(ExactMarginalLogLikelihood):
+    """The leave-one-out log pseudo-likelihood as a training criterion, with gpytorch's scaling: the sum of the N leave-one-out
+    predictive log-densities plus the prior log-densities, divided by N (``MultivariateNormal.loo_log_prob``)."""
+
+    def forward(self, function_dist: MultivariateNormal, target: torch.Tensor, *params):
+        if not isinstance(function_dist, MultivariateNormal):
+            raise RuntimeError("LeaveOneOutPseudoLikelihood can only operate on Gaussian random variables")
+        num_data = function_dist.event_shape.numel()
+        output = self.likelihood(function_dist, *params)
+        res = output.loo_log_prob(target)
+        prior_sum = self._prior_sum(res.dtype)
+        if prior_sum is not None:
+            res = res + prior_sum
+        return res / num_data

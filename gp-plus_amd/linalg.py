@@ -25,7 +25,7 @@ from .backend import (KIND_RBF, OP_MLL_EVAL, UPLO_FULL, UPLO_UPPER, GppContext, 
 from .errors import NanError, NotPSDError
 from . import settings
 
-__all__ = ["KernelSpec", "exact_mll", "ExactMLLFunction", "EvalWorkspace", "dense_kernel", "cross_kernel",
+__all__ = ["KernelSpec", "exact_mll", "ExactMLLFunction", "exact_loo", "ExactLOOFunction", "loo_moments", "EvalWorkspace", "dense_kernel", "cross_kernel",
            "FactorCache", "factorize", "dense_log_prob", "predict_mean", "predict_var", "predictive_cov_upper",
            "train_post_cov_upper", "mvn_root", "mvn_draw"]
 
@@ -57,6 +57,16 @@ class EvalWorkspace:
         self.info_host = torch.zeros(1, dtype=torch.int32).pin_memory()
         self.info_event = torch.cuda.Event()
         self.epoch = 0
+        self._loo = None
+
+    def loo_vectors(self):
+        """The O(N) vectors of a leave-one-out evaluation (ExactLOOFunction), allocated on first use: d, a, sqrt(b), beta, the
+        scratch z / out3 of beta's solve (the evaluation's own z and out3 stay what the value was computed from) and the value."""
+        if self._loo is None:
+            from types import SimpleNamespace
+            v = lambda n: torch.empty(n, dtype=torch.float64, device=self.A.device)  # noqa: E731
+            self._loo = SimpleNamespace(d=v(self.N), a=v(self.N), sb=v(self.N), beta=v(self.N), z=v(self.N), out3=v(3), val=v(1))
+        return self._loo
 
 
 _workspaces: Dict[Tuple[int, int, int], EvalWorkspace] = {}
@@ -294,6 +304,115 @@ def exact_mll(U: torch.Tensor, spec: KernelSpec, tau: torch.Tensor, mean: torch.
     return ExactMLLFunction.apply(U, spec.w, spec.sf2, tau, mean, y, grp, spec.kind, spec.d_split, int(n_grad_dims), slot)
 
 
+class ExactLOOFunction(torch.autograd.Function):
+    """Leave-one-out log pseudo-likelihood (Rasmussen & Williams 5.4.2; gpytorch LeaveOneOutPseudoLikelihood without its 1/N)
+        loo = sum_i log N(y_i | mu_i, s2_i),   s2_i = 1 / P_ii,   mu_i = y_i - alpha_i / P_ii,   P = Ky^-1, alpha = P (y - mean)
+    with the inputs, gradients and autograd contract of :class:`ExactMLLFunction`.  With a = dloo/dalpha = -alpha / d,
+    b = dloo/dd = 1 / (2 d) + alpha^2 / (2 d^2), beta = P a:
+        dloo = sum_ij W_ij dKy_ij,   W = -(alpha beta^T + beta alpha^T) / 2 - P diag(b) P,   dloo/dmean = -beta,   dloo/dy = beta.
+    Sequence (all enqueued ahead of the host's wait for the factorisation status, as in ExactMLLFunction): build + potrf, trtri,
+    z, alpha, gpp_loo_scalars (d from the rows of Linv: no LAUUM for the value); with a gradient: beta by the same two
+    triangular products, plain LAUUM into Ki, S = diag(sqrt b) P as a full square into A (dead since trtri), the lower triangle
+    of S^T S by the TN GEMM into Li (dead since beta), gpp_loo_grad_reduce.  No fourth N x N buffer; the value is produced by the
+    same kernels on the same inputs with and without a gradient.  Reference: optim/mll_noise_continuation.py:54 names the
+    criterion and never evaluates it."""
+
+    @staticmethod
+    def forward(ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slot):
+        get_context(U.device)  # raises GppError for anything but a GPU: there is no CPU path
+        with torch.cuda.device(U.device):
+            return ExactLOOFunction._forward(ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slot)
+
+    @staticmethod
+    def _forward(ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slot):
+        if torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("the leave-one-out objective is not available inside a graph capture")
+        dev = U.device
+        gctx = get_context(dev)
+        N, D = U.shape
+        Ud, wd, sd, td = _as_f64(U.detach(), dev), _as_f64(w.detach(), dev), _as_f64(sf2.detach().reshape(1), dev), \
+            _as_f64(tau.detach().reshape(-1), dev)
+        S = td.numel()
+        if grp is not None and grp.dtype != torch.int32:
+            grp = grp.to(torch.int32)
+        ws = get_workspace(gctx, N, slot)
+        ws.epoch += 1
+        lv = ws.loo_vectors()
+        torch.sub(_as_f64(y.detach(), dev), _as_f64(mean.detach(), dev), out=ws.r)
+        need = ctx.needs_input_grad
+        need_grad = any(need[:6])
+        need_U = need[0] and dU > 0
+        g_w = g_s = g_t = g_Ud = None
+        if need_grad:
+            g_w = torch.empty(D, dtype=torch.float64, device=dev)
+            g_s = torch.empty(1, dtype=torch.float64, device=dev)
+            g_t = torch.empty(S, dtype=torch.float64, device=dev)
+            g_Ud = torch.empty(N, dU, dtype=torch.float64, device=dev) if need_U else None
+
+        def rest():
+            with _stage("trtri"):
+                gctx.trtri(ws.A, ws.Li, ws.Ki)
+            with _stage("mll_reduce"):
+                gctx.mll_reduce(ws.A, ws.Li, ws.r, ws.z, ws.out3)
+            with _stage("alpha"):
+                gctx.alpha(ws.Li, ws.z, ws.alpha)
+            with _stage("loo_scalars"):
+                gctx.loo_scalars(ws.Li, ws.alpha, None, lv.d, a=lv.a, sqrtb=lv.sb, loo=lv.val)
+            if not need_grad:
+                return
+            with _stage("loo_beta"):  # beta = Ky^-1 a = Linv^T (Linv a), into scratch: ws.z / ws.out3 stay the evaluation's
+                gctx.mll_reduce(ws.A, ws.Li, lv.a, lv.z, lv.out3)
+                gctx.alpha(ws.Li, lv.z, lv.beta)
+            with _stage("lauum"):
+                gctx.lauum(ws.Li, ws.Ki)
+            with _stage("sym_rowscale"):
+                gctx.sym_rowscale(ws.Ki, lv.sb, ws.A)
+            with _stage("loo_gemm"):  # C(lower) = S^T S = P diag(b) P: M = N = K, row-contiguous TN
+                gctx.gemm(1, 0, N, N, N, 1.0, ws.A, ws.A, 0.0, ws.Li, c_tri=1)
+            with _stage("loo_grad_reduce"):
+                gctx.loo_grad_reduce(Ud, wd, sd, grp, S, ws.alpha, lv.beta, ws.Li, dU if need_U else 0, g_w, g_s, g_t, g_Ud,
+                                     kind=kind, d_split=d_split)
+
+        _factor(gctx, ws, Ud, wd, sd, td, grp, kind, d_split, after=rest)
+        ctx.saved = (g_w, g_s, g_t, g_Ud, lv.beta.clone() if need_grad else None, (N, D, dU))
+        ctx.in_dtypes = (U.dtype, w.dtype, sf2.dtype, tau.dtype, mean.dtype, y.dtype)
+        ctx.shapes = (sf2.shape, tau.shape)
+        return lv.val[0].clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        g_w, g_s, g_t, g_Ud, beta, (N, D, dU) = ctx.saved
+        need = ctx.needs_input_grad
+        go = grad_out.to(torch.float64)
+        g_U = None
+        if need[0]:
+            g_U = torch.zeros(N, D, dtype=torch.float64, device=beta.device)
+            if g_Ud is not None:
+                g_U[:, :dU] = g_Ud
+        dt = ctx.in_dtypes
+        sf2_shape, tau_shape = ctx.shapes
+        return (None if g_U is None else (go * g_U).to(dt[0]),
+                (go * g_w).to(dt[1]) if need[1] else None,
+                (go * g_s).reshape(sf2_shape).to(dt[2]) if need[2] else None,
+                (go * g_t).reshape(tau_shape).to(dt[3]) if need[3] else None,
+                (-go * beta).to(dt[4]) if need[4] else None,
+                (go * beta).to(dt[5]) if need[5] else None,
+                None, None, None, None, None)
+
+
+def exact_loo(U: torch.Tensor, spec: KernelSpec, tau: torch.Tensor, mean: torch.Tensor, y: torch.Tensor,
+              grp: Optional[torch.Tensor] = None, n_grad_dims: Optional[int] = None, slot: Optional[int] = None) -> torch.Tensor:
+    """Leave-one-out log pseudo-likelihood sum_i log p(y_i | y_-i) on the GPU; the signature and the autograd contract of
+    :func:`exact_mll` (differentiable w.r.t. U[:, :n_grad_dims], spec.w, spec.sf2, tau, mean, y)."""
+    if slot is None:
+        slot = current_slot()
+    if n_grad_dims is None:
+        n_grad_dims = U.shape[1] if U.requires_grad else 0
+    if settings.sharded_evaluation.value() is not None:
+        raise NotImplementedError("the leave-one-out objective is not available under settings.sharded_evaluation")
+    return ExactLOOFunction.apply(U, spec.w, spec.sf2, tau, mean, y, grp, spec.kind, spec.d_split, int(n_grad_dims), slot)
+
+
 # ---------------------------------------------------------------------------------------------------
 # dense evaluations (no autograd): .evaluate(), cross covariances, prediction
 # ---------------------------------------------------------------------------------------------------
@@ -378,6 +497,19 @@ def _factorize(U, spec: KernelSpec, tau, grp, mean, y) -> FactorCache:
     gctx.alpha(ws.Li, ws.z, ws.alpha)
     return FactorCache(gctx, ws.A, ws.Li, ws.alpha.clone(), Ud, KernelSpec(wd, sd.reshape(()), spec.kind, spec.d_split), jit, ws,
                        z=ws.z.clone(), refactor=(td.clone(), None if grp is None else grp.clone(), ws.r.clone()))
+
+
+@torch.no_grad()
+def loo_moments(cache: FactorCache, y: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Leave-one-out predictive mean and variance of every training target from a factor cache, O(N^2): mu_i = y_i - alpha_i / d_i,
+    s2_i = 1 / d_i with d = diag(Ky^-1) read off the rows of ``cache.Linv`` (gpp_loo_scalars) — no LAUUM, no N x N scratch."""
+    cache.refresh()  # another model of the same size may have factored into the shared workspace since
+    dev = cache.U.device
+    N = cache.U.shape[0]
+    with torch.cuda.device(dev):
+        d, mu, s2 = (torch.empty(N, dtype=torch.float64, device=dev) for _ in range(3))
+        cache.gctx.loo_scalars(cache.Linv, cache.alpha, _as_f64(y.reshape(-1), dev), d, mu=mu, s2=s2)
+    return mu, s2
 
 
 @torch.no_grad()

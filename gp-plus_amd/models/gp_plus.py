@@ -296,10 +296,14 @@ class GP_Plus(GPR):
     # ---- fit -----------------------------------------------------------------------------------------
     def fit(self, add_prior: bool = True, num_restarts: int = 64, theta0_list: Optional[List[np.ndarray]] = None,
             jac: bool = True, options: Dict = {}, n_jobs: int = -1, method='L-BFGS-B', constraint=False, bounds=False,
-            regularization_parameter: List[int] = [0, 0], optim_type='scipy'):
+            regularization_parameter: List[int] = [0, 0], optim_type='scipy', objective: str = "mll"):
         """gp_plus.py:547-599.  On a GPU device the reference always ends in ``fit_model_torch`` (64 restarts for
         'adam_torch', otherwise a warning and 4 restarts) — reproduced here.  The CPU branches
-        (scipy / continuation drivers) do not exist in this build: the exact-GP path only runs on the MI355X."""
+        (scipy / continuation drivers) do not exist in this build: the exact-GP path only runs on the MI355X.
+        ``objective``: "mll" (the exact marginal log-likelihood, as the reference) or "loo" (the leave-one-out log
+        pseudo-likelihood; the restarts then run one after the other, every evaluation eagerly)."""
+        from ..optim.mll_torch import check_objective
+        check_objective(objective)
         print("## Learning the model's parameters has started ##")
         if self.tkwargs['device'].type != 'cuda':
             raise RuntimeError("this build evaluates the marginal likelihood only on an MI355X (device='cuda'); "
@@ -314,7 +318,10 @@ class GP_Plus(GPR):
         # iteration: same start points in the same RNG order, same per-run optimiser and early stop, same winner —
         # optim/mll_batched.py) while the problem is small enough for that to pay and for the B x 3 N^2 workspace to fit;
         # settings.batched_restarts(False) restores the sequential loop, 'adam_torch_batched' asks for the batched one.
-        if optim_type == 'adam_torch_batched' or self._restarts_fit_one_batch(restarts + 1):
+        if objective == "loo":
+            out = fit_model_torch(model=self, model_param_groups=None, lr_default=0.01, num_iter=100,
+                                  num_restarts=restarts, break_steps=50, objective="loo")
+        elif optim_type == 'adam_torch_batched' or self._restarts_fit_one_batch(restarts + 1):
             from ..optim import fit_model_torch_batched
             out = fit_model_torch_batched(self, lr_default=0.01, num_iter=100, num_restarts=restarts, break_steps=50)
         else:
@@ -362,6 +369,19 @@ class GP_Plus(GPR):
         Xtest = data_type_check(Xtest)
         with gpp_settings.differentiable_predictions(True):
             return super().predict(Xtest.to(self.tkwargs['device']), return_std=return_std, include_noise=include_noise)
+
+    def loo_predict(self):
+        """Leave-one-out predictions at the training points: ``(mean, std)`` of p(y_i | X, y_-i) for every i, in the units of the
+        training targets, from the cached factorisation in O(N^2) — mu_i = y_i - alpha_i / (Ky^-1)_ii, sigma_i^2 = 1 / (Ky^-1)_ii
+        (Rasmussen & Williams 5.4.2), the diagonal read off the inverse factor by gpp_loo_scalars.  The variance is that of the
+        held-out OBSERVATION (its noise included)."""
+        from ..linalg import loo_moments
+
+        self.eval()
+        with torch.no_grad():
+            cache = self._ensure_prediction_cache()
+            mu, s2 = loo_moments(cache, self.train_targets)
+            return self.y_min + self.y_std * mu, s2.sqrt() * torch.abs(self.y_std)
 
     def noise_value(self):
         return self.likelihood.noise_covar.noise.detach() * self.y_std ** 2

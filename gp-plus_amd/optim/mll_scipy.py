@@ -25,10 +25,12 @@ from scipy.optimize import Bounds, OptimizeResult, minimize
 from ..errors import NanError, NotPSDError
 
 
-def marginal_log_likelihood(model, add_prior: bool, regularization_parameter=[0, 0]):
-    """optim/mll_scipy.py:37-60 (exact log-marginal + priors, un-normalised)."""
+def marginal_log_likelihood(model, add_prior: bool, regularization_parameter=[0, 0], objective: str = "mll"):
+    """optim/mll_scipy.py:37-60 (exact log-marginal + priors, un-normalised).  ``objective="loo"``: the leave-one-out log
+    pseudo-likelihood in place of the log-marginal."""
     output = model(*model.train_inputs)
-    out = model.likelihood(output).log_prob(model.train_targets)
+    noisy = model.likelihood(output)
+    out = noisy.loo_log_prob(model.train_targets) if objective == "loo" else noisy.log_prob(model.train_targets)
     if add_prior:
         for _, module, prior, closure, _ in model.named_priors():
             out = out + prior.log_prob(closure(module)).sum().to(out)
@@ -40,8 +42,11 @@ def marginal_log_likelihood(model, add_prior: bool, regularization_parameter=[0,
 class MLLObjective:
     """optim/mll_scipy.py:63-127."""
 
-    def __init__(self, model, add_prior, regularization_parameter):
+    def __init__(self, model, add_prior, regularization_parameter, objective: str = "mll"):
+        from .mll_torch import check_objective
+
         self.model, self.add_prior, self.regularization_parameter = model, add_prior, regularization_parameter
+        self.objective = check_objective(objective)
         self.param_shapes = OrderedDict()
         for n, p in self.model.named_parameters():
             if p.requires_grad:
@@ -84,7 +89,7 @@ class MLLObjective:
             params = list(self._params().values())
             dev = params[0].device if params else torch.device("cpu")
             n_points = self.model.train_inputs[0].shape[0]
-            ok = (settings.graphed_objective.value() and dev.type == "cuda" and n_points < LOOKAHEAD_MIN_N
+            ok = (self.objective == "mll" and settings.graphed_objective.value() and dev.type == "cuda" and n_points < LOOKAHEAD_MIN_N
                   and settings.sharded_evaluation.value() is None and not getattr(self.model, "interval_score", False))
             if not ok:
                 self._graph_failed = True
@@ -121,7 +126,7 @@ class MLLObjective:
         old.update(self.unpack_parameters(x))
         self.model.load_state_dict(old)
         self.model.zero_grad()
-        obj = -marginal_log_likelihood(self.model, self.add_prior, self.regularization_parameter)
+        obj = -marginal_log_likelihood(self.model, self.add_prior, self.regularization_parameter, self.objective)
         if return_grad:
             obj.backward()
             return obj.item(), self.pack_grads()
@@ -164,7 +169,11 @@ def _fit_model_from_state(likobj, theta0, jac, options, method='L-BFGS-B', const
 
 def fit_model_scipy(model, add_prior: bool = True, num_restarts: int = 1, theta0_list: Optional[List[np.ndarray]] = None,
                     jac: bool = True, options: Dict = {}, n_jobs: int = -1, method='L-BFGS-B', constraint=False,
-                    bounds=False, regularization_parameter: List[int] = [0, 0]) -> Tuple[List[OptimizeResult], float]:
+                    bounds=False, regularization_parameter: List[int] = [0, 0],
+                    objective: str = "mll") -> Tuple[List[OptimizeResult], float]:
+    from .mll_torch import check_objective
+
+    check_objective(objective)  # "loo": the leave-one-out log pseudo-likelihood (+ priors), evaluated eagerly
     if method == 'L-BFGS-B':
         defaults = {'ftol': 1e-6, 'gtol': 1e-5, 'maxfun': 5000, 'maxiter': 2000}
     elif method == 'trust-constr':
@@ -185,7 +194,7 @@ def fit_model_scipy(model, add_prior: bool = True, num_restarts: int = 1, theta0
         defaults[key] = options[key]
 
     model.train()
-    likobj = MLLObjective(model, add_prior, regularization_parameter)
+    likobj = MLLObjective(model, add_prior, regularization_parameter, objective)
     if theta0_list is None:
         theta0_list = [likobj.pack_parameters()]
         if num_restarts > -1:

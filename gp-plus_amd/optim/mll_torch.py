@@ -9,7 +9,17 @@ import torch
 from tqdm import tqdm
 
 from ..backend import INFO_PANEL_TIMEOUT
-from ..gpcore.mlls import ExactMarginalLogLikelihood
+from ..gpcore.mlls import ExactMarginalLogLikelihood, LeaveOneOutPseudoLikelihood
+
+#: what the fit drivers maximise (per datum, priors included): the exact marginal log-likelihood, or the leave-one-out log
+#: pseudo-likelihood (Rasmussen & Williams 5.4.2) — the latter always as the eager evaluation: no batched restarts, no replayed graph
+OBJECTIVES = ("mll", "loo")
+
+
+def check_objective(objective: str) -> str:
+    if objective not in OBJECTIVES:
+        raise ValueError(f"objective must be one of {OBJECTIVES} (got {objective!r})")
+    return objective
 
 
 def _plateaued(history: List[float], j: int, window: int) -> bool:
@@ -89,18 +99,24 @@ def _adam_run(model, mll, params, lr: float, num_iter: int, break_steps: int, ve
 
 
 def fit_model_torch(model, model_param_groups: Optional[List] = None, lr_default: float = 0.01, num_iter: int = 100,
-                    num_restarts: int = 0, break_steps: int = 50, verbose: bool = True) -> float:
+                    num_restarts: int = 0, break_steps: int = 50, verbose: bool = True, objective: str = "mll") -> float:
     """Optimize the log-posterior of a GP+ model with ``torch.optim.Adam`` (optim/mll_torch.py:56-141).
+
+    ``objective="loo"`` maximises the leave-one-out log pseudo-likelihood (plus the priors) instead of the marginal likelihood;
+    every evaluation is then the eager one.
 
     :returns: ``(f_inc, loss_hist_total)`` — best (negative, per-datum) log-posterior found and the loss histories.
     """
+    loo = check_objective(objective) == "loo"
     model.train()
-    mll = ExactMarginalLogLikelihood(model.likelihood, model)
+    mll = (LeaveOneOutPseudoLikelihood if loo else ExactMarginalLogLikelihood)(model.likelihood, model)
     best_loss, best_state = math.inf, model.state_dict()
     histories = []
     # the evaluation as one replayed HIP graph at the examples' sizes (the reference's notebooks and BO loop call this function
     # directly): captured once per fit, the restarts only change the parameters' values
-    graphed = _graphed_step(model, mll, list(model.parameters()), (num_restarts + 1) * num_iter) if model_param_groups is None else None
+    graphed = None
+    if model_param_groups is None and not loo:
+        graphed = _graphed_step(model, mll, list(model.parameters()), (num_restarts + 1) * num_iter)
     fit_model_torch.last_graph = None
     for restart in range(num_restarts + 1):
         params = model.parameters() if model_param_groups is None else model_param_groups

@@ -353,6 +353,34 @@ int gpp_grad_reduce(gpp_handle_t h, const double* U, int64_t N, int D, const dou
                     int64_t ldk, int dU, double* g_w, double* g_sf2, double* g_tau, double* g_U);
 
 /*
+ * Leave-one-out pseudo-likelihood (Rasmussen & Williams 5.4.2; gpytorch LeaveOneOutPseudoLikelihood).  The reference names a LOOCV
+ * criterion (optim/mll_noise_continuation.py:54) and only ever computes the scalar error of :28-42; there is no call site to replace.
+ * With P = Ky^-1, alpha = P (y - m) and d = diag(P):
+ *   d[i] = sum_{j >= i} Linv[i][j]^2   (row i of the Linv buffer from the diagonal on: column i of L^-1 through the mirror)
+ *   mu[i] = y[i] - alpha[i] / d[i]      s2[i] = 1 / d[i]                       (leave-one-out predictive mean and variance)
+ *   a[i]  = -alpha[i] / d[i]            sqrtb[i] = sqrt(1 / (2 d[i]) + alpha[i]^2 / (2 d[i]^2))
+ *   loo[0] = sum_i [ 0.5 log d[i] - alpha[i]^2 / (2 d[i]) ] - (N / 2) log 2 pi
+ * Linv: the complete inverse factor with its mirror.  mu (with y), s2, a, sqrtb and loo may each be NULL; d is always written.
+ * Deterministic: a row's sum does not depend on the launch shape, and loo is added in a fixed order (no atomics).
+ */
+int gpp_loo_scalars(gpp_handle_t h, const double* Linv, int64_t ldi, int64_t N, const double* alpha, const double* y, double* d,
+                    double* mu, double* s2, double* a, double* sqrtb, double* loo);
+
+/* S[i,j] = s[i] * Kinv[max(i,j), min(i,j)] for 0 <= i, j < N: the FULL square, row-scaled, from the LOWER triangle of Kinv (as the
+ * LAUUM leaves it; nothing above its diagonal is read).  Out of place (S != Kinv).  With s = sqrtb the lower triangle of
+ * P diag(b) P is the TN product S^T S (gpp_gemm with transA = 1, c_tri = 1).  Columns [N, lds) of S are not written. */
+int gpp_sym_rowscale(gpp_handle_t h, const double* Kinv, int64_t N, int64_t ldk, const double* s, double* S, int64_t lds);
+
+/*
+ * The K7 reduction with the weights of the leave-one-out pseudo-likelihood: W_ij = -0.5 (alpha_i beta_j + beta_i alpha_j) - C_ij,
+ * beta = P a and C = P diag(b) P (LOWER triangle read).  g_w, g_sf2, g_tau, g_U are defined as for gpp_grad_reduce with this W;
+ * the same kinds, d_split, D, S, dU, workspace and bitwise repeatability.  dLOO/dmean = -beta, dLOO/dy = +beta.
+ */
+int gpp_loo_grad_reduce(gpp_handle_t h, const double* U, int64_t N, int D, const double* w, const double* sf2,
+                        const int32_t* grp, int S, int kind, int d_split, const double* alpha, const double* beta,
+                        const double* C, int64_t ldc, int dU, double* g_w, double* g_sf2, double* g_tau, double* g_U);
+
+/*
  * The same reduction restricted to the block rows of Kinv this rank owns in a sharded evaluation (SURVEY.md §8(e) mode 2;
  * BASELINE config 5): rows [b*nb, (b+1)*nb) with b % nranks == rank (nb a multiple of 64).  Only those rows of Kinv are
  * read; the outputs are this rank's PARTIAL sums (the caller all-reduces them).  nranks == 1 is gpp_grad_reduce.
