@@ -22,6 +22,7 @@ from ._lib import GppError, check
 KIND_RBF, KIND_MATERN32, KIND_MATERN52 = 0, 1, 2
 UPLO_FULL, UPLO_LOWER, UPLO_UPPER = 0, 1, 2
 OPT_COOP_PANEL, OPT_PANEL_FAULT, OPT_PANEL_TIMEOUT_MS, OPT_EXEC_SCHED, OPT_DAG_SCHED = 1, 2, 3, 4, 5  # gpp_set_option (include/gpp.h)
+OPT_GEMM_TILE = 6  # tile of gemm / gemm_batched: 0 by grid size, 1 = 32x32, 2 = 64x64, 3 = 128x128, 4 = 128x32 (tests)
 OP_MLL_EVAL, OP_PREDICT, OP_PREDICT_GRAD = 0, 1, 2
 NOT_SUPPORTED = 2001  # GPP_NOT_SUPPORTED: gpp_lauum_grad does not take these arguments, nothing was enqueued
 NO_WORKSPACE = 2002   # GPP_NO_WORKSPACE: gpp_lauum_grad found no (or too small a) scratch workspace on the handle

@@ -917,6 +917,7 @@ int gpp_create(gpp_handle_t* out, int device) {
   h->shard_ready = nullptr;
   h->dag_clock = 0;
   h->dag_sched = 1;
+  h->gemm_tile = 0;
   h->ncu = 0;
   if (hipDeviceGetAttribute(&h->ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || h->ncu < 2) {
     (void)hipGetLastError();
@@ -991,6 +992,9 @@ int gpp_set_option(gpp_handle_t h, int option, int value) {
   else if (option == GPP_OPT_PANEL_TIMEOUT_MS) {
     if (value < 1 || value > 60000) return -3;
     h->panel_timeout_ms = value;
+  } else if (option == GPP_OPT_GEMM_TILE) {
+    if (value < 0 || value > 4) return -3;
+    h->gemm_tile = value;
   } else return -2;
   return 0;
 }
@@ -1791,6 +1795,13 @@ int gpp_cross_grad(gpp_handle_t h, const double* Ua, int64_t M, const double* Ub
   return 0;
 }
 
+// GPP_OPT_GEMM_TILE: the work-group tile the two exported products below hand to gpp_launch_gemm (0, 0: chosen by grid size)
+static void forced_gemm_tile(const gpp_handle_s* h, int* tile_m, int* tile_n) {
+  static const int tm[5] = {0, 32, 64, 128, 128}, tn[5] = {0, 32, 64, 128, 32};
+  *tile_m = tm[h->gemm_tile];
+  *tile_n = tn[h->gemm_tile];
+}
+
 int gpp_gemm(gpp_handle_t h, int transA, int transB, int64_t M, int64_t N, int64_t K, double alpha, const double* A,
              int64_t lda, const double* B, int64_t ldb, double beta, double* C, int64_t ldc, int a_mask, int b_mask,
              int klo_mode, int khi_mode, int c_tri) {
@@ -1810,7 +1821,10 @@ int gpp_gemm(gpp_handle_t h, int transA, int transB, int64_t M, int64_t N, int64
   GemmArgs g = mk(A, lda, B, ldb, C, ldc, M, N, K, alpha, beta);
   g.a_mask = a_mask; g.b_mask = b_mask; g.klo_mode = klo_mode; g.khi_mode = khi_mode; g.c_lower = c_tri;
   if (h->cu_split == 1 && h->stream == h->panel_stream) g.cu_hint = h->panel_cus;
-  GPP_TRY(gpp_launch_gemm(h->stream, variant, g, 1));
+  int tile_m, tile_n;
+  forced_gemm_tile(h, &tile_m, &tile_n);
+  if (c_tri && tile_m != tile_n) return -19;  // gpp_launch_gemm enumerates a triangle of square tiles only
+  GPP_TRY(gpp_launch_gemm(h->stream, variant, g, 1, tile_m, tile_n));
   return 0;
 }
 
@@ -1836,7 +1850,10 @@ int gpp_gemm_batched(gpp_handle_t h, int transA, int transB, int64_t M, int64_t 
   g.a_mask = a_mask; g.b_mask = b_mask; g.klo_mode = klo_mode; g.khi_mode = khi_mode; g.c_lower = c_tri;
   g.sA = sA; g.sB = sB; g.sC = sC;
   if (h->cu_split == 1 && h->stream == h->panel_stream) g.cu_hint = h->panel_cus;
-  GPP_TRY(gpp_launch_gemm(h->stream, variant, g, batch));
+  int tile_m, tile_n;
+  forced_gemm_tile(h, &tile_m, &tile_n);
+  if (c_tri && tile_m != tile_n) return -23;
+  GPP_TRY(gpp_launch_gemm(h->stream, variant, g, batch, tile_m, tile_n));
   return 0;
 }
 

@@ -51,6 +51,7 @@ struct gpp_handle_s {
   int32_t* shard_info;
   hipEvent_t shard_ready;     // counters cleared + groups bound: what the caller's communication stream waits for before a gate / signal
   int dag_sched;             // GPP_OPT_DAG_SCHED
+  int gemm_tile;             // GPP_OPT_GEMM_TILE: work-group tile of gpp_gemm / gpp_gemm_batched, 0 = by grid size (tests)
   int split_builds;          // gpp_build_potrf_ws calls that built Ky split around panel 0 (gpp_debug_split_builds)
   // gpp_shard.hip: the collectives of gpp_shard_eval (the caller's callbacks, or RCCL opened at run time) and its own stream
   gpp_comm_t comm;

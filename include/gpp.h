@@ -74,6 +74,9 @@ int gpp_internal_stream(gpp_handle_t h, int which, void** out);
  * reports *info = GPP_INFO_PANEL_TIMEOUT + the milliseconds the abandoned wait had waited (low 20 bits) — the
  * caller switches the option off and factors again (gp-plus_amd/linalg.py does).  GPP_OPT_PANEL_FAULT (default 0): the NEXT
  * panel launch reports that time-out without running (one shot; for tests of the caller's recovery).
+ * GPP_OPT_GEMM_TILE (default 0; for tests): the work-group tile of gpp_gemm and gpp_gemm_batched — 0 chosen by grid size, 1 = 32 x 32,
+ * 2 = 64 x 64, 3 = 128 x 128, 4 = 128 x 32 (full output only: with c_tri the two entry points report their c_tri argument); any other
+ * value returns -3.  No other entry point reads it.
  * No reference counterpart: the reference's factorisation is torch.linalg.cholesky_ex behind gpytorch (optim/mll_torch.py:116). */
 #define GPP_OPT_COOP_PANEL 1
 #define GPP_OPT_PANEL_FAULT 2
@@ -83,6 +86,7 @@ int gpp_internal_stream(gpp_handle_t h, int which, void** out);
                               * beside it) as ONE list of tile tasks in topological order that persistent work-groups take by atomic
                               * ticket (gpp_dag.hip, gpp_dag_f64) — needs no co-residency of its work-groups; the diagonal blocks still
                               * run as cooperative panel launches (GPP_OPT_COOP_PANEL) */
+#define GPP_OPT_GEMM_TILE 6
 #define GPP_INFO_PANEL_TIMEOUT (1 << 30)
 /* a wait of one of the DAG executor's work-groups (gpp_dag_f64, its gate kernels) timed out — status =
  * GPP_INFO_EXEC_TIMEOUT + milliseconds: the caller switches GPP_OPT_DAG_SCHED off and factors again; the
@@ -429,8 +433,17 @@ int gpp_cross_grad(gpp_handle_t h, const double* Ua, int64_t M, const double* Ub
  * transA: 0 = A stored M x K, 1 = A stored K x M;  transB: 0 = B stored K x N, 1 = B stored N x K.
  * Supported (transA,transB): (0,1) "NT", (0,0) "NN", (1,0) "TN".
  * a_mask/b_mask: 0 none, 1 keep entries with k <= row, 2 keep entries with k >= row (row = m for A, n for B);
- * klo_mode: 0 -> 0, 1 -> tile_m*128, 2 -> tile_n*128, 3 -> max of both;  khi_mode: 0 -> K, 1 -> (tile_m+1)*128,
- * 2 -> (tile_n+1)*128;  c_tri: 0 full output, 1 only entries with n <= m, 2 only entries with n >= m (M == N).
+ * c_tri: 0 full output, 1 only entries with n <= m, 2 only entries with n >= m (M == N); every other entry of C is left as it is.
+ * klo_mode / khi_mode: the range of k each work-group tile runs over, from the tile's own first row m0 and first column n0 and its
+ * own edge (TM rows x TN columns, chosen by the launcher: 32, 64 or 128) —
+ *   klo_mode: 0 -> 0, 1 -> m0, 2 -> n0, 3 -> max(m0, n0);   khi_mode: 0 -> K, 1 -> min(K, m0 + TM), 2 -> min(K, n0 + TN).
+ * A mode is a HINT that saves the chunks the masks zero anyway: it is valid only where the masks already exclude every k outside
+ * the range, and under that condition the result does not depend on the tile (nor, bit for bit, on the hint).  The legal pairs:
+ *   khi_mode 1 needs a_mask 1,  khi_mode 2 needs b_mask 1,  klo_mode 1 needs a_mask 2,  klo_mode 2 needs b_mask 2,
+ *   klo_mode 3 needs a_mask 2 and b_mask 2.
+ * Any other combination drops terms of the product, differently for every tile size.  A tile whose range is empty (khi <= klo)
+ * gets beta*C.  lda, ldb, ldc: even; A, B, C: 16-byte aligned; a row's last 16-byte load may read one double past an odd extent,
+ * inside ld.
  */
 int gpp_gemm(gpp_handle_t h, int transA, int transB, int64_t M, int64_t N, int64_t K, double alpha, const double* A,
              int64_t lda, const double* B, int64_t ldb, double beta, double* C, int64_t ldc, int a_mask, int b_mask,
