@@ -95,10 +95,18 @@ def panel_timed_out(ctx: "GppContext", info: int) -> bool:
     return True
 
 
+def row_stride(n: int) -> int:
+    """Row stride of an n-column fp64 matrix: n padded to a multiple of 16 doubles (128-byte lines)."""
+    return max(16, (n + 15) // 16 * 16)
+
+
+def rows_buffer(m: int, n: int, device) -> torch.Tensor:
+    """Uninitialised m x n fp64 matrix with padded rows (``row_stride``)."""
+    return torch.empty((m, row_stride(n)), dtype=torch.float64, device=device)[:, :n]
+
+
 def square_buffer(n: int, device) -> torch.Tensor:
-    """Uninitialised n x n fp64 matrix whose rows are padded to a multiple of 16 doubles (128-byte lines)."""
-    ld = max(16, (n + 15) // 16 * 16)
-    return torch.empty((n, ld), dtype=torch.float64, device=device)[:, :n]
+    return rows_buffer(n, n, device)
 
 
 def _ld(m: torch.Tensor) -> int:
@@ -585,8 +593,7 @@ class GppContext:
     # matrices: (B, N, ld) views of a (B, N, ld) allocation ([:, :, :N]); vectors: (B, N) views of a (B, sv) allocation
     # with sv even (``batched_vector``); parameters (B, D), (B,), (B, S)
     def batched_buffer(self, B: int, n: int) -> torch.Tensor:
-        ld = max(16, (n + 15) // 16 * 16)
-        return torch.empty((B, n, ld), dtype=torch.float64, device=self.device)[:, :, :n]
+        return torch.empty((B, n, row_stride(n)), dtype=torch.float64, device=self.device)[:, :, :n]
 
     def batched_vector(self, B: int, n: int) -> torch.Tensor:
         return torch.empty((B, n + (n & 1)), dtype=torch.float64, device=self.device)[:, :n]

@@ -19,7 +19,8 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from .backend import KIND_RBF, UPLO_UPPER, GppContext, get_context
-from . import settings
+from .linalg import _as_f64
+from .psd_safe import jitter_schedule
 
 __all__ = ["BatchedWorkspace", "BatchedMLLFunction", "batched_mll"]
 
@@ -53,10 +54,6 @@ def get_batched_workspace(ctx: GppContext, B: int, N: int) -> BatchedWorkspace:
     return ws
 
 
-def _f64(t: torch.Tensor, dev) -> torch.Tensor:
-    return t.detach().to(device=dev, dtype=torch.float64).contiguous()
-
-
 def _factor_batched(gctx: GppContext, ws: BatchedWorkspace, U, w, sf2, tau, grp, kind, d_split, after=None) -> torch.Tensor:
     """Build + factor all elements; failing ones are retried with gpytorch's jitter schedule added to THEIR noise.
     Returns the boolean mask (B,) of elements that are positive definite in the end.  ``after()`` enqueues the rest of
@@ -69,7 +66,7 @@ def _factor_batched(gctx: GppContext, ws: BatchedWorkspace, U, w, sf2, tau, grp,
         if after is not None:
             after()
         return ws.info == 0
-    jitters = [settings.cholesky_jitter.value() * (10 ** i) for i in range(settings.cholesky_max_tries.value())]
+    jitters = jitter_schedule()[1:]  # (the first attempt is the unjittered one)
     extra = torch.zeros(ws.B, 1, dtype=torch.float64, device=U.device)
     ok = None
     for attempt in range(len(jitters) + 1):
@@ -97,13 +94,14 @@ class BatchedMLLFunction(torch.autograd.Function):
         gctx = get_context(dev)
         B, D = w.shape
         N = U.shape[-2]
-        Ud, wd, sd, td = _f64(U, dev), _f64(w, dev), _f64(sf2.reshape(B), dev), _f64(tau.reshape(B, -1), dev)
+        Ud, wd, sd, td = _as_f64(U.detach(), dev), _as_f64(w.detach(), dev), _as_f64(sf2.detach().reshape(B), dev), \
+            _as_f64(tau.detach().reshape(B, -1), dev)
         S = td.shape[1]
         if grp is not None and grp.dtype != torch.int32:
             grp = grp.to(torch.int32)
         ws = get_batched_workspace(gctx, B, N)
         ws.epoch += 1
-        torch.sub(_f64(y, dev).expand(B, N), _f64(mean, dev).expand(B, N), out=ws.r)
+        torch.sub(_as_f64(y.detach(), dev).expand(B, N), _as_f64(mean.detach(), dev).expand(B, N), out=ws.r)
         need = ctx.needs_input_grad
         need_grad = any(need[:6])
         need_U = need[0] and dU > 0

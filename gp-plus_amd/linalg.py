@@ -8,21 +8,20 @@ Replaces, for the path ``optim/mll_torch.py:114-117``:
              tiled reduction of W = (alpha alpha^T - Ky^-1)/2 against dKy/dtheta.
 Both halves are ENQUEUED together in the Function's forward when a gradient is wanted (see ExactMLLFunction), so that
 the single host sync of an evaluation — reading the factorisation status — comes after all of its device work.
-Jitter policy restates gpytorch.utils.cholesky.psd_safe_cholesky [3P]: 1e-8 * 10^i, i = 0..2 (fp64), warn, then
-``NotPSDError``; NaN inputs raise ``NanError``.
+Jitter policy (``psd_safe.py``, one driver for every factorisation of the package) restates
+gpytorch.utils.cholesky.psd_safe_cholesky [3P]: 1e-8 * 10^i, i = 0..2 (fp64), warn, then ``NotPSDError``; NaN inputs raise ``NanError``.
 """
 from __future__ import annotations
 
 import threading
-import warnings
 from contextlib import contextmanager
 from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
 
 import torch
 
-from .backend import (KIND_RBF, OP_MLL_EVAL, UPLO_FULL, UPLO_UPPER, GppContext, get_context, panel_timed_out, square_buffer)
-from .errors import NanError, NotPSDError
+from .backend import KIND_RBF, UPLO_FULL, UPLO_UPPER, GppContext, get_context, rows_buffer, square_buffer
+from .psd_safe import inputs_nan_probe, psd_safe
 from . import settings
 
 __all__ = ["KernelSpec", "exact_mll", "ExactMLLFunction", "exact_loo", "ExactLOOFunction", "loo_moments", "EvalWorkspace", "dense_kernel", "cross_kernel",
@@ -151,10 +150,8 @@ def _factor(ctx: GppContext, ws: EvalWorkspace, U, w, sf2, tau, grp, kind, d_spl
         if after is not None:
             after()
         return 0.0
-    jitters = [0.0] + [settings.cholesky_jitter.value() * (10 ** i) for i in range(settings.cholesky_max_tries.value())]
-    attempts = list(jitters)
-    while attempts:
-        jit = attempts.pop(0)
+
+    def attempt(jit):
         # The factorisation's launches (a DAG over the library's internal streams, ~1000 launches at N = 20000) run fastest
         # when they are enqueued while the device executes them, and measurably slower when they were parked in the
         # queues beforehand — N = 20000: potrf 55.7 ms when enqueued on an idle device, 58.0 when enqueued ~1 ms ahead
@@ -183,20 +180,94 @@ def _factor(ctx: GppContext, ws: EvalWorkspace, U, w, sf2, tau, grp, kind, d_spl
         if after is not None:
             after()
         ws.info_event.synchronize()
-        info = int(ws.info_host[0])
-        if panel_timed_out(ctx, info):
-            attempts.insert(0, jit)  # not a statement about the matrix: the same attempt again, without the panel
-            continue
-        if info == 0:
-            if jit > 0:
-                warnings.warn(f"A not p.d., added jitter of {jit:.1e} to the diagonal", RuntimeWarning)
-            return jit
-        if jit == 0.0:
-            bad = [n for n, t in (("inputs", U), ("weights", w), ("outputscale", sf2), ("noise", tau)) if not torch.isfinite(t).all()]
-            if bad:
-                raise NanError(f"cholesky: NaN/Inf in {', '.join(bad)} of the covariance")
-    raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {jitters[-1]:.1e} "
-                      f"(leading minor {info}).")
+        return int(ws.info_host[0])
+
+    return psd_safe(ctx, attempt, inputs_nan_probe(U, w, sf2, tau))
+
+
+# ---------------------------------------------------------------------------------------------------
+# what the evaluation Functions share (ExactMLLFunction, ExactLOOFunction, sharded.ShardedMLLFunction)
+# ---------------------------------------------------------------------------------------------------
+def _operands(U, w, sf2, tau, grp):
+    """The operands of an evaluation as the kernels take them: U, w, sf2 (1,) and tau (S,) detached, fp64 and contiguous on U's
+    device, and ``grp`` as int32."""
+    dev = U.device
+    Ud, wd, sd, td = _as_f64(U.detach(), dev), _as_f64(w.detach(), dev), _as_f64(sf2.detach().reshape(1), dev), \
+        _as_f64(tau.detach().reshape(-1), dev)
+    if grp is not None and grp.dtype != torch.int32:
+        grp = grp.to(torch.int32)
+    return Ud, wd, sd, td, grp
+
+
+def _eval_operands(ctx, U, w, sf2, tau, mean, y, grp, dU):
+    """``_operands``, the number of noise groups S, and (need_grad, need_U) from ``ctx.needs_input_grad``.  Notes on ``ctx`` what
+    ``_eval_backward`` needs to hand every gradient back in its input's dtype and shape."""
+    Ud, wd, sd, td, grp = _operands(U, w, sf2, tau, grp)
+    need = ctx.needs_input_grad
+    ctx.in_dtypes = (U.dtype, w.dtype, sf2.dtype, tau.dtype, mean.dtype, y.dtype)
+    ctx.shapes = (sf2.shape, tau.shape)
+    return Ud, wd, sd, td, grp, td.numel(), any(need[:6]), need[0] and dU > 0
+
+
+def _eval_backward(ctx, grad_out, g_w, g_s, g_t, g_Ud, g_mean):
+    """The gradients of (U, w, sf2, tau, mean, y) from the fp64 ones an evaluation produced, scaled by ``grad_out``, each in its
+    input's dtype (and shape): ``g_Ud`` (N x dU, or None) fills the leading columns of U's, the others are zero; ``g_mean`` is the
+    objective's derivative by the mean (alpha for the MLL, -beta for LOO) and y receives its negative."""
+    need = ctx.needs_input_grad
+    go = grad_out.to(torch.float64)
+    g_U = None
+    if need[0]:
+        g_U = torch.zeros(g_mean.shape[0], g_w.shape[0], dtype=torch.float64, device=g_mean.device)
+        if g_Ud is not None:
+            g_U[:, :g_Ud.shape[1]] = g_Ud
+    dt = ctx.in_dtypes
+    sf2_shape, tau_shape = ctx.shapes
+    return (None if g_U is None else (go * g_U).to(dt[0]),
+            (go * g_w).to(dt[1]) if need[1] else None,
+            (go * g_s).reshape(sf2_shape).to(dt[2]) if need[2] else None,
+            (go * g_t).reshape(tau_shape).to(dt[3]) if need[3] else None,
+            (go * g_mean).to(dt[4]) if need[4] else None,
+            (-go * g_mean).to(dt[5]) if need[5] else None)
+
+
+def _exact_forward(fn, ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slot):
+    """The forward of the single-GPU objectives.  ``fn`` (ExactMLLFunction / ExactLOOFunction) supplies what differs: whether the
+    value alone needs alpha, the ``tail`` of the enqueued sequence behind trtri, z and alpha, and its ``result``."""
+    gctx = get_context(U.device)  # raises GppError for anything but a GPU: there is no CPU path
+    with torch.cuda.device(U.device):  # streams, events and the library's launches all refer to the model's GPU
+        if not fn.capturable and torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("the leave-one-out objective is not available inside a graph capture")
+        dev = U.device
+        N, D = U.shape
+        Ud, wd, sd, td, grp, S, need_grad, need_U = _eval_operands(ctx, U, w, sf2, tau, mean, y, grp, dU)
+        ws = get_workspace(gctx, N, slot)
+        ws.epoch += 1
+        torch.sub(_as_f64(y.detach(), dev), _as_f64(mean.detach(), dev), out=ws.r)
+        g_w = g_s = g_t = g_Ud = None
+        if need_grad:
+            g_w = torch.empty(D, dtype=torch.float64, device=dev)
+            g_s = torch.empty(1, dtype=torch.float64, device=dev)
+            g_t = torch.empty(S, dtype=torch.float64, device=dev)
+            g_Ud = torch.empty(N, dU, dtype=torch.float64, device=dev) if need_U else None
+        ops, grads = (Ud, wd, sd, grp, S), (dU if need_U else 0, g_w, g_s, g_t, g_Ud)
+
+        def rest():
+            with _stage("trtri"):
+                gctx.trtri(ws.A, ws.Li, ws.Ki)
+            with _stage("mll_reduce"):
+                gctx.mll_reduce(ws.A, ws.Li, ws.r, ws.z, ws.out3)
+            # (Measured and NOT adopted: z, the MLL scalars and alpha on a side stream beside the LAUUM launch — the extra
+            #  stream perturbs the hardware-queue mapping of the NEXT evaluation's factorisation DAG: potrf 53.3 -> 58-60 ms,
+            #  137 -> 142-144 ms per evaluation at N = 20000, tools/attic/side_ab.py.)
+            if need_grad or fn.value_needs_alpha:
+                with _stage("alpha"):
+                    gctx.alpha(ws.Li, ws.z, ws.alpha)
+            fn.tail(gctx, ws, need_grad, ops, grads, kind, d_split)
+
+        _factor(gctx, ws, Ud, wd, sd, td, grp, kind, d_split, after=rest)
+        value, g_mean = fn.result(ws, need_grad)
+        ctx.saved = (g_w, g_s, g_t, g_Ud, g_mean)
+        return value
 
 
 class ExactMLLFunction(torch.autograd.Function):
@@ -207,86 +278,36 @@ class ExactMLLFunction(torch.autograd.Function):
     the device then works through the Python that lies between the reference's ``-mll(...)`` and ``loss.backward()``
     (optim/mll_torch.py:116-117), and ``backward`` only scales the stored gradients by the incoming one."""
 
+    capturable, value_needs_alpha = True, False
+
     @staticmethod
     def forward(ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slot):
-        get_context(U.device)  # raises GppError for anything but a GPU: there is no CPU path
-        with torch.cuda.device(U.device):  # streams, events and the library's launches all refer to the model's GPU
-            return ExactMLLFunction._forward(ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slot)
+        return _exact_forward(ExactMLLFunction, ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slot)
 
     @staticmethod
-    def _forward(ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slot):
-        dev = U.device
-        gctx = get_context(dev)
-        N, D = U.shape
-        Ud, wd, sd, td = _as_f64(U.detach(), dev), _as_f64(w.detach(), dev), _as_f64(sf2.detach().reshape(1), dev), \
-            _as_f64(tau.detach().reshape(-1), dev)
-        S = td.numel()
-        if grp is not None and grp.dtype != torch.int32:
-            grp = grp.to(torch.int32)
-        ws = get_workspace(gctx, N, slot)
-        ws.epoch += 1
-        torch.sub(_as_f64(y.detach(), dev), _as_f64(mean.detach(), dev), out=ws.r)
-        need = ctx.needs_input_grad
-        need_grad = any(need[:6])
-        need_U = need[0] and dU > 0
-        g_w = g_s = g_t = g_Ud = None
-        if need_grad:
-            g_w = torch.empty(D, dtype=torch.float64, device=dev)
-            g_s = torch.empty(1, dtype=torch.float64, device=dev)
-            g_t = torch.empty(S, dtype=torch.float64, device=dev)
-            g_Ud = torch.empty(N, dU, dtype=torch.float64, device=dev) if need_U else None
+    def tail(gctx, ws, need_grad, ops, grads, kind, d_split):
+        if not need_grad:
+            return
+        # Above FUSED_GRAD_MIN_N the gradient reduction is the EPILOGUE of the LAUUM's tiles where the library supports it (RBF,
+        # D <= 16, no feature gradients): Ky^-1 is then neither written nor read, and ws.Ki holds the inverse's scratch, not
+        # Ky^-1 (nothing reads it after a training evaluation: the prediction and sampling paths form their own).
+        fused = False
+        with _stage("lauum"):
+            if ws.N > FUSED_GRAD_MIN_N:
+                fused = gctx.lauum_grad(ws.Li, *ops, ws.alpha, *grads[:4], kind=kind)
+            if not fused:
+                gctx.lauum(ws.Li, ws.Ki)
+        with _stage("grad_reduce"):
+            if not fused:
+                gctx.grad_reduce(*ops, ws.alpha, ws.Ki, *grads, kind=kind, d_split=d_split)
 
-        def rest():
-            with _stage("trtri"):
-                gctx.trtri(ws.A, ws.Li, ws.Ki)
-            with _stage("mll_reduce"):
-                gctx.mll_reduce(ws.A, ws.Li, ws.r, ws.z, ws.out3)
-            if not need_grad:
-                return
-            # (Measured and NOT adopted: z, the MLL scalars and alpha on a side stream beside the LAUUM launch — the extra
-            #  stream perturbs the hardware-queue mapping of the NEXT evaluation's factorisation DAG: potrf 53.3 -> 58-60 ms,
-            #  137 -> 142-144 ms per evaluation at N = 20000, tools/attic/side_ab.py.)
-            with _stage("alpha"):
-                gctx.alpha(ws.Li, ws.z, ws.alpha)
-            # Above FUSED_GRAD_MIN_N the gradient reduction is the EPILOGUE of the LAUUM's tiles where the library supports it (RBF,
-            # D <= 16, no feature gradients): Ky^-1 is then neither written nor read, and ws.Ki holds the inverse's scratch, not
-            # Ky^-1 (nothing reads it after a training evaluation: the prediction and sampling paths form their own).
-            fused = False
-            with _stage("lauum"):
-                if N > FUSED_GRAD_MIN_N:
-                    fused = gctx.lauum_grad(ws.Li, Ud, wd, sd, grp, S, ws.alpha, dU if need_U else 0, g_w, g_s, g_t, kind=kind)
-                if not fused:
-                    gctx.lauum(ws.Li, ws.Ki)
-            with _stage("grad_reduce"):
-                if not fused:
-                    gctx.grad_reduce(Ud, wd, sd, grp, S, ws.alpha, ws.Ki, dU if need_U else 0, g_w, g_s, g_t, g_Ud, kind=kind,
-                                     d_split=d_split)
-
-        _factor(gctx, ws, Ud, wd, sd, td, grp, kind, d_split, after=rest)
-        ctx.saved = (g_w, g_s, g_t, g_Ud, ws.alpha.clone() if need_grad else None, (N, D, dU))
-        ctx.in_dtypes = (U.dtype, w.dtype, sf2.dtype, tau.dtype, mean.dtype, y.dtype)
-        ctx.shapes = (sf2.shape, tau.shape)
-        return ws.out3[2].clone()
+    @staticmethod
+    def result(ws, need_grad):
+        return ws.out3[2].clone(), (ws.alpha.clone() if need_grad else None)
 
     @staticmethod
     def backward(ctx, grad_out):
-        g_w, g_s, g_t, g_Ud, alpha, (N, D, dU) = ctx.saved
-        need = ctx.needs_input_grad
-        go = grad_out.to(torch.float64)
-        g_U = None
-        if need[0]:
-            g_U = torch.zeros(N, D, dtype=torch.float64, device=alpha.device)
-            if g_Ud is not None:
-                g_U[:, :dU] = g_Ud
-        dt = ctx.in_dtypes
-        sf2_shape, tau_shape = ctx.shapes
-        return (None if g_U is None else (go * g_U).to(dt[0]),
-                (go * g_w).to(dt[1]) if need[1] else None,
-                (go * g_s).reshape(sf2_shape).to(dt[2]) if need[2] else None,
-                (go * g_t).reshape(tau_shape).to(dt[3]) if need[3] else None,
-                (go * alpha).to(dt[4]) if need[4] else None,
-                (-go * alpha).to(dt[5]) if need[5] else None,
-                None, None, None, None, None)
+        return _eval_backward(ctx, grad_out, *ctx.saved) + (None,) * 5
 
 
 def exact_mll(U: torch.Tensor, spec: KernelSpec, tau: torch.Tensor, mean: torch.Tensor, y: torch.Tensor,
@@ -317,87 +338,39 @@ class ExactLOOFunction(torch.autograd.Function):
     same kernels on the same inputs with and without a gradient.  Reference: optim/mll_noise_continuation.py:54 names the
     criterion and never evaluates it."""
 
+    capturable, value_needs_alpha = False, True
+
     @staticmethod
     def forward(ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slot):
-        get_context(U.device)  # raises GppError for anything but a GPU: there is no CPU path
-        with torch.cuda.device(U.device):
-            return ExactLOOFunction._forward(ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slot)
+        return _exact_forward(ExactLOOFunction, ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slot)
 
     @staticmethod
-    def _forward(ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slot):
-        if torch.cuda.is_current_stream_capturing():
-            raise NotImplementedError("the leave-one-out objective is not available inside a graph capture")
-        dev = U.device
-        gctx = get_context(dev)
-        N, D = U.shape
-        Ud, wd, sd, td = _as_f64(U.detach(), dev), _as_f64(w.detach(), dev), _as_f64(sf2.detach().reshape(1), dev), \
-            _as_f64(tau.detach().reshape(-1), dev)
-        S = td.numel()
-        if grp is not None and grp.dtype != torch.int32:
-            grp = grp.to(torch.int32)
-        ws = get_workspace(gctx, N, slot)
-        ws.epoch += 1
+    def tail(gctx, ws, need_grad, ops, grads, kind, d_split):
+        N, lv = ws.N, ws.loo_vectors()
+        with _stage("loo_scalars"):
+            gctx.loo_scalars(ws.Li, ws.alpha, None, lv.d, a=lv.a, sqrtb=lv.sb, loo=lv.val)
+        if not need_grad:
+            return
+        with _stage("loo_beta"):  # beta = Ky^-1 a = Linv^T (Linv a), into scratch: ws.z / ws.out3 stay the evaluation's
+            gctx.mll_reduce(ws.A, ws.Li, lv.a, lv.z, lv.out3)
+            gctx.alpha(ws.Li, lv.z, lv.beta)
+        with _stage("lauum"):
+            gctx.lauum(ws.Li, ws.Ki)
+        with _stage("sym_rowscale"):
+            gctx.sym_rowscale(ws.Ki, lv.sb, ws.A)
+        with _stage("loo_gemm"):  # C(lower) = S^T S = P diag(b) P: M = N = K, row-contiguous TN
+            gctx.gemm(1, 0, N, N, N, 1.0, ws.A, ws.A, 0.0, ws.Li, c_tri=1)
+        with _stage("loo_grad_reduce"):
+            gctx.loo_grad_reduce(*ops, ws.alpha, lv.beta, ws.Li, *grads, kind=kind, d_split=d_split)
+
+    @staticmethod
+    def result(ws, need_grad):
         lv = ws.loo_vectors()
-        torch.sub(_as_f64(y.detach(), dev), _as_f64(mean.detach(), dev), out=ws.r)
-        need = ctx.needs_input_grad
-        need_grad = any(need[:6])
-        need_U = need[0] and dU > 0
-        g_w = g_s = g_t = g_Ud = None
-        if need_grad:
-            g_w = torch.empty(D, dtype=torch.float64, device=dev)
-            g_s = torch.empty(1, dtype=torch.float64, device=dev)
-            g_t = torch.empty(S, dtype=torch.float64, device=dev)
-            g_Ud = torch.empty(N, dU, dtype=torch.float64, device=dev) if need_U else None
-
-        def rest():
-            with _stage("trtri"):
-                gctx.trtri(ws.A, ws.Li, ws.Ki)
-            with _stage("mll_reduce"):
-                gctx.mll_reduce(ws.A, ws.Li, ws.r, ws.z, ws.out3)
-            with _stage("alpha"):
-                gctx.alpha(ws.Li, ws.z, ws.alpha)
-            with _stage("loo_scalars"):
-                gctx.loo_scalars(ws.Li, ws.alpha, None, lv.d, a=lv.a, sqrtb=lv.sb, loo=lv.val)
-            if not need_grad:
-                return
-            with _stage("loo_beta"):  # beta = Ky^-1 a = Linv^T (Linv a), into scratch: ws.z / ws.out3 stay the evaluation's
-                gctx.mll_reduce(ws.A, ws.Li, lv.a, lv.z, lv.out3)
-                gctx.alpha(ws.Li, lv.z, lv.beta)
-            with _stage("lauum"):
-                gctx.lauum(ws.Li, ws.Ki)
-            with _stage("sym_rowscale"):
-                gctx.sym_rowscale(ws.Ki, lv.sb, ws.A)
-            with _stage("loo_gemm"):  # C(lower) = S^T S = P diag(b) P: M = N = K, row-contiguous TN
-                gctx.gemm(1, 0, N, N, N, 1.0, ws.A, ws.A, 0.0, ws.Li, c_tri=1)
-            with _stage("loo_grad_reduce"):
-                gctx.loo_grad_reduce(Ud, wd, sd, grp, S, ws.alpha, lv.beta, ws.Li, dU if need_U else 0, g_w, g_s, g_t, g_Ud,
-                                     kind=kind, d_split=d_split)
-
-        _factor(gctx, ws, Ud, wd, sd, td, grp, kind, d_split, after=rest)
-        ctx.saved = (g_w, g_s, g_t, g_Ud, lv.beta.clone() if need_grad else None, (N, D, dU))
-        ctx.in_dtypes = (U.dtype, w.dtype, sf2.dtype, tau.dtype, mean.dtype, y.dtype)
-        ctx.shapes = (sf2.shape, tau.shape)
-        return lv.val[0].clone()
+        return lv.val[0].clone(), (lv.beta.neg() if need_grad else None)  # dloo/dmean = -beta
 
     @staticmethod
     def backward(ctx, grad_out):
-        g_w, g_s, g_t, g_Ud, beta, (N, D, dU) = ctx.saved
-        need = ctx.needs_input_grad
-        go = grad_out.to(torch.float64)
-        g_U = None
-        if need[0]:
-            g_U = torch.zeros(N, D, dtype=torch.float64, device=beta.device)
-            if g_Ud is not None:
-                g_U[:, :dU] = g_Ud
-        dt = ctx.in_dtypes
-        sf2_shape, tau_shape = ctx.shapes
-        return (None if g_U is None else (go * g_U).to(dt[0]),
-                (go * g_w).to(dt[1]) if need[1] else None,
-                (go * g_s).reshape(sf2_shape).to(dt[2]) if need[2] else None,
-                (go * g_t).reshape(tau_shape).to(dt[3]) if need[3] else None,
-                (-go * beta).to(dt[4]) if need[4] else None,
-                (go * beta).to(dt[5]) if need[5] else None,
-                None, None, None, None, None)
+        return _eval_backward(ctx, grad_out, *ctx.saved) + (None,) * 5
 
 
 def exact_loo(U: torch.Tensor, spec: KernelSpec, tau: torch.Tensor, mean: torch.Tensor, y: torch.Tensor,
@@ -436,8 +409,7 @@ def cross_kernel(Ua: torch.Tensor, Ub: torch.Tensor, spec: KernelSpec) -> torch.
     dev = Ua.device
     gctx = get_context(dev)
     M, N = Ua.shape[0], Ub.shape[0]
-    ld = max(16, (N + 15) // 16 * 16)
-    out = torch.empty((M, ld), dtype=torch.float64, device=dev)[:, :N]
+    out = rows_buffer(M, N, dev)
     gctx.cross_kernel(_as_f64(Ua, dev), _as_f64(Ub, dev), _as_f64(spec.w, dev), _as_f64(spec.sf2.reshape(1), dev), out,
                       kind=spec.kind, d_split=spec.d_split)
     return out
@@ -484,10 +456,7 @@ def _factorize(U, spec: KernelSpec, tau, grp, mean, y) -> FactorCache:
     dev = U.device
     gctx = get_context(dev)
     N = U.shape[0]
-    Ud, wd = _as_f64(U, dev), _as_f64(spec.w, dev)
-    sd, td = _as_f64(spec.sf2.reshape(1), dev), _as_f64(tau.reshape(-1), dev)
-    if grp is not None:
-        grp = grp.to(torch.int32)
+    Ud, wd, sd, td, grp = _operands(U, spec.w, spec.sf2, tau, grp)
     ws = get_workspace(gctx, N, slot=-1)
     ws.epoch += 1
     jit = _factor(gctx, ws, Ud, wd, sd, td, grp, spec.kind, spec.d_split)
@@ -526,8 +495,7 @@ def predict_from_cache(cache: FactorCache, Us: torch.Tensor, need_var: bool = Tr
         gctx.predict(cache.Linv, cache.alpha, Ksn, None, None, mean, None)
         return mean, None, None
     Kns = cross_kernel(cache.U, Us, cache.spec)  # N x M
-    ldv = max(16, (N + 15) // 16 * 16)
-    V = torch.empty((M, ldv), dtype=torch.float64, device=dev)[:, :N]
+    V = rows_buffer(M, N, dev)
     kss = cache.spec.sf2.reshape(1).expand(M).contiguous()
     var = torch.empty(M, dtype=torch.float64, device=dev)
     gctx.predict_tn(cache.Linv, cache.z, Kns, kss, V, mean, var)
@@ -612,7 +580,7 @@ class PredictVarFunction(torch.autograd.Function):
             # B = V Linv against the lower triangle of the Linv buffer (its upper triangle holds the mirror; keep k >= n), as the
             # row-contiguous TN product from V^T: the NN form of the same product measured 95 ms against 55 for the forward's TN
             # product at M = 8192, N = 20000 (the k-contiguous variant, gpp_predict_tn); the transpose costs 2 M N doubles of traffic
-            Vt = torch.empty((N, max(16, (M + 15) // 16 * 16)), dtype=torch.float64, device=V.device)[:, :M]
+            Vt = rows_buffer(N, M, V.device)
             cache.gctx.transpose(V, Vt)
             cache.gctx.gemm(1, 0, M, N, N, 1.0, Vt, cache.Linv, 0.0, B, b_mask=2, klo_mode=2)
             del Vt
@@ -644,24 +612,18 @@ def dense_log_prob(cov: torch.Tensor, diff: torch.Tensor) -> torch.Tensor:
     A.copy_(cov)
     Li, T = square_buffer(N, dev), square_buffer(N, dev)
     info = torch.zeros(1, dtype=torch.int32, device=dev)
-    jitters = [0.0] + [settings.cholesky_jitter.value() * (10 ** i) for i in range(settings.cholesky_max_tries.value())]
-    prev, attempts, fresh = 0.0, list(jitters), True
-    while attempts:
-        jit = attempts.pop(0)
+    fresh = True
+
+    def attempt(jit):
+        nonlocal fresh
         if not fresh:
             A.copy_(cov)
             A.diagonal().add_(jit)
         fresh = False
         gctx.potrf(A, Li, info)
-        status = int(info.item())
-        if panel_timed_out(gctx, status):
-            attempts.insert(0, jit)  # the same attempt again, without the cooperative panel
-            continue
-        if status == 0:
-            break
-        prev = jit
-    else:
-        raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {prev:.1e}.")
+        return int(info.item())
+
+    psd_safe(gctx, attempt)
     gctx.trtri(A, Li, T)
     z = torch.empty(N, dtype=torch.float64, device=dev)
     out3 = torch.empty(3, dtype=torch.float64, device=dev)
@@ -726,23 +688,14 @@ def mvn_root(build_upper, n: int, device) -> Tuple[torch.Tensor, float]:
     gctx = get_context(dev)
     A, Li, T = square_buffer(n, dev), square_buffer(n, dev), square_buffer(n, dev)
     info = torch.zeros(1, dtype=torch.int32, device=dev)
-    jitters = [0.0] + [settings.cholesky_jitter.value() * (10 ** i) for i in range(settings.cholesky_max_tries.value())]
-    prev, attempts = 0.0, list(jitters)
-    while attempts:
-        jit = attempts.pop(0)
+
+    def attempt(jit):
         build_upper(A, jit)
         with _stage("sample_potrf"):
             gctx.potrf(A, Li, info, T)
-        status = int(info.item())
-        if panel_timed_out(gctx, status):
-            attempts.insert(0, jit)  # the same attempt again, without the cooperative panel
-            continue
-        if status == 0:
-            if jit > 0:
-                warnings.warn(f"A not p.d., added jitter of {jit:.1e} to the diagonal", RuntimeWarning)
-            return A, jit
-        prev = jit
-    raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {prev:.1e}.")
+        return int(info.item())
+
+    return A, psd_safe(gctx, attempt)
 
 
 @torch.no_grad()
@@ -752,10 +705,9 @@ def mvn_draw(U: torch.Tensor, loc: torch.Tensor, Z: torch.Tensor) -> torch.Tenso
     dev = U.device
     gctx = get_context(dev)
     S, M = Z.shape
-    ld = max(16, (M + 15) // 16 * 16)
-    Zp = torch.empty((S, ld), dtype=torch.float64, device=dev)[:, :M]
+    Zp = rows_buffer(S, M, dev)
     Zp.copy_(Z)
-    out = torch.empty((S, ld), dtype=torch.float64, device=dev)[:, :M]
+    out = rows_buffer(S, M, dev)
     out.copy_(_as_f64(loc, dev).expand(S, M))
     if S > 0 and M > 0:
         gctx.gemm(0, 0, S, M, M, 1.0, Zp, U, 1.0, out, b_mask=1, khi_mode=2)

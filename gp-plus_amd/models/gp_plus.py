@@ -334,6 +334,7 @@ class GP_Plus(GPR):
         """True when ``B`` restarts of this model should be evaluated together: batched restarts enabled, N within the batched
         kernels' range, and three B x N x N fp64 buffers within a third of the device memory that is free right now."""
         from .. import settings as gpp_settings
+        from ..backend import row_stride
         from ..optim.mll_batched import BATCHED_MAX_N
 
         if not gpp_settings.batched_restarts.value():
@@ -341,8 +342,7 @@ class GP_Plus(GPR):
         N = int(self.train_targets.shape[0])
         if N > BATCHED_MAX_N:
             return False
-        ld = max(16, (N + 15) // 16 * 16)
-        need = 3 * B * N * ld * 8
+        need = 3 * B * N * row_stride(N) * 8
         free, _ = torch.cuda.mem_get_info(self.tkwargs['device'])
         return need <= free // 3
 

@@ -52,15 +52,16 @@ the RCCL branch runs on a single GPU (tests/test_gpu_sharded.py).
 """
 from __future__ import annotations
 
-import warnings
 from typing import List, Optional, Tuple
 
 import torch
 import torch.distributed as dist
 
-from .backend import INFO_PANEL_TIMEOUT, KIND_RBF, UPLO_FULL, GppContext, get_context, panel_timed_out, square_buffer
+from .backend import (INFO_PANEL_TIMEOUT, KIND_RBF, UPLO_FULL, GppContext, check_status, get_context, panel_timed_out,
+                      square_buffer)
 from . import push as _push
-from .errors import NanError, NotPSDError
+from .linalg import _as_f64, _eval_backward, _eval_operands, _stage
+from .psd_safe import inputs_nan_probe, psd_safe
 from . import settings
 
 __all__ = ["ShardedWorkspace", "sharded_mll", "ShardedMLLFunction"]
@@ -713,23 +714,16 @@ class ShardedMLLFunction(torch.autograd.Function):
         dev = U.device
         gctx = get_context(dev)
         comm = _Comm(group)
-        N, D = U.shape
-        f64 = lambda t: t.detach().to(device=dev, dtype=torch.float64).contiguous()
-        Ud, wd, sd, td = f64(U), f64(w), f64(sf2).reshape(1), f64(tau).reshape(-1)
-        if grp is not None and grp.dtype != torch.int32:
-            grp = grp.to(torch.int32)
+        Ud, wd, sd, td, grp, S, need_grad, _ = _eval_operands(ctx, U, w, sf2, tau, mean, y, grp, dU)
         comm.log = COMM_LOG
-        ws = _workspace(gctx, N, nb, comm.rank, comm.world)
+        ws = _workspace(gctx, U.shape[0], nb, comm.rank, comm.world)
         ws.epoch += 1
-        jitters = [0.0] + [settings.cholesky_jitter.value() * (10 ** i) for i in range(settings.cholesky_max_tries.value())]
-        from .linalg import _stage
-        need_grad = any(ctx.needs_input_grad[:6])
         for redo in (False, True):
-            swept, used = ShardedMLLFunction._factor_with_jitter(gctx, comm, ws, Ud, wd, sd, td, grp, kind, d_split, jitters)
+            swept = ShardedMLLFunction._factor_with_jitter(gctx, comm, ws, Ud, wd, sd, td, grp, kind, d_split)
             if not swept:
                 with _stage("shard_inverse"):
                     _forward(gctx, comm, ws)
-            torch.sub(f64(y), f64(mean), out=ws.r)
+            torch.sub(_as_f64(y.detach(), dev), _as_f64(mean.detach(), dev), out=ws.r)
             comm.stage = "vectors"
             _vectors(gctx, comm, ws, need_alpha=need_grad)
             st = 0
@@ -742,57 +736,42 @@ class ShardedMLLFunction(torch.autograd.Function):
             # here): its input is destroyed.  Every rank switches the executor off and the evaluation is repeated on the
             # launch-per-product path — once; a second failure is reported on all ranks alike.
             if redo or not panel_timed_out(gctx, st):
-                from .backend import check_status
                 check_status(st)
                 raise RuntimeError(f"sharded evaluation: back-substitution list status {st:#x}")
             comm.stage = "factor"
         ws.comm_calls = comm.calls  # (tests: the collectives really ran)
-        ctx.saved = (gctx, comm, ws, ws.epoch, Ud, wd, sd, grp, td.numel(), kind, d_split, dU)
-        ctx.in_dtypes = (U.dtype, w.dtype, sf2.dtype, tau.dtype, mean.dtype, y.dtype)
-        ctx.shapes = (sf2.shape, tau.shape)
+        ctx.saved = (gctx, comm, ws, ws.epoch, Ud, wd, sd, grp, S, kind, d_split, dU)
         return ws.out3[2].clone()
 
     @staticmethod
-    def _factor_with_jitter(gctx, comm, ws, Ud, wd, sd, td, grp, kind, d_split, jitters):
+    def _factor_with_jitter(gctx, comm, ws, Ud, wd, sd, td, grp, kind, d_split) -> bool:
         """gpytorch's psd_safe_cholesky policy around the distributed factorisation (optim/mll_torch.py:116 reaches it through
-        ``log_prob``): returns (the list also swept the owned column blocks of L^-1, the jitter that succeeded)."""
-        from .linalg import _stage
-        used = None
+        ``log_prob``): returns whether the list also swept the owned column blocks of L^-1."""
         swept = False
-        attempts = list(jitters)
         timeouts = 0
-        while attempts:
-            jit = attempts.pop(0)
+
+        def attempt(jit):
+            nonlocal swept
             with _stage("shard_factor"):
                 info = _factor_list(gctx, comm, ws, Ud, wd, sd, td, grp, kind, d_split, jit) if _USE_LIST else None
                 swept = info is not None  # (the list builds the owned column blocks of L^-1 beside the factorisation)
                 if info is None:
                     info = _factor(gctx, comm, ws, Ud, wd, sd, td, grp, kind, d_split, jit)
-            if info >= INFO_PANEL_TIMEOUT:
-                _push.disable()  # (a message may be missing somewhere: the ranks' message numbers no longer agree; broadcasts from here)
-                # (the status is the MAX over the ranks: every rank sees it and repeats the attempt; the rank whose panel gave up —
-                #  or every rank, it costs 1-2 % — switches the panel off)
-                timeouts += 1
-                if timeouts > 2:  # every rank has switched its panel off by now: this is not a time-out any more
-                    from .backend import check_status
-                    check_status(info)
-                if gctx.coop_panel:
-                    panel_timed_out(gctx, info)
-                attempts.insert(0, jit)
-                continue
-            if info == 0:
-                used = jit
-                break
-            if jit == 0.0:
-                bad = [n for n, t in (("inputs", Ud), ("weights", wd), ("outputscale", sd), ("noise", td))
-                       if not torch.isfinite(t).all()]
-                if bad:
-                    raise NanError(f"cholesky: NaN/Inf in {', '.join(bad)} of the covariance")
-        if used is None:
-            raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {jitters[-1]:.1e}.")
-        if used > 0:
-            warnings.warn(f"A not p.d., added jitter of {used:.1e} to the diagonal", RuntimeWarning)
-        return swept, used
+            return info
+
+        def timed_out(gctx, info):
+            nonlocal timeouts
+            _push.disable()  # (a message may be missing somewhere: the ranks' message numbers no longer agree; broadcasts from here)
+            # (the status is the MAX over the ranks: every rank sees it and repeats the attempt; the rank whose panel gave up —
+            #  or every rank, it costs 1-2 % — switches the panel off)
+            timeouts += 1
+            if timeouts > 2:  # every rank has switched its panel off by now: this is not a time-out any more
+                check_status(info)
+            if gctx.coop_panel:
+                panel_timed_out(gctx, info)
+
+        psd_safe(gctx, attempt, inputs_nan_probe(Ud, wd, sd, td), on_timeout=timed_out)
+        return swept
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -812,22 +791,7 @@ class ShardedMLLFunction(torch.autograd.Function):
         comm.stage = "grad"
         comm.allreduce(flat)
         ws.comm_calls = comm.calls
-        g_U = None
-        if ctx.needs_input_grad[0]:
-            g_U = torch.zeros(N, D, dtype=torch.float64, device=dev)
-            if need_U:
-                g_U[:, :dU] = g_Ud
-        go = grad_out.to(torch.float64)
-        dt = ctx.in_dtypes
-        sf2_shape, tau_shape = ctx.shapes
-        alpha = ws.alpha
-        return (None if g_U is None else (go * g_U).to(dt[0]),
-                (go * g_w).to(dt[1]) if ctx.needs_input_grad[1] else None,
-                (go * g_s).reshape(sf2_shape).to(dt[2]) if ctx.needs_input_grad[2] else None,
-                (go * g_t).reshape(tau_shape).to(dt[3]) if ctx.needs_input_grad[3] else None,
-                (go * alpha).to(dt[4]) if ctx.needs_input_grad[4] else None,
-                (-go * alpha).to(dt[5]) if ctx.needs_input_grad[5] else None,
-                None, None, None, None, None, None)
+        return _eval_backward(ctx, grad_out, g_w, g_s, g_t, g_Ud, ws.alpha) + (None,) * 6
 
 
 def sharded_mll(U: torch.Tensor, w: torch.Tensor, sf2: torch.Tensor, tau: torch.Tensor, mean: torch.Tensor, y: torch.Tensor,

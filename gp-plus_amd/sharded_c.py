@@ -12,9 +12,9 @@ from ctypes import CFUNCTYPE, Structure, c_int, c_int64, c_size_t, c_void_p
 import torch
 import torch.distributed as dist
 
-from .backend import OP_MLL_EVAL, GppContext, check, check_status, get_context
-from .errors import NotPSDError
-from . import settings
+from .backend import OP_MLL_EVAL, GppContext, check, check_status, get_context, row_stride
+from .linalg import _as_f64, _operands
+from .psd_safe import psd_safe
 
 __all__ = ["sharded_eval_c", "GPP_SHARD_UNSUPPORTED"]
 
@@ -105,11 +105,8 @@ def sharded_eval_c(U, w, sf2, tau, mean, y, grp=None, kind: int = 0, d_split: in
     lib = ctx.lib
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     N, D = U.shape
-    f64 = lambda t: t.detach().to(device=dev, dtype=torch.float64).contiguous()  # noqa: E731
-    Ud, wd, sd, td = f64(U), f64(w), f64(sf2).reshape(1), f64(tau).reshape(-1)
+    Ud, wd, sd, td, grp = _operands(U, w, sf2, tau, grp)
     S = td.numel()
-    if grp is not None and grp.dtype != torch.int32:
-        grp = grp.to(torch.int32)
     # The handle has ONE communicator slot (gpp_set_comm / gpp_comm_init_rccl overwrite it): the key names the group by its member
     # ranks (``id(group)`` can be reused by a later group object) and ``_state["installed", device]`` says which key the handle
     # currently carries — another group or backend re-installs before the call instead of running with the previous one's collectives.
@@ -137,7 +134,7 @@ def sharded_eval_c(U, w, sf2, tau, mean, y, grp=None, kind: int = 0, d_split: in
             _state[key] = (cb, comm)  # (kept alive: the library calls them)
         _state[("installed", ctx.index)] = key
     n = lambda which: int(lib.gpp_shard_buffer_doubles(N, nb, rank, world, which))  # noqa: E731
-    ld = (N + 15) // 16 * 16
+    ld = row_stride(N)
     nblk = -(-N // nb)
     wc = max(len(range(rank, nblk, world)), 1) * nb
     mk = lambda k: torch.empty(k, dtype=torch.float64, device=dev)  # noqa: E731
@@ -150,26 +147,24 @@ def sharded_eval_c(U, w, sf2, tau, mean, y, grp=None, kind: int = 0, d_split: in
         _state[("bufs", key, N, nb)] = bufs
     dU = int(n_grad_dims) if need_grad else 0
     flat = torch.zeros(D + 1 + S + N * dU, dtype=torch.float64, device=dev)
-    torch.sub(f64(y), f64(mean), out=bufs["r"])
+    torch.sub(_as_f64(y.detach(), dev), _as_f64(mean.detach(), dev), out=bufs["r"])
     b = _Buffers(bufs["A"].data_ptr(), ld, bufs["Kc"].data_ptr(), bufs["Lc"].data_ptr(), wc, bufs["D"].data_ptr(), bufs["W0"].data_ptr(),
                  bufs["W1"].data_ptr(), bufs["W2"].data_ptr(), ld, bufs["msg"].data_ptr(), bufs["z"].data_ptr(), bufs["alpha"].data_ptr(),
                  bufs["r"].data_ptr(), flat.data_ptr(), bufs["out3"].data_ptr(), bufs["info"].data_ptr())
     ctx.ensure_workspace(OP_MLL_EVAL, N, 0, D, S)
     ctx._stream()
     info = c_int(0)
-    jitters = [0.0] + [settings.cholesky_jitter.value() * (10 ** i) for i in range(settings.cholesky_max_tries.value())]
-    for jit in jitters:
+
+    def attempt(jit):
         rc = lib.gpp_shard_eval(ctx.h, N, nb, Ud.data_ptr(), D, wd.data_ptr(), sd.data_ptr(), td.data_ptr(),
                                 None if grp is None else grp.data_ptr(), S, kind, d_split, float(jit), dU, 1 if need_grad else 0,
                                 ctypes.byref(b), ctypes.byref(info))
         if rc == GPP_SHARD_UNSUPPORTED:
             raise NotImplementedError("gpp_shard_eval: the ticket lists do not apply to this size / block height")
         check(rc, "gpp_shard_eval")
-        if info.value == 0:
-            break
-        check_status(info.value)  # (a time-out: raises)
-    else:
-        raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {jitters[-1]:.1e}.")
+        return info.value
+
+    psd_safe(ctx, attempt, on_timeout=lambda _ctx, status: check_status(status))  # (a time-out: raises)
     mll = bufs["out3"][2].clone()
     if not need_grad:
         return mll, None, None, None, None, None

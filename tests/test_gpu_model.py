@@ -174,6 +174,99 @@ def test_duplicate_rows_and_jitter_policy(gpu_ctx):
         exact_mll(Ud, spec, torch.tensor([-0.5], dtype=torch.float64, device="cuda"), mean, y)
 
 
+def _duplicate_rows_problem():
+    """The input of ``test_duplicate_rows_and_jitter_policy``: N = 200, rows 100... duplicate rows ...100, w = 0.3, sf2 = 1."""
+    from gpplus_amd.linalg import KernelSpec
+
+    rng = np.random.default_rng(3)
+    U = rng.standard_normal((200, 3))
+    U[100:] = U[:100]
+    Ud = torch.tensor(U, device="cuda")
+    spec = KernelSpec(torch.full((3,), 0.3, dtype=torch.float64, device="cuda"), torch.tensor(1.0, dtype=torch.float64, device="cuda"))
+    y = torch.tensor(rng.standard_normal(200), device="cuda")
+    return Ud, spec, y
+
+
+def test_jitter_policy_of_dense_log_prob_and_mvn_root(gpu_ctx):
+    """The dense factorisations follow the same policy as the evaluation: the singular covariance of the duplicate-rows input is
+    factored after a warning, with a jitter from the schedule, and an indefinite one raises NotPSDError."""
+    from gpplus_amd.gpcore import NotPSDError
+    from gpplus_amd.linalg import dense_kernel, dense_log_prob, mvn_root
+    from gpplus_amd.psd_safe import jitter_schedule
+
+    Ud, spec, y = _duplicate_rows_problem()
+    K = dense_kernel(Ud, spec)
+
+    def builder(cov):
+        def build(A, jit):
+            A.copy_(cov)
+            A.diagonal().add_(jit)
+        return build
+
+    with pytest.warns(RuntimeWarning, match="added jitter"):
+        lp = dense_log_prob(K, y)
+    print("dense_log_prob", float(lp))
+    assert torch.isfinite(lp)
+    with pytest.warns(RuntimeWarning, match="added jitter"):
+        root, jit = mvn_root(builder(K), 200, K.device)
+    print("mvn_root jitter", jit)
+    assert jit in jitter_schedule()[1:]
+    assert torch.isfinite(torch.triu(root)).all()
+    bad = K.clone()
+    bad.diagonal().add_(-0.5)
+    with pytest.raises(NotPSDError):
+        dense_log_prob(bad, y)
+    with pytest.raises(NotPSDError):
+        mvn_root(builder(bad), 200, K.device)
+
+
+def test_duplicate_rows_and_jitter_policy_loo(gpu_ctx):
+    """``exact_loo`` on the noise values of ``test_duplicate_rows_and_jitter_policy``: finite, finite after a warning, NotPSDError."""
+    from gpplus_amd.gpcore import NotPSDError
+    from gpplus_amd.linalg import exact_loo
+
+    Ud, spec, y = _duplicate_rows_problem()
+    mean = torch.zeros(200, dtype=torch.float64, device="cuda")
+    ok = exact_loo(Ud, spec, torch.tensor([1e-3], dtype=torch.float64, device="cuda"), mean, y)
+    assert torch.isfinite(ok)
+    with pytest.warns(RuntimeWarning):
+        v = exact_loo(Ud, spec, torch.tensor([0.0], dtype=torch.float64, device="cuda"), mean, y)
+    print("exact_loo", float(ok), float(v))
+    assert torch.isfinite(v)
+    with pytest.raises(NotPSDError):
+        exact_loo(Ud, spec, torch.tensor([-0.5], dtype=torch.float64, device="cuda"), mean, y)
+
+
+@pytest.mark.parametrize("objective", ["exact_mll", "exact_loo"])
+def test_backward_contract_of_the_objectives(gpu_ctx, objective):
+    """What both objectives' backward promises, whatever it is handed: every gradient in its input's dtype and shape (fp32 mean and
+    y, a 0-d outputscale, a (2, 1) noise), d/dmean = -d/dy, linear in the incoming gradient, and zero feature-gradient columns
+    beyond ``n_grad_dims``.  N = 300 (more than one tile), D = 3, two noise groups."""
+    from gpplus_amd import linalg
+
+    N, D, dU = 300, 3, 1
+    g = torch.Generator().manual_seed(11)
+    f64 = dict(dtype=torch.float64, device="cuda")
+    U = torch.randn(N, D, generator=g, dtype=torch.float64).to("cuda").requires_grad_()
+    w = torch.tensor([0.7, 1.3, 0.4], **f64).requires_grad_()
+    sf2 = torch.tensor(1.5, **f64).requires_grad_()
+    tau = torch.tensor([[0.05], [0.2]], **f64).requires_grad_()
+    mean = torch.full((N,), 0.1, dtype=torch.float32, device="cuda").requires_grad_()
+    y = torch.randn(N, generator=g, dtype=torch.float32).to("cuda").requires_grad_()
+    grp = (torch.arange(N) % 2).to("cuda")  # int64: the Function casts it
+    inputs = (U, w, sf2, tau, mean, y)
+    value = getattr(linalg, objective)(U, linalg.KernelSpec(w, sf2), tau, mean, y, grp, n_grad_dims=dU)
+    assert value.dtype == torch.float64 and value.shape == () and torch.isfinite(value)
+    one = torch.autograd.grad(value, inputs, retain_graph=True)
+    two = torch.autograd.grad(value, inputs, grad_outputs=torch.tensor(2.0, **f64))
+    for name, x, g1, g2 in zip(("U", "w", "sf2", "tau", "mean", "y"), inputs, one, two):
+        assert g1.dtype == x.dtype and g1.shape == x.shape, name
+        assert torch.isfinite(g1).all() and g1.abs().max() > 0, name
+        assert torch.equal(g2, 2 * g1), name
+    assert torch.equal(one[4], -one[5])
+    assert torch.equal(one[0][:, dU:], torch.zeros(N, D - dU, **f64))
+
+
 def test_fit_model_torch_improves_and_restores_best_state(gpu_ctx):
     from gpplus_amd.optim import fit_model_torch
     from gpplus_amd.utils import set_seed
