@@ -669,6 +669,58 @@ class GppContext:
                                                g_w.data_ptr(), g_sf2.data_ptr(), g_tau.data_ptr(), _ptr(g_U), B),
               "gpp_grad_reduce_batched")
 
+    @_on_own_device
+    def loo_scalars_batched(self, Linv, alpha, y, d, mu=None, s2=None, a=None, sqrtb=None, loo=None):
+        """``loo_scalars`` for B problems in one launch: Linv (B, N, ld) view; alpha, y, d, mu, s2, a, sqrtb (B, N) views that share
+        one even row stride (``batched_vector``); loo (B,) contiguous.  y, mu, s2, a, sqrtb and loo may each be None."""
+        B, N = Linv.shape[0], Linv.shape[1]
+        _need(Linv, torch.float64, "Linv")
+        vecs = [(t, n) for t, n in ((alpha, "alpha"), (y, "y"), (d, "d"), (mu, "mu"), (s2, "s2"), (a, "a"), (sqrtb, "sqrtb"))
+                if t is not None]
+        for t, n in vecs:
+            _need(t, torch.float64, n)
+            if t.dim() != 2 or t.shape[0] != B or t.shape[1] != N:
+                raise GppError(f"{n} must be a ({B}, {N}) batched vector")
+        if mu is not None and y is None:
+            raise GppError("loo_scalars_batched: mu needs y")
+        if loo is not None:
+            _need(loo, torch.float64, "loo")
+            if loo.numel() < B or not loo.is_contiguous():
+                raise GppError(f"loo must be a contiguous vector of {B} doubles")
+        self._stream()
+        check(self.lib.gpp_loo_scalars_batched(self.h, Linv.data_ptr(), Linv.stride(1), Linv.stride(0), N, alpha.data_ptr(), _ptr(y),
+                                               d.data_ptr(), _ptr(mu), _ptr(s2), _ptr(a), _ptr(sqrtb), self._sv(*(t for t, _ in vecs)),
+                                               _ptr(loo), B), "gpp_loo_scalars_batched")
+
+    @_on_own_device
+    def sym_rowscale_batched(self, Kinv, s, out):
+        """``sym_rowscale`` for B problems in one launch: Kinv and out (B, N, ld) views, s a (B, N) batched vector."""
+        B, N = Kinv.shape[0], Kinv.shape[1]
+        for t, n in ((Kinv, "Kinv"), (s, "s"), (out, "S")):
+            _need(t, torch.float64, n)
+        if tuple(out.shape) != (B, N, N) or tuple(s.shape) != (B, N):
+            raise GppError("sym_rowscale_batched: shapes do not match")
+        if out.data_ptr() == Kinv.data_ptr():
+            raise GppError("sym_rowscale works out of place")
+        self._stream()
+        check(self.lib.gpp_sym_rowscale_batched(self.h, Kinv.data_ptr(), N, Kinv.stride(1), Kinv.stride(0), s.data_ptr(), self._sv(s),
+                                                out.data_ptr(), out.stride(1), out.stride(0), B), "gpp_sym_rowscale_batched")
+        return out
+
+    @_on_own_device
+    def loo_grad_reduce_batched(self, U, w, sf2, grp, S, alpha, beta, C, dU, g_w, g_sf2, g_tau, g_U, *, kind=KIND_RBF, d_split=0):
+        """``grad_reduce_batched`` with the leave-one-out weights of ``loo_grad_reduce``: beta (B, N) beside alpha, C (B, N, ld)."""
+        B, N = C.shape[0], C.shape[1]
+        D = w.shape[1]
+        _check_features(D)
+        sU = 0 if U.dim() == 2 else U.stride(0)
+        self.ensure_workspace_batched(B, N, D, S)
+        self._stream()
+        check(self.lib.gpp_loo_grad_reduce_batched(self.h, U.data_ptr(), sU, N, D, w.data_ptr(), sf2.data_ptr(), _ptr(grp), S, kind,
+                                                   d_split, alpha.data_ptr(), beta.data_ptr(), self._sv(alpha, beta), C.data_ptr(),
+                                                   C.stride(1), C.stride(0), dU, g_w.data_ptr(), g_sf2.data_ptr(), g_tau.data_ptr(),
+                                                   _ptr(g_U), B), "gpp_loo_grad_reduce_batched")
+
 
 def get_context(device) -> GppContext:
     device = torch.device(device)

@@ -1981,4 +1981,67 @@ int gpp_grad_reduce_batched(gpp_handle_t h, const double* U, int64_t sU, int64_t
   return 0;
 }
 
+int gpp_loo_scalars_batched(gpp_handle_t h, const double* Linv, int64_t ldi, int64_t sLi, int64_t N, const double* alpha,
+                            const double* y, double* d, double* mu, double* s2, double* a, double* sqrtb, int64_t sv, double* loo,
+                            int batch) {
+  if (!h) return -1;
+  if (N < 0) return -5;
+  if (int q = check_mat(Linv, ldi, N, 2)) return q;
+  if (sLi & 1) return -4;
+  if (!alpha) return -6;
+  if (mu && !y) return -7;
+  if (!d) return -8;
+  if (sv < N || (sv & 1)) return -13;  // the vectors of element b start at b*sv
+  if (int q = check_batch(batch, 15)) return q;
+  GPP_TRY(gpp_launch_loo_scalars_batched(h->stream, Linv, ldi, N, alpha, y, d, mu, s2, a, sqrtb, loo, batch, sLi, sv));
+  return 0;
+}
+
+int gpp_sym_rowscale_batched(gpp_handle_t h, const double* Kinv, int64_t N, int64_t ldk, int64_t sK, const double* s, int64_t sv,
+                             double* S, int64_t lds, int64_t sS, int batch) {
+  if (!h) return -1;
+  if (N < 0) return -3;
+  if (int r = check_mat(Kinv, ldk, N, 2)) return r;
+  if (sK & 1) return -5;
+  if (!s) return -6;
+  if (sv < N || (sv & 1)) return -7;
+  if (int r = check_mat(S, lds, N, 8)) return r;
+  if (S == Kinv) return -8;  // out of place only
+  if (sS & 1) return -10;
+  if (int r = check_batch(batch, 11)) return r;
+  GPP_TRY(gpp_launch_sym_rowscale_batched(h->stream, Kinv, ldk, N, s, S, lds, batch, sK, sv, sS));
+  return 0;
+}
+
+int gpp_loo_grad_reduce_batched(gpp_handle_t h, const double* U, int64_t sU, int64_t N, int D, const double* w, const double* sf2,
+                                const int32_t* grp, int S, int kind, int d_split, const double* alpha, const double* beta,
+                                int64_t sv, const double* C, int64_t ldc, int64_t sC, int dU, double* g_w, double* g_sf2,
+                                double* g_tau, double* g_U, int batch) {
+  if (!h) return -1;
+  if (!U) return -2;
+  if (sU != 0 && sU < N * D) return -3;
+  if (N < 0) return -4;
+  if (D < 1 || D > 64) return -5;
+  if (!w) return -6;
+  if (!sf2) return -7;
+  if (S < 1 || S > 64) return -9;
+  if (kind < 0 || kind > 2) return -10;
+  if (d_split < 0 || d_split > D) return -11;
+  if (!alpha) return -12;
+  if (!beta) return -13;
+  if (sv < N || (sv & 1)) return -14;
+  if (int q = check_mat(C, ldc, N, 15)) return q;
+  if (sC & 1) return -17;
+  if (dU < 0 || dU > D) return -18;
+  if (!g_w) return -19;
+  if (!g_sf2) return -20;
+  if (!g_tau) return -21;
+  if (dU > 0 && !g_U) return -22;
+  if (int q = check_batch(batch, 23)) return q;
+  if (!h->ws || h->ws_bytes < (size_t)batch * gpp_grad_ws_bytes(N, D, S, dU)) return -1;
+  GPP_TRY(gpp_launch_grad_reduce(h->stream, U, N, D, w, sf2, grp, S, kind, d_split, alpha, C, ldc, dU, g_w, g_sf2, g_tau, g_U,
+                                 h->ws, h->ws_bytes, 0, 0, 1, batch, sU, sC, sv, 0, beta));
+  return 0;
+}
+
 }  // extern "C"

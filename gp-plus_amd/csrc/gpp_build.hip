@@ -323,12 +323,17 @@ hipError_t gpp_launch_post_cov_train(hipStream_t s, const double* Kinv, int64_t 
 // i > j.  Every element of S[0..N) x [0..N) is written exactly once; nothing above Kinv's diagonal is read.  Out of place.
 // HBM-bound: N^2/2 doubles read, N^2 written.  Columns [N, lds) of S are NOT written: the TN GEMM that consumes S masks its loads
 // by the true extents (load_mc: gk < kend, gr < R, the second element of a pair by gr + 1 < R; gpp_gemm never sets pad_ok).
+// Batch element blockIdx.y: Kinv + b*sK, sv + b*sv_stride, S + b*sS (even strides: every element's rows stay 16-byte aligned).
 namespace {
 
 __global__ __launch_bounds__(256) void gpp_sym_rowscale_tile(const double* __restrict__ Kinv, int64_t ldk, int64_t N,
-                                                             const double* __restrict__ sv, double* __restrict__ S, int64_t lds) {
+                                                             const double* __restrict__ sv, double* __restrict__ S, int64_t lds,
+                                                             int64_t sK, int64_t sv_stride, int64_t sS) {
   __shared__ double t[PC_Q][PC_Q + 1];  // t[c][r] = Kinv[i0 + r][j0 + c]; padded against bank conflicts of the transposed writes
   typedef double v2d __attribute__((ext_vector_type(2)));
+  Kinv += (int64_t)blockIdx.y * sK;
+  sv += (int64_t)blockIdx.y * sv_stride;
+  S += (int64_t)blockIdx.y * sS;
   int64_t ti, tj;  // lower-triangle tile ti >= tj, row-major enumeration
   {
     const int64_t tt = blockIdx.x;
@@ -393,9 +398,16 @@ __global__ __launch_bounds__(256) void gpp_sym_rowscale_tile(const double* __res
 
 }  // namespace
 
-hipError_t gpp_launch_sym_rowscale(hipStream_t s, const double* Kinv, int64_t ldk, int64_t N, const double* sv, double* S, int64_t lds) {
-  if (N <= 0) return hipSuccess;
+hipError_t gpp_launch_sym_rowscale_batched(hipStream_t s, const double* Kinv, int64_t ldk, int64_t N, const double* sv, double* S,
+                                           int64_t lds, int batch, int64_t sK, int64_t sv_stride, int64_t sS) {
+  if (N <= 0 || batch <= 0) return hipSuccess;
+  if (batch > 65535) return hipErrorInvalidValue;  // gridDim.y
   const int64_t nt = (N + PC_T - 1) / PC_T;
-  hipLaunchKernelGGL(gpp_sym_rowscale_tile, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, s, Kinv, ldk, N, sv, S, lds);
+  hipLaunchKernelGGL(gpp_sym_rowscale_tile, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)batch), dim3(256), 0, s, Kinv, ldk, N, sv,
+                     S, lds, sK, sv_stride, sS);
   return hipGetLastError();
+}
+
+hipError_t gpp_launch_sym_rowscale(hipStream_t s, const double* Kinv, int64_t ldk, int64_t N, const double* sv, double* S, int64_t lds) {
+  return gpp_launch_sym_rowscale_batched(s, Kinv, ldk, N, sv, S, lds, 1, 0, 0, 0);
 }

@@ -326,6 +326,10 @@ hipError_t gpp_launch_post_cov_train(hipStream_t s, const double* Kinv, int64_t 
                                      const double* d, double jitter, double* A, int64_t lda);
 // S (full square) = diag(sv) sym(Kinv) from Kinv's lower triangle, out of place (gpp_sym_rowscale)
 hipError_t gpp_launch_sym_rowscale(hipStream_t s, const double* Kinv, int64_t ldk, int64_t N, const double* sv, double* S, int64_t lds);
+// the same for `batch` problems in one launch: element b at Kinv + b*sK, sv + b*sv_stride, S + b*sS (strides even); the single-problem
+// launcher is this one with batch 1 and strides 0
+hipError_t gpp_launch_sym_rowscale_batched(hipStream_t s, const double* Kinv, int64_t ldk, int64_t N, const double* sv, double* S,
+                                           int64_t lds, int batch, int64_t sK, int64_t sv_stride, int64_t sS);
 
 // ---- reductions (gpp_reduce.hip) --------------------------------------------------------------
 // batch > 1 (all reductions): matrices at + b*sT, vectors at + b*sv (sv even, >= N), out3 at + 3*b
@@ -343,10 +347,15 @@ hipError_t gpp_launch_grad_reduce(hipStream_t s, const double* U, int64_t N, int
                                   int shard_nranks = 1, int batch = 1, int64_t sU = 0, int64_t sK = 0, int64_t sv = 0,
                                   int shard_cols = 0, const double* beta = nullptr);
 // (beta != nullptr: the leave-one-out weights W_ij = -0.5 (alpha_i beta_j + beta_i alpha_j) - Kinv_ij, `Kinv` holding
-//  C = P diag(b) P — gpp_loo_grad_reduce in gpp.h; unbatched and unsharded callers only)
+//  C = P diag(b) P — gpp_loo_grad_reduce / gpp_loo_grad_reduce_batched in gpp.h, beta at + b*sv; unsharded callers only)
 // d_i = sum_{j >= i} Linv[i][j]^2 and the leave-one-out vectors / value derived from it (gpp_loo_scalars in gpp.h; mu, s2, a, sb, loo may be null)
 hipError_t gpp_launch_loo_scalars(hipStream_t s, const double* Linv, int64_t ldi, int64_t N, const double* alpha, const double* y,
                                   double* d, double* mu, double* s2, double* a, double* sb, double* loo);
+// the same for `batch` problems in one launch: the matrix at Linv + b*sLi, every vector at + b*sv, loo + b; the single-problem launcher
+// is this one with batch 1 and strides 0 (same kernels, same summation orders)
+hipError_t gpp_launch_loo_scalars_batched(hipStream_t s, const double* Linv, int64_t ldi, int64_t N, const double* alpha,
+                                          const double* y, double* d, double* mu, double* s2, double* a, double* sb, double* loo,
+                                          int batch, int64_t sLi, int64_t sv);
 // the finish of gpp_launch_grad_reduce alone, over `nrec` records of D + 1 sums (gpp_lauum_grad: one per 128 x 128 tile)
 size_t gpp_lauum_grad_ws_bytes(int64_t N, int D);
 hipError_t gpp_launch_grad_finish(hipStream_t s, const double* rec, int64_t nrec, int D, int S, const double* wdiag,

@@ -189,14 +189,16 @@ __global__ __launch_bounds__(1024) void gpp_mll_scalars(const double* __restrict
 // butterfly: a row's sum depends on N and i only, never on the grid.  Lane 0 then writes what the caller asked for:
 //   mu_i = y_i - alpha_i / d_i,  s2_i = 1 / d_i,  a_i = -alpha_i / d_i,  sb_i = sqrt(b_i),  b_i = 1 / (2 d_i) + alpha_i^2 / (2 d_i^2)
 // HBM-read-bound: 4 N^2 bytes.  (No reference counterpart: optim/mll_noise_continuation.py:54 names the criterion only.)
+// Batch element blockIdx.y: its matrix at Linv + b*sLi, its vectors at + b*sv (a single problem is batch 1 with strides 0).
 __global__ __launch_bounds__(256) void gpp_loo_rows(const double* __restrict__ Linv, int64_t ldi, int64_t N,
                                                     const double* __restrict__ alpha, const double* __restrict__ y,
                                                     double* __restrict__ d, double* __restrict__ mu, double* __restrict__ s2,
-                                                    double* __restrict__ a, double* __restrict__ sb) {
+                                                    double* __restrict__ a, double* __restrict__ sb, int64_t sLi, int64_t sv) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t i = (int64_t)blockIdx.x * 4 + wave;
   if (i >= N) return;
-  const double* row = Linv + i * ldi;
+  const int64_t vo = (int64_t)blockIdx.y * sv;  // this element's vectors
+  const double* row = Linv + (int64_t)blockIdx.y * sLi + i * ldi;
   double acc = 0.0;
   int64_t k0 = i;
   if (k0 & 1) {  // align the vector loop to an even column
@@ -213,19 +215,24 @@ __global__ __launch_bounds__(256) void gpp_loo_rows(const double* __restrict__ L
   if (lane == 0 && ((N - k0) & 1)) acc = fma(row[N - 1], row[N - 1], acc);
   acc = wave_sum(acc);
   if (lane == 0) {
-    const double di = acc, al = alpha[i], inv = 1.0 / di;
-    d[i] = di;
-    if (mu) mu[i] = y[i] - al * inv;
-    if (s2) s2[i] = inv;
-    if (a) a[i] = -al * inv;
-    if (sb) sb[i] = sqrt(0.5 * inv + 0.5 * (al * inv) * (al * inv));
+    const int64_t o = vo + i;
+    const double di = acc, al = alpha[o], inv = 1.0 / di;
+    d[o] = di;
+    if (mu) mu[o] = y[o] - al * inv;
+    if (s2) s2[o] = inv;
+    if (a) a[o] = -al * inv;
+    if (sb) sb[o] = sqrt(0.5 * inv + 0.5 * (al * inv) * (al * inv));
   }
 }
 
-// loo = sum_i [ 0.5 log d_i - alpha_i^2 / (2 d_i) ] - (N / 2) log 2pi : one work-group, the summation order of gpp_mll_scalars
+// loo = sum_i [ 0.5 log d_i - alpha_i^2 / (2 d_i) ] - (N / 2) log 2pi : one work-group per batch element (blockIdx.x), the
+// summation order of gpp_mll_scalars
 __global__ __launch_bounds__(1024) void gpp_loo_value(const double* __restrict__ d, const double* __restrict__ alpha, int64_t N,
-                                                      double* __restrict__ out) {
+                                                      double* __restrict__ out, int64_t sv) {
   __shared__ double sp[16];
+  d += (int64_t)blockIdx.x * sv;  // batch element
+  alpha += (int64_t)blockIdx.x * sv;
+  out += blockIdx.x;
   double s = 0.0;
   for (int64_t i = threadIdx.x; i < N; i += 1024) {
     const double di = d[i], al = alpha[i];
@@ -877,12 +884,21 @@ hipError_t gpp_launch_mll_scalars(hipStream_t s, const double* L, int64_t ld, in
   return hipGetLastError();
 }
 
+hipError_t gpp_launch_loo_scalars_batched(hipStream_t s, const double* Linv, int64_t ldi, int64_t N, const double* alpha,
+                                          const double* y, double* d, double* mu, double* s2, double* a, double* sb, double* loo,
+                                          int batch, int64_t sLi, int64_t sv) {
+  if (batch <= 0) return hipSuccess;
+  if (batch > 65535) return hipErrorInvalidValue;  // gridDim.y
+  if (N > 0)
+    hipLaunchKernelGGL(gpp_loo_rows, dim3((unsigned)((N + 3) / 4), (unsigned)batch), dim3(256), 0, s, Linv, ldi, N, alpha, y, d, mu,
+                       s2, a, sb, sLi, sv);
+  if (loo) hipLaunchKernelGGL(gpp_loo_value, dim3((unsigned)batch), dim3(1024), 0, s, d, alpha, N, loo, sv);
+  return hipGetLastError();
+}
+
 hipError_t gpp_launch_loo_scalars(hipStream_t s, const double* Linv, int64_t ldi, int64_t N, const double* alpha, const double* y,
                                   double* d, double* mu, double* s2, double* a, double* sb, double* loo) {
-  if (N > 0)
-    hipLaunchKernelGGL(gpp_loo_rows, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, Linv, ldi, N, alpha, y, d, mu, s2, a, sb);
-  if (loo) hipLaunchKernelGGL(gpp_loo_value, dim3(1), dim3(1024), 0, s, d, alpha, N, loo);
-  return hipGetLastError();
+  return gpp_launch_loo_scalars_batched(s, Linv, ldi, N, alpha, y, d, mu, s2, a, sb, loo, 1, 0, 0);
 }
 
 size_t gpp_grad_ws_bytes(int64_t N, int D, int S, int dU) {

@@ -301,7 +301,9 @@ class GP_Plus(GPR):
         'adam_torch', otherwise a warning and 4 restarts) — reproduced here.  The CPU branches
         (scipy / continuation drivers) do not exist in this build: the exact-GP path only runs on the MI355X.
         ``objective``: "mll" (the exact marginal log-likelihood, as the reference) or "loo" (the leave-one-out log
-        pseudo-likelihood; the restarts then run one after the other, every evaluation eagerly)."""
+        pseudo-likelihood).  Both take the same route: all restarts advance together, one batched evaluation per Adam step replayed
+        as a HIP graph, while the problem is small enough (see below); otherwise, and under ``settings.batched_restarts(False)``,
+        the restarts run one after the other, the leave-one-out objective then with every evaluation eager."""
         from ..optim.mll_torch import check_objective
         check_objective(objective)
         print("## Learning the model's parameters has started ##")
@@ -318,15 +320,13 @@ class GP_Plus(GPR):
         # iteration: same start points in the same RNG order, same per-run optimiser and early stop, same winner —
         # optim/mll_batched.py) while the problem is small enough for that to pay and for the B x 3 N^2 workspace to fit;
         # settings.batched_restarts(False) restores the sequential loop, 'adam_torch_batched' asks for the batched one.
-        if objective == "loo":
-            out = fit_model_torch(model=self, model_param_groups=None, lr_default=0.01, num_iter=100,
-                                  num_restarts=restarts, break_steps=50, objective="loo")
-        elif optim_type == 'adam_torch_batched' or self._restarts_fit_one_batch(restarts + 1):
+        if optim_type == 'adam_torch_batched' or self._restarts_fit_one_batch(restarts + 1):
             from ..optim import fit_model_torch_batched
-            out = fit_model_torch_batched(self, lr_default=0.01, num_iter=100, num_restarts=restarts, break_steps=50)
+            out = fit_model_torch_batched(self, lr_default=0.01, num_iter=100, num_restarts=restarts, break_steps=50,
+                                          objective=objective)
         else:
             out = fit_model_torch(model=self, model_param_groups=None, lr_default=0.01, num_iter=100,
-                                  num_restarts=restarts, break_steps=50)
+                                  num_restarts=restarts, break_steps=50, objective=objective)
         print("## Learning the model's parameters is successfully finished ##")
         return out
 

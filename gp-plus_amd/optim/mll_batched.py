@@ -1,5 +1,6 @@
 """Restart-parallel Adam fit on ONE GPU: all ``num_restarts + 1`` runs of ``optim/mll_torch.py:99-141`` advance together,
-every iteration being one batched evaluation (``batched.BatchedMLLFunction``: B problems per kernel launch).
+every iteration being one batched evaluation (``batched.BatchedMLLFunction`` or, for ``objective="loo"``, the leave-one-out
+pseudo-likelihood ``batched.BatchedLOOFunction``: B problems per kernel launch).
 
 The reference runs its restarts one after the other; for the data sizes of its examples (N = 100 ... 500) a single
 evaluation leaves an MI355X almost empty, so evaluating the 5 ... 65 parameter sets together costs about as much as
@@ -22,9 +23,10 @@ from typing import Dict, List, Tuple
 import torch
 from torch.func import functional_call
 
-from ..batched import batched_mll
+from ..batched import batched_loo, batched_mll
 from ..gpcore.kernels import LazyKernelMatrix
 from ..gpcore.mlls import ExactMarginalLogLikelihood
+from .mll_torch import check_objective
 
 __all__ = ["BatchedObjective", "fit_model_torch_batched", "BATCHED_MAX_N"]
 
@@ -33,9 +35,12 @@ BATCHED_MAX_N = 6144
 
 
 class BatchedObjective:
-    """``loss()`` -> (B,) tensor of ``-(log p(y) + log priors) / N`` for the B stacked parameter sets ``self.theta``."""
+    """``loss()`` -> (B,) tensor of ``-(log p(y) + log priors) / N`` for the B stacked parameter sets ``self.theta``; with
+    ``objective="loo"`` the leave-one-out log pseudo-likelihood takes the place of log p(y), in the normalisation of
+    ``gpcore.LeaveOneOutPseudoLikelihood``."""
 
-    def __init__(self, model, B: int):
+    def __init__(self, model, B: int, objective: str = "mll"):
+        self.objective = check_objective(objective)  # (before anything touches a device)
         self.model, self.B = model, B
         model.train()
         self.mll = ExactMarginalLogLikelihood(model.likelihood, model)
@@ -113,7 +118,8 @@ class BatchedObjective:
         learn_U = U.requires_grad and dz > 0
         if not learn_U:
             U = U[0]  # identical features for every run: share them
-        mll = batched_mll(U, w, sf2, tau, mean, self.model.train_targets, grp, kind, d_split, dz if learn_U else 0)
+        value = batched_loo if self.objective == "loo" else batched_mll
+        mll = value(U, w, sf2, tau, mean, self.model.train_targets, grp, kind, d_split, dz if learn_U else 0)
         return -(mll + prior) / N
 
 
@@ -137,6 +143,8 @@ class _GraphedLossAndGrad:
         self.params = params
         N = int(obj.model.train_targets.shape[0])
         self.ws = get_batched_workspace(get_context(dev), obj.B, N)  # held: dropped from the cache when another (B, N) is asked for
+        if obj.objective == "loo":
+            self.ws.loo_vectors()  # allocated here, on the fit's stream: the warm-up passes and the capture allocate none of them
         self.status_host = torch.zeros(obj.B, dtype=torch.int32).pin_memory()
         self.done = torch.cuda.Event()
 
@@ -176,16 +184,18 @@ class _GraphedLossAndGrad:
 
 
 def fit_model_torch_batched(model, lr_default: float = 0.01, num_iter: int = 100, num_restarts: int = 0,
-                            break_steps: int = 50, verbose: bool = False) -> Tuple[float, List[List[float]]]:
-    """Drop-in for ``fit_model_torch`` (same return value) that advances all restarts together."""
+                            break_steps: int = 50, verbose: bool = False, objective: str = "mll") -> Tuple[float, List[List[float]]]:
+    """Drop-in for ``fit_model_torch`` (same return value) that advances all restarts together.  ``objective="loo"`` maximises the
+    leave-one-out log pseudo-likelihood (plus the priors) in the same way: batched, and replayed as a HIP graph."""
+    check_objective(objective)
     B = num_restarts + 1
     N = int(model.train_targets.shape[0])
     if N > BATCHED_MAX_N:
         # gpp_potrf_batched factors each problem right-looking in leaf steps and rejects larger matrices; at these sizes
         # one evaluation fills the GPU by itself, so the sequential driver loses nothing
         from .mll_torch import fit_model_torch
-        return fit_model_torch(model, None, lr_default, num_iter, num_restarts, break_steps, verbose=verbose)
-    obj = BatchedObjective(model, B)
+        return fit_model_torch(model, None, lr_default, num_iter, num_restarts, break_steps, verbose=verbose, objective=objective)
+    obj = BatchedObjective(model, B, objective)
     obj.sample_restarts()
     params = list(obj.theta.values())
     opt = torch.optim.Adam(params, lr=lr_default)

@@ -12,7 +12,8 @@ from ..backend import INFO_PANEL_TIMEOUT
 from ..gpcore.mlls import ExactMarginalLogLikelihood, LeaveOneOutPseudoLikelihood
 
 #: what the fit drivers maximise (per datum, priors included): the exact marginal log-likelihood, or the leave-one-out log
-#: pseudo-likelihood (Rasmussen & Williams 5.4.2) — the latter always as the eager evaluation: no batched restarts, no replayed graph
+#: pseudo-likelihood (Rasmussen & Williams 5.4.2).  In THIS driver and in fit_model_scipy the latter is always the eager evaluation,
+#: no replayed graph; fit_model_torch_batched evaluates all restarts of either objective together and replays the step as a graph
 OBJECTIVES = ("mll", "loo")
 
 

@@ -482,6 +482,22 @@ int gpp_grad_reduce_batched(gpp_handle_t h, const double* U, int64_t sU, int64_t
                             const double* Kinv, int64_t ldk, int64_t sK, int dU, double* g_w, double* g_sf2, double* g_tau,
                             double* g_U, int batch);
 
+/* The leave-one-out pseudo-likelihood in the same batched form (all restarts of an objective="loo" fit in one launch).  Element b
+ * reads Linv + b*sLi and alpha / y + b*sv, writes d / mu / s2 / a / sqrtb + b*sv and loo + b; gpp_sym_rowscale_batched reads
+ * Kinv + b*sK and s + b*sv and writes S + b*sS; gpp_loo_grad_reduce_batched is gpp_grad_reduce_batched with beta + b*sv and
+ * C + b*sC = P_b diag(b_b) P_b (same workspace, batch * gpp_workspace_bytes(GPP_OP_MLL_EVAL, ...), same output layout).  All strides
+ * even, sv >= N.  The kernels, the per-row arithmetic and the summation orders are those of gpp_loo_scalars / gpp_sym_rowscale /
+ * gpp_loo_grad_reduce (which are these with batch = 1): an element's results are bitwise those of the single-problem call. */
+int gpp_loo_scalars_batched(gpp_handle_t h, const double* Linv, int64_t ldi, int64_t sLi, int64_t N, const double* alpha,
+                            const double* y, double* d, double* mu, double* s2, double* a, double* sqrtb, int64_t sv, double* loo,
+                            int batch);
+int gpp_sym_rowscale_batched(gpp_handle_t h, const double* Kinv, int64_t N, int64_t ldk, int64_t sK, const double* s, int64_t sv,
+                             double* S, int64_t lds, int64_t sS, int batch);
+int gpp_loo_grad_reduce_batched(gpp_handle_t h, const double* U, int64_t sU, int64_t N, int D, const double* w, const double* sf2,
+                                const int32_t* grp, int S, int kind, int d_split, const double* alpha, const double* beta,
+                                int64_t sv, const double* C, int64_t ldc, int64_t sC, int dU, double* g_w, double* g_sf2,
+                                double* g_tau, double* g_U, int batch);
+
 #ifdef __cplusplus
 }
 #endif
