@@ -24,6 +24,9 @@ UPLO_FULL, UPLO_LOWER, UPLO_UPPER = 0, 1, 2
 OPT_COOP_PANEL, OPT_PANEL_FAULT, OPT_PANEL_TIMEOUT_MS, OPT_EXEC_SCHED, OPT_DAG_SCHED = 1, 2, 3, 4, 5  # gpp_set_option (include/gpp.h)
 OPT_GEMM_TILE = 6  # tile of gemm / gemm_batched: 0 by grid size, 1 = 32x32, 2 = 64x64, 3 = 128x128, 4 = 128x32 (tests)
 OP_MLL_EVAL, OP_PREDICT, OP_PREDICT_GRAD = 0, 1, 2
+OP_APPLY = 3  # gpp_kernel_apply / gpp_rff_apply: N carries the contracted length
+#: longest contraction gpp_kernel_apply / gpp_rff_apply run without scratch (gpp_apply.hip AP_SPLIT)
+APPLY_SPLIT = 2048
 NOT_SUPPORTED = 2001  # GPP_NOT_SUPPORTED: gpp_lauum_grad does not take these arguments, nothing was enqueued
 NO_WORKSPACE = 2002   # GPP_NO_WORKSPACE: gpp_lauum_grad found no (or too small a) scratch workspace on the handle
 #: the tile kernels stage at most this many feature columns (manifold + quantitative) per point in LDS (gpp_build.hip DMAX)
@@ -230,6 +233,50 @@ class GppContext:
         check(self.lib.gpp_cross_kernel(self.h, Ua.data_ptr(), Ua.shape[0], Ub.data_ptr(), Ub.shape[0], Ua.shape[1],
                                         w.data_ptr(), sf2.data_ptr(), kind, d_split, out.data_ptr(), _ld(out)),
               "gpp_cross_kernel")
+        return out
+
+    def _apply_checks(self, Ua, second, C, out, sf2):
+        M, D = Ua.shape
+        L, S = C.shape
+        _check_features(D)
+        for t, n in ((Ua, "Ua"), (second, "Ub / Omega"), (C, "C / Theta"), (out, "Out")):
+            _need(t, torch.float64, n)
+        if not (Ua.is_contiguous() and second.is_contiguous()):
+            raise GppError("Ua and Ub / Omega must be contiguous")
+        if second.shape != (L, D):
+            raise GppError(f"the second operand must be {L} x {D} (got {tuple(second.shape)})")
+        if out.shape != (M, S):
+            raise GppError(f"Out must be {M} x {S} (got {tuple(out.shape)})")
+        if min(M, L, S) < 1:
+            raise GppError("gpp_kernel_apply / gpp_rff_apply take M, N (F), S >= 1")
+        _need(sf2, torch.float64, "sf2")
+        if sf2.numel() < 1:
+            raise GppError("sf2 must hold one value")
+        self.ensure_workspace(OP_APPLY, L, M, D, S)
+        return M, D, L, S
+
+    @_on_own_device
+    def kernel_apply(self, Ua, Ub, w, sf2, C, out, *, beta=0.0, kind=KIND_RBF, d_split=0):
+        """out = beta out + sf2 k(Ua, Ub; w) C without forming the M x N kernel block (gpp_kernel_apply)."""
+        M, D, N, S = self._apply_checks(Ua, Ub, C, out, sf2)
+        _need(w, torch.float64, "w")
+        if w.numel() != D:
+            raise GppError(f"w has {w.numel()} entries for {D} features")
+        self._stream()
+        check(self.lib.gpp_kernel_apply(self.h, Ua.data_ptr(), M, Ub.data_ptr(), N, D, w.data_ptr(), sf2.data_ptr(), kind, d_split,
+                                        C.data_ptr(), _ld(C), S, float(beta), out.data_ptr(), _ld(out)), "gpp_kernel_apply")
+        return out
+
+    @_on_own_device
+    def rff_apply(self, Ua, omega, phase, sf2, theta, out, *, beta=0.0):
+        """out = beta out + Phi(Ua) theta with Phi[a,f] = sqrt(2 sf2 / F) cos(omega_f . Ua_a + phase_f) (gpp_rff_apply)."""
+        M, D, F, S = self._apply_checks(Ua, omega, theta, out, sf2)
+        _need(phase, torch.float64, "phase")
+        if phase.numel() != F:
+            raise GppError(f"phase has {phase.numel()} entries for {F} features")
+        self._stream()
+        check(self.lib.gpp_rff_apply(self.h, Ua.data_ptr(), M, D, omega.data_ptr(), phase.data_ptr(), F, sf2.data_ptr(),
+                                     theta.data_ptr(), _ld(theta), S, float(beta), out.data_ptr(), _ld(out)), "gpp_rff_apply")
         return out
 
     @_on_own_device

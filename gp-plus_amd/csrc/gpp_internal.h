@@ -331,6 +331,19 @@ hipError_t gpp_launch_sym_rowscale(hipStream_t s, const double* Kinv, int64_t ld
 hipError_t gpp_launch_sym_rowscale_batched(hipStream_t s, const double* Kinv, int64_t ldk, int64_t N, const double* sv, double* S,
                                            int64_t lds, int batch, int64_t sK, int64_t sv_stride, int64_t sS);
 
+// ---- generated-matrix products (gpp_apply.hip) ---------------------------------------------------
+// Out = beta Out + G C with G = sf2 k(Ua, Ub; w) (M x N) or the random-feature matrix sqrt(2 sf2 / F) cos(Ua Omega^T + phase) (M x F),
+// generated tile by tile in registers.  A contracted length L above 2048 is cut into gpp_apply_pieces(L) pieces whose partial
+// results go through `ws` (gpp_apply_ws_bytes) and are added in a fixed order.
+int gpp_apply_pieces(int64_t L);
+size_t gpp_apply_ws_bytes(int64_t L, int64_t M, int S);
+hipError_t gpp_launch_kernel_apply(hipStream_t s, const double* Ua, int64_t M, const double* Ub, int64_t N, int D, const double* w,
+                                   const double* sf2, int kind, int d_split, const double* C, int64_t ldc, int S, double beta,
+                                   double* Out, int64_t ldo, void* ws, size_t ws_bytes);
+hipError_t gpp_launch_rff_apply(hipStream_t s, const double* Ua, int64_t M, int D, const double* Omega, const double* phase, int64_t F,
+                                const double* sf2, const double* Theta, int64_t ldt, int S, double beta, double* Out, int64_t ldo,
+                                void* ws, size_t ws_bytes);
+
 // ---- reductions (gpp_reduce.hip) --------------------------------------------------------------
 // batch > 1 (all reductions): matrices at + b*sT, vectors at + b*sv (sv even, >= N), out3 at + 3*b
 hipError_t gpp_launch_trmv_lower(hipStream_t s, const double* T, int64_t ldt, int64_t N, const double* x, double* y,

@@ -471,6 +471,21 @@ class GP_Plus(GPR):
             if swap:
                 lik.fidel_indices = saved
 
+    def sample_paths(self, size=1, num_features=2048, generator=None):
+        """``size`` draws of the posterior FUNCTION as a :class:`~gpplus_amd.pathwise.PosteriorPaths` (Matheron's rule on
+        ``num_features`` random Fourier features of the prior): built once from the cached factor in O(N^2 size), then
+        ``paths(X)`` evaluates every draw at any inputs in O(N + num_features) per point and draw — the same function at every
+        call, which ``sample_y`` (a fresh vector per call, O(M^3)) cannot offer.  The draws are of the latent function, without
+        observation noise, in the scaled target space of ``sample_y``, and carry no autograd graph.  ``generator``: a CPU
+        ``torch.Generator`` (all random numbers are drawn on the CPU: one seed gives the same paths everywhere); None draws from
+        torch's default generator.  No reference counterpart."""
+        from ..pathwise import PosteriorPaths
+
+        self.eval()
+        with torch.no_grad():
+            cache = self._ensure_prediction_cache()
+        return PosteriorPaths(self, cache, size=size, num_features=num_features, generator=generator)
+
     def get_latent_space(self):
         if len(self.qual_dict_list) > 0:
             return [self.A_matrix[i](self.zeta[i].to(**self.tkwargs)).detach() for i in range(len(self.qual_kernel_columns))]

@@ -49,6 +49,8 @@ typedef struct gpp_handle_s* gpp_handle_t;
 #define GPP_OP_MLL_EVAL 0   /* potrf + trtri + lauum + mll_reduce + grad_reduce for an N-point model */
 #define GPP_OP_PREDICT  1   /* gpp_predict with M test points */
 #define GPP_OP_PREDICT_GRAD 2 /* gpp_cross_grad with M test points, N training points, D features; S carries dB (0..D) */
+#define GPP_OP_APPLY 3      /* gpp_kernel_apply / gpp_rff_apply: N = the contracted length (training points or random features),
+                               M rows, S columns; 0 extra bytes up to a contracted length of 2048 */
 
 const char* gpp_version(void);
 
@@ -112,6 +114,25 @@ int gpp_kernel_build(gpp_handle_t h, const double* U, int64_t N, int D, const do
 /* K8 cross block (models/gpregression.py:126 self(x) -> test/train covariance): Kab[a,b] = sf2*k(Ua_a, Ub_b; w) */
 int gpp_cross_kernel(gpp_handle_t h, const double* Ua, int64_t Ma, const double* Ub, int64_t Nb, int D,
                      const double* w, const double* sf2, int kind, int d_split, double* Kab, int64_t ld);
+
+/*
+ * Products with a GENERATED matrix, for pathwise posterior draws (no reference counterpart: the reference samples only vectors,
+ * models/gp_plus.py:985-998).  Neither forms its M x N / M x F matrix in memory: tiles of it are generated in registers and fed
+ * to the fp64 MFMA.
+ *   gpp_kernel_apply:  Out[a,s] = beta Out[a,s] + sum_j sf2 k(Ua_a, Ub_j; w) C[j,s]          (kind / d_split as gpp_cross_kernel)
+ *   gpp_rff_apply:     Out[a,s] = beta Out[a,s] + sum_f sqrt(2 sf2 / F) cos(Omega_f . Ua_a + phase_f) Theta[f,s]
+ * Ua: M x D, Ub: N x D, Omega: F x D row-major and contiguous; phase: F; C (N x S, ldc >= S), Theta (F x S, ldt >= S) and Out
+ * (M x S, ldo >= S) row-major with any leading dimension and 8-byte alignment.  M, N, F, S >= 1, D <= 64.  beta == 0 overwrites Out
+ * without reading it.  Nothing outside the stated extents is read or written.  A contracted length (N or F) above 2048 is cut into
+ * pieces of 2048 whose partial products go through the handle workspace (gpp_workspace_bytes(GPP_OP_APPLY, length, M, D, S);
+ * GPP_NO_WORKSPACE when it is missing) and are added in a fixed order by a second launch: the count of pieces depends on the
+ * contracted length only, so a row's result does not depend on the other rows of the call, and two launches agree bit for bit.
+ */
+int gpp_kernel_apply(gpp_handle_t h, const double* Ua, int64_t M, const double* Ub, int64_t N, int D, const double* w,
+                     const double* sf2, int kind, int d_split, const double* C, int64_t ldc, int S, double beta, double* Out,
+                     int64_t ldo);
+int gpp_rff_apply(gpp_handle_t h, const double* Ua, int64_t M, int D, const double* Omega, const double* phase, int64_t F,
+                  const double* sf2, const double* Theta, int64_t ldt, int S, double beta, double* Out, int64_t ldo);
 
 /*
  * K5 (gpytorch psd_safe_cholesky -> torch.linalg.cholesky_ex reached from optim/mll_torch.py:116):
