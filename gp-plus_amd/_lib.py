@@ -38,6 +38,10 @@ _SIGNATURES = {
                                  c_int64, c_int, c_double, c_void_p, c_int64]),
     "gpp_rff_apply": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int,
                               c_double, c_void_p, c_int64]),
+    "gpp_kernel_apply_grad": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                      c_int64, c_int, c_void_p, c_int64, c_double, c_void_p, c_int64]),
+    "gpp_rff_apply_grad": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int,
+                                   c_void_p, c_int64, c_double, c_void_p, c_int64]),
     "gpp_potrf": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
     "gpp_potrf_ws": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "gpp_build_potrf_ws": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_int,

@@ -25,6 +25,7 @@ OPT_COOP_PANEL, OPT_PANEL_FAULT, OPT_PANEL_TIMEOUT_MS, OPT_EXEC_SCHED, OPT_DAG_S
 OPT_GEMM_TILE = 6  # tile of gemm / gemm_batched: 0 by grid size, 1 = 32x32, 2 = 64x64, 3 = 128x128, 4 = 128x32 (tests)
 OP_MLL_EVAL, OP_PREDICT, OP_PREDICT_GRAD = 0, 1, 2
 OP_APPLY = 3  # gpp_kernel_apply / gpp_rff_apply: N carries the contracted length
+OP_APPLY_GRAD = 4  # gpp_kernel_apply_grad / gpp_rff_apply_grad: N carries the contracted length
 #: longest contraction gpp_kernel_apply / gpp_rff_apply run without scratch (gpp_apply.hip AP_SPLIT)
 APPLY_SPLIT = 2048
 NOT_SUPPORTED = 2001  # GPP_NOT_SUPPORTED: gpp_lauum_grad does not take these arguments, nothing was enqueued
@@ -235,7 +236,8 @@ class GppContext:
               "gpp_cross_kernel")
         return out
 
-    def _apply_checks(self, Ua, second, C, out, sf2):
+    def _apply_checks(self, Ua, second, C, out, sf2, g_Ua=None):
+        """Shared by the two products and their gradients; ``out`` is the M x S operand (Out, or Gbar with ``g_Ua`` given)."""
         M, D = Ua.shape
         L, S = C.shape
         _check_features(D)
@@ -252,7 +254,11 @@ class GppContext:
         _need(sf2, torch.float64, "sf2")
         if sf2.numel() < 1:
             raise GppError("sf2 must hold one value")
-        self.ensure_workspace(OP_APPLY, L, M, D, S)
+        if g_Ua is not None:
+            _need(g_Ua, torch.float64, "g_Ua")
+            if g_Ua.shape != (M, D):
+                raise GppError(f"g_Ua must be {M} x {D} (got {tuple(g_Ua.shape)})")
+        self.ensure_workspace(OP_APPLY if g_Ua is None else OP_APPLY_GRAD, L, M, D, S)
         return M, D, L, S
 
     @_on_own_device
@@ -278,6 +284,32 @@ class GppContext:
         check(self.lib.gpp_rff_apply(self.h, Ua.data_ptr(), M, D, omega.data_ptr(), phase.data_ptr(), F, sf2.data_ptr(),
                                      theta.data_ptr(), _ld(theta), S, float(beta), out.data_ptr(), _ld(out)), "gpp_rff_apply")
         return out
+
+    @_on_own_device
+    def kernel_apply_grad(self, Ua, Ub, w, sf2, C, gbar, g_Ua, *, beta=0.0, kind=KIND_RBF, d_split=0):
+        """g_Ua = beta g_Ua + d sum(gbar o (sf2 k(Ua, Ub; w) C)) / d Ua, without forming an M x N block (gpp_kernel_apply_grad)."""
+        M, D, N, S = self._apply_checks(Ua, Ub, C, gbar, sf2, g_Ua)
+        _need(w, torch.float64, "w")
+        if w.numel() != D:
+            raise GppError(f"w has {w.numel()} entries for {D} features")
+        self._stream()
+        check(self.lib.gpp_kernel_apply_grad(self.h, Ua.data_ptr(), M, Ub.data_ptr(), N, D, w.data_ptr(), sf2.data_ptr(), kind, d_split,
+                                             C.data_ptr(), _ld(C), S, gbar.data_ptr(), _ld(gbar), float(beta), g_Ua.data_ptr(),
+                                             _ld(g_Ua)), "gpp_kernel_apply_grad")
+        return g_Ua
+
+    @_on_own_device
+    def rff_apply_grad(self, Ua, omega, phase, sf2, theta, gbar, g_Ua, *, beta=0.0):
+        """g_Ua = beta g_Ua + d sum(gbar o (Phi(Ua) theta)) / d Ua, Phi as in ``rff_apply`` (gpp_rff_apply_grad)."""
+        M, D, F, S = self._apply_checks(Ua, omega, theta, gbar, sf2, g_Ua)
+        _need(phase, torch.float64, "phase")
+        if phase.numel() != F:
+            raise GppError(f"phase has {phase.numel()} entries for {F} features")
+        self._stream()
+        check(self.lib.gpp_rff_apply_grad(self.h, Ua.data_ptr(), M, D, omega.data_ptr(), phase.data_ptr(), F, sf2.data_ptr(),
+                                          theta.data_ptr(), _ld(theta), S, gbar.data_ptr(), _ld(gbar), float(beta), g_Ua.data_ptr(),
+                                          _ld(g_Ua)), "gpp_rff_apply_grad")
+        return g_Ua
 
     @_on_own_device
     def potrf(self, A, Linv, info, T=None):

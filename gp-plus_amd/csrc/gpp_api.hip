@@ -1235,6 +1235,7 @@ size_t gpp_workspace_bytes(gpp_handle_t h, int op, int64_t N, int64_t M, int D, 
   if (op == GPP_OP_PREDICT) return 256;
   if (op == GPP_OP_PREDICT_GRAD) return gpp_pgrad_ws_bytes(M, N, D, D, S) + 256;
   if (op == GPP_OP_APPLY) return gpp_apply_ws_bytes(N, M, S) + 256;
+  if (op == GPP_OP_APPLY_GRAD) return gpp_apply_ws_bytes(N, M, D) + 256;
   return 0;
 }
 
@@ -1325,6 +1326,56 @@ int gpp_rff_apply(gpp_handle_t h, const double* Ua, int64_t M, int D, const doub
   if (ldo < S) return -14;
   if (gpp_apply_pieces(F) > 1 && (!h->ws || h->ws_bytes < gpp_apply_ws_bytes(F, M, S))) return GPP_NO_WORKSPACE;
   GPP_TRY(gpp_launch_rff_apply(h->stream, Ua, M, D, Omega, phase, F, sf2, Theta, ldt, S, beta, Out, ldo, h->ws, h->ws_bytes));
+  return 0;
+}
+
+int gpp_kernel_apply_grad(gpp_handle_t h, const double* Ua, int64_t M, const double* Ub, int64_t N, int D, const double* w,
+                          const double* sf2, int kind, int d_split, const double* C, int64_t ldc, int S, const double* Gbar,
+                          int64_t ldg, double beta, double* g_Ua, int64_t ldu) {
+  if (!h) return -1;
+  if (!Ua) return -2;
+  if (M < 1) return -3;
+  if (!Ub) return -4;
+  if (N < 1) return -5;
+  if (D < 1 || D > 64) return -6;
+  if (!w) return -7;
+  if (!sf2) return -8;
+  if (kind < 0 || kind > 2) return -9;
+  if (d_split < 0 || d_split > D) return -10;
+  if (!C) return -11;
+  if (S < 1) return -13;
+  if (ldc < S) return -12;
+  if (!Gbar) return -14;
+  if (ldg < S) return -15;
+  if (!g_Ua) return -17;
+  if (ldu < D) return -18;
+  if (gpp_apply_pieces(N) > 1 && (!h->ws || h->ws_bytes < gpp_apply_ws_bytes(N, M, D))) return GPP_NO_WORKSPACE;
+  GPP_TRY(gpp_launch_kernel_apply_grad(h->stream, Ua, M, Ub, N, D, w, sf2, kind, d_split, C, ldc, S, Gbar, ldg, beta, g_Ua, ldu, h->ws,
+                                       h->ws_bytes));
+  return 0;
+}
+
+int gpp_rff_apply_grad(gpp_handle_t h, const double* Ua, int64_t M, int D, const double* Omega, const double* phase, int64_t F,
+                       const double* sf2, const double* Theta, int64_t ldt, int S, const double* Gbar, int64_t ldg, double beta,
+                       double* g_Ua, int64_t ldu) {
+  if (!h) return -1;
+  if (!Ua) return -2;
+  if (M < 1) return -3;
+  if (D < 1 || D > 64) return -4;
+  if (!Omega) return -5;
+  if (!phase) return -6;
+  if (F < 1) return -7;
+  if (!sf2) return -8;
+  if (!Theta) return -9;
+  if (S < 1) return -11;
+  if (ldt < S) return -10;
+  if (!Gbar) return -12;
+  if (ldg < S) return -13;
+  if (!g_Ua) return -15;
+  if (ldu < D) return -16;
+  if (gpp_apply_pieces(F) > 1 && (!h->ws || h->ws_bytes < gpp_apply_ws_bytes(F, M, D))) return GPP_NO_WORKSPACE;
+  GPP_TRY(gpp_launch_rff_apply_grad(h->stream, Ua, M, D, Omega, phase, F, sf2, Theta, ldt, S, Gbar, ldg, beta, g_Ua, ldu, h->ws,
+                                    h->ws_bytes));
   return 0;
 }
 

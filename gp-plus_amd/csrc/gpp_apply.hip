@@ -13,6 +13,17 @@
 // depends on the contracted length alone, every output element is the sum of the same terms in the same order wherever its row
 // stands in the call, there are no float atomics and no work-group waits for another one: a row's result does not depend on the
 // other rows of the call and two launches agree bit for bit.
+//
+// The gradient with respect to Ua (gpp_kernel_apply_grad, gpp_rff_apply_grad; gpp_apply_grad_tile below), for an upstream Gbar (M x S):
+//   g_Ua[a,d] = beta g_Ua[a,d] + sum_j V[a,j] dG[a,j]/dUa[a,d],     V = Gbar C^T  (never written to memory either)
+// With the staged values a = sqrt(w) ua, b = sqrt(w) ub, the distance accumulators q1 (RBF dims) and q2 (Matern dims), e1 = exp(-q1)
+// and h the Matern factor, dG/dua_d = 2 sqrt(w_d) (a_d - b_d) m_f, where f is the factor feature d belongs to and
+//   m_0 = -G = -sf2 e1 h,     m_1 = sf2 e1 h'(q2),     h' = -3 e^-r (Matern 3/2),  -(5/3) (1 + r) e^-r (Matern 5/2)
+// (h' is dh/dq2 / 2, formed without a division by r: finite where a row of Ua equals a row of Ub).  For the random features
+// dG[a,f]/dua_d = -amp sin(omega_f . ua + b_f) omega_fd.  So with W_f = V o m_f (one per factor)
+//   g_Ua[a,d] = 2 sqrt(w_d) (a_d sum_j W_f[a,j] - sum_j W_f[a,j] b[j,d])         (kernel)
+//   g_Ua[a,d] = sum_j W[a,j] (omega_jd / 2 pi),     W = -(2 pi amp) V o sin        (random features)
+// i.e. two MFMA products per chunk, V = Gbar-tile C-chunk^T (K = S) and W [b | 1] (K = 32), with the generation between them.
 #include "gpp_internal.h"
 
 #include <atomic>
@@ -121,6 +132,33 @@ struct KernelGen {
     }
     return sf2 * v;
   }
+  // gradient: one ones-column per factor gives the row sums of W_f; m_f as in the file header
+  static constexpr int NROWSUM = NACC;
+  __device__ __forceinline__ void dvalue(const double (&acc)[NACC], double (&m)[NACC]) const {
+    const double e1 = sf2 * gpp_exp_nonpos(-acc[0], ec);
+    if constexpr (MAT) {
+      double h, hp;
+      if (kind == 1) {
+        const double r = sqrt(3.0 * 2.0 * acc[1]);
+        const double er = gpp_exp_nonpos(-r, ec);
+        h = (1.0 + r) * er;
+        hp = -3.0 * er;
+      } else {
+        const double r = sqrt(5.0 * 2.0 * acc[1]);
+        const double er = gpp_exp_nonpos(-r, ec);
+        h = (1.0 + r + r * r * (1.0 / 3.0)) * er;
+        hp = (-5.0 / 3.0) * (1.0 + r) * er;
+      }
+      m[0] = -(e1 * h);
+      m[1] = e1 * hp;
+    } else {
+      m[0] = -e1;
+    }
+  }
+  // g = out_scale (a_d rowsum_f - (W_f b)[d])
+  __device__ __forceinline__ double finish(double wb, double a, double rowsum, double scale_a_d) const {
+    return (2.0 * scale_a_d) * fma(a, rowsum, -wb);
+  }
 };
 
 struct RffGen {
@@ -144,6 +182,16 @@ struct RffGen {
     const double t = acc[0];
     return amp * gpp_cos_turns(t - __builtin_rint(t), cc);
   }
+  // gradient: sin(2 pi r) = sign(r) cos(2 pi (|r| - 1/4)), the cosine's argument within a quarter turn (|r| - 1/4 is exact from
+  // |r| = 1/8 on and errs by at most 2^-56 turns below); the staged frequencies are omega / 2 pi, so 2 pi goes into W
+  static constexpr int NROWSUM = 0;
+  __device__ __forceinline__ void dvalue(const double (&acc)[1], double (&m)[1]) const {
+    const double t = acc[0];
+    const double r = t - __builtin_rint(t);
+    const double c = gpp_cos_turns(__builtin_fabs(r) - 0.25, cc);
+    m[0] = -(amp * cc.two_pi) * (r < 0.0 ? -c : c);
+  }
+  __device__ __forceinline__ double finish(double wb, double, double, double) const { return wb; }
 };
 
 struct ApplyArgs {
@@ -342,6 +390,249 @@ hipError_t ap_launch(hipStream_t s, ApplyArgs a, void* ws, size_t ws_bytes) {
   return hipSuccess;
 }
 
+// ---- the gradient with respect to Ua ---------------------------------------------------------------------------------------------
+constexpr int AG_LDV = AP_TS + 2;  // [row][s] rows of the staged tile of Gbar and chunk of C: 528-byte rows, as AP_LDG's 272 (A-operand reads)
+constexpr int AG_NB = (AP_DMAX + 2 + 15) / 16;  // most 16-column blocks of [b | 1]
+
+struct ApplyGradArgs {
+  const double* Ua;     // M x D
+  const double* Ub;     // L x D: training features, or Omega
+  const double* extra;  // L (the phases) or null
+  const double* w;      // D or null
+  const double* sf2;
+  const double* C;      // L x S, ldc
+  const double* Gbar;   // M x S, ldg
+  double* Out;          // M x D, ldo — or the partial tiles [piece][M][D] when pieces > 1
+  int64_t M, L, ldc, ldg, ldo;
+  int D, S, kind, d_split, pieces;
+  double beta, nfeat;
+};
+
+template <class GEN>
+constexpr size_t ag_lds_bytes(int D) {
+  return ((size_t)D * AP_TM + (size_t)16 * ((D + GEN::NROWSUM + 15) / 16) * AP_LDG + AP_BK + 2 * AP_DMAX + (size_t)AP_TM * AG_LDV +
+          (size_t)AP_BK * AG_LDV + (size_t)GEN::NACC * AP_TM * AP_LDG) * sizeof(double);
+}
+
+// where row r of the tile stands in sa: the four rows 16 wave + 4 v + k (v = 0..3) a lane holds of an accumulator are adjacent
+__device__ __forceinline__ int ag_row_slot(int r) { return (r & 48) | ((r & 3) << 2) | ((r >> 2) & 3); }
+
+// One 256-thread work-group owns 64 rows of Ua and all D columns of the gradient, walks all S columns of Gbar / C in blocks of 64
+// inside each chunk of 32 of the contracted index, and its piece of the contracted index as gpp_apply_tile does.
+template <class GEN>
+__global__ __launch_bounds__(256) void gpp_apply_grad_tile(const ApplyGradArgs p) {
+  extern __shared__ __attribute__((aligned(16))) double ag_smem[];
+  constexpr int NF = GEN::NACC;      // factors of G: one W each
+  constexpr int NRS = GEN::NROWSUM;  // ones-columns behind the D feature columns of the second operand
+  constexpr bool MAT = NF > 1;
+  const int D = p.D, S = p.S;
+  const int nd = (D + NRS + 15) >> 4;  // 16-column blocks of [b | 1] (uniform)
+  double* sa = ag_smem;                              // [d][64 rows of Ua], scaled, rows at ag_row_slot
+  double* sb = sa + (size_t)D * AP_TM;               // [16 nd][AP_LDG]: rows d < D the chunk of the second operand, scaled; then the ones-rows; zeros
+  double* sx = sb + (size_t)16 * nd * AP_LDG;        // [32] per-column scalars
+  double* sw = sx + AP_BK;                           // [2][AP_DMAX] the staging factors of feature d
+  double* sg = sw + 2 * AP_DMAX;                     // [64 rows][AG_LDV] block of Gbar's tile
+  double* sc = sg + (size_t)AP_TM * AG_LDV;          // [32 j][AG_LDV] block of the chunk of C, as it lies in memory
+  double* sv = sc + (size_t)AP_BK * AG_LDV;          // [NF][64 rows][AP_LDG] W_f
+
+  GEN gen;
+  gen.setup(p);
+
+  const int tid = threadIdx.x;
+  const int64_t i0 = (int64_t)blockIdx.x * AP_TM;
+  const int64_t k0 = (int64_t)blockIdx.z * AP_SPLIT;
+  const int64_t k1 = p.pieces > 1 ? (k0 + AP_SPLIT < p.L ? k0 + AP_SPLIT : p.L) : p.L;
+  double* __restrict__ Out = p.Out + (p.pieces > 1 ? (int64_t)blockIdx.z * p.M * p.ldo : 0);
+  const double beta = p.pieces > 1 ? 0.0 : p.beta;
+
+  if (tid < D) {
+    sw[tid] = gen.scale_a(tid);
+    sw[AP_DMAX + tid] = gen.scale_b(tid);
+  }
+  for (int e = D * AP_LDG + tid; e < 16 * nd * AP_LDG; e += 256) sb[e] = (e / AP_LDG - D < NRS) ? 1.0 : 0.0;
+  __syncthreads();
+  for (int e = tid; e < D * AP_TM; e += 256) {
+    const int r = e / D, d = e - r * D;
+    sa[d * AP_TM + ag_row_slot(r)] = (i0 + r < p.M) ? p.Ua[(i0 + r) * D + d] * sw[d] : 0.0;
+  }
+
+  const int wave = tid >> 6, lane = tid & 63;
+  const int li = lane & 15, lk = lane >> 4;
+
+  // does block b of [b | 1] hold a column of factor f (uniform), and is column c one (per lane)?
+  auto block_has = [&](int b, int f) {
+    if (!MAT) return true;
+    if (f == 0) return 16 * b < p.d_split || (D >> 4) == b;
+    return (16 * b + 15 >= p.d_split && 16 * b < D) || ((D + 1) >> 4) == b;
+  };
+  auto column_of = [&](int c, int f) {
+    if (!MAT) return true;
+    return c < D ? (c >= p.d_split) == (f == 1) : c == D + f;
+  };
+
+  v4d gacc[AG_NB];
+#pragma unroll
+  for (int b = 0; b < AG_NB; ++b) gacc[b] = (v4d){0.0, 0.0, 0.0, 0.0};
+
+  for (int64_t kb = k0; kb < k1; kb += AP_BK) {
+    // V (64 x 32) = Gbar-tile C-chunk^T: element v of vacc[b] is row wave * 16 + 4 v + (l >> 4), column 16 b + (l & 15) of the chunk
+    v4d vacc[2] = {(v4d){0.0, 0.0, 0.0, 0.0}, (v4d){0.0, 0.0, 0.0, 0.0}};
+    for (int s0 = 0; s0 < S; s0 += AP_TS) {
+      __syncthreads();  // the reads of what is staged next are done (and, the first time, sa and sb's constant rows are complete)
+      if (s0 == 0) {
+        for (int e = tid; e < D * AP_BK; e += 256) {
+          const int r = e / D, d = e - r * D;
+          sb[d * AP_LDG + r] = (kb + r < k1) ? p.Ub[(kb + r) * D + d] * sw[AP_DMAX + d] : 0.0;
+        }
+        if (GEN::HAS_EXTRA && tid < AP_BK) sx[tid] = (kb + tid < k1) ? p.extra[kb + tid] * gen.scale_extra() : 0.0;
+      }
+      if (S > AP_TS || kb == k0) {  // Gbar's tile stays when it is one block
+#pragma unroll
+        for (int i = 0; i < AP_TM * AP_TS / 256; ++i) {
+          const int e = tid + 256 * i;
+          const int r = e >> 6, c = e & 63;
+          const bool ok = (i0 + r < p.M) & (s0 + c < S);
+          sg[r * AG_LDV + c] = ok ? p.Gbar[(i0 + r) * p.ldg + s0 + c] : 0.0;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < AP_BK * AP_TS / 256; ++i) {
+        const int e = tid + 256 * i;
+        const int k = e >> 6, c = e & 63;
+        const bool ok = (kb + k < k1) & (s0 + c < S);
+        sc[k * AG_LDV + c] = ok ? p.C[(kb + k) * p.ldc + s0 + c] : 0.0;
+      }
+      __syncthreads();
+      // lane (i = l & 15, k = l >> 4) supplies Gbar[row i][s = k] and C[j = i][s = k]: both row reads of a [..][AG_LDV] image
+      const int nk = (min(AP_TS, S - s0) + 3) >> 2;
+      const double* ga = sg + (wave * 16 + li) * AG_LDV + lk;
+      const double* cb = sc + li * AG_LDV + lk;
+      for (int kk = 0; kk < nk; ++kk) {
+        const double af = ga[4 * kk], b0 = cb[4 * kk], b1 = cb[16 * AG_LDV + 4 * kk];
+        vacc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(af, b0, vacc[0], 0, 0, 0);
+        vacc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(af, b1, vacc[1], 0, 0, 0);
+      }
+    }
+
+    {  // W_f = V o m_f at the 4 x 2 entries this lane holds of V
+      double acc[4][2][NF];
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const double x = GEN::HAS_EXTRA ? sx[16 * b + li] : 0.0;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) gen.init(acc[v][b], x);
+      }
+      for (int d = 0; d < D; ++d) {
+        const v2d a01 = reinterpret_cast<const v2d*>(sa + d * AP_TM + 16 * wave + 4 * lk)[0];
+        const v2d a23 = reinterpret_cast<const v2d*>(sa + d * AP_TM + 16 * wave + 4 * lk)[1];
+        const double ua[4] = {a01.x, a01.y, a23.x, a23.y}, ub[2] = {sb[d * AP_LDG + li], sb[d * AP_LDG + 16 + li]};
+        const bool second = gen.second(d);
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) gen.step(acc[v][b], ua[v], ub[b], second);
+      }
+      const bool ok[2] = {kb + li < k1, kb + 16 + li < k1};  // entries past the contracted length are exact zeros
+#pragma unroll
+      for (int v = 0; v < 4; ++v)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+          double m[NF];
+          gen.dvalue(acc[v][b], m);
+#pragma unroll
+          for (int f = 0; f < NF; ++f)
+            sv[(f * AP_TM + wave * 16 + 4 * v + lk) * AP_LDG + 16 * b + li] = ok[b] ? vacc[b][v] * m[f] : 0.0;
+        }
+    }
+    __syncthreads();
+
+    // gacc (64 x 16 nd) += W_f [b | 1]: lane (i, k) supplies W_f[row i][j = k] and sb[column i][j = k]
+    const double* wa = sv + (wave * 16 + li) * AP_LDG + lk;
+    const double* bb = sb + li * AP_LDG + lk;
+#pragma unroll
+    for (int b = 0; b < AG_NB; ++b) {
+      if (b >= nd) continue;
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+        if (!block_has(b, f)) continue;
+        const bool mine = column_of(16 * b + li, f);
+#pragma unroll
+        for (int kk = 0; kk < AP_BK / 4; ++kk) {
+          const double af = wa[f * AP_TM * AP_LDG + 4 * kk];
+          double bf = bb[16 * b * AP_LDG + 4 * kk];
+          if (MAT) bf = mine ? bf : 0.0;
+          gacc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af, bf, gacc[b], 0, 0, 0);
+        }
+      }
+    }
+  }
+
+  // element v of gacc[b]: row wave * 16 + 4 v + (l >> 4), column 16 b + (l & 15); the row sums of W_f stand in column D + f
+  double rs[NRS > 0 ? NRS : 1][4];
+#pragma unroll
+  for (int f = 0; f < NRS; ++f)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      double x = 0.0;
+#pragma unroll
+      for (int b = 0; b < AG_NB; ++b) x = ((D + f) >> 4) == b ? gacc[b][v] : x;
+      rs[f][v] = __shfl(x, (lane & 48) | ((D + f) & 15));
+    }
+#pragma unroll
+  for (int b = 0; b < AG_NB; ++b) {
+    const int d = 16 * b + li;
+    if (d >= D) continue;
+    const int f = gen.second(d) ? NF - 1 : 0;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int64_t i = i0 + wave * 16 + 4 * v + lk;
+      if (i >= p.M) continue;
+      double rowsum = 0.0;
+      if constexpr (NRS > 0) rowsum = (MAT && f) ? rs[NRS - 1][v] : rs[0][v];
+      double x = gen.finish(gacc[b][v], sa[d * AP_TM + 16 * wave + 4 * lk + v], rowsum, sw[d]);
+      double* o = Out + i * p.ldo + d;
+      if (beta != 0.0) x = fma(beta, *o, x);
+      *o = x;
+    }
+  }
+}
+
+template <class GEN>
+hipError_t ag_launch(hipStream_t s, ApplyGradArgs a, void* ws, size_t ws_bytes) {
+  static std::atomic<bool> done[64];  // more than 48 KiB of dynamic LDS needs the opt-in, once per device
+  if (ag_lds_bytes<GEN>(a.D) > 48 * 1024) {
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+    if (!(dev >= 0 && dev < 64 && done[dev])) {
+      if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gpp_apply_grad_tile<GEN>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)ag_lds_bytes<GEN>(AP_DMAX));
+          e != hipSuccess)
+        return e;
+      if (dev >= 0 && dev < 64) done[dev] = true;
+    }
+  }
+  const int pieces = gpp_apply_pieces(a.L);
+  const int64_t tiles_m = (a.M + AP_TM - 1) / AP_TM;
+  if (tiles_m > 0x7fffffff || pieces > 65535) return hipErrorInvalidValue;
+  a.pieces = pieces;
+  double* out = a.Out;
+  const int64_t ldo = a.ldo;
+  if (pieces > 1) {
+    if (!ws || ws_bytes < (size_t)pieces * a.M * a.D * sizeof(double)) return hipErrorInvalidValue;  // (checked by the caller)
+    a.Out = static_cast<double*>(ws);
+    a.ldo = a.D;
+  }
+  hipLaunchKernelGGL((gpp_apply_grad_tile<GEN>), dim3((unsigned)tiles_m, 1, (unsigned)pieces), dim3(256), ag_lds_bytes<GEN>(a.D), s, a);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  if (pieces > 1) {  // the pieces in their order, as the forward's: gpp_apply_finish with S := D
+    const int64_t n = a.M * a.D;
+    hipLaunchKernelGGL(gpp_apply_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, static_cast<const double*>(ws), pieces,
+                       a.M, a.D, a.beta, out, ldo);
+    return hipGetLastError();
+  }
+  return hipSuccess;
+}
+
 }  // namespace
 
 int gpp_apply_pieces(int64_t L) { return L <= AP_SPLIT ? 1 : (int)((L + AP_SPLIT - 1) / AP_SPLIT); }
@@ -372,4 +663,28 @@ hipError_t gpp_launch_rff_apply(hipStream_t s, const double* Ua, int64_t M, int 
   a.D = D; a.S = S; a.kind = 0; a.d_split = 0;
   a.beta = beta; a.nfeat = (double)F;
   return ap_launch<RffGen>(s, a, ws, ws_bytes);
+}
+
+hipError_t gpp_launch_kernel_apply_grad(hipStream_t s, const double* Ua, int64_t M, const double* Ub, int64_t N, int D, const double* w,
+                                        const double* sf2, int kind, int d_split, const double* C, int64_t ldc, int S,
+                                        const double* Gbar, int64_t ldg, double beta, double* g_Ua, int64_t ldu, void* ws,
+                                        size_t ws_bytes) {
+  ApplyGradArgs a{};
+  a.Ua = Ua; a.Ub = Ub; a.extra = nullptr; a.w = w; a.sf2 = sf2; a.C = C; a.Gbar = Gbar; a.Out = g_Ua;
+  a.M = M; a.L = N; a.ldc = ldc; a.ldg = ldg; a.ldo = ldu;
+  a.D = D; a.S = S; a.kind = kind; a.d_split = d_split;
+  a.beta = beta; a.nfeat = 0.0;
+  if (kind == 0) return ag_launch<KernelGen<false>>(s, a, ws, ws_bytes);
+  return ag_launch<KernelGen<true>>(s, a, ws, ws_bytes);
+}
+
+hipError_t gpp_launch_rff_apply_grad(hipStream_t s, const double* Ua, int64_t M, int D, const double* Omega, const double* phase,
+                                     int64_t F, const double* sf2, const double* Theta, int64_t ldt, int S, const double* Gbar,
+                                     int64_t ldg, double beta, double* g_Ua, int64_t ldu, void* ws, size_t ws_bytes) {
+  ApplyGradArgs a{};
+  a.Ua = Ua; a.Ub = Omega; a.extra = phase; a.w = nullptr; a.sf2 = sf2; a.C = Theta; a.Gbar = Gbar; a.Out = g_Ua;
+  a.M = M; a.L = F; a.ldc = ldt; a.ldg = ldg; a.ldo = ldu;
+  a.D = D; a.S = S; a.kind = 0; a.d_split = 0;
+  a.beta = beta; a.nfeat = (double)F;
+  return ag_launch<RffGen>(s, a, ws, ws_bytes);
 }

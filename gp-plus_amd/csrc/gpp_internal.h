@@ -343,6 +343,15 @@ hipError_t gpp_launch_kernel_apply(hipStream_t s, const double* Ua, int64_t M, c
 hipError_t gpp_launch_rff_apply(hipStream_t s, const double* Ua, int64_t M, int D, const double* Omega, const double* phase, int64_t F,
                                 const double* sf2, const double* Theta, int64_t ldt, int S, double beta, double* Out, int64_t ldo,
                                 void* ws, size_t ws_bytes);
+// g_Ua = beta g_Ua + the gradient of sum(Gbar o (G C)) with respect to Ua (M x D), G as above; the partial tiles of a contraction cut
+// in pieces are M x D (gpp_apply_ws_bytes(L, M, D))
+hipError_t gpp_launch_kernel_apply_grad(hipStream_t s, const double* Ua, int64_t M, const double* Ub, int64_t N, int D, const double* w,
+                                        const double* sf2, int kind, int d_split, const double* C, int64_t ldc, int S,
+                                        const double* Gbar, int64_t ldg, double beta, double* g_Ua, int64_t ldu, void* ws,
+                                        size_t ws_bytes);
+hipError_t gpp_launch_rff_apply_grad(hipStream_t s, const double* Ua, int64_t M, int D, const double* Omega, const double* phase,
+                                     int64_t F, const double* sf2, const double* Theta, int64_t ldt, int S, const double* Gbar,
+                                     int64_t ldg, double beta, double* g_Ua, int64_t ldu, void* ws, size_t ws_bytes);
 
 // ---- reductions (gpp_reduce.hip) --------------------------------------------------------------
 // batch > 1 (all reductions): matrices at + b*sT, vectors at + b*sv (sv even, >= N), out3 at + 3*b

@@ -13,7 +13,9 @@ T = diag(tau[grp] + jitter) and Ky = K + T:
 
 E_s[f_s(x)] is the exact posterior mean whatever F is; the covariance of the paths is the posterior covariance with the prior
 kernel replaced by its F-feature estimate in the terms that do not pass through Ky^-1.  The two sums over F and N are the HIP
-kernels gpp_rff_apply and gpp_kernel_apply (csrc/gpp_apply.hip).
+kernels gpp_rff_apply and gpp_kernel_apply (csrc/gpp_apply.hip); their gradients with respect to u(x), gpp_rff_apply_grad and
+gpp_kernel_apply_grad, make a path differentiable in x (``paths_with_grad``), which is what lets ``minimize`` search every draw for
+its minimiser (Thompson sampling, ``bayesian_optimizations.thompson_sample``).
 
 Every random number (omega, b, theta, eps) is drawn in float64 on the CPU from one ``torch.Generator`` and then moved to the
 device: a seed gives the same paths on every machine.
@@ -21,11 +23,13 @@ device: a seed gives the same paths on every machine.
 from __future__ import annotations
 
 import math
-from typing import Optional, Tuple
+from dataclasses import dataclass
+from typing import Dict, Optional, Tuple
 
 import torch
+from torch.autograd.function import once_differentiable
 
-__all__ = ["draw_spectral", "PosteriorPaths"]
+__all__ = ["draw_spectral", "PosteriorPaths", "PathMinimum"]
 
 #: scratch the chunked evaluation lets gpp_kernel_apply ask for (partial products of a contraction cut in pieces)
 WORKSPACE_BYTES = 256 << 20
@@ -70,6 +74,44 @@ def draw_spectral(spec, D: int, F: int, generator: Optional[torch.Generator] = N
         omega[:, d_split:] *= (two_nu / g).sqrt().unsqueeze(1)
     phase = torch.rand(F, dtype=torch.float64, generator=generator) * (2.0 * math.pi)
     return omega, phase
+
+
+class _PathChunk(torch.autograd.Function):
+    """g_s(x) + k(x, X) c_s at one chunk of feature rows (M_c x S): the two applies of ``paths`` forward, their fused gradients
+    backward.  Everything but the features is a constant of the drawn paths."""
+
+    @staticmethod
+    def forward(ctx, Us, paths):
+        buf = torch.empty(Us.shape[0], paths.size, dtype=torch.float64, device=Us.device)
+        paths.gctx.rff_apply(Us, paths.omega, paths.phase, paths._sf2, paths.theta, buf)
+        paths.gctx.kernel_apply(Us, paths.U, paths.spec.w, paths._sf2, paths.coef, buf, beta=1.0, kind=paths.spec.kind,
+                                d_split=paths.spec.d_split)
+        ctx.paths = paths
+        ctx.save_for_backward(Us)
+        return buf
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gbar):
+        (Us,), paths = ctx.saved_tensors, ctx.paths
+        gbar = gbar.to(torch.float64).contiguous()
+        g = torch.empty_like(Us)
+        with torch.cuda.device(Us.device):
+            paths.gctx.rff_apply_grad(Us, paths.omega, paths.phase, paths._sf2, paths.theta, gbar, g)
+            paths.gctx.kernel_apply_grad(Us, paths.U, paths.spec.w, paths._sf2, paths.coef, gbar, g, beta=1.0, kind=paths.spec.kind,
+                                         d_split=paths.spec.d_split)
+        return g, None
+
+
+@dataclass
+class PathMinimum:
+    """What :meth:`PosteriorPaths.minimize` returns: ``x`` (S x p) the best point found for every draw and ``f`` (S) its value
+    f_s(x_s); ``f_candidates`` (S) the best value among the random candidates; ``x_starts`` (S x num_starts x p) the candidates the
+    descent started from."""
+    x: torch.Tensor
+    f: torch.Tensor
+    f_candidates: torch.Tensor
+    x_starts: torch.Tensor
 
 
 class PosteriorPaths:
@@ -190,3 +232,116 @@ class PosteriorPaths:
         return out
 
     __call__ = paths
+
+    def paths_with_grad(self, X, chunk: Optional[int] = None) -> torch.Tensor:
+        """:meth:`paths` with an autograd graph: the same values, bit for bit (the same launches under the same chunking rule),
+        connected to ``X``'s quantitative columns through the model's own forward for features and prior mean; categorical and
+        source columns get zero gradient, as in ``predict_with_grad``.  The frequencies, phases, weights, coefficients, kernel
+        parameters and training features are constants of the drawn paths.  One autograd node per row chunk; its backward is
+        gpp_rff_apply_grad followed by gpp_kernel_apply_grad into one buffer, O(N + F) per point and path like the forward, and
+        cannot itself be differentiated again."""
+        from .gpcore.kernels import LazyKernelMatrix
+        from .gpcore.module import Module
+
+        model = self.model
+        if self._parameter_versions() != self._versions:
+            raise RuntimeError("the model's parameters changed since these paths were drawn (their coefficients belong to the old "
+                               "parameters): call sample_paths again")
+        ref = model.train_inputs[0]
+        X = torch.as_tensor(X)
+        if X.dim() == 1:
+            X = X.unsqueeze(0) if ref.shape[1] > 1 else X.unsqueeze(1)
+        if X.dim() != 2 or X.shape[1] != ref.shape[1]:
+            raise ValueError(f"X must have the {ref.shape[1]} columns of the training inputs (got shape {tuple(X.shape)})")
+        if chunk is not None and int(chunk) < 1:
+            raise ValueError(f"chunk must be at least 1 (got {chunk})")
+        X = X.to(device=ref.device, dtype=ref.dtype)
+        dev = self.U.device
+        rows = self._chunk_rows() if chunk is None else int(chunk)
+        model.eval()
+        out = []
+        with torch.cuda.device(dev):
+            for i0 in range(0, X.shape[0], rows):
+                prior = Module.__call__(model, X[i0:i0 + rows])
+                cov = prior.lazy_covariance_matrix
+                if not isinstance(cov, LazyKernelMatrix):
+                    raise RuntimeError("pathwise draws need the model's forward to return a lazy kernel covariance")
+                buf = _PathChunk.apply(cov.U1.to(torch.float64).contiguous(), self)
+                out.append((buf + prior.mean.to(torch.float64).unsqueeze(1)).T)
+        if not out:
+            return torch.empty(self.size, 0, dtype=torch.float64, device=dev)
+        return out[0] if len(out) == 1 else torch.cat(out, dim=1)
+
+    def minimize(self, lower, upper, fixed: Optional[Dict[int, float]] = None, num_candidates: int = 1024, num_starts: int = 4,
+                 steps: int = 50, maximize: bool = False, generator: Optional[torch.Generator] = None, lr: float = 0.05) -> PathMinimum:
+        """arg min_x f_s(x) over the box [lower, upper] for every draw s (arg max with ``maximize``): a Thompson-sampling step.
+
+        ``lower`` / ``upper`` have one entry per input column; ``fixed`` maps a column to the value it keeps (every categorical and
+        source column must be fixed; a quantitative one may be).  ``num_candidates`` points are drawn uniformly in the box from the
+        CPU ``generator`` and all draws are scored on them with :meth:`paths`; each draw's best ``num_starts`` candidates are then
+        advanced together, S * num_starts points per :meth:`paths_with_grad` call, by ``steps`` steps of Adam on the free
+        quantitative columns in box units (step ``lr`` of the box width), projected back into the box after every step.  The loss
+        is the sum of each point's own draw, so a point only ever sees its own gradient.  The best value seen along each
+        trajectory is kept — the start included, so ``f <= f_candidates`` (``>=`` with ``maximize``).  Nothing inside the loop
+        waits for the GPU.  Evaluating every draw at every point costs a factor S more than needed in the contraction, which is
+        immaterial at these sizes."""
+        model = self.model
+        ref = model.train_inputs[0]
+        p, S = ref.shape[1], self.size
+        num_candidates, num_starts, steps = int(num_candidates), int(num_starts), int(steps)
+        if num_starts < 1 or num_candidates < num_starts or steps < 0:
+            raise ValueError(f"minimize needs num_candidates >= num_starts >= 1 and steps >= 0 (got {num_candidates}, {num_starts}, {steps})")
+        generator = _cpu_generator(generator)
+        lo = torch.as_tensor(lower, dtype=torch.float64).reshape(-1).clone()
+        hi = torch.as_tensor(upper, dtype=torch.float64).reshape(-1).clone()
+        if lo.numel() != p or hi.numel() != p:
+            raise ValueError(f"lower and upper need one entry for each of the {p} input columns")
+        fixed = {int(c): float(v) for c, v in (fixed or {}).items()}
+        if any(c < 0 or c >= p for c in fixed):
+            raise ValueError(f"fixed names a column outside 0..{p - 1}")
+        for c, v in fixed.items():
+            lo[c] = hi[c] = v
+        if bool((lo > hi).any()):
+            raise ValueError("lower must not exceed upper")
+        quant = set(int(c) for c in model.quant_index.tolist())
+        loose = [c for c in range(p) if c not in quant and c not in fixed]
+        if loose:
+            raise ValueError(f"columns {loose} are categorical or source columns: give their values in fixed")
+        free = torch.zeros(p, dtype=torch.float64)
+        free[[c for c in sorted(quant) if c not in fixed]] = 1.0
+
+        dev = self.U.device
+        cand = lo + torch.rand(num_candidates, p, dtype=torch.float64, generator=generator) * (hi - lo)
+        cand = torch.minimum(torch.maximum(cand, lo), hi).to(dev)
+        lo, hi, free = lo.to(dev), hi.to(dev), free.to(dev)
+        sign = -1.0 if maximize else 1.0
+        scores = sign * self.paths(cand)                                   # S x candidates
+        start_f, start_i = torch.topk(scores, num_starts, dim=1, largest=False)
+        x_starts = cand[start_i]                                           # S x starts x p
+        x = x_starts.reshape(S * num_starts, p).to(ref.dtype)
+        own = torch.arange(S, device=dev).repeat_interleave(num_starts).unsqueeze(0)
+        width = (hi - lo) * free                                           # 0 on the columns that stay
+        best_f = torch.full((S * num_starts,), float("inf"), dtype=torch.float64, device=dev)
+        best_x = x.clone()
+        m1, m2 = torch.zeros_like(x, dtype=torch.float64), torch.zeros_like(x, dtype=torch.float64)
+        b1, b2, eps = 0.9, 0.999, 1e-8
+        for t in range(1, steps + 1):
+            xg = x.detach().requires_grad_(True)
+            f = sign * self.paths_with_grad(xg).gather(0, own).squeeze(0)  # each point's own draw
+            (g,) = torch.autograd.grad(f.sum(), xg)
+            better = f.detach() < best_f
+            best_f = torch.where(better, f.detach(), best_f)
+            best_x = torch.where(better.unsqueeze(1), x, best_x)
+            gz = g.to(torch.float64) * width                               # the gradient in box units
+            m1.mul_(b1).add_(gz, alpha=1.0 - b1)
+            m2.mul_(b2).addcmul_(gz, gz, value=1.0 - b2)
+            step = (lr / (1.0 - b1 ** t)) * m1 / ((m2 / (1.0 - b2 ** t)).sqrt() + eps)
+            x = torch.minimum(torch.maximum(x.to(torch.float64) - step * width, lo), hi).to(ref.dtype)
+        f = sign * self.paths(x).gather(0, own).squeeze(0)
+        better = f < best_f
+        best_f = torch.where(better, f, best_f)
+        best_x = torch.where(better.unsqueeze(1), x, best_x)
+        win = best_f.reshape(S, num_starts).argmin(dim=1)
+        rows = torch.arange(S, device=dev)
+        return PathMinimum(x=best_x.reshape(S, num_starts, p)[rows, win], f=sign * best_f.reshape(S, num_starts)[rows, win],
+                           f_candidates=sign * start_f[:, 0], x_starts=x_starts)

@@ -51,6 +51,8 @@ typedef struct gpp_handle_s* gpp_handle_t;
 #define GPP_OP_PREDICT_GRAD 2 /* gpp_cross_grad with M test points, N training points, D features; S carries dB (0..D) */
 #define GPP_OP_APPLY 3      /* gpp_kernel_apply / gpp_rff_apply: N = the contracted length (training points or random features),
                                M rows, S columns; 0 extra bytes up to a contracted length of 2048 */
+#define GPP_OP_APPLY_GRAD 4 /* gpp_kernel_apply_grad / gpp_rff_apply_grad: N = the contracted length, M rows, D features: pieces * M * D
+                               doubles above a contracted length of 2048, 0 extra bytes up to it */
 
 const char* gpp_version(void);
 
@@ -133,6 +135,23 @@ int gpp_kernel_apply(gpp_handle_t h, const double* Ua, int64_t M, const double* 
                      int64_t ldo);
 int gpp_rff_apply(gpp_handle_t h, const double* Ua, int64_t M, int D, const double* Omega, const double* phase, int64_t F,
                   const double* sf2, const double* Theta, int64_t ldt, int S, double beta, double* Out, int64_t ldo);
+
+/*
+ * The gradients of the two products above with respect to Ua, for an upstream Gbar (M x S, ldg >= S): with Out = G C,
+ *   g_Ua[a,d] = beta g_Ua[a,d] + sum_j (sum_s Gbar[a,s] C[j,s]) dG[a,j]/dUa[a,d]
+ * in one fused launch: neither G, its derivative nor the M x N block Gbar C^T is formed in memory (gpp_cross_grad needs the latter as
+ * its operand B).  Operands, checks and status codes as gpp_kernel_apply / gpp_rff_apply; g_Ua is M x D row-major, ldu >= D, and
+ * beta == 0 overwrites it without reading it.  A feature with w_d == 0 gets an exact 0; a row of Ua that equals a row of Ub gets a
+ * finite gradient for the Matern kinds too.  Contracted lengths above 2048 go through the handle workspace
+ * (gpp_workspace_bytes(GPP_OP_APPLY_GRAD, length, M, D, S); GPP_NO_WORKSPACE when it is missing, with nothing enqueued) exactly as in
+ * the forward: no float atomics, a row's gradient does not depend on the other rows of the call, two launches agree bit for bit.
+ */
+int gpp_kernel_apply_grad(gpp_handle_t h, const double* Ua, int64_t M, const double* Ub, int64_t N, int D, const double* w,
+                          const double* sf2, int kind, int d_split, const double* C, int64_t ldc, int S, const double* Gbar,
+                          int64_t ldg, double beta, double* g_Ua, int64_t ldu);
+int gpp_rff_apply_grad(gpp_handle_t h, const double* Ua, int64_t M, int D, const double* Omega, const double* phase, int64_t F,
+                       const double* sf2, const double* Theta, int64_t ldt, int S, const double* Gbar, int64_t ldg, double beta,
+                       double* g_Ua, int64_t ldu);
 
 /*
  * K5 (gpytorch psd_safe_cholesky -> torch.linalg.cholesky_ex reached from optim/mll_torch.py:116):

@@ -8,7 +8,12 @@
 Medians of ``repeats`` runs, each between two device synchronisations (stages: HIP events).  For each M the floor
 max(2 M N S / 78.6 TFLOP/s, M N V / 3.9e13) is printed beside the measured kernel time, V = VALU instructions per generated
 entry (``--valu``; count them in the disassembly of gpp_apply_tile).
-usage: python tools/bench_paths.py [N] [S] [F] [repeats] [--valu V] [--max-m M]"""
+``--grad`` times the backward of a path instead, for M in {1, 1024, 65 536}: gpp_rff_apply_grad and gpp_kernel_apply_grad (HIP events,
+each kernel alone), the forward gpp_kernel_apply at the same M beside them, and the materialised route — gpp_gemm for the M x N
+block Gbar C^T, then gpp_cross_grad with gvar = 1 and that block as B, in row chunks of at most 8192 — whose gradient is checked
+in the same run to agree with the fused one to 1e-10 of max |g|.  Floor of gpp_kernel_apply_grad:
+max(2 M N (S + D + 1) / 78.6 TFLOP/s, M N V' / 3.9e13), V' the VALU instructions per generated entry of gpp_apply_grad_tile.
+usage: python tools/bench_paths.py [N] [S] [F] [repeats] [--valu V] [--max-m M] [--grad]"""
 import os
 import sys
 import time
@@ -30,6 +35,9 @@ def _opt(name, default):
     return default
 
 
+GRAD = "--grad" in sys.argv
+if GRAD:
+    sys.argv.remove("--grad")
 VALU = _opt("--valu", 0.0)
 MAX_M = _opt("--max-m", 1000000)
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 20000
@@ -80,6 +88,53 @@ print(f"construction (factor cached)                       {t_build:10.3f}")
 
 gctx, spec = paths.gctx, paths.spec
 lo, hi = X.min(0)[0], X.max(0)[0]
+
+
+def grad_section():
+    D = X.shape[1]
+    Cb = rows_buffer(N, S, "cuda")
+    Cb.copy_(paths.coef)
+    for M in (1, 1024, 65536):
+        if M > MAX_M:
+            continue
+        Us = (lo + (hi - lo) * torch.rand(M, D, dtype=torch.float64, generator=torch.Generator().manual_seed(M))).cuda().contiguous()
+        gbar = torch.randn(M, S, dtype=torch.float64, generator=torch.Generator().manual_seed(M + 1)).cuda()
+        buf = torch.empty(M, S, dtype=torch.float64, device="cuda")
+        g = torch.empty(M, D, dtype=torch.float64, device="cuda")
+        t_fwd = event_ms(lambda: gctx.kernel_apply(Us, paths.U, spec.w, paths._sf2, paths.coef, buf, kind=spec.kind, d_split=spec.d_split))
+        t_rff = event_ms(lambda: gctx.rff_apply_grad(Us, paths.omega, paths.phase, paths._sf2, paths.theta, gbar, g))
+        t_ker = event_ms(lambda: gctx.kernel_apply_grad(Us, paths.U, spec.w, paths._sf2, paths.coef, gbar, g, kind=spec.kind,
+                                                        d_split=spec.d_split))
+        fused = g.clone()  # the kernel term alone (beta = 0)
+        mc = min(M, 8192)
+        Bb, ones = rows_buffer(mc, N, "cuda"), torch.ones(mc, dtype=torch.float64, device="cuda")
+        gm = torch.empty(M, D, dtype=torch.float64, device="cuda")
+
+        def materialised(i0=0):
+            gctx.gemm(0, 1, mc, N, S, 1.0, gbar[i0:i0 + mc], Cb, 0.0, Bb)
+            gctx.cross_grad(Us[i0:i0 + mc], paths.U, spec.w, paths._sf2, None, None, ones, Bb, gm[i0:i0 + mc], None, None, None,
+                            kind=spec.kind, d_split=spec.d_split)
+
+        t_mat = (M / mc) * event_ms(materialised)
+        for i0 in range(0, M, mc):  # (M is a multiple of the chunk)
+            materialised(i0)
+        torch.cuda.synchronize()
+        err = (fused - gm).abs().max().item() / gm.abs().max().item()
+        floor_mfma = 1e3 * 2.0 * M * N * (S + D + 1) / 78.6e12
+        line = (f"backward M={M:8d}: gpp_rff_apply_grad {t_rff:9.3f}   gpp_kernel_apply_grad {t_ker:10.3f}   forward gpp_kernel_apply "
+                f"{t_fwd:10.3f}   floor(kernel_apply_grad) MFMA {floor_mfma:9.3f}")
+        if VALU:
+            line += f" VALU {1e3 * M * N * VALU / 3.9e13:9.3f}"
+        print(line + f"   materialised route {t_mat:10.3f}   fused / materialised {t_ker / t_mat:5.2f}   "
+              f"max |fused - materialised| / max |g| {err:.2e}")
+        if not err <= 1e-10:
+            raise SystemExit("the fused and the materialised gradients differ")
+        del Bb, gm, Us, gbar, buf, g
+
+
+if GRAD:
+    grad_section()
+    sys.exit(0)
 for M in (1, 1024, 65536, 1000000):
     if M > MAX_M:
         continue
