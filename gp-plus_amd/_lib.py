@@ -128,6 +128,9 @@ _SIGNATURES = {
     "gpp_loo_grad_reduce_batched": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                             c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
                                             c_void_p, c_void_p, c_int]),
+    "gpp_cv_blocks": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int64]),
+    "gpp_cv_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int64, c_void_p,
+                            c_int64]),
 }
 
 _lib = None

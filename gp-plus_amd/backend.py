@@ -801,6 +801,84 @@ class GppContext:
                                                    _ptr(g_U), B), "gpp_loo_grad_reduce_batched")
 
 
+    # -- grouped cross-validation: ragged lists of folds as CSR (idx ascending inside a fold, off with nfolds + 1 entries) ------
+    def _check_csr(self, idx, off, N: int, mp: int) -> Tuple[int, int]:
+        """The kernels trust the CSR list: they gather rows idx[.] unchecked, walk m_f = off[f + 1] - off[f] entries of a fold and
+        (gpp_cv_rows) write the rows off[f] + a.  Shapes are verified on every call, the CONTENTS once per pair of index tensors
+        (a device read, i.e. a host sync; remembered per index tensor OBJECT, as ``_check_groups`` does): offsets ascending inside idx, every fold at most ``mp``
+        rows, every index in [0, N) and ascending inside its fold.  Returns (nfolds, the largest offset)."""
+        for t, n in ((idx, "idx"), (off, "off")):
+            _need(t, torch.int32, n)
+            if t.dim() != 1 or not t.is_contiguous():
+                raise GppError(f"{n} must be a contiguous int32 vector")
+        if off.numel() < 1:
+            raise GppError("off must hold nfolds + 1 entries")
+        nfolds = off.numel() - 1
+        cache = self.__dict__.setdefault("_csr_ok", {})  # id(off) -> (idx, off as weak references, what was checked, largest offset)
+        key = (idx._version, off._version, N, mp)
+        seen = cache.get(id(off))
+        if seen is not None and seen[0]() is idx and seen[1]() is off and seen[2] == key:
+            return nfolds, seen[3]
+        for k in [k for k, v in cache.items() if v[0]() is None or v[1]() is None]:
+            del cache[k]  # (lists whose tensors are gone: an evaluation keeps one entry per bucket of its folds alive)
+        o, i = off.cpu().numpy().astype("int64"), idx.cpu().numpy().astype("int64")
+        sizes = o[1:] - o[:-1]
+        if o[0] < 0 or (sizes < 0).any() or o[-1] > i.shape[0]:
+            raise GppError(f"fold offsets must ascend from >= 0 to at most the {i.shape[0]} entries of idx")
+        if nfolds and int(sizes.max()) > mp:
+            raise GppError(f"a fold of {int(sizes.max())} rows does not fit the {mp} x {mp} blocks of this call")
+        used = i[o[0]:o[-1]]
+        if used.shape[0] and (int(used.min()) < 0 or int(used.max()) >= N):
+            raise GppError(f"fold index out of range: values in [{int(used.min())}, {int(used.max())}] for {N} rows")
+        if used.shape[0] > 1:
+            inner = used[1:] > used[:-1]
+            inner[(o[1:-1] - o[0] - 1)[(o[1:-1] > o[0]) & (o[1:-1] < o[-1])]] = True  # (a fold's first entry follows another fold's last)
+            if not inner.all():
+                raise GppError("fold indices must be strictly ascending inside every fold")
+        cache[id(off)] = (weakref.ref(idx), weakref.ref(off), key, int(o[-1]))
+        return nfolds, int(o[-1])
+
+    @_on_own_device
+    def cv_blocks(self, Linv, idx, off, out):
+        """The upper triangles of P_FF = (Ky^-1)[F, F] for every fold of the CSR list, identity-padded to out's (nfolds, mp, mp)
+        blocks, from the rows of the inverse factor with its mirror (gpp_cv_blocks).  ``out``: a ``batched_buffer`` view."""
+        _need(Linv, torch.float64, "Linv"); _need(out, torch.float64, "B")
+        if Linv.dim() != 2 or Linv.shape[0] != Linv.shape[1]:
+            raise GppError("cv_blocks: Linv must be square")
+        if out.dim() != 3 or out.shape[1] != out.shape[2] or out.stride(2) != 1:
+            raise GppError("cv_blocks: B must be a (nfolds, mp, mp) batched matrix")
+        nfolds, _ = self._check_csr(idx, off, Linv.shape[0], out.shape[1])
+        if out.shape[0] != nfolds:
+            raise GppError(f"cv_blocks: B holds {out.shape[0]} blocks for {nfolds} folds")
+        self._stream()
+        check(self.lib.gpp_cv_blocks(self.h, Linv.data_ptr(), _ld(Linv), Linv.shape[0], idx.data_ptr(), off.data_ptr(), nfolds,
+                                     out.shape[1], out.data_ptr(), out.stride(1), out.stride(0)), "gpp_cv_blocks")
+        return out
+
+    @_on_own_device
+    def cv_rows(self, G, idx, off, Psq, S):
+        """S[off[f] + a, :] = sum_b G[f, a, b] Psq[idx[off[f] + b], :] for every fold of the CSR list (gpp_cv_rows).  G: (nfolds,
+        mp, mp) batched matrix whose padding is not read (no fold longer than mp); Psq: the full symmetric N x N square; S: at least
+        off[-1] rows of N."""
+        for t, n in ((G, "G"), (Psq, "Psq"), (S, "S")):
+            _need(t, torch.float64, n)
+        if G.dim() != 3 or G.shape[1] != G.shape[2] or G.stride(2) != 1 or G.stride(1) < G.shape[2] \
+                or (G.shape[0] > 1 and G.stride(0) < G.shape[1] * G.stride(1)):
+            raise GppError("cv_rows: G must be a (nfolds, mp, mp) batched matrix")
+        N = Psq.shape[0]
+        if Psq.dim() != 2 or S.dim() != 2 or Psq.shape[1] != N or S.shape[1] != N:
+            raise GppError("cv_rows: Psq must be N x N and S must have N columns")
+        nfolds, rows = self._check_csr(idx, off, N, G.shape[1])
+        if G.shape[0] != nfolds:
+            raise GppError(f"cv_rows: G holds {G.shape[0]} blocks for {nfolds} folds")
+        if S.shape[0] < rows:
+            raise GppError(f"cv_rows: S has {S.shape[0]} rows, the folds write up to row {rows}")
+        self._stream()
+        check(self.lib.gpp_cv_rows(self.h, G.data_ptr(), G.stride(1), G.stride(0), idx.data_ptr(), off.data_ptr(), nfolds,
+                                   Psq.data_ptr(), _ld(Psq), N, S.data_ptr(), _ld(S)), "gpp_cv_rows")
+        return S
+
+
 def get_context(device) -> GppContext:
     device = torch.device(device)
     if device.type != "cuda":

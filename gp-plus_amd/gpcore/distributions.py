@@ -185,6 +185,21 @@ class MultivariateNormal:
 
         return exact_loo(cov.U1, cov.spec, cov.tau, self.loc, value, cov.grp, cov.n_grad_dims)
 
+    def cv_log_prob(self, value: torch.Tensor, folds) -> torch.Tensor:
+        """Grouped cross-validation log pseudo-likelihood sum_F log p(value_F | value_-F) of a (noisy) lazy kernel covariance for
+        ``folds`` — an int k, one integer label per row, or a ``cv.FoldIndex`` (``linalg.exact_cv``: every fold from one
+        factorisation)."""
+        cov = self._covar
+        if not isinstance(cov, LazyKernelMatrix):
+            raise NotImplementedError("cv_log_prob needs the lazy kernel covariance of a training evaluation")
+        if not cov.is_square:
+            raise RuntimeError("cv_log_prob needs a square covariance")
+        if cov.tau is None:
+            raise RuntimeError("cv_log_prob of a noise-free kernel matrix: apply the likelihood first")
+        from ..linalg import exact_cv
+
+        return exact_cv(cov.U1, cov.spec, cov.tau, self.loc, value, folds, cov.grp, cov.n_grad_dims)
+
     # -- sampling --------------------------------------------------------------------------------
     def root_factor(self) -> torch.Tensor:
         """Upper Cholesky factor U of the covariance (U^T U = Sigma; an M x M view whose strict lower triangle is not part of

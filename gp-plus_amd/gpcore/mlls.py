@@ -2,6 +2,8 @@
     (log p(y | X) + sum of prior log-densities) / N
 and ``LeaveOneOutPseudoLikelihood`` (gpytorch.mlls.LeaveOneOutPseudoLikelihood; Rasmussen & Williams 5.4.2):
     (sum_i log p(y_i | X, y_-i) + sum of prior log-densities) / N
+and ``CrossValidationPseudoLikelihood``, its grouped (k-fold, leave-one-group-out) form (no gpytorch counterpart):
+    (sum_F log p(y_F | X, y_-F) + sum of prior log-densities) / N
 """
 import torch
 
@@ -50,6 +52,29 @@ class LeaveOneOutPseudoLikelihood(ExactMarginalLogLikelihood):
         num_data = function_dist.event_shape.numel()
         output = self.likelihood(function_dist, *params)
         res = output.loo_log_prob(target)
+        prior_sum = self._prior_sum(res.dtype)
+        if prior_sum is not None:
+            res = res + prior_sum
+        return res / num_data
+
+
+class CrossValidationPseudoLikelihood(ExactMarginalLogLikelihood):
+    """The grouped cross-validation log pseudo-likelihood as a training criterion, in the scaling of
+    :class:`LeaveOneOutPseudoLikelihood`: the sum over the folds of the held-out log-densities log p(y_F | X, y_-F) plus the prior
+    log-densities, divided by N (``MultivariateNormal.cv_log_prob``).  ``folds``: an int k (a seeded random partition), one integer
+    label per training row, or a ``cv.FoldIndex``; normalised once, here."""
+
+    def __init__(self, likelihood, model, folds):
+        super().__init__(likelihood, model)
+        from ..cv import FoldIndex
+        self.folds = FoldIndex.make(folds, int(model.train_targets.shape[0]))
+
+    def forward(self, function_dist: MultivariateNormal, target: torch.Tensor, *params):
+        if not isinstance(function_dist, MultivariateNormal):
+            raise RuntimeError("CrossValidationPseudoLikelihood can only operate on Gaussian random variables")
+        num_data = function_dist.event_shape.numel()
+        output = self.likelihood(function_dist, *params)
+        res = output.cv_log_prob(target, self.folds)
         prior_sum = self._prior_sum(res.dtype)
         if prior_sum is not None:
             res = res + prior_sum

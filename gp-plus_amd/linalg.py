@@ -13,6 +13,7 @@ gpytorch.utils.cholesky.psd_safe_cholesky [3P]: 1e-8 * 10^i, i = 0..2 (fp64), wa
 """
 from __future__ import annotations
 
+import math
 import threading
 from contextlib import contextmanager
 from dataclasses import dataclass
@@ -24,7 +25,8 @@ from .backend import KIND_RBF, UPLO_FULL, UPLO_UPPER, GppContext, get_context, r
 from .psd_safe import inputs_nan_probe, psd_safe
 from . import settings
 
-__all__ = ["KernelSpec", "exact_mll", "ExactMLLFunction", "exact_loo", "ExactLOOFunction", "loo_moments", "EvalWorkspace", "dense_kernel", "cross_kernel",
+__all__ = ["KernelSpec", "exact_mll", "ExactMLLFunction", "exact_loo", "ExactLOOFunction", "loo_moments", "exact_cv", "ExactCVFunction",
+           "cv_moments", "EvalWorkspace", "dense_kernel", "cross_kernel",
            "FactorCache", "factorize", "dense_log_prob", "predict_mean", "predict_var", "predictive_cov_upper",
            "train_post_cov_upper", "mvn_root", "mvn_draw"]
 
@@ -236,7 +238,7 @@ def _exact_forward(fn, ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slo
     gctx = get_context(U.device)  # raises GppError for anything but a GPU: there is no CPU path
     with torch.cuda.device(U.device):  # streams, events and the library's launches all refer to the model's GPU
         if not fn.capturable and torch.cuda.is_current_stream_capturing():
-            raise NotImplementedError("the leave-one-out objective is not available inside a graph capture")
+            raise NotImplementedError(f"{getattr(fn, 'what', 'the leave-one-out objective')} is not available inside a graph capture")
         dev = U.device
         N, D = U.shape
         Ud, wd, sd, td, grp, S, need_grad, need_U = _eval_operands(ctx, U, w, sf2, tau, mean, y, grp, dU)
@@ -386,6 +388,84 @@ def exact_loo(U: torch.Tensor, spec: KernelSpec, tau: torch.Tensor, mean: torch.
     return ExactLOOFunction.apply(U, spec.w, spec.sf2, tau, mean, y, grp, spec.kind, spec.d_split, int(n_grad_dims), slot)
 
 
+class _CVEvaluation:
+    """What ``_exact_forward`` asks of an objective (``capturable``, ``value_needs_alpha``, ``tail``, ``result``) for ONE evaluation
+    of the cross-validation objective: unlike the marginal likelihood and leave-one-out it carries an argument of its own, the folds."""
+
+    capturable, value_needs_alpha, what = False, True, "the cross-validation objective"
+
+    def __init__(self, folds):
+        self.folds, self.terms, self.infos = folds, None, None
+
+    def tail(self, gctx, ws, need_grad, ops, grads, kind, d_split):
+        from .cv import fold_gradient_factors, fold_solves
+        N, lv = ws.N, ws.loo_vectors()
+        with _stage("cv_folds"):  # one batched sequence per bucket: P_FF, its factor and inverse factor, z, a, diag P_FF^-1, the terms
+            a, _, self.terms, self.infos, kept = fold_solves(gctx, ws.Li, ws.alpha, self.folds, keep_factors=need_grad)
+        if not need_grad:
+            return
+        lv.a.copy_(a)
+        with _stage("cv_beta"):  # beta = Ky^-1 a by the two triangular products, as ExactLOOFunction
+            gctx.mll_reduce(ws.A, ws.Li, lv.a, lv.z, lv.out3)
+            gctx.alpha(ws.Li, lv.z, lv.beta)
+        with _stage("lauum"):
+            gctx.lauum(ws.Li, ws.Ki)
+        with _stage("sym_rowscale"):  # Psq: the full symmetric square of Ky^-1 into A (dead since trtri)
+            gctx.sym_rowscale(ws.Ki, torch.ones(N, dtype=torch.float64, device=ws.A.device), ws.A)
+        with _stage("cv_rows"):  # S = the row blocks G_F P[F, :] stacked bucket after bucket into Li (dead after the LAUUM)
+            for b, Li_b, z, na, out3 in kept:
+                G = fold_gradient_factors(b, Li_b, z, na, out3)
+                gctx.cv_rows(G, b.idx, b.off, ws.A, ws.Li[b.base:b.base + b.rows])
+                del G
+        del kept
+        with _stage("cv_gemm"):  # C(lower) = S^T S = sum_F P[:, F] (dcv/dP_FF) P[F, :] into A (Psq is dead)
+            gctx.gemm(1, 0, N, N, N, 1.0, ws.Li, ws.Li, 0.0, ws.A, c_tri=1)
+        with _stage("loo_grad_reduce"):
+            gctx.loo_grad_reduce(*ops, ws.alpha, lv.beta, ws.A, *grads, kind=kind, d_split=d_split)
+
+    def result(self, ws, need_grad):
+        from .cv import check_infos
+        check_infos(self.infos, self.folds)  # (no jitter retry on a fold block: a jittered P_FF has no meaning)
+        value = self.terms.sum() - 0.5 * ws.N * math.log(2.0 * math.pi)
+        return value, (ws.loo_vectors().beta.neg() if need_grad else None)  # dcv/dmean = -beta
+
+
+class ExactCVFunction(torch.autograd.Function):
+    """Grouped (k-fold) cross-validation log pseudo-likelihood from one factorisation (gp-plus_amd/cv.py, gpp.h gpp_cv_blocks):
+        cv = sum_F log p(y_F | y_-F) = sum_F [ -1/2 alpha_F' P_FF^-1 alpha_F + 1/2 log|P_FF| ] - (N / 2) log 2 pi,   P = Ky^-1
+    with the inputs, gradients and autograd contract of :class:`ExactLOOFunction` plus the folds (a ``cv.FoldIndex``).  With
+    a_F = -P_FF^-1 alpha_F = dcv/dalpha on F, dcv/dP_FF = (a_F a_F' + P_FF^-1) / 2 = G_F' G_F and beta = P a:
+        dcv = sum_ij W_ij dKy_ij,   W = -(alpha beta^T + beta alpha^T) / 2 - S^T S,   dcv/dmean = -beta,   dcv/dy = beta,
+    S the row blocks G_F P[F, :] stacked — leave-one-out's shape with a block-diagonal matrix in place of diag(b), so
+    gpp_loo_grad_reduce takes it unchanged.  Sequence: build + potrf, trtri, z, alpha, the per-bucket batched fold solves
+    (``cv.fold_solves``); with a gradient: beta, plain LAUUM into Ki, the full square Psq into A, G by element-wise torch ops on the
+    small batches, gpp_cv_rows into Li, the TN GEMM into A's lower triangle, gpp_loo_grad_reduce.  No fourth N x N buffer; the value
+    comes from the same kernels with and without a gradient.  Not capturable (the fold blocks' status is read on the host)."""
+
+    @staticmethod
+    def forward(ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slot, folds):
+        return _exact_forward(_CVEvaluation(folds), ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slot)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return _eval_backward(ctx, grad_out, *ctx.saved) + (None,) * 6
+
+
+def exact_cv(U: torch.Tensor, spec: KernelSpec, tau: torch.Tensor, mean: torch.Tensor, y: torch.Tensor, folds,
+             grp: Optional[torch.Tensor] = None, n_grad_dims: Optional[int] = None, slot: Optional[int] = None) -> torch.Tensor:
+    """Grouped cross-validation log pseudo-likelihood sum_F log p(y_F | y_-F) on the GPU for ``folds`` (an int k, one integer label
+    per row, or a ``cv.FoldIndex``); the autograd contract of :func:`exact_loo`."""
+    from .cv import FoldIndex
+    folds = FoldIndex.make(folds, U.shape[0])  # host work: its errors come before a device is touched
+    if slot is None:
+        slot = current_slot()
+    if n_grad_dims is None:
+        n_grad_dims = U.shape[1] if U.requires_grad else 0
+    if settings.sharded_evaluation.value() is not None:
+        raise NotImplementedError("the cross-validation objective is not available under settings.sharded_evaluation")
+    return ExactCVFunction.apply(U, spec.w, spec.sf2, tau, mean, y, grp, spec.kind, spec.d_split, int(n_grad_dims), slot, folds)
+
+
 # ---------------------------------------------------------------------------------------------------
 # dense evaluations (no autograd): .evaluate(), cross covariances, prediction
 # ---------------------------------------------------------------------------------------------------
@@ -479,6 +559,22 @@ def loo_moments(cache: FactorCache, y: torch.Tensor) -> Tuple[torch.Tensor, torc
         d, mu, s2 = (torch.empty(N, dtype=torch.float64, device=dev) for _ in range(3))
         cache.gctx.loo_scalars(cache.Linv, cache.alpha, _as_f64(y.reshape(-1), dev), d, mu=mu, s2=s2)
     return mu, s2
+
+
+@torch.no_grad()
+def cv_moments(cache: FactorCache, y: torch.Tensor, folds) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Held-out predictive mean and variance of every training target under the folds (an int k, labels or a ``cv.FoldIndex``) from a
+    factor cache: mu_F = y_F - P_FF^-1 alpha_F, s2_F = diag(P_FF^-1), in the original row order.  The per-bucket batched fold solves
+    of ``cv.fold_solves`` on the cached inverse factor: no LAUUM, no N x N scratch, O(N sum m_F^2)."""
+    from .cv import FoldIndex, check_infos, fold_solves
+    folds = FoldIndex.make(folds, cache.U.shape[0])
+    cache.refresh()
+    dev = cache.U.device
+    with torch.cuda.device(dev):
+        a, d, _, infos, _ = fold_solves(cache.gctx, cache.Linv, cache.alpha, folds)
+        check_infos(infos, folds)
+        mu = _as_f64(y.reshape(-1), dev) + a
+    return mu, d
 
 
 @torch.no_grad()

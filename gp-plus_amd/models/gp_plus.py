@@ -296,16 +296,19 @@ class GP_Plus(GPR):
     # ---- fit -----------------------------------------------------------------------------------------
     def fit(self, add_prior: bool = True, num_restarts: int = 64, theta0_list: Optional[List[np.ndarray]] = None,
             jac: bool = True, options: Dict = {}, n_jobs: int = -1, method='L-BFGS-B', constraint=False, bounds=False,
-            regularization_parameter: List[int] = [0, 0], optim_type='scipy', objective: str = "mll"):
+            regularization_parameter: List[int] = [0, 0], optim_type='scipy', objective: str = "mll", folds=None):
         """gp_plus.py:547-599.  On a GPU device the reference always ends in ``fit_model_torch`` (64 restarts for
         'adam_torch', otherwise a warning and 4 restarts) — reproduced here.  The CPU branches
         (scipy / continuation drivers) do not exist in this build: the exact-GP path only runs on the MI355X.
         ``objective``: "mll" (the exact marginal log-likelihood, as the reference) or "loo" (the leave-one-out log
         pseudo-likelihood).  Both take the same route: all restarts advance together, one batched evaluation per Adam step replayed
         as a HIP graph, while the problem is small enough (see below); otherwise, and under ``settings.batched_restarts(False)``,
-        the restarts run one after the other, the leave-one-out objective then with every evaluation eager."""
-        from ..optim.mll_torch import check_objective
-        check_objective(objective)
+        the restarts run one after the other, the leave-one-out objective then with every evaluation eager.
+        ``objective="cv"`` with ``folds=`` (an int k, one integer label per training row — ``cv.group_labels`` makes them from
+        columns of X — or a ``cv.FoldIndex``) maximises the grouped cross-validation log pseudo-likelihood: always the sequential,
+        eager route."""
+        from ..optim.mll_torch import check_objective_folds
+        folds = check_objective_folds(objective, folds, int(self.train_targets.shape[0]))
         print("## Learning the model's parameters has started ##")
         if self.tkwargs['device'].type != 'cuda':
             raise RuntimeError("this build evaluates the marginal likelihood only on an MI355X (device='cuda'); "
@@ -320,7 +323,10 @@ class GP_Plus(GPR):
         # iteration: same start points in the same RNG order, same per-run optimiser and early stop, same winner —
         # optim/mll_batched.py) while the problem is small enough for that to pay and for the B x 3 N^2 workspace to fit;
         # settings.batched_restarts(False) restores the sequential loop, 'adam_torch_batched' asks for the batched one.
-        if optim_type == 'adam_torch_batched' or self._restarts_fit_one_batch(restarts + 1):
+        if objective == "cv":
+            out = fit_model_torch(model=self, model_param_groups=None, lr_default=0.01, num_iter=100,
+                                  num_restarts=restarts, break_steps=50, objective=objective, folds=folds)
+        elif optim_type == 'adam_torch_batched' or self._restarts_fit_one_batch(restarts + 1):
             from ..optim import fit_model_torch_batched
             out = fit_model_torch_batched(self, lr_default=0.01, num_iter=100, num_restarts=restarts, break_steps=50,
                                           objective=objective)
@@ -382,6 +388,24 @@ class GP_Plus(GPR):
             cache = self._ensure_prediction_cache()
             mu, s2 = loo_moments(cache, self.train_targets)
             return self.y_min + self.y_std * mu, s2.sqrt() * torch.abs(self.y_std)
+
+    def cv_predict(self, folds, return_std=True, generator=None):
+        """Held-out predictions at the training points under grouped cross-validation: the mean (and std) of p(y_F | X, y_-F) at
+        every row of every fold F, in the units and conventions of ``loo_predict`` (training-target units, the held-out
+        observation's noise included).  ``folds``: an int k (a random partition drawn from the CPU ``generator``, or a fixed seed),
+        one integer label per training row (``cv.group_labels(X, columns)`` for leave-one-level-combination-out or
+        leave-one-source-out), or a ``cv.FoldIndex``.  From the cached factorisation: mu_F = y_F - P_FF^-1 alpha_F and
+        diag(P_FF^-1) with P = Ky^-1, every fold in one batched sequence per size bucket (gpp_cv_blocks); nothing is factored again."""
+        from ..cv import FoldIndex
+        from ..linalg import cv_moments
+
+        folds = FoldIndex.make(folds, int(self.train_targets.shape[0]), generator=generator)
+        self.eval()
+        with torch.no_grad():
+            cache = self._ensure_prediction_cache()
+            mu, s2 = cv_moments(cache, self.train_targets, folds)
+            mean = self.y_min + self.y_std * mu
+            return (mean, s2.sqrt() * torch.abs(self.y_std)) if return_std else mean
 
     def noise_value(self):
         return self.likelihood.noise_covar.noise.detach() * self.y_std ** 2

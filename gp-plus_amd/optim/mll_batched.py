@@ -26,7 +26,7 @@ from torch.func import functional_call
 from ..batched import batched_loo, batched_mll
 from ..gpcore.kernels import LazyKernelMatrix
 from ..gpcore.mlls import ExactMarginalLogLikelihood
-from .mll_torch import check_objective
+from .mll_torch import check_objective, check_objective_folds
 
 __all__ = ["BatchedObjective", "fit_model_torch_batched", "BATCHED_MAX_N"]
 
@@ -184,12 +184,17 @@ class _GraphedLossAndGrad:
 
 
 def fit_model_torch_batched(model, lr_default: float = 0.01, num_iter: int = 100, num_restarts: int = 0,
-                            break_steps: int = 50, verbose: bool = False, objective: str = "mll") -> Tuple[float, List[List[float]]]:
+                            break_steps: int = 50, verbose: bool = False, objective: str = "mll",
+                            folds=None) -> Tuple[float, List[List[float]]]:
     """Drop-in for ``fit_model_torch`` (same return value) that advances all restarts together.  ``objective="loo"`` maximises the
     leave-one-out log pseudo-likelihood (plus the priors) in the same way: batched, and replayed as a HIP graph."""
-    check_objective(objective)
-    B = num_restarts + 1
     N = int(model.train_targets.shape[0])
+    folds = check_objective_folds(objective, folds, N)
+    if objective == "cv":  # the cross-validation objective has no batched form: the sequential, eager driver
+        from .mll_torch import fit_model_torch
+        return fit_model_torch(model, None, lr_default, num_iter, num_restarts, break_steps, verbose=verbose, objective=objective,
+                               folds=folds)
+    B = num_restarts + 1
     if N > BATCHED_MAX_N:
         # gpp_potrf_batched factors each problem right-looking in leaf steps and rejects larger matrices; at these sizes
         # one evaluation fills the GPU by itself, so the sequential driver loses nothing

@@ -25,12 +25,18 @@ from scipy.optimize import Bounds, OptimizeResult, minimize
 from ..errors import NanError, NotPSDError
 
 
-def marginal_log_likelihood(model, add_prior: bool, regularization_parameter=[0, 0], objective: str = "mll"):
+def marginal_log_likelihood(model, add_prior: bool, regularization_parameter=[0, 0], objective: str = "mll", folds=None):
     """optim/mll_scipy.py:37-60 (exact log-marginal + priors, un-normalised).  ``objective="loo"``: the leave-one-out log
-    pseudo-likelihood in place of the log-marginal."""
+    pseudo-likelihood in place of the log-marginal; ``objective="cv"``: the grouped cross-validation one over ``folds``."""
+    from .mll_torch import check_objective_folds
+
+    folds = check_objective_folds(objective, folds, int(model.train_targets.shape[0]))
     output = model(*model.train_inputs)
     noisy = model.likelihood(output)
-    out = noisy.loo_log_prob(model.train_targets) if objective == "loo" else noisy.log_prob(model.train_targets)
+    if objective == "cv":
+        out = noisy.cv_log_prob(model.train_targets, folds)
+    else:
+        out = noisy.loo_log_prob(model.train_targets) if objective == "loo" else noisy.log_prob(model.train_targets)
     if add_prior:
         for _, module, prior, closure, _ in model.named_priors():
             out = out + prior.log_prob(closure(module)).sum().to(out)
@@ -42,11 +48,12 @@ def marginal_log_likelihood(model, add_prior: bool, regularization_parameter=[0,
 class MLLObjective:
     """optim/mll_scipy.py:63-127."""
 
-    def __init__(self, model, add_prior, regularization_parameter, objective: str = "mll"):
-        from .mll_torch import check_objective
+    def __init__(self, model, add_prior, regularization_parameter, objective: str = "mll", folds=None):
+        from .mll_torch import check_objective, check_objective_folds
 
         self.model, self.add_prior, self.regularization_parameter = model, add_prior, regularization_parameter
         self.objective = check_objective(objective)
+        self.folds = check_objective_folds(objective, folds, int(model.train_targets.shape[0]))  # normalised once per fit
         self.param_shapes = OrderedDict()
         for n, p in self.model.named_parameters():
             if p.requires_grad:
@@ -126,7 +133,7 @@ class MLLObjective:
         old.update(self.unpack_parameters(x))
         self.model.load_state_dict(old)
         self.model.zero_grad()
-        obj = -marginal_log_likelihood(self.model, self.add_prior, self.regularization_parameter, self.objective)
+        obj = -marginal_log_likelihood(self.model, self.add_prior, self.regularization_parameter, self.objective, self.folds)
         if return_grad:
             obj.backward()
             return obj.item(), self.pack_grads()
@@ -170,10 +177,11 @@ def _fit_model_from_state(likobj, theta0, jac, options, method='L-BFGS-B', const
 def fit_model_scipy(model, add_prior: bool = True, num_restarts: int = 1, theta0_list: Optional[List[np.ndarray]] = None,
                     jac: bool = True, options: Dict = {}, n_jobs: int = -1, method='L-BFGS-B', constraint=False,
                     bounds=False, regularization_parameter: List[int] = [0, 0],
-                    objective: str = "mll") -> Tuple[List[OptimizeResult], float]:
-    from .mll_torch import check_objective
+                    objective: str = "mll", folds=None) -> Tuple[List[OptimizeResult], float]:
+    from .mll_torch import check_objective_folds
 
-    check_objective(objective)  # "loo": the leave-one-out log pseudo-likelihood (+ priors), evaluated eagerly
+    # "loo" / "cv": the leave-one-out / grouped cross-validation log pseudo-likelihood (+ priors), evaluated eagerly
+    folds = check_objective_folds(objective, folds, int(model.train_targets.shape[0]))
     if method == 'L-BFGS-B':
         defaults = {'ftol': 1e-6, 'gtol': 1e-5, 'maxfun': 5000, 'maxiter': 2000}
     elif method == 'trust-constr':
@@ -194,7 +202,7 @@ def fit_model_scipy(model, add_prior: bool = True, num_restarts: int = 1, theta0
         defaults[key] = options[key]
 
     model.train()
-    likobj = MLLObjective(model, add_prior, regularization_parameter, objective)
+    likobj = MLLObjective(model, add_prior, regularization_parameter, objective, folds)
     if theta0_list is None:
         theta0_list = [likobj.pack_parameters()]
         if num_restarts > -1:

@@ -9,18 +9,34 @@ import torch
 from tqdm import tqdm
 
 from ..backend import INFO_PANEL_TIMEOUT
-from ..gpcore.mlls import ExactMarginalLogLikelihood, LeaveOneOutPseudoLikelihood
+from ..gpcore.mlls import CrossValidationPseudoLikelihood, ExactMarginalLogLikelihood, LeaveOneOutPseudoLikelihood
 
 #: what the fit drivers maximise (per datum, priors included): the exact marginal log-likelihood, or the leave-one-out log
 #: pseudo-likelihood (Rasmussen & Williams 5.4.2).  In THIS driver and in fit_model_scipy the latter is always the eager evaluation,
-#: no replayed graph; fit_model_torch_batched evaluates all restarts of either objective together and replays the step as a graph
-OBJECTIVES = ("mll", "loo")
+#: no replayed graph; fit_model_torch_batched evaluates all restarts of either objective together and replays the step as a graph.
+#: "cv" is the grouped cross-validation log pseudo-likelihood over the ``folds`` the caller gives (gp-plus_amd/cv.py): always the
+#: sequential, eager route (fit_model_torch_batched hands it to fit_model_torch)
+OBJECTIVES = ("mll", "loo", "cv")
 
 
 def check_objective(objective: str) -> str:
     if objective not in OBJECTIVES:
         raise ValueError(f"objective must be one of {OBJECTIVES} (got {objective!r})")
     return objective
+
+
+def check_objective_folds(objective: str, folds, n_points: int):
+    """``check_objective`` plus the pairing of ``objective`` and ``folds``: "cv" needs folds, no other objective takes them.  Returns
+    the folds normalised once for the whole fit (a ``cv.FoldIndex``; an int k becomes ONE seeded partition), or None.  Host work only."""
+    check_objective(objective)
+    if objective == "cv":
+        if folds is None:
+            raise ValueError('objective="cv" needs folds= (an int k, one integer label per training row, or a cv.FoldIndex)')
+        from ..cv import FoldIndex
+        return FoldIndex.make(folds, n_points)
+    if folds is not None:
+        raise ValueError(f'folds= belongs to objective="cv" (got objective={objective!r})')
+    return None
 
 
 def _plateaued(history: List[float], j: int, window: int) -> bool:
@@ -100,17 +116,22 @@ def _adam_run(model, mll, params, lr: float, num_iter: int, break_steps: int, ve
 
 
 def fit_model_torch(model, model_param_groups: Optional[List] = None, lr_default: float = 0.01, num_iter: int = 100,
-                    num_restarts: int = 0, break_steps: int = 50, verbose: bool = True, objective: str = "mll") -> float:
+                    num_restarts: int = 0, break_steps: int = 50, verbose: bool = True, objective: str = "mll", folds=None) -> float:
     """Optimize the log-posterior of a GP+ model with ``torch.optim.Adam`` (optim/mll_torch.py:56-141).
 
     ``objective="loo"`` maximises the leave-one-out log pseudo-likelihood (plus the priors) instead of the marginal likelihood;
-    every evaluation is then the eager one.
+    every evaluation is then the eager one.  ``objective="cv"`` with ``folds=`` (an int k, one integer label per training row, or a
+    ``cv.FoldIndex``) maximises the grouped cross-validation log pseudo-likelihood, eagerly as well.
 
     :returns: ``(f_inc, loss_hist_total)`` — best (negative, per-datum) log-posterior found and the loss histories.
     """
-    loo = check_objective(objective) == "loo"
+    folds = check_objective_folds(objective, folds, int(model.train_targets.shape[0]))
+    loo = objective != "mll"  # (neither pseudo-likelihood is captured)
     model.train()
-    mll = (LeaveOneOutPseudoLikelihood if loo else ExactMarginalLogLikelihood)(model.likelihood, model)
+    if objective == "cv":
+        mll = CrossValidationPseudoLikelihood(model.likelihood, model, folds)
+    else:
+        mll = (LeaveOneOutPseudoLikelihood if loo else ExactMarginalLogLikelihood)(model.likelihood, model)
     best_loss, best_state = math.inf, model.state_dict()
     histories = []
     # the evaluation as one replayed HIP graph at the examples' sizes (the reference's notebooks and BO loop call this function

@@ -538,6 +538,35 @@ int gpp_loo_grad_reduce_batched(gpp_handle_t h, const double* U, int64_t sU, int
                                 int64_t sv, const double* C, int64_t ldc, int64_t sC, int dU, double* g_w, double* g_sf2,
                                 double* g_tau, double* g_U, int batch);
 
+/*
+ * Grouped (k-fold, leave-one-group-out) cross-validation from ONE factorisation.  With P = Ky^-1, alpha = P (y - m) and a fold F (an
+ * index set of size m_F), p(y_F | y_-F) = N(y_F - P_FF^-1 alpha_F, P_FF^-1) and
+ *   cv = sum_F [ -0.5 alpha_F' P_FF^-1 alpha_F + 0.5 log|P_FF| ] - (N / 2) log 2 pi
+ * (folds of one point: the leave-one-out quantities above; one fold of everything: the marginal likelihood).  The reference has no
+ * counterpart (optim/mll_noise_continuation.py:54 names LOOCV only).  The folds of a call are a CSR list: idx (int32, off[nfolds]
+ * entries, every value in [0, N), ASCENDING inside a fold) and off (int32, nfolds + 1 entries, off[0] = 0 not required).  Both products
+ * run on v_mfma_f64_16x16x4_f64 in 64 x 64 tiles, one launch for the whole list; no atomics, no workspace; a fold's output does not
+ * depend on the other folds of the call and is bitwise repeatable.
+ *
+ * gpp_cv_blocks: for fold f the UPPER triangle of the mp x mp block at B + f*sB (m_f <= mp <= ldb, ldb and sB even):
+ *   B_f[a][b] = P_FF[a][b] = sum_{j >= max(i_a, i_b)} Linv[i_a][j] Linv[i_b][j]   for a <= b < m_f,  i_a = idx[off[f] + a]
+ *   B_f[a][b] = (a == b)                                                           for a <= b, m_f <= b < mp (identity padding: the
+ *               block factors to diag(chol P_FF, I), its log-determinant and solves are those of P_FF)
+ * Linv: the complete inverse factor with its mirror (row i from the diagonal on = column i of L^-1, as gpp_loo_scalars reads it);
+ * row i is read at columns j >= i only, and a tile's chunks start at its smallest gathered index.  The strict lower triangle of a
+ * block is never written.
+ *
+ * gpp_cv_rows: S[off[f] + a][c] = sum_{b < m_f} G_f[a][b] Psq[idx[off[f] + b]][c]   for a < m_f, c < N
+ * G_f = G + f*sG: m_f x m_f, row-major with rows of ldg doubles (m_f <= ldg, and m_f * ldg <= sG when nfolds > 1; ldg, sG even); its
+ * padding (rows and columns from m_f on) is never read.  Psq: the full symmetric N x N square (gpp_sym_rowscale with s = 1 gives it
+ * exactly from the LAUUM's lower triangle).  With G_f'G_f = dcv/dP_FF the rows of S stack G_F P[F, :], and the lower triangle of
+ * S'S (gpp_gemm, transA = 1, c_tri = 1) is the matrix C of gpp_loo_grad_reduce.  Columns [N, lds) of S are never written.
+ */
+int gpp_cv_blocks(gpp_handle_t h, const double* Linv, int64_t ldi, int64_t N, const int32_t* idx, const int32_t* off, int nfolds,
+                  int mp, double* B, int64_t ldb, int64_t sB);
+int gpp_cv_rows(gpp_handle_t h, const double* G, int64_t ldg, int64_t sG, const int32_t* idx, const int32_t* off, int nfolds,
+                const double* Psq, int64_t ldp, int64_t N, double* S, int64_t lds);
+
 #ifdef __cplusplus
 }
 #endif
