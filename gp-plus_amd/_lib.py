@@ -131,6 +131,8 @@ _SIGNATURES = {
     "gpp_cv_blocks": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int64]),
     "gpp_cv_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int64, c_void_p,
                             c_int64]),
+    "gpp_chol_append": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

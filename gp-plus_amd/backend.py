@@ -26,6 +26,7 @@ OPT_GEMM_TILE = 6  # tile of gemm / gemm_batched: 0 by grid size, 1 = 32x32, 2 =
 OP_MLL_EVAL, OP_PREDICT, OP_PREDICT_GRAD = 0, 1, 2
 OP_APPLY = 3  # gpp_kernel_apply / gpp_rff_apply: N carries the contracted length
 OP_APPLY_GRAD = 4  # gpp_kernel_apply_grad / gpp_rff_apply_grad: N carries the contracted length
+OP_APPEND = 5  # gpp_chol_append: N cached points, M carries the appended count q
 #: longest contraction gpp_kernel_apply / gpp_rff_apply run without scratch (gpp_apply.hip AP_SPLIT)
 APPLY_SPLIT = 2048
 NOT_SUPPORTED = 2001  # GPP_NOT_SUPPORTED: gpp_lauum_grad does not take these arguments, nothing was enqueued
@@ -877,6 +878,44 @@ class GppContext:
         check(self.lib.gpp_cv_rows(self.h, G.data_ptr(), G.stride(1), G.stride(0), idx.data_ptr(), off.data_ptr(), nfolds,
                                    Psq.data_ptr(), _ld(Psq), N, S.data_ptr(), _ld(S)), "gpp_cv_rows")
         return S
+
+    # -- bordering a cached factorisation --------------------------------------------------------------------------------------
+    @_on_own_device
+    def chol_append(self, A, Linv, N, q, k, C, rq, z, alpha, info):
+        """Border the N x N factorisation held in the leading windows of the buffers ``A`` (upper factor) and ``Linv`` (inverse
+        factor with its mirror) with q new points (gpp_chol_append): k the N x q cross block, C the q x q corner (upper), rq the new
+        residuals; z and alpha hold N entries and have room for N + q.  Everything is checked before any launch."""
+        N, q = int(N), int(q)
+        if N < 1 or q < 1:
+            raise GppError(f"chol_append needs N >= 1 cached and q >= 1 new points (got {N}, {q})")
+        for t, n in ((A, "A"), (Linv, "Linv"), (k, "k"), (C, "C"), (rq, "rq"), (z, "z"), (alpha, "alpha")):
+            _need(t, torch.float64, n)
+        _need(info, torch.int32, "info")
+        for t, n, rows, cols in ((A, "A", N + q, N + q), (Linv, "Linv", N + q, N + q), (k, "k", N, q), (C, "C", q, q)):
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise GppError(f"{n} must be 2-D with unit column stride")
+            if (n in ("A", "Linv") and (t.shape[0] < rows or t.shape[1] < cols)) or (n in ("k", "C") and tuple(t.shape) != (rows, cols)):
+                raise GppError(f"{n} is {tuple(t.shape)}: chol_append with N = {N}, q = {q} needs "
+                               f"{'at least ' if n in ('A', 'Linv') else ''}{rows} x {cols}")
+            ld = _ld(t)
+            if ld & 1 or ld < cols:
+                raise GppError(f"{n}: the leading dimension ({ld}) must be even and at least {cols}")
+            if t.data_ptr() & 15:
+                raise GppError(f"{n} must be 16-byte aligned")
+        if rq.dim() != 1 or rq.numel() != q or not rq.is_contiguous():
+            raise GppError(f"rq must be a contiguous vector of {q} doubles")
+        for t, n in ((z, "z"), (alpha, "alpha")):
+            if t.dim() != 1 or t.numel() < N + q or not t.is_contiguous():
+                raise GppError(f"{n} must be a contiguous vector with room for {N + q} doubles (got {t.numel()})")
+        if info.numel() < 1:
+            raise GppError("info must hold one int32")
+        self.ensure_workspace(OP_APPEND, N, q, 0, 0)
+        self._stream()
+        status = self.lib.gpp_chol_append(self.h, A.data_ptr(), _ld(A), Linv.data_ptr(), _ld(Linv), N, q, k.data_ptr(), _ld(k),
+                                          C.data_ptr(), _ld(C), rq.data_ptr(), z.data_ptr(), alpha.data_ptr(), info.data_ptr())
+        if status == NO_WORKSPACE:
+            raise GppError("gpp_chol_append: the handle's scratch workspace is missing or too small")
+        check(status, "gpp_chol_append")
 
 
 def get_context(device) -> GppContext:

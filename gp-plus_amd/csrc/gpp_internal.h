@@ -60,6 +60,28 @@ struct gpp_handle_s {
   hipStream_t comm_stream;
   hipEvent_t comm_event;
 };
+// The handle's record of the diagonal blocks the last gpp_potrf_ws inverted (inv_N, inv_nblocks, inv_o, inv_n), as one value: an
+// entry point that factors a matrix of its own in between (gpp_chol_append's Schur complement) saves it and puts it back, so that
+// the caller's next gpp_trtri still finds what the caller's own factorisation left.  A new field of that record belongs in here.
+struct GppInvBlocks {
+  int64_t N;
+  int nblocks;
+  decltype(gpp_handle_s::inv_o) o;
+  decltype(gpp_handle_s::inv_n) n;
+};
+inline GppInvBlocks gpp_inv_blocks_save(const gpp_handle_s* h) {
+  GppInvBlocks k;
+  k.N = h->inv_N;
+  k.nblocks = h->inv_nblocks;
+  static_assert(sizeof(k.o) == sizeof(h->inv_o) && sizeof(k.n) == sizeof(h->inv_n), "one record");
+  for (size_t i = 0; i < sizeof(k.o) / sizeof(k.o[0]); ++i) { k.o[i] = h->inv_o[i]; k.n[i] = h->inv_n[i]; }
+  return k;
+}
+inline void gpp_inv_blocks_restore(gpp_handle_s* h, const GppInvBlocks& k) {
+  h->inv_N = k.N;
+  h->inv_nblocks = k.nblocks;
+  for (size_t i = 0; i < sizeof(k.o) / sizeof(k.o[0]); ++i) { h->inv_o[i] = k.o[i]; h->inv_n[i] = k.n[i]; }
+}
 extern "C" void gpp_shard_release_comm(gpp_handle_s* h);
 
 // Every environment variable the library reads (INTEGRATION.md has the table), parsed ONCE per process by gpp_env() (gpp_api.hip) on
@@ -352,6 +374,9 @@ hipError_t gpp_launch_kernel_apply_grad(hipStream_t s, const double* Ua, int64_t
 hipError_t gpp_launch_rff_apply_grad(hipStream_t s, const double* Ua, int64_t M, int D, const double* Omega, const double* phase,
                                      int64_t F, const double* sf2, const double* Theta, int64_t ldt, int S, const double* Gbar,
                                      int64_t ldg, double beta, double* g_Ua, int64_t ldu, void* ws, size_t ws_bytes);
+
+// ---- bordering a cached factorisation (gpp_append.hip) ------------------------------------------
+size_t gpp_append_ws_bytes(int64_t N, int64_t q);  // scratch of gpp_chol_append
 
 // ---- reductions (gpp_reduce.hip) --------------------------------------------------------------
 // batch > 1 (all reductions): matrices at + b*sT, vectors at + b*sv (sv even, >= N), out3 at + 3*b

@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import math
 import threading
-from contextlib import contextmanager
+from contextlib import contextmanager, nullcontext
 from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
 
@@ -27,7 +27,7 @@ from . import settings
 
 __all__ = ["KernelSpec", "exact_mll", "ExactMLLFunction", "exact_loo", "ExactLOOFunction", "loo_moments", "exact_cv", "ExactCVFunction",
            "cv_moments", "EvalWorkspace", "dense_kernel", "cross_kernel",
-           "FactorCache", "factorize", "dense_log_prob", "predict_mean", "predict_var", "predictive_cov_upper",
+           "FactorCache", "factorize", "append_to_cache", "dense_log_prob", "predict_mean", "predict_var", "predictive_cov_upper",
            "train_post_cov_upper", "mvn_root", "mvn_draw"]
 
 
@@ -506,6 +506,9 @@ class FactorCache:
         # them.  ``stale()`` tells the owner to factor again instead of predicting from someone else's matrices.
         self._ws, self._epoch = ws, (ws.epoch if ws is not None else 0)
         self._refactor = refactor  # (tau, grp, r = y - m): what ``refresh`` needs besides U and spec (O(N) copies)
+        # ``append_to_cache``: the pair of matrices this cache's L / Linv are leading windows of when it owns them (never stale), and
+        # how it was made: None (factorised), "in_place", "copy" or "refactor"
+        self._own, self.route = None, None
 
     def stale(self) -> bool:
         return self._ws is not None and self._ws.epoch != self._epoch
@@ -546,6 +549,118 @@ def _factorize(U, spec: KernelSpec, tau, grp, mean, y) -> FactorCache:
     gctx.alpha(ws.Li, ws.z, ws.alpha)
     return FactorCache(gctx, ws.A, ws.Li, ws.alpha.clone(), Ud, KernelSpec(wd, sd.reshape(()), spec.kind, spec.d_split), jit, ws,
                        z=ws.z.clone(), refactor=(td.clone(), None if grp is None else grp.clone(), ws.r.clone()))
+
+
+#: ``append_to_cache`` borders the factor for q <= min(N, APPEND_MAX_Q) new rows and factors all N + q rows from scratch above.
+#: 2048 is the largest q the append was MEASURED at (tools/bench_condition.py, N = 20 000: 50.9 ms in place / 52.9 by copy against
+#: 117.9 for the factorisation of 22 048 rows; the margin shrinks with q: 8.3x at 256, 2.3x at 2048): nothing above it is claimed.
+APPEND_MAX_Q = 2048
+
+
+class _OwnedFactors:
+    """The two square matrices a conditioned cache owns: capacity x capacity buffers whose leading ``filled`` x ``filled`` windows hold
+    the factor and the inverse factor.  Several caches may hold windows of one pair (a chain of in-place appends): a cache may
+    append in place only while its own extent is the filled extent, i.e. while nobody has appended behind it."""
+
+    def __init__(self, capacity: int, device):
+        self.capacity, self.filled = capacity, 0
+        self.A = square_buffer(capacity, device)
+        self.Linv = square_buffer(capacity, device)
+
+
+def _owned_copy(src: FactorCache, n: int, capacity: int) -> _OwnedFactors:
+    own = _OwnedFactors(capacity, src.U.device)
+    own.A[:n, :n].copy_(src.L[:n, :n])
+    own.Linv[:n, :n].copy_(src.Linv[:n, :n])
+    own.filled = n
+    return own
+
+
+def _owned_cache(gctx, own, n, alpha, U, spec, jitter, z, refactor, route) -> FactorCache:
+    out = FactorCache(gctx, own.A[:n, :n], own.Linv[:n, :n], alpha, U, spec, jitter, ws=None, z=z, refactor=refactor)
+    out._own, out.route = own, route
+    return out
+
+
+@torch.no_grad()
+def append_to_cache(cache: FactorCache, Uq, tau, grp_q, mean_q, y_q, reserve: int = 256) -> FactorCache:
+    """A new ``FactorCache`` of the N cached rows plus the q rows with features ``Uq``, noise groups ``grp_q`` (into ``tau``), prior
+    means ``mean_q`` and targets ``y_q``, in O(N^2 q) by bordering the cached factor (gpp_chol_append) instead of O((N + q)^3).
+    The result owns its matrices (capacity N + q + reserve; never stale, ``refresh`` does nothing); ``cache`` stays valid and
+    bitwise unchanged.  ``route`` on the result tells what was done:
+      "in_place"  ``cache`` owns its matrices, nobody has appended behind it and the capacity suffices: the new rows and columns
+                  go into the same pair (the leading windows are not touched, so ``cache`` and its other holders go on reading them);
+      "copy"      otherwise — the first append to a cache of the shared prediction workspace (refreshed first), a second child
+                  of one parent, a full pair: the windows are copied into a new pair;
+      "refactor"  the Schur complement was not positive definite, or q > min(N, APPEND_MAX_Q = 2048, the largest measured q): all N + q rows are factorised
+                  from scratch under the jitter-retry policy of ``factorize``, and the factor is copied into an owned pair."""
+    if settings.sharded_evaluation.value() is not None:
+        raise NotImplementedError("appending to a factor cache is not available under settings.sharded_evaluation")
+    dev = cache.U.device
+    gctx = cache.gctx
+    on_gpu = dev.type == "cuda"  # (anything else only under a stand-in context: the library itself has no CPU path)
+    with torch.cuda.device(dev) if on_gpu else nullcontext():
+        if on_gpu and torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("appending to a factor cache is not available inside a graph capture")
+        n, reserve = cache.U.shape[0], max(int(reserve), 0)
+        Uq = _as_f64(Uq.detach(), dev)
+        q = Uq.shape[0]
+        if q < 1 or Uq.dim() != 2 or Uq.shape[1] != cache.U.shape[1]:
+            raise ValueError(f"the new rows must be q >= 1 rows of {cache.U.shape[1]} features (got {tuple(Uq.shape)})")
+        tau0, grp0, r0 = cache._refactor
+        # One vector of noise levels serves the old and the new rows.  The two may differ in length by the zero-noise group that
+        # Multifidelity_noise appends for rows of an unlisted source (present on one side only): the longer one is used, and the
+        # levels both sides know must be the same numbers — the cached factor was built from the cache's.
+        tau = _as_f64(tau.detach().reshape(-1), dev)
+        both = min(tau.numel(), tau0.numel())
+        if not torch.equal(tau[:both], tau0[:both]):
+            raise ValueError("the noise levels of the new rows differ from those the cache was factorised with "
+                             "(parameters changed since? factorise again instead of appending)")
+        if tau.numel() < tau0.numel():
+            tau = tau0
+        if (grp0 is None) != (grp_q is None):
+            raise ValueError("the new rows must carry noise groups exactly when the cached rows do")
+        if grp_q is not None:
+            grp_q = grp_q.to(device=dev, dtype=torch.int32).reshape(-1)
+            if grp_q.numel() != q:
+                raise ValueError(f"noise-group index has {grp_q.numel()} entries for {q} new rows")
+        r_q = _as_f64(y_q.detach().reshape(-1), dev) - _as_f64(mean_q.detach().reshape(-1), dev)
+        if r_q.numel() != q:
+            raise ValueError(f"{r_q.numel()} targets / means for {q} new rows")
+        U2 = torch.cat([cache.U, Uq])
+        refactor = (tau.clone(), None if grp0 is None else torch.cat([grp0, grp_q]), torch.cat([r0, r_q]))
+        spec = cache.spec
+
+        def from_scratch():
+            fresh = _factorize(U2, spec, refactor[0], refactor[1], torch.zeros_like(refactor[2]), refactor[2])
+            own = _owned_copy(fresh, n + q, n + q + reserve)
+            return _owned_cache(gctx, own, n + q, fresh.alpha, U2, fresh.spec, fresh.jitter, fresh.z, refactor, "refactor")
+
+        if q > min(n, APPEND_MAX_Q):
+            return from_scratch()
+        cache.refresh()  # (a cache of the shared workspace that another model has factored into since)
+        own = cache._own
+        if own is not None and own.filled == n and n + q <= own.capacity:
+            route = "in_place"
+        else:
+            own, route = _owned_copy(cache, n, n + q + reserve), "copy"
+        with _stage("append_operands"):
+            k = gctx.cross_kernel(cache.U, Uq, spec.w, spec.sf2.reshape(1), rows_buffer(n, q, dev), kind=spec.kind,
+                                  d_split=spec.d_split)  # N x q
+            C = square_buffer(q, dev)
+            gctx.kernel_build(Uq, spec.w, spec.sf2.reshape(1), tau, grp_q, C, jitter=cache.jitter, kind=spec.kind,
+                              d_split=spec.d_split, uplo=UPLO_UPPER)
+        z = torch.empty(n + q, dtype=torch.float64, device=dev)
+        alpha = torch.empty(n + q, dtype=torch.float64, device=dev)
+        z[:n].copy_(cache.z)
+        alpha[:n].copy_(cache.alpha)
+        info = torch.zeros(1, dtype=torch.int32, device=dev)
+        with _stage("chol_append"):
+            gctx.chol_append(own.A, own.Linv, n, q, k, C, r_q, z, alpha, info)
+        if int(info.item()) != 0:  # (the windows are untouched and ``filled`` stays: the pair serves the next attempt)
+            return from_scratch()
+        own.filled = n + q
+        return _owned_cache(gctx, own, n + q, alpha, U2, spec, cache.jitter, z, refactor, route)
 
 
 @torch.no_grad()

@@ -30,6 +30,7 @@ from ..optim import fit_model_torch
 from ..preprocessing import setlevels
 from ..priors import MollifiedUniformPrior
 from ..utils import data_type_check, set_seed  # noqa: F401
+from ..likelihoods_noise.multifidelity import Multifidelity_likelihood
 from .gpregression import GPR
 
 _QUANT_CLASSES = ['Rough_RBF', 'RBFKernel', 'Matern32Kernel', 'Matern12Kernel', 'Matern52Kernel']  # gp_plus.py:150
@@ -406,6 +407,38 @@ class GP_Plus(GPR):
             mu, s2 = cv_moments(cache, self.train_targets, folds)
             mean = self.y_min + self.y_std * mu
             return (mean, s2.sqrt() * torch.abs(self.y_std)) if return_std else mean
+
+    def _check_new_rows(self, X):
+        """``condition_on``: every categorical level and — where sources carry a mean or a noise of their own — every source of the
+        new rows must occur in the training data (the level lookup renumbers the levels of [training; new] rows jointly: an unseen
+        one would shift the training rows' own)."""
+        cat = [int(c) for c in self.qual_dict_list.tolist()]
+        cols = list(cat)
+        # (not hasattr(likelihood, 'fidel_indices'): GPR.predict leaves that attribute on a single-noise likelihood too)
+        if (self.m_gp.startswith('multi') or isinstance(self.likelihood, Multifidelity_likelihood)) and X.shape[1] - 1 not in cols:
+            cols.append(X.shape[1] - 1)
+        if not cols:
+            return
+        tr = self.train_inputs[0]
+        seen = getattr(self, '_seen_levels', None)  # (the training rows' values per column, read from the device once)
+        if seen is None or seen[0] is not tr or seen[1] != tr._version:
+            host = tr.detach().cpu()
+            seen = (tr, tr._version, {c: set(host[:, c].tolist()) for c in cols})
+            self._seen_levels = seen
+        Xh = X.detach().cpu()
+        for c in cols:
+            new = set(Xh[:, c].tolist()) - seen[2][c]
+            if new:
+                what = "categorical level" if c in cat else "source"
+                raise ValueError(f"condition_on: column {c} holds a {what} the model has not seen: {sorted(new)}")
+
+    def _after_copy(self, child):
+        import weakref
+
+        for enc in child.A_matrix:  # (a deep copy keeps a weak reference as it is: the encoders would read THIS model's weights)
+            object.__setattr__(enc, '_owner', weakref.ref(child))
+        child._cat_cache = {}
+        child.__dict__.pop('_seen_levels', None)
 
     def noise_value(self):
         return self.likelihood.noise_covar.noise.detach() * self.y_std ** 2

@@ -104,6 +104,94 @@ class GPR(ExactGP):
     def fantasize(self, X, sampler, observation_noise=True, **kwargs):
         raise NotImplementedError("botorch fantasize glue (models/gpregression.py:177-221) is out of scope of this build")
 
+    def _check_new_rows(self, X: torch.Tensor) -> None:
+        """Hook of ``condition_on``: raise ``ValueError`` for rows the model cannot take (GP_Plus: unseen levels or sources)."""
+
+    def _after_copy(self, child) -> None:
+        """Hook of ``condition_on``: mend whatever a deep copy of the model leaves pointing at the original."""
+
+    def condition_on(self, X, y, reserve: int = 256):
+        """A NEW model, in eval mode, that has the q observations (X, y) beside this model's training data, made by bordering
+        the cached factorisation in O(N^2 q) (``linalg.append_to_cache``, gpp_chol_append) instead of factorising N + q rows in
+        O((N + q)^3).  No reference counterpart: the reference's BO loop builds and refits a new model at every iteration
+        (bayesian_optimizations/BO_GP_plus.py); its ``fantasize`` is botorch glue and stays out of scope.
+
+        The receiver's data, parameters and cache are not modified (it is put in eval mode, as by ``predict``; without a cache it
+        is factorised first, O(N^3) once).  The hyperparameters are COPIED, neither shared nor refitted: fitting either model
+        later leaves the other alone.  The new targets are scaled with THIS model's ``y_min`` / ``y_std`` — the hyperparameters
+        were fitted in that scaling — and both buffers are kept; a model constructed on all N + q rows would rescale by the joint
+        range, so its ``y_scaled`` (and, after a fit, its parameters) differ from the conditioned model's.  The new rows go
+        through the model's own ``forward`` and likelihood as the training rows do: latent map, per-source means, per-source
+        noise of the rows' own source column.  ``reserve``: rows of spare capacity in the new model's matrices; appends within
+        it run in place (``prediction_strategy.route`` is "in_place", "copy" or "refactor").  ``train()`` on the new model drops
+        the cache like on any model, and ``fit()`` then trains on N + q points.
+
+        ``ValueError`` before any kernel runs: wrong column count, length mismatch, NaN / inf, q = 0, a categorical level or a
+        source the model has not seen.  ``NotImplementedError`` under ``settings.sharded_evaluation`` or a graph capture."""
+        import copy
+
+        from .. import settings as gpp_settings
+        from ..backend import get_context
+        from ..gpcore.module import Module
+        from ..linalg import append_to_cache
+        from ..utils import data_type_check
+
+        X, y = data_type_check(X), data_type_check(y)
+        train_x = self.train_inputs[0]
+        if X.dim() != 2 or X.shape[1] != train_x.shape[1]:
+            raise ValueError(f"condition_on: X must be (q, {train_x.shape[1]}) like the training inputs (got {tuple(X.shape)})")
+        y = y.reshape(-1)
+        if y.shape[0] != X.shape[0]:
+            raise ValueError(f"condition_on: {X.shape[0]} rows of X for {y.shape[0]} targets")
+        if X.shape[0] == 0:
+            raise ValueError("condition_on: no observation given (q = 0)")
+        if not (bool(torch.isfinite(X).all()) and bool(torch.isfinite(y).all())):
+            raise ValueError("condition_on: X and y must be finite (NaN or inf found)")
+        self._check_new_rows(X)
+        if gpp_settings.sharded_evaluation.value() is not None:
+            raise NotImplementedError("condition_on is not available under settings.sharded_evaluation")
+        get_context(train_x.device)  # (raises for anything but a GPU: there is no CPU path)
+
+        Xq = X.to(train_x)
+        yq = (y.to(self.train_targets) - self.y_min) / self.y_std
+        self.eval()
+        with torch.no_grad():
+            cache = self._ensure_prediction_cache()
+            out_q = Module.__call__(self, Xq)
+            cov_q = out_q.lazy_covariance_matrix
+            lik = self.likelihood
+            swap = hasattr(lik, "fidel_indices")
+            if swap:  # the noise groups of the new rows' own source column, as _ensure_prediction_cache does for the training rows
+                saved, lik.fidel_indices = lik.fidel_indices, Xq[:, -1]
+            try:
+                noisy = lik(out_q).lazy_covariance_matrix
+            finally:
+                if swap:
+                    lik.fidel_indices = saved
+            new_cache = append_to_cache(cache, cov_q.U1, noisy.tau, noisy.grp, out_q.mean, yq, reserve)
+
+            held, self.prediction_strategy = self.prediction_strategy, None  # (the N x N factors are not part of the copy)
+            # (predict_with_grad leaves ``fidel_indices`` — a slice of its differentiable input — on the model and the likelihood:
+            #  such non-leaf attributes are copied detached)
+            memo = {id(v): v.detach().clone() for mod in self.modules() for v in vars(mod).values()
+                    if torch.is_tensor(v) and not v.is_leaf}
+            try:
+                child = copy.deepcopy(self, memo)
+            finally:
+                self.prediction_strategy = held
+            self._after_copy(child)
+            child.train_inputs = (torch.cat([train_x, Xq]),)
+            targets = torch.cat([self.train_targets, yq])
+            child.train_targets = targets
+            child.y_scaled = targets
+            if hasattr(child.likelihood, "fidel_indices"):
+                child.likelihood.fidel_indices = child.train_inputs[0][:, -1]
+            if hasattr(child, "count"):
+                child.count = targets.shape[0]
+            child.eval()
+            child.prediction_strategy = new_cache
+        return child
+
     def reset_parameters(self) -> None:
         """Reset parameters by sampling from their priors (models/gpregression.py:168-174)."""
         # The reference builds its priors from Python numbers (torch's default dtype, float32) and never casts them on its

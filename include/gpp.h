@@ -53,6 +53,7 @@ typedef struct gpp_handle_s* gpp_handle_t;
                                M rows, S columns; 0 extra bytes up to a contracted length of 2048 */
 #define GPP_OP_APPLY_GRAD 4 /* gpp_kernel_apply_grad / gpp_rff_apply_grad: N = the contracted length, M rows, D features: pieces * M * D
                                doubles above a contracted length of 2048, 0 extra bytes up to it */
+#define GPP_OP_APPEND 5     /* gpp_chol_append: N cached points, M = q appended points (D and S are not read) */
 
 const char* gpp_version(void);
 
@@ -566,6 +567,28 @@ int gpp_cv_blocks(gpp_handle_t h, const double* Linv, int64_t ldi, int64_t N, co
                   int mp, double* B, int64_t ldb, int64_t sB);
 int gpp_cv_rows(gpp_handle_t h, const double* G, int64_t ldg, int64_t sG, const int32_t* idx, const int32_t* off, int nfolds,
                 const double* Psq, int64_t ldp, int64_t N, double* S, int64_t lds);
+
+/*
+ * Border a cached factorisation with q new points in O(N^2 q): no refactorisation (the reference refits, and so refactorises, at every
+ * step of bayesian_optimizations/BO_GP_plus.py).  A (the upper factor U = L^T) and Linv (L^-1, lower, with its mirror) hold an N x N
+ * window as gpp_potrf + gpp_trtri leave it, inside buffers of at least N + q rows with ld, ldi >= N + q (even; 16-byte aligned).
+ *   k:  the cross block K(X, Xq), N x q row-major (ldk >= q, even; 16-byte aligned)
+ *   C:  the corner K(Xq, Xq) + noise + jitter, q x q, UPPER triangle read (ldc >= q, even; 16-byte aligned); not modified
+ *   rq: the q new residuals y_q - m(Xq);   z = Linv r and alpha = Linv^T z: N entries on entry, room for N + q
+ * With V = (Linv k)^T, S = C - V V^T = Ls Ls^T, W = -Ls^-1 (V Linv), zq = Ls^-1 (rq - V z), on success:
+ *   A[0..N, N..N+q) = V^T,  A[N.., N..) upper = Ls^T                       (the strict lower triangle of the corner is not written)
+ *   Linv[N.., 0..N) = W,  Linv[0..N, N..) = W^T (mirror),  Linv[N.., N..) = Ls^-1 with its mirror
+ *   z[N..) = zq,   alpha[0..N) += W^T zq,   alpha[N..) = Ls^-T zq
+ * *info_dev is what gpp_potrf reports for S (0, or k > 0: leading minor k of the Schur complement is not positive definite); then
+ * the new rows and columns, z[N..) and alpha[N..) are unspecified and alpha[0..N) is left as it was, on both routes.  The N x N
+ * windows are never written, whatever happens, and nothing outside the (N + q) x (N + q) extents is read or written.  q <= 16
+ * runs dedicated kernels that read the N x N buffer of Linv once
+ * (the lower triangle for V, the mirror for V Linv); q > 16 composes gpp_gemm, gpp_potrf and gpp_trtri.  Scratch: the handle
+ * workspace, gpp_workspace_bytes(h, GPP_OP_APPEND, N, q, 0, 0) bytes; GPP_NO_WORKSPACE with nothing enqueued when it is missing.
+ * Plain launches on the handle's stream, no float atomics, sums in an order fixed by (N, q): two calls agree bit for bit.
+ */
+int gpp_chol_append(gpp_handle_t h, double* A, int64_t ld, double* Linv, int64_t ldi, int64_t N, int64_t q, const double* k,
+                    int64_t ldk, const double* C, int64_t ldc, const double* rq, double* z, double* alpha, int32_t* info_dev);
 
 #ifdef __cplusplus
 }
