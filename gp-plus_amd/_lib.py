@@ -133,6 +133,8 @@ _SIGNATURES = {
                             c_int64]),
     "gpp_chol_append": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gpp_post_cross_sq": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                  c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

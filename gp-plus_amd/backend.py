@@ -27,6 +27,7 @@ OP_MLL_EVAL, OP_PREDICT, OP_PREDICT_GRAD = 0, 1, 2
 OP_APPLY = 3  # gpp_kernel_apply / gpp_rff_apply: N carries the contracted length
 OP_APPLY_GRAD = 4  # gpp_kernel_apply_grad / gpp_rff_apply_grad: N carries the contracted length
 OP_APPEND = 5  # gpp_chol_append: N cached points, M carries the appended count q
+OP_POST_CROSS = 6  # gpp_post_cross_sq: N carries the reference count M_r, M the candidate count M_c
 #: longest contraction gpp_kernel_apply / gpp_rff_apply run without scratch (gpp_apply.hip AP_SPLIT)
 APPLY_SPLIT = 2048
 NOT_SUPPORTED = 2001  # GPP_NOT_SUPPORTED: gpp_lauum_grad does not take these arguments, nothing was enqueued
@@ -916,6 +917,59 @@ class GppContext:
         if status == NO_WORKSPACE:
             raise GppError("gpp_chol_append: the handle's scratch workspace is missing or too small")
         check(status, "gpp_chol_append")
+
+    # -- expected variance reduction ---------------------------------------------------------------------------------------------
+    @_on_own_device
+    def post_cross_sq(self, Uc, Ur, w, sf2, Vc, Vr, K, out, *, omega=None, kind=KIND_RBF, d_split=0, transposed=False):
+        """out[c] = sum_r omega_r (sf2 k(Uc_c, Ur_r; w) - sum_{n < K} Vc[c, n] Vr[r, n])^2 without forming the M_c x M_r block
+        (gpp_post_cross_sq).  ``Vc`` / ``Vr``: M_c x (>= K) and M_r x (>= K) windows of row-major buffers, or with ``transposed`` the
+        (>= K) x M_c and (>= K) x M_r windows of the transposed operands; what lies beyond K is not read.  ``omega``: M_r weights or
+        None for all ones.  Everything is checked before any launch."""
+        K = int(K)
+        for t, n in ((Uc, "Uc"), (Ur, "Ur"), (w, "w"), (sf2, "sf2"), (Vc, "Vc"), (Vr, "Vr"), (out, "out")):
+            _need(t, torch.float64, n)
+        if Uc.dim() != 2 or Ur.dim() != 2 or Uc.shape[1] != Ur.shape[1]:
+            raise GppError(f"Uc and Ur must be matrices with the same feature count (got {tuple(Uc.shape)}, {tuple(Ur.shape)})")
+        (Mc, D), Mr = Uc.shape, Ur.shape[0]
+        _check_features(D)
+        if min(Mc, Mr, K) < 1:
+            raise GppError(f"post_cross_sq takes M_c, M_r, K >= 1 (got {Mc}, {Mr}, {K})")
+        if not (Uc.is_contiguous() and Ur.is_contiguous()):
+            raise GppError("Uc and Ur must be contiguous")
+        if w.numel() != D or not w.is_contiguous():
+            raise GppError(f"w must be a contiguous vector of {D} weights (got {w.numel()})")
+        if sf2.numel() < 1:
+            raise GppError("sf2 must hold one value")
+        if not (0 <= int(d_split) <= D) or kind not in (KIND_RBF, KIND_MATERN32, KIND_MATERN52):
+            raise GppError(f"bad kernel kind / d_split ({kind}, {d_split}) for {D} features")
+        for t, n, pts in ((Vc, "Vc", Mc), (Vr, "Vr", Mr)):
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise GppError(f"{n} must be 2-D with unit column stride")
+            rows, cols = (K, pts) if transposed else (pts, K)
+            if t.shape[0] < rows or t.shape[1] < cols or (t.shape[1 if transposed else 0] != pts):
+                raise GppError(f"{n} is {tuple(t.shape)}: post_cross_sq with {pts} points and K = {K} needs "
+                               f"{'at least ' + str(K) + ' x ' + str(pts) if transposed else str(pts) + ' x at least ' + str(K)}")
+            ld = _ld(t)
+            if ld & 1 or ld < cols:
+                raise GppError(f"{n}: the leading dimension ({ld}) must be even and at least {cols}")
+            if t.data_ptr() & 15:
+                raise GppError(f"{n} must be 16-byte aligned")
+        if omega is not None:
+            _need(omega, torch.float64, "omega")
+            if omega.dim() != 1 or omega.numel() != Mr or not omega.is_contiguous():
+                raise GppError(f"omega must be a contiguous vector of {Mr} weights (got {tuple(omega.shape)})")
+        if out.dim() != 1 or out.numel() < Mc or not out.is_contiguous():
+            raise GppError(f"out must be a contiguous vector with room for {Mc} doubles (got {out.numel()})")
+        self.ensure_workspace(OP_POST_CROSS, Mr, Mc, 0, 0)
+        self._stream()
+        status = self.lib.gpp_post_cross_sq(self.h, Uc.data_ptr(), Mc, Ur.data_ptr(), Mr, D, w.data_ptr(), sf2.data_ptr(), int(kind),
+                                            int(d_split), Vc.data_ptr(), _ld(Vc), Vr.data_ptr(), _ld(Vr), K, 1 if transposed else 0,
+                                            _ptr(omega), out.data_ptr())
+        if status == NO_WORKSPACE:
+            raise GppError("gpp_post_cross_sq: the handle's scratch workspace is missing or too small")
+        check(status, "gpp_post_cross_sq")
+        return out
+
 
 
 def get_context(device) -> GppContext:

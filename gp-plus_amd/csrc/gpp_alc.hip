@@ -1,0 +1,65 @@
+// gpp_alc.hip — expected variance reduction of candidate observations (active learning: Cohn's ALC, IMSE over a reference set).
+//
+// gpp_post_cross_sq (gpp.h): out[c] = sum_r omega_r c(x_r, x_c)^2 with the posterior cross-covariance c = sf2 k - Vc Vr^T of a
+// fitted model, V = K_*N Linv^T as gpp_predict leaves it.  No reference counterpart: the reference refits per candidate.
+// The product and the square-and-sum run in ONE launch of gpp_post_cross_f64 (gpp_gemm.hip, beside the tile body it shares with
+// gpp_gemm), which leaves one record of 128 row sums per 128 x 128 tile in the handle workspace; the finish kernel below adds the
+// records of a row tile's column tiles in index order.  The M_c x M_r block is never written.
+#include "../../include/gpp.h"
+#include "gpp_internal.h"
+
+namespace {
+
+inline bool alc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline int alc_rc(hipError_t e) { return e == hipSuccess ? 0 : 1000 + (int)e; }
+
+// one thread per candidate: tiles_n terms, added in the order of the column tiles
+__global__ __launch_bounds__(256) void gpp_post_cross_finish(const double* __restrict__ rec, int tiles_n, int Mc, double* __restrict__ out) {
+  const int c = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (c >= Mc) return;
+  const double* p = rec + ((int64_t)(c >> 7) * tiles_n) * 128 + (c & 127);
+  double s = 0.0;
+  for (int tn = 0; tn < tiles_n; ++tn) s += p[(int64_t)tn * 128];
+  out[c] = s;
+}
+
+}  // namespace
+
+size_t gpp_post_cross_ws_bytes(int64_t Mc, int64_t Mr) {
+  if (Mc < 1 || Mr < 1) return 0;
+  return (size_t)(((Mc + 127) / 128) * ((Mr + 127) / 128) * 128) * sizeof(double);
+}
+
+extern "C" int gpp_post_cross_sq(gpp_handle_t h, const double* Uc, int64_t Mc, const double* Ur, int64_t Mr, int D, const double* w,
+                                 const double* sf2, int kind, int d_split, const double* Vc, int64_t ldc, const double* Vr,
+                                 int64_t ldr, int64_t K, int vt, const double* omega, double* out) {
+  if (!h) return -1;
+  if (!Uc) return -2;
+  if (Mc < 1 || Mc > 0x7ffffff0) return -3;
+  if (!Ur) return -4;
+  if (Mr < 1 || Mr > 0x7ffffff0) return -5;
+  if (D < 1 || D > 64) return -6;
+  if (!w) return -7;
+  if (!sf2) return -8;
+  if (kind < 0 || kind > 2) return -9;
+  if (d_split < 0 || d_split > D) return -10;
+  if (K < 1 || K > 0x7ffffff0) return -15;
+  if (vt != 0 && vt != 1) return -16;
+  if (!Vc || !alc_aligned16(Vc) || (ldc & 1) || ldc < (vt ? Mc : K)) return -11;
+  if (!Vr || !alc_aligned16(Vr) || (ldr & 1) || ldr < (vt ? Mr : K)) return -13;
+  if (!out) return -18;
+  const int64_t tiles_m = (Mc + 127) / 128, tiles_n = (Mr + 127) / 128;
+  if (tiles_m * tiles_n >= ((int64_t)1 << 31)) return -3;
+  if (!h->ws || h->ws_bytes < gpp_post_cross_ws_bytes(Mc, Mr)) return GPP_NO_WORKSPACE;
+  GemmArgs g{};
+  g.A = Vc; g.B = Vr; g.C = nullptr;
+  g.lda = ldc; g.ldb = ldr;
+  g.M = (int)Mc; g.N = (int)Mr; g.K = (int)K;
+  PostCrossArgs e{};
+  e.Uc = Uc; e.Ur = Ur; e.w = w; e.sf2 = sf2; e.omega = omega;
+  e.rec = reinterpret_cast<double*>(h->ws);
+  e.dk = D | (kind << 8) | (d_split << 16);
+  if (hipError_t r = gpp_launch_post_cross(h->stream, vt ? 2 : 0, g, e); r != hipSuccess) return alc_rc(r);
+  hipLaunchKernelGGL(gpp_post_cross_finish, dim3((unsigned)((Mc + 255) / 256)), dim3(256), 0, h->stream, e.rec, (int)tiles_n, (int)Mc, out);
+  return alc_rc(hipGetLastError());
+}

@@ -1237,6 +1237,7 @@ size_t gpp_workspace_bytes(gpp_handle_t h, int op, int64_t N, int64_t M, int D, 
   if (op == GPP_OP_APPLY) return gpp_apply_ws_bytes(N, M, S) + 256;
   if (op == GPP_OP_APPLY_GRAD) return gpp_apply_ws_bytes(N, M, D) + 256;
   if (op == GPP_OP_APPEND) return gpp_append_ws_bytes(N, M) + 256;
+  if (op == GPP_OP_POST_CROSS) return gpp_post_cross_ws_bytes(M, N) + 256;
   return 0;
 }
 

@@ -390,7 +390,7 @@ __device__ __forceinline__ void gemm_tile(const P& p, const int tm, const int tn
   for (; c < nch; ++c) general_iter(c);
   before_epilogue();
   if constexpr (!__is_same(E, GemmStoreC)) {
-    static_assert(VAR == 2 && WTM == 64 && WTN == 64 && WR == 2, "accumulator epilogues are written for the big TN tile");
+    static_assert((VAR == 2 || VAR == 0) && WTM == 64 && WTN == 64 && WR == 2, "accumulator epilogues are written for the big tile");
     epi(acc4, row0, col0, p.M, smem);  // (every wave is past the barrier behind the last chunk's LDS reads)
     return;
   }
@@ -646,6 +646,144 @@ __global__ __launch_bounds__(256, 2) void gpp_lauum_grad_f64(GemmArgs p, GradEpi
   while (tm * (tm + 1) / 2 > t) --tm;
   const int tn = t - tm * (tm + 1) / 2;
   gemm_tile<2, 64, 64, 2, 16, 2, 2>(p, tm, tn, p.A, p.B, nullptr, nullptr, smem, GemmNoHook(), GradEpilogue<DT>{e, t});
+}
+
+// ---- Vc Vr^T with the weighted squared posterior cross-covariance as its epilogue (gpp_post_cross_sq in gpp.h) -------------------
+// Entry (c, r) of a 128 x 128 tile of Vc Vr^T never reaches memory: the epilogue regenerates g = sf2 k(Uc_c, Ur_r; w) with the
+// arithmetic of gpp_cov_tile (features staged times sqrt(w_d), r2 summed by fma in the order of d, kfun's factors), forms
+// omega_r (g - acc)^2 and sums it along the tile's columns.  The slab idiom of GradEpilogue: the 16 values of slab a4 pass through
+// lane-private LDS slots, the arithmetic runs in a rolled loop over half-slabs of 2 rows x 4 columns per lane.  The features are
+// staged DC dims at a time: D <= DC once for the whole tile; above, every half-slab walks the chunks (two barriers per chunk — the
+// r2 sums of a half-slab stay in registers, so the tile's 64 entries per lane never need D-many staged dims at once; the re-read
+// feature rows are L2-resident and ~1 MB per tile at D = 64 against the 2 x 128 x K doubles of the main loop).
+// Deterministic, and the same for every row of the tile: a lane adds its 4 columns (16 b + li) in the order of b, a fixed butterfly
+// adds the 16 lanes of a row, the two column halves (waves) are added in order — ONE record of 128 row sums per tile, every slot
+// written exactly once, summed over the column tiles by gpp_post_cross_finish (gpp_alc.hip) in index order.
+template <bool MAT>
+struct PostCrossEpilogue {
+  PostCrossArgs e;
+  int tile, Mr;
+  static constexpr int T = 128, DC = 16;
+  static constexpr int SLAB = 2 * DC * T + T + 2 * T;  // doubles in front of the slab
+  static_assert((SLAB & 1) == 0 && (SLAB + 16 * 256) * sizeof(double) <= 2 * 2 * BK16 * ldt_mc(T) * sizeof(double) &&
+                    (SLAB + 16 * 256) * sizeof(double) <= 2 * 2 * T * LDK * sizeof(double),
+                "the epilogue lives in the main loop's LDS");
+  __device__ __forceinline__ void operator()(const v4d (&acc4)[4][4], int row0, int col0, int Mc, double* __restrict__ smem) const {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64, li = lane & 15, lk = lane >> 4;
+    const int D = e.dk & 255, kind = (e.dk >> 8) & 255;
+    const int dsp = (!MAT || kind == 0) ? D : (e.dk >> 16);  // dims below go to the RBF factor, the others to the Matern factor
+    double* __restrict__ sa = smem;           // staged features of the tile's rows (candidates), [d][r], times sqrt(w_d)
+    double* __restrict__ sb = sa + DC * T;    // ... of its columns (reference points)
+    double* __restrict__ som = sb + DC * T;   // omega of the columns, 0 beyond M_r
+    double* __restrict__ rs = som + T;        // [2 column halves][T] row sums
+    double* __restrict__ slab = smem + SLAB;  // [16 values][256 lanes]
+    // (what the staging of a later chunk and the record need is parked in VGPRs: with the exponential's 28 constant SGPRs on top
+    //  of the tile body's own, the scalar file would spill)
+    const double* __restrict__ Uc = e.Uc;
+    const double* __restrict__ Ur = e.Ur;
+    const double* __restrict__ wp = e.w;
+    double* __restrict__ rec = e.rec + (int64_t)tile * T;
+    Uc += (int64_t)row0 * (e.dk & 255);
+    Ur += (int64_t)col0 * (e.dk & 255);
+    int rlim = Mc - row0, clim = Mr - col0;  // rows / columns of the tile inside the block
+    asm volatile("" : "+v"(Uc), "+v"(Ur), "+v"(wp), "+v"(rec), "+v"(rlim), "+v"(clim));
+    auto stage = [&](int d0) {
+      for (int x = tid; x < DC * T; x += 256) {
+        const int dd = x / T, r = x - dd * T, d = d0 + dd;
+        const bool okd = d < D;
+        const double sw = okd ? sqrt(wp[okd ? d : 0]) : 0.0;
+        sa[x] = (okd && r < rlim) ? Uc[r * D + d] * sw : 0.0;
+        sb[x] = (okd && r < clim) ? Ur[r * D + d] * sw : 0.0;
+      }
+    };
+    if (tid < T) som[tid] = (tid < clim) ? (e.omega ? e.omega[col0 + tid] : 1.0) : 0.0;
+    const bool one = (D <= DC);  // work-group uniform
+    if (one) stage(0);
+    __syncthreads();
+
+    const double sf2 = *e.sf2;
+    const GppExpConsts ec = gpp_exp_consts();
+#pragma unroll
+    for (int a4 = 0; a4 < 4; ++a4) {
+#pragma unroll
+      for (int v = 0; v < 4; ++v)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) slab[(v * 4 + b) * 256 + tid] = acc4[a4][b][v];
+#pragma unroll 1
+      for (int h = 0; h < 2; ++h) {
+        const int ra = wm + 16 * a4 + 8 * h + lk;  // this half's rows inside the tile: ra and ra + 4
+        const int cb = wn + li;                    // its columns: cb + 16 b
+        double r2[2][4], r2m[MAT ? 2 : 1][MAT ? 4 : 1];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            r2[a][b] = 0.0;
+            if (MAT) r2m[MAT ? a : 0][MAT ? b : 0] = 0.0;
+          }
+#pragma unroll 1
+        for (int d0 = 0; d0 < D; d0 += DC) {
+          if (!one) {
+            __syncthreads();  // (every wave has read the previous chunk)
+            stage(d0);
+            __syncthreads();
+          }
+          const int nd = min(DC, D - d0);
+#pragma unroll 2
+          for (int dd = 0; dd < nd; ++dd) {
+            const double ua[2] = {sa[dd * T + ra], sa[dd * T + ra + 4]};
+            const bool second = MAT && (d0 + dd >= dsp);
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+              const double ub = sb[dd * T + cb + 16 * b];
+#pragma unroll
+              for (int a = 0; a < 2; ++a) {
+                const double df = ua[a] - ub;
+                if (MAT && second) r2m[MAT ? a : 0][MAT ? b : 0] = fma(df, df, r2m[MAT ? a : 0][MAT ? b : 0]);
+                else r2[a][b] = fma(df, df, r2[a][b]);
+              }
+            }
+          }
+        }
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+          double s = 0.0;
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            double kv = gpp_exp_nonpos(-r2[a][b], ec);
+            if constexpr (MAT) {  // the factors of kfun (gpp_build.hip)
+              if (kind == 1) {
+                const double r = sqrt(3.0 * 2.0 * r2m[MAT ? a : 0][MAT ? b : 0]);
+                kv *= (1.0 + r) * gpp_exp_nonpos(-r, ec);
+              } else if (kind == 2) {
+                const double r = sqrt(5.0 * 2.0 * r2m[MAT ? a : 0][MAT ? b : 0]);
+                kv *= (1.0 + r + r * r * (1.0 / 3.0)) * gpp_exp_nonpos(-r, ec);
+              }
+            }
+            const double c = sf2 * kv - slab[((2 * h + a) * 4 + b) * 256 + tid];
+            double t = c * c;
+            t = (cb + 16 * b < clim) ? t : 0.0;  // (a select: whatever a column beyond M_r holds never reaches a sum)
+            s = fma(som[cb + 16 * b], t, s);
+          }
+#pragma unroll
+          for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o);  // the 16 lanes (li) that share this row
+          if (li == 0) rs[(wave & 1) * T + ra + 4 * a] = s;
+        }
+      }
+    }
+    __syncthreads();
+    if (tid < T) rec[tid] = rs[tid] + rs[T + tid];
+  }
+};
+
+// one work-group per tile of the M_c x M_r block, row by row (consecutive work-groups share the candidates' chunks)
+template <int VAR, bool MAT>
+__global__ __launch_bounds__(256, VAR == 2 ? 2 : 1) void gpp_post_cross_f64(GemmArgs p, PostCrossArgs e) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int t = (int)blockIdx.x;
+  const int tm = t / p.tiles_n, tn = t - tm * p.tiles_n;
+  gemm_tile<VAR, 64, 64, 2, 16, 2, 2>(p, tm, tn, p.A, p.B, nullptr, nullptr, smem, GemmNoHook(), PostCrossEpilogue<MAT>{e, t, p.N});
 }
 
 // LDS bytes of an instantiation (dynamic: the wide-chunk variants exceed the 64 KiB static limit)
@@ -952,6 +1090,32 @@ hipError_t gpp_launch_lauum_grad(hipStream_t s, const GemmArgs& a_in, const Grad
   hipError_t err = hipGetDevice(&dev);
   if (err != hipSuccess) return err;
   const int which = e.D <= 8 ? 0 : 1;
+  if (dev < 0 || dev >= 64 || !attr_set[which][dev]) {
+    err = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (err != hipSuccess) return err;
+    if (dev >= 0 && dev < 64) attr_set[which][dev] = true;
+  }
+  hipLaunchKernelGGL(fn, dim3((unsigned)nt), dim3(256), bytes, s, a, e);
+  return hipGetLastError();
+}
+
+// a: M = M_c, N = M_r, K, the operands' leading dimensions; everything else is set here
+hipError_t gpp_launch_post_cross(hipStream_t s, int variant, const GemmArgs& a_in, const PostCrossArgs& e) {
+  GemmArgs a = a_in;
+  if (a.M <= 0 || a.N <= 0 || a.K <= 0 || (variant != 0 && variant != 2)) return hipErrorInvalidValue;
+  a.tiles_m = (a.M + 127) / 128;
+  a.tiles_n = (a.N + 127) / 128;
+  const int64_t nt = (int64_t)a.tiles_m * a.tiles_n;
+  if (nt >= (int64_t)1 << 31) return hipErrorInvalidValue;
+  const bool mat = ((e.dk >> 8) & 255) != 0;
+  const size_t bytes = gemm_lds_bytes(variant, 128, 128, 16, 2);
+  auto* fn = variant == 2 ? (mat ? gpp_post_cross_f64<2, true> : gpp_post_cross_f64<2, false>)
+                          : (mat ? gpp_post_cross_f64<0, true> : gpp_post_cross_f64<0, false>);
+  static std::atomic<bool> attr_set[4][64];  // per instantiation and device
+  int dev = 0;
+  hipError_t err = hipGetDevice(&dev);
+  if (err != hipSuccess) return err;
+  const int which = (variant == 2 ? 2 : 0) + (mat ? 1 : 0);
   if (dev < 0 || dev >= 64 || !attr_set[which][dev]) {
     err = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (err != hipSuccess) return err;

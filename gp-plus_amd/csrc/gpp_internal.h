@@ -219,6 +219,21 @@ struct GradEpiArgs {
 };
 hipError_t gpp_launch_lauum_grad(hipStream_t s, const GemmArgs& lauum, const GradEpiArgs& e);
 
+// The product Vc Vr^T whose epilogue is the weighted squared posterior cross-covariance (gpp_gemm.hip; gpp_post_cross_sq in gpp.h):
+// tile (tm, tn) of the M_c x M_r block goes into the 128 row sums rec[(tm tiles_n + tn) 128 ..], not to memory
+struct PostCrossArgs {
+  const double* Uc;     // M_c x D features, row-major
+  const double* Ur;     // M_r x D
+  const double* w;      // D weights
+  const double* sf2;
+  const double* omega;  // M_r weights, or null for all ones
+  double* rec;          // [tiles_m][tiles_n][128]
+  int dk;               // D | kind << 8 | d_split << 16: one scalar register across the main loop instead of three
+};
+// variant: 0 = NT (Vc[c][k], Vr[r][k]), 2 = TN (Vc[k][c], Vr[k][r]); p.M = M_c, p.N = M_r, no masks, C unused
+hipError_t gpp_launch_post_cross(hipStream_t s, int variant, const GemmArgs& p, const PostCrossArgs& e);
+size_t gpp_post_cross_ws_bytes(int64_t Mc, int64_t Mr);  // gpp_alc.hip
+
 // one-wave kernels on a stream (gpp_gemm.hip): wait until counters[id] >= target — a wait that exceeds `budget` ticks of the 100 MHz
 // clock sets the abort word counters[0] and *info = GPP_INFO_EXEC_TIMEOUT + ms —, and counters[id] += 1 behind a release fence
 hipError_t gpp_launch_exec_gate(hipStream_t s, int* counters, int id, int target, int32_t* info, long long budget);

@@ -693,10 +693,11 @@ def cv_moments(cache: FactorCache, y: torch.Tensor, folds) -> Tuple[torch.Tensor
 
 
 @torch.no_grad()
-def predict_from_cache(cache: FactorCache, Us: torch.Tensor, need_var: bool = True, need_V: bool = False):
+def predict_from_cache(cache: FactorCache, Us: torch.Tensor, need_var: bool = True, need_V: bool = False, V=None):
     """K8: mean contribution K_*N alpha and prior-minus-explained variance; optionally V = K_*N Linv^T.
     Mean only: the [test][train] cross block and one row reduction, O(M N).  With the variance: the TRANSPOSED cross block, so that
-    V = Kns^T Linv^T is the row-contiguous TN product (gpp_predict_tn), and both outputs come from one pass over V."""
+    V = Kns^T Linv^T is the row-contiguous TN product (gpp_predict_tn), and both outputs come from one pass over V.
+    ``V``: an M x N window of the caller's own buffer to receive V (``variance_reduction`` keeps spare columns behind it)."""
     dev = Us.device
     gctx = cache.gctx
     M, N = Us.shape[0], cache.U.shape[0]
@@ -706,11 +707,125 @@ def predict_from_cache(cache: FactorCache, Us: torch.Tensor, need_var: bool = Tr
         gctx.predict(cache.Linv, cache.alpha, Ksn, None, None, mean, None)
         return mean, None, None
     Kns = cross_kernel(cache.U, Us, cache.spec)  # N x M
-    V = rows_buffer(M, N, dev)
+    if V is None:
+        V = rows_buffer(M, N, dev)
     kss = cache.spec.sf2.reshape(1).expand(M).contiguous()
     var = torch.empty(M, dtype=torch.float64, device=dev)
     gctx.predict_tn(cache.Linv, cache.z, Kns, kss, V, mean, var)
     return mean, var, V
+
+
+#: Operand form ``variance_reduction`` hands gpp_post_cross_sq: False = V as ``predict_from_cache`` leaves it (points x K, the NT
+#: tile body), True = V^T (K x points, the row-contiguous TN body; one extra transposition of each V, O(M N)).  MEASURED
+#: (tools/bench_alc.py, N = 20 000, M_c = M_r = 4096 / 16384): the fused launch takes 16.7 / 267.6 ms on V and 9.3 / 148.9 ms on V^T,
+#: and a q = 16 greedy run with everything included 358 ms against 232 ms at 4096: V^T, as gpp_predict_tn found for the prediction.
+ALC_TRANSPOSED = True
+
+
+@torch.no_grad()
+def variance_reduction(cache: FactorCache, Uc, tau_c, Ur, omega=None, q: int = 1, cost=None, transposed: Optional[bool] = None):
+    """Expected reduction of the omega-weighted posterior variance of the latent f over the reference features ``Ur`` (M_r x D) from
+    ONE noisy observation at each candidate ``Uc`` (M_c x D; ``tau_c``: the candidates' own noise levels, M_c), and a greedy batch of
+    ``q`` of them.  With v(x) = Linv k(X, x) and c(x, x') = sf2 k(x, x') - v(x)^T v(x'):
+        dV(c) = sum_r omega_r c(x_r, x_c)^2 / s_c,    s_c = max(c(x_c, x_c), 0) + tau_c + jitter  (the diagonal ``append_to_cache`` uses)
+    whatever the observed value.  The M_c x M_r block of c never exists: the sums come from gpp_post_cross_sq on the V of
+    ``predict_from_cache``.  After a pick j every point gains the coordinate c(x, x_j) / sqrt(s_j) (one ``cross_kernel`` column and two
+    matrix-vector products, O((M_c + M_r)(N + t))), appended in place to buffers with q - 1 spare columns; the kernel then runs with
+    K = N + t.  The q gains add up to the reduction from conditioning on all q picks at once.  A picked candidate is excluded from
+    later rounds; with ``cost`` (M_c positive numbers) the pick maximises gain / cost and the reported gains stay undivided.
+    ``omega`` None: 1 / M_r each.  Returns (the M_c first-round scores, the q picked rows of ``Uc`` in pick order, their gains), in
+    the cache's (scaled-target) units.  The cache is only read.  Refused under ``settings.sharded_evaluation`` and inside a graph
+    capture, like ``append_to_cache``."""
+    if settings.sharded_evaluation.value() is not None:
+        raise NotImplementedError("variance_reduction is not available under settings.sharded_evaluation")
+    dev = cache.U.device
+    gctx = cache.gctx
+    on_gpu = dev.type == "cuda"  # (anything else only under a stand-in context: the library itself has no CPU path)
+    transposed = ALC_TRANSPOSED if transposed is None else bool(transposed)
+    with torch.cuda.device(dev) if on_gpu else nullcontext():
+        if on_gpu and torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("variance_reduction is not available inside a graph capture")
+        Uc, Ur = _as_f64(Uc.detach(), dev).contiguous(), _as_f64(Ur.detach(), dev).contiguous()
+        D, q = cache.U.shape[1], int(q)
+        for U, name in ((Uc, "candidates"), (Ur, "reference points")):
+            if U.dim() != 2 or U.shape[0] < 1 or U.shape[1] != D:
+                raise ValueError(f"the {name} must be at least one row of {D} features (got {tuple(U.shape)})")
+        Mc, Mr = Uc.shape[0], Ur.shape[0]
+        if q < 1 or q > Mc:
+            raise ValueError(f"q must be between 1 and the number of candidates ({Mc}); got {q}")
+        tau_c = _as_f64(tau_c.detach().reshape(-1), dev)
+        if tau_c.numel() != Mc:
+            raise ValueError(f"{tau_c.numel()} noise levels for {Mc} candidates")
+        if omega is None:
+            omega = torch.full((Mr,), 1.0 / Mr, dtype=torch.float64, device=dev)
+        else:
+            omega = _as_f64(omega.detach().reshape(-1), dev).contiguous()
+            if omega.numel() != Mr:
+                raise ValueError(f"{omega.numel()} weights for {Mr} reference points")
+        if cost is not None:
+            cost = _as_f64(cost.detach().reshape(-1), dev)
+            if cost.numel() != Mc:
+                raise ValueError(f"{cost.numel()} costs for {Mc} candidates")
+        cache.refresh()  # (a cache of the shared workspace that another model has factored into since)
+        N, spec = cache.U.shape[0], cache.spec
+        w, sf2 = spec.w, spec.sf2.reshape(1)
+        Kmax = N + q - 1
+        with _stage("alc_operands"):
+            if transposed:
+                bufs = []
+                for U in (Uc, Ur):
+                    _, var, V = predict_from_cache(cache, U, need_V=True)
+                    Vt = rows_buffer(Kmax, U.shape[0], dev)
+                    gctx.transpose(V, Vt[:N])
+                    bufs.append((Vt, var))
+            else:
+                bufs = []
+                for U in (Uc, Ur):
+                    Vb = rows_buffer(U.shape[0], Kmax, dev)
+                    _, var, _ = predict_from_cache(cache, U, need_V=True, V=Vb[:, :N])
+                    bufs.append((Vb, var))
+        (Vc, var_c), (Vr, _) = bufs
+        Ucr = torch.cat([Uc, Ur]) if q > 1 else None
+        num = torch.empty(Mc, dtype=torch.float64, device=dev)
+        taken = torch.zeros(Mc, dtype=torch.bool, device=dev)
+        picks, gains, first = [], [], None
+        for t in range(q):
+            K = N + t
+            s = var_c.clamp_min(0.0) + tau_c + cache.jitter
+            with _stage("post_cross_sq"):
+                gctx.post_cross_sq(Uc, Ur, w, sf2, Vc[:K] if transposed else Vc[:, :K], Vr[:K] if transposed else Vr[:, :K], K, num,
+                                   omega=omega, kind=spec.kind, d_split=spec.d_split, transposed=transposed)
+            dv = num / s
+            if t == 0:
+                first = dv.clone()
+            rank = (dv if cost is None else dv / cost).masked_fill(taken, float("-inf"))
+            j = int(torch.argmax(rank))
+            picks.append(j)
+            gains.append(dv[j])
+            taken[j] = True
+            if t + 1 == q:
+                break
+            # the new coordinate of every point: c(x, x_j) / sqrt(s_j), c by the current (N + t)-long vectors
+            with _stage("alc_append"):
+                col = gctx.cross_kernel(Ucr, Uc[j:j + 1], w, sf2, rows_buffer(Mc + Mr, 1, dev), kind=spec.kind, d_split=spec.d_split)
+                if transposed:
+                    vj = rows_buffer(K, 1, dev)
+                    vj.copy_(Vc[:K, j:j + 1])
+                    gctx.gemm(1, 0, Mc, 1, K, -1.0, Vc[:K], vj, 1.0, col[:Mc])
+                    gctx.gemm(1, 0, Mr, 1, K, -1.0, Vr[:K], vj, 1.0, col[Mc:])
+                else:
+                    vj = Vc[j:j + 1, :K]
+                    gctx.gemm(0, 1, Mc, 1, K, -1.0, Vc[:, :K], vj, 1.0, col[:Mc])
+                    gctx.gemm(0, 1, Mr, 1, K, -1.0, Vr[:, :K], vj, 1.0, col[Mc:])
+                col.div_(s[j].sqrt())
+                if transposed:
+                    Vc[K].copy_(col[:Mc, 0])
+                    Vr[K].copy_(col[Mc:, 0])
+                else:
+                    Vc[:, K].copy_(col[:Mc, 0])
+                    Vr[:, K].copy_(col[Mc:, 0])
+                var_c = var_c - col[:Mc, 0] ** 2
+        return first, torch.tensor(picks, dtype=torch.int64, device=dev), torch.stack(gains)
 
 
 # ---------------------------------------------------------------------------------------------------

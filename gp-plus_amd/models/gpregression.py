@@ -192,6 +192,97 @@ class GPR(ExactGP):
             child.prediction_strategy = new_cache
         return child
 
+    def _alc_rows(self, X, name: str) -> torch.Tensor:
+        """A candidate or reference set of ``variance_reduction``, checked on the host like ``condition_on``'s new rows."""
+        from ..utils import data_type_check
+
+        X = data_type_check(X)
+        train_x = self.train_inputs[0]
+        if X.dim() != 2 or X.shape[1] != train_x.shape[1]:
+            raise ValueError(f"variance_reduction: {name} must be (m, {train_x.shape[1]}) like the training inputs "
+                             f"(got {tuple(X.shape)})")
+        if X.shape[0] == 0:
+            raise ValueError(f"variance_reduction: {name} is empty")
+        if not bool(torch.isfinite(X).all()):
+            raise ValueError(f"variance_reduction: {name} must be finite (NaN or inf found)")
+        self._check_new_rows(X)
+        return X
+
+    def _variance_reduction(self, Xcand, Xref, weights=None, q: int = 1, cost=None):
+        """(first-round scores, picked rows of ``Xcand``, their gains) of ``linalg.variance_reduction``, in y^2 units: the work behind
+        ``variance_reduction`` and ``bayesian_optimizations.select_by_variance_reduction``.  Everything is validated on the host
+        before any device work."""
+        from .. import settings as gpp_settings
+        from ..backend import get_context
+        from ..gpcore.module import Module
+        from ..linalg import variance_reduction
+        from ..utils import data_type_check
+
+        Xc, Xr = self._alc_rows(Xcand, "Xcand"), self._alc_rows(Xref, "Xref")
+        Mc, Mr = Xc.shape[0], Xr.shape[0]
+        if weights is not None:
+            weights = data_type_check(weights).reshape(-1).to(torch.float64)
+            if weights.shape[0] != Mr:
+                raise ValueError(f"variance_reduction: {weights.shape[0]} weights for {Mr} reference rows")
+            if not bool(torch.isfinite(weights).all()) or bool((weights < 0).any()):
+                raise ValueError("variance_reduction: the weights must be finite and non-negative")
+            if not bool((weights > 0).any()):
+                raise ValueError("variance_reduction: the weights are all zero")
+        if cost is not None:
+            cost = data_type_check(cost).reshape(-1).to(torch.float64)
+            if cost.shape[0] != Mc:
+                raise ValueError(f"variance_reduction: {cost.shape[0]} costs for {Mc} candidates")
+            if not bool(torch.isfinite(cost).all()) or bool((cost <= 0).any()):
+                raise ValueError("variance_reduction: the costs must be finite and positive")
+        q = int(q)
+        if q < 1 or q > Mc:
+            raise ValueError(f"variance_reduction: q must be between 1 and the number of candidates ({Mc}); got {q}")
+        if gpp_settings.sharded_evaluation.value() is not None:
+            raise NotImplementedError("variance_reduction is not available under settings.sharded_evaluation")
+        train_x = self.train_inputs[0]
+        get_context(train_x.device)  # (raises for anything but a GPU: there is no CPU path)
+
+        Xc, Xr = Xc.to(train_x), Xr.to(train_x)
+        self.eval()
+        with torch.no_grad():
+            cache = self._ensure_prediction_cache()
+            out_c = Module.__call__(self, Xc)
+            Ur = Module.__call__(self, Xr).lazy_covariance_matrix.U1
+            lik = self.likelihood
+            swap = hasattr(lik, "fidel_indices")
+            if swap:  # the noise of each candidate's own source, as condition_on gives a new row
+                saved, lik.fidel_indices = lik.fidel_indices, Xc[:, -1]
+            try:
+                noisy = lik(out_c).lazy_covariance_matrix
+            finally:
+                if swap:
+                    lik.fidel_indices = saved
+            tau = noisy.tau.detach().reshape(-1).to(torch.float64)
+            tau_c = tau[noisy.grp.long()] if noisy.grp is not None else tau[:1].expand(Mc)
+            dev = train_x.device
+            first, picks, gains = variance_reduction(cache, out_c.lazy_covariance_matrix.U1, tau_c, Ur,
+                                                     omega=None if weights is None else weights.to(dev), q=q,
+                                                     cost=None if cost is None else cost.to(dev))
+            scale = self.y_std.to(torch.float64) ** 2
+            return first * scale, picks, gains * scale
+
+    def variance_reduction(self, Xcand, Xref, weights=None) -> torch.Tensor:
+        """Active learning (Cohn's ALC; IMSE over a reference set): for every row of ``Xcand`` the expected reduction of the
+        weighted posterior variance of the latent f over the rows of ``Xref`` from ONE noisy observation at that row,
+            sum_r w_r var_before(x_r) - sum_r w_r var_after(x_r),        w_r = ``weights`` (default 1 / M_r each),
+        in the units of y^2 (``predict``'s std squared).  The posterior variance after an observation does not depend on the
+        observed value, so nothing is conditioned and nothing is factorised: the scores come from the cached factor through
+        gpp_post_cross_sq, which never forms the M_c x M_r cross-covariance.  No reference counterpart.
+
+        Rows go through the model's ``forward`` and likelihood as ``condition_on`` sends new rows: latent map, per-source noise of
+        each candidate's own source column.  A multi-fidelity user passes candidates of several sources and reference rows of the
+        high-fidelity source.  The model is put in eval mode and is otherwise untouched; a warm cache is reused.
+
+        ``ValueError`` before any device work: wrong column count, an empty set, NaN / inf, negative or all-zero weights, a wrong
+        weights length, a categorical level or source the model has not seen.  ``NotImplementedError`` under
+        ``settings.sharded_evaluation`` or a graph capture."""
+        return self._variance_reduction(Xcand, Xref, weights)[0]
+
     def reset_parameters(self) -> None:
         """Reset parameters by sampling from their priors (models/gpregression.py:168-174)."""
         # The reference builds its priors from Python numbers (torch's default dtype, float32) and never casts them on its

@@ -54,6 +54,7 @@ typedef struct gpp_handle_s* gpp_handle_t;
 #define GPP_OP_APPLY_GRAD 4 /* gpp_kernel_apply_grad / gpp_rff_apply_grad: N = the contracted length, M rows, D features: pieces * M * D
                                doubles above a contracted length of 2048, 0 extra bytes up to it */
 #define GPP_OP_APPEND 5     /* gpp_chol_append: N cached points, M = q appended points (D and S are not read) */
+#define GPP_OP_POST_CROSS 6 /* gpp_post_cross_sq: N = M_r reference points, M = M_c candidates (D and S are not read) */
 
 const char* gpp_version(void);
 
@@ -589,6 +590,23 @@ int gpp_cv_rows(gpp_handle_t h, const double* G, int64_t ldg, int64_t sG, const 
  */
 int gpp_chol_append(gpp_handle_t h, double* A, int64_t ld, double* Linv, int64_t ldi, int64_t N, int64_t q, const double* k,
                     int64_t ldk, const double* C, int64_t ldc, const double* rq, double* z, double* alpha, int32_t* info_dev);
+
+/*
+ * Weighted sum of squared posterior cross-covariances, the numerator of the expected-variance-reduction (ALC / IMSE) score:
+ *   out[c] = sum_r omega_r ( sf2 k(Uc_c, Ur_r; w) - sum_{n < K} Vc[c,n] Vr[r,n] )^2
+ * Uc (M_c x D) and Ur (M_r x D) are row-major feature rows; kind / d_split as in gpp_cross_kernel.  vt = 0: Vc is M_c x K and Vr is
+ * M_r x K, row-major, the V of gpp_predict (ldc, ldr >= K); vt = 1: the transposed operands, Vc K x M_c and Vr K x M_r (ldc >= M_c,
+ * ldr >= M_r).  Leading dimensions even, buffers 16-byte aligned.  omega: M_r weights, or NULL for all ones.  out: M_c doubles.
+ * K, M_c, M_r >= 1, D <= 64.  The M_c x M_r block never reaches memory: 128 x 128 tiles of Vc Vr^T on the MFMA path of gpp_gemm,
+ * whose epilogue regenerates k per entry, subtracts, squares, weights and sums along the tile's columns into one record of 128 row
+ * sums per tile in the handle workspace (gpp_workspace_bytes(h, GPP_OP_POST_CROSS, M_r, M_c, 0, 0) bytes; GPP_NO_WORKSPACE with
+ * nothing enqueued when it is missing); a second launch adds the column tiles' records in index order.  No float atomics, the number
+ * and order of the terms of out[c] depend on (M_r, K) only: two calls agree bit for bit, and a candidate's value does not depend on
+ * its row or on the other candidates.  Nothing outside the stated extents is read (the columns [K, ld) may hold anything).
+ */
+int gpp_post_cross_sq(gpp_handle_t h, const double* Uc, int64_t Mc, const double* Ur, int64_t Mr, int D, const double* w,
+                      const double* sf2, int kind, int d_split, const double* Vc, int64_t ldc, const double* Vr, int64_t ldr,
+                      int64_t K, int vt, const double* omega, double* out);
 
 #ifdef __cplusplus
 }
