@@ -135,6 +135,8 @@ _SIGNATURES = {
                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "gpp_post_cross_sq": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                   c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "gpp_post_cross_min": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                   c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
 }
 
 _lib = None

@@ -28,6 +28,9 @@ OP_APPLY = 3  # gpp_kernel_apply / gpp_rff_apply: N carries the contracted lengt
 OP_APPLY_GRAD = 4  # gpp_kernel_apply_grad / gpp_rff_apply_grad: N carries the contracted length
 OP_APPEND = 5  # gpp_chol_append: N cached points, M carries the appended count q
 OP_POST_CROSS = 6  # gpp_post_cross_sq: N carries the reference count M_r, M the candidate count M_c
+OP_POST_CROSS_MIN = 7  # gpp_post_cross_min: N carries M_r, M carries M_c, S the node count Q
+#: most quadrature nodes gpp_post_cross_min takes (gpp_gemm.hip PostCrossMinEpilogue::QMAX)
+MAX_NODES = 64
 #: longest contraction gpp_kernel_apply / gpp_rff_apply run without scratch (gpp_apply.hip AP_SPLIT)
 APPLY_SPLIT = 2048
 NOT_SUPPORTED = 2001  # GPP_NOT_SUPPORTED: gpp_lauum_grad does not take these arguments, nothing was enqueued
@@ -970,6 +973,68 @@ class GppContext:
         check(status, "gpp_post_cross_sq")
         return out
 
+    # -- knowledge gradient ------------------------------------------------------------------------------------------------------
+    @_on_own_device
+    def post_cross_min(self, Uc, Ur, w, sf2, Vc, Vr, K, m, scale, nodes, out, *, kind=KIND_RBF, d_split=0, transposed=False):
+        """out[c, k] = min_r (m_r + nodes_k scale_c (sf2 k(Uc_c, Ur_r; w) - sum_{n < K} Vc[c, n] Vr[r, n])) without forming the
+        M_c x M_r block (gpp_post_cross_min).  ``Vc`` / ``Vr`` and ``transposed`` as in ``post_cross_sq``; ``m``: M_r offsets,
+        ``scale``: M_c factors, ``nodes``: 1..64 values, ``out``: a contiguous M_c x Q matrix.  Everything is checked before any
+        launch."""
+        K = int(K)
+        for t, n in ((Uc, "Uc"), (Ur, "Ur"), (w, "w"), (sf2, "sf2"), (Vc, "Vc"), (Vr, "Vr"), (m, "m"), (scale, "scale"),
+                     (nodes, "nodes"), (out, "out")):
+            _need(t, torch.float64, n)
+        if Uc.dim() != 2 or Ur.dim() != 2 or Uc.shape[1] != Ur.shape[1]:
+            raise GppError(f"Uc and Ur must be matrices with the same feature count (got {tuple(Uc.shape)}, {tuple(Ur.shape)})")
+        (Mc, D), Mr = Uc.shape, Ur.shape[0]
+        _check_features(D)
+        if min(Mc, Mr, K) < 1:
+            raise GppError(f"post_cross_min takes M_c, M_r, K >= 1 (got {Mc}, {Mr}, {K})")
+        if not (Uc.is_contiguous() and Ur.is_contiguous()):
+            raise GppError("Uc and Ur must be contiguous")
+        if w.numel() != D or not w.is_contiguous():
+            raise GppError(f"w must be a contiguous vector of {D} weights (got {w.numel()})")
+        if sf2.numel() < 1:
+            raise GppError("sf2 must hold one value")
+        if not (0 <= int(d_split) <= D) or kind not in (KIND_RBF, KIND_MATERN32, KIND_MATERN52):
+            raise GppError(f"bad kernel kind / d_split ({kind}, {d_split}) for {D} features")
+        for t, n, pts in ((Vc, "Vc", Mc), (Vr, "Vr", Mr)):
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise GppError(f"{n} must be 2-D with unit column stride")
+            rows, cols = (K, pts) if transposed else (pts, K)
+            if t.shape[0] < rows or t.shape[1] < cols or (t.shape[1 if transposed else 0] != pts):
+                raise GppError(f"{n} is {tuple(t.shape)}: post_cross_min with {pts} points and K = {K} needs "
+                               f"{'at least ' + str(K) + ' x ' + str(pts) if transposed else str(pts) + ' x at least ' + str(K)}")
+            ld = _ld(t)
+            if ld & 1 or ld < cols:
+                raise GppError(f"{n}: the leading dimension ({ld}) must be even and at least {cols}")
+            if t.data_ptr() & 15:
+                raise GppError(f"{n} must be 16-byte aligned")
+        if nodes.dim() != 1 or not (1 <= nodes.numel() <= MAX_NODES) or not nodes.is_contiguous():
+            raise GppError(f"nodes must be a contiguous vector of 1..{MAX_NODES} values (got {tuple(nodes.shape)})")
+        Q = nodes.numel()
+        for t, n, pts in ((m, "m", Mr), (scale, "scale", Mc)):
+            if t.dim() != 1 or t.numel() != pts or not t.is_contiguous():
+                raise GppError(f"{n} must be a contiguous vector of {pts} values (got {tuple(t.shape)})")
+        if out.dim() != 2 or out.shape[0] < Mc or out.shape[1] != Q or not out.is_contiguous():
+            raise GppError(f"out must be a contiguous matrix of (at least) {Mc} x {Q} doubles (got {tuple(out.shape)})")
+        self.ensure_workspace(OP_POST_CROSS_MIN, Mr, Mc, 0, Q)
+        self._stream()
+        status = self.lib.gpp_post_cross_min(self.h, Uc.data_ptr(), Mc, Ur.data_ptr(), Mr, D, w.data_ptr(), sf2.data_ptr(), int(kind),
+                                             int(d_split), Vc.data_ptr(), _ld(Vc), Vr.data_ptr(), _ld(Vr), K, 1 if transposed else 0,
+                                             m.data_ptr(), scale.data_ptr(), nodes.data_ptr(), Q, out.data_ptr())
+        if status == NO_WORKSPACE:
+            raise GppError("gpp_post_cross_min: the handle's scratch workspace is missing or too small")
+        check(status, "gpp_post_cross_min")
+        return out
+
+
+
+def post_cross_min_workspace_bytes(Mc: int, Mr: int, Q: int) -> int:
+    """Scratch bytes of one ``post_cross_min`` launch (a host-side query: no handle, no device)."""
+    from ._lib import load
+
+    return int(load().gpp_workspace_bytes(None, OP_POST_CROSS_MIN, int(Mr), int(Mc), 0, int(Q)))
 
 
 def get_context(device) -> GppContext:

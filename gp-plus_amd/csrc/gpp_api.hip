@@ -1238,6 +1238,7 @@ size_t gpp_workspace_bytes(gpp_handle_t h, int op, int64_t N, int64_t M, int D, 
   if (op == GPP_OP_APPLY_GRAD) return gpp_apply_ws_bytes(N, M, D) + 256;
   if (op == GPP_OP_APPEND) return gpp_append_ws_bytes(N, M) + 256;
   if (op == GPP_OP_POST_CROSS) return gpp_post_cross_ws_bytes(M, N) + 256;
+  if (op == GPP_OP_POST_CROSS_MIN) return gpp_post_cross_min_ws_bytes(M, N, S) + 256;
   return 0;
 }
 

@@ -786,6 +786,164 @@ __global__ __launch_bounds__(256, VAR == 2 ? 2 : 1) void gpp_post_cross_f64(Gemm
   gemm_tile<VAR, 64, 64, 2, 16, 2, 2>(p, tm, tn, p.A, p.B, nullptr, nullptr, smem, GemmNoHook(), PostCrossEpilogue<MAT>{e, t, p.N});
 }
 
+// ---- Vc Vr^T with the minima of affine images of the posterior cross-covariance as its epilogue (gpp_post_cross_min in gpp.h) -----
+// The knowledge gradient's reduction: for every node k < Q, min_r (m_r + t_ck c_cr) with c = g - acc as in PostCrossEpilogue (the
+// same staging, r2 order, exponential and Matern factors) and t_ck = nodes[k] * scale[c], one rounded product per row and node.
+// The 8 entries of a half-slab (2 rows x 4 columns per lane) stay in registers while a rolled loop walks the nodes: per node and
+// row 4 fma + min, then the 16-lane butterfly, after which every lane of the row holds the half-slab's final minimum — nothing is
+// collected in LDS.  Lane li keeps node 16 j + li, so each group of 16 nodes leaves as one 128-byte store per row.  A column beyond
+// M_r enters with c = 0 and m = +inf (selects): it yields +inf, never m_r + 0.  The two column halves (waves) record separately:
+// rec[((tile 2 + half) 128 + row) Q + k], every slot written exactly once (rows beyond M_c too: they are never read);
+// gpp_post_cross_min_finish (gpp_alc.hip) takes the minimum over a row's records in index order.  Minima are exact and
+// order-independent, so no rounding depends on the tiling.
+// (the scalar-file remark in PostCrossEpilogue holds here as well: the nodes sit in LDS, not behind a uniform pointer)
+template <bool MAT>
+struct PostCrossMinEpilogue {
+  PostCrossMinArgs e;
+  int tile, Mr;
+  static constexpr int T = 128, DC = 16, QMAX = 64;
+  static constexpr int SLAB = 2 * DC * T + 2 * T + QMAX;  // doubles in front of the slab
+  static_assert((SLAB & 1) == 0 && (SLAB + 16 * 256) * sizeof(double) <= 2 * 2 * BK16 * ldt_mc(T) * sizeof(double) &&
+                    (SLAB + 16 * 256) * sizeof(double) <= 2 * 2 * T * LDK * sizeof(double),
+                "the epilogue lives in the main loop's LDS");
+  __device__ __forceinline__ void operator()(const v4d (&acc4)[4][4], int row0, int col0, int Mc, double* __restrict__ smem) const {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64, li = lane & 15, lk = lane >> 4;
+    const int D = e.dk & 255, kind = (e.dk >> 8) & 255;
+    const int dsp = (!MAT || kind == 0) ? D : ((e.dk >> 16) & 255);
+    const int Q = e.dk >> 24;
+    double* __restrict__ sa = smem;           // staged features of the tile's rows (candidates), [d][r], times sqrt(w_d)
+    double* __restrict__ sb = sa + DC * T;    // ... of its columns (reference points)
+    double* __restrict__ sm = sb + DC * T;    // m of the columns, +inf beyond M_r
+    double* __restrict__ ss = sm + T;         // scale of the rows, 0 beyond M_c
+    double* __restrict__ sz = ss + T;         // the nodes
+    double* __restrict__ slab = smem + SLAB;  // [16 values][256 lanes]
+    const double* __restrict__ Uc = e.Uc;
+    const double* __restrict__ Ur = e.Ur;
+    const double* __restrict__ wp = e.w;
+    // this wave's records: column half (wave & 1) of the tile
+    double* __restrict__ rec = e.rec + ((int64_t)tile * 2 + (wave & 1)) * T * Q;
+    Uc += (int64_t)row0 * (e.dk & 255);
+    Ur += (int64_t)col0 * (e.dk & 255);
+    int rlim = Mc - row0, clim = Mr - col0;  // rows / columns of the tile inside the block
+    asm volatile("" : "+v"(Uc), "+v"(Ur), "+v"(wp), "+v"(rec), "+v"(rlim), "+v"(clim));
+    auto stage = [&](int d0) {
+      for (int x = tid; x < DC * T; x += 256) {
+        const int dd = x / T, r = x - dd * T, d = d0 + dd;
+        const bool okd = d < D;
+        const double sw = okd ? sqrt(wp[okd ? d : 0]) : 0.0;
+        sa[x] = (okd && r < rlim) ? Uc[r * D + d] * sw : 0.0;
+        sb[x] = (okd && r < clim) ? Ur[r * D + d] * sw : 0.0;
+      }
+    };
+    if (tid < T) sm[tid] = (tid < clim) ? e.m[col0 + tid] : __builtin_huge_val();
+    else ss[tid - T] = (tid - T < rlim) ? e.scale[row0 + tid - T] : 0.0;
+    if (tid < Q) sz[tid] = e.nodes[tid];
+    const bool one = (D <= DC);  // work-group uniform
+    if (one) stage(0);
+    __syncthreads();
+
+    const double sf2 = *e.sf2;
+    const GppExpConsts ec = gpp_exp_consts();
+#pragma unroll
+    for (int a4 = 0; a4 < 4; ++a4) {
+#pragma unroll
+      for (int v = 0; v < 4; ++v)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) slab[(v * 4 + b) * 256 + tid] = acc4[a4][b][v];
+#pragma unroll 1
+      for (int h = 0; h < 2; ++h) {
+        const int ra = wm + 16 * a4 + 8 * h + lk;  // this half's rows inside the tile: ra and ra + 4
+        const int cb = wn + li;                    // its columns: cb + 16 b
+        double r2[2][4], r2m[MAT ? 2 : 1][MAT ? 4 : 1];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            r2[a][b] = 0.0;
+            if (MAT) r2m[MAT ? a : 0][MAT ? b : 0] = 0.0;
+          }
+#pragma unroll 1
+        for (int d0 = 0; d0 < D; d0 += DC) {
+          if (!one) {
+            __syncthreads();  // (every wave has read the previous chunk)
+            stage(d0);
+            __syncthreads();
+          }
+          const int nd = min(DC, D - d0);
+#pragma unroll 2
+          for (int dd = 0; dd < nd; ++dd) {
+            const double ua[2] = {sa[dd * T + ra], sa[dd * T + ra + 4]};
+            const bool second = MAT && (d0 + dd >= dsp);
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+              const double ub = sb[dd * T + cb + 16 * b];
+#pragma unroll
+              for (int a = 0; a < 2; ++a) {
+                const double df = ua[a] - ub;
+                if (MAT && second) r2m[MAT ? a : 0][MAT ? b : 0] = fma(df, df, r2m[MAT ? a : 0][MAT ? b : 0]);
+                else r2[a][b] = fma(df, df, r2[a][b]);
+              }
+            }
+          }
+        }
+        double cv[2][4], mb[4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) mb[b] = sm[cb + 16 * b];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            double kv = gpp_exp_nonpos(-r2[a][b], ec);
+            if constexpr (MAT) {  // the factors of kfun (gpp_build.hip)
+              if (kind == 1) {
+                const double r = sqrt(3.0 * 2.0 * r2m[MAT ? a : 0][MAT ? b : 0]);
+                kv *= (1.0 + r) * gpp_exp_nonpos(-r, ec);
+              } else if (kind == 2) {
+                const double r = sqrt(5.0 * 2.0 * r2m[MAT ? a : 0][MAT ? b : 0]);
+                kv *= (1.0 + r + r * r * (1.0 / 3.0)) * gpp_exp_nonpos(-r, ec);
+              }
+            }
+            const double c = sf2 * kv - slab[((2 * h + a) * 4 + b) * 256 + tid];
+            cv[a][b] = (cb + 16 * b < clim) ? c : 0.0;  // (a select: whatever a column beyond M_r holds never reaches a minimum)
+          }
+        const double sc[2] = {ss[ra], ss[ra + 4]};
+        double keep[2] = {0.0, 0.0};
+#pragma unroll 1
+        for (int k = 0; k < Q; ++k) {
+          const double z = sz[k];
+#pragma unroll
+          for (int a = 0; a < 2; ++a) {
+            const double t = z * sc[a];
+            double s = fma(cv[a][0], t, mb[0]);
+#pragma unroll
+            for (int b = 1; b < 4; ++b) s = fmin(s, fma(cv[a][b], t, mb[b]));
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) s = fmin(s, __shfl_xor(s, o));  // the 16 lanes (li) that share this row
+            keep[a] = (li == (k & 15)) ? s : keep[a];
+          }
+          if ((k & 15) == 15 || k + 1 == Q) {  // (uniform) nodes (k & ~15) .. k leave, one per lane
+            const int kn = (k & ~15) + li;
+            if (kn <= k) {
+              rec[(int64_t)ra * Q + kn] = keep[0];
+              rec[(int64_t)(ra + 4) * Q + kn] = keep[1];
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();  // (the caller may stage another tile at once)
+  }
+};
+
+template <int VAR, bool MAT>
+__global__ __launch_bounds__(256, VAR == 2 ? 2 : 1) void gpp_post_cross_min_f64(GemmArgs p, PostCrossMinArgs e) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int t = (int)blockIdx.x;
+  const int tm = t / p.tiles_n, tn = t - tm * p.tiles_n;
+  gemm_tile<VAR, 64, 64, 2, 16, 2, 2>(p, tm, tn, p.A, p.B, nullptr, nullptr, smem, GemmNoHook(), PostCrossMinEpilogue<MAT>{e, t, p.N});
+}
+
 // LDS bytes of an instantiation (dynamic: the wide-chunk variants exceed the 64 KiB static limit)
 constexpr size_t gemm_lds_bytes(int var, int tm, int tn, int bk, int nbuf) {
   const int tx = tm > tn ? tm : tn;
@@ -1111,6 +1269,33 @@ hipError_t gpp_launch_post_cross(hipStream_t s, int variant, const GemmArgs& a_i
   const size_t bytes = gemm_lds_bytes(variant, 128, 128, 16, 2);
   auto* fn = variant == 2 ? (mat ? gpp_post_cross_f64<2, true> : gpp_post_cross_f64<2, false>)
                           : (mat ? gpp_post_cross_f64<0, true> : gpp_post_cross_f64<0, false>);
+  static std::atomic<bool> attr_set[4][64];  // per instantiation and device
+  int dev = 0;
+  hipError_t err = hipGetDevice(&dev);
+  if (err != hipSuccess) return err;
+  const int which = (variant == 2 ? 2 : 0) + (mat ? 1 : 0);
+  if (dev < 0 || dev >= 64 || !attr_set[which][dev]) {
+    err = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (err != hipSuccess) return err;
+    if (dev >= 0 && dev < 64) attr_set[which][dev] = true;
+  }
+  hipLaunchKernelGGL(fn, dim3((unsigned)nt), dim3(256), bytes, s, a, e);
+  return hipGetLastError();
+}
+
+// as gpp_launch_post_cross; e.dk carries Q
+hipError_t gpp_launch_post_cross_min(hipStream_t s, int variant, const GemmArgs& a_in, const PostCrossMinArgs& e) {
+  GemmArgs a = a_in;
+  const int Q = e.dk >> 24;
+  if (a.M <= 0 || a.N <= 0 || a.K <= 0 || (variant != 0 && variant != 2) || Q < 1 || Q > 64) return hipErrorInvalidValue;
+  a.tiles_m = (a.M + 127) / 128;
+  a.tiles_n = (a.N + 127) / 128;
+  const int64_t nt = (int64_t)a.tiles_m * a.tiles_n;
+  if (nt >= (int64_t)1 << 31) return hipErrorInvalidValue;
+  const bool mat = ((e.dk >> 8) & 255) != 0;
+  const size_t bytes = gemm_lds_bytes(variant, 128, 128, 16, 2);
+  auto* fn = variant == 2 ? (mat ? gpp_post_cross_min_f64<2, true> : gpp_post_cross_min_f64<2, false>)
+                          : (mat ? gpp_post_cross_min_f64<0, true> : gpp_post_cross_min_f64<0, false>);
   static std::atomic<bool> attr_set[4][64];  // per instantiation and device
   int dev = 0;
   hipError_t err = hipGetDevice(&dev);

