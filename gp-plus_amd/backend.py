@@ -29,6 +29,7 @@ OP_APPLY_GRAD = 4  # gpp_kernel_apply_grad / gpp_rff_apply_grad: N carries the c
 OP_APPEND = 5  # gpp_chol_append: N cached points, M carries the appended count q
 OP_POST_CROSS = 6  # gpp_post_cross_sq: N carries the reference count M_r, M the candidate count M_c
 OP_POST_CROSS_MIN = 7  # gpp_post_cross_min: N carries M_r, M carries M_c, S the node count Q
+OP_POINT_GRAM = 8  # gpp_point_gram with a weighted sum: M points, D carries the rows per point
 #: most quadrature nodes gpp_post_cross_min takes (gpp_gemm.hip PostCrossMinEpilogue::QMAX)
 MAX_NODES = 64
 #: longest contraction gpp_kernel_apply / gpp_rff_apply run without scratch (gpp_apply.hip AP_SPLIT)
@@ -1027,6 +1028,84 @@ class GppContext:
             raise GppError("gpp_post_cross_min: the handle's scratch workspace is missing or too small")
         check(status, "gpp_post_cross_min")
         return out
+
+    # -- posterior of the gradient -----------------------------------------------------------------------------------------------
+    @_on_own_device
+    def cross_kernel_dx(self, Ua, Ub, w, sf2, d0, nd, out, *, kind=KIND_RBF, d_split=0):
+        """out[n, a nd + j] = d/du_{d0+j} sf2 k(u, Ub_n; w) at u = Ua_a: the derivative cross block with the training points as rows,
+        the operand ``predict_tn`` takes (gpp_cross_kernel_dx).  ``out``: an N x (M nd) window of a row-major buffer with an even
+        leading dimension, 16-byte aligned; what lies beyond column M nd is not written.  Everything is checked before the launch."""
+        d0, nd = int(d0), int(nd)
+        for t, n in ((Ua, "Ua"), (Ub, "Ub"), (w, "w"), (sf2, "sf2"), (out, "Dk")):
+            _need(t, torch.float64, n)
+        if Ua.dim() != 2 or Ub.dim() != 2 or Ua.shape[1] != Ub.shape[1]:
+            raise GppError(f"Ua and Ub must be matrices with the same feature count (got {tuple(Ua.shape)}, {tuple(Ub.shape)})")
+        (M, D), N = Ua.shape, Ub.shape[0]
+        _check_features(D)
+        if min(M, N) < 1:
+            raise GppError(f"cross_kernel_dx takes M, N >= 1 (got {M}, {N})")
+        if not (Ua.is_contiguous() and Ub.is_contiguous()):
+            raise GppError("Ua and Ub must be contiguous")
+        if w.numel() != D or not w.is_contiguous():
+            raise GppError(f"w must be a contiguous vector of {D} weights (got {w.numel()})")
+        if sf2.numel() < 1:
+            raise GppError("sf2 must hold one value")
+        if not (0 <= int(d_split) <= D) or kind not in (KIND_RBF, KIND_MATERN32, KIND_MATERN52):
+            raise GppError(f"bad kernel kind / d_split ({kind}, {d_split}) for {D} features")
+        if nd < 1 or d0 < 0 or d0 + nd > D:
+            raise GppError(f"the differentiated columns [{d0}, {d0 + nd}) must be a non-empty range of the {D} features")
+        if out.dim() != 2 or out.stride(1) != 1 or out.shape != (N, M * nd):
+            raise GppError(f"Dk must be {N} x {M * nd} with unit column stride (got {tuple(out.shape)})")
+        ld = _ld(out)
+        if ld & 1 or ld < M * nd:
+            raise GppError(f"Dk: the leading dimension ({ld}) must be even and at least {M * nd}")
+        if out.data_ptr() & 15:
+            raise GppError("Dk must be 16-byte aligned")
+        self._stream()
+        check(self.lib.gpp_cross_kernel_dx(self.h, Ua.data_ptr(), M, Ub.data_ptr(), N, D, w.data_ptr(), sf2.data_ptr(), int(kind),
+                                           int(d_split), d0, nd, out.data_ptr(), ld), "gpp_cross_kernel_dx")
+        return out
+
+    @_on_own_device
+    def point_gram(self, Q, nd, G=None, Gsum=None, *, omega=None):
+        """G[a] = Q_a Q_a^T of the ``nd`` consecutive rows of each point in ``Q`` ((M nd) x N, a window of a row-major buffer with an
+        even leading dimension, 16-byte aligned; nd <= 16) and / or Gsum = sum_a omega_a G[a] (gpp_point_gram).  ``G``: a contiguous
+        M x nd x nd tensor or None; ``Gsum``: a contiguous nd x nd matrix or None; ``omega``: M weights or None for all ones.
+        Everything is checked before any launch."""
+        nd = int(nd)
+        _need(Q, torch.float64, "Q")
+        if Q.dim() != 2 or Q.stride(1) != 1:
+            raise GppError("Q must be 2-D with unit column stride")
+        if nd < 1 or nd > 16:
+            raise GppError(f"point_gram takes 1..16 rows per point (got {nd})")
+        rows, N = Q.shape
+        if rows < nd or rows % nd or N < 1:
+            raise GppError(f"Q is {tuple(Q.shape)}: its rows must be a positive multiple of nd = {nd} and it needs a column")
+        M = rows // nd
+        ld = _ld(Q)
+        if ld & 1 or ld < N:
+            raise GppError(f"Q: the leading dimension ({ld}) must be even and at least {N}")
+        if Q.data_ptr() & 15:
+            raise GppError("Q must be 16-byte aligned")
+        if G is None and Gsum is None:
+            raise GppError("point_gram needs G or Gsum")
+        for t, n, shape in ((G, "G", (M, nd, nd)), (Gsum, "Gsum", (nd, nd))):
+            if t is not None:
+                _need(t, torch.float64, n)
+                if tuple(t.shape) != shape or not t.is_contiguous():
+                    raise GppError(f"{n} must be a contiguous {shape} tensor (got {tuple(t.shape)})")
+        if omega is not None:
+            _need(omega, torch.float64, "omega")
+            if omega.dim() != 1 or omega.numel() != M or not omega.is_contiguous():
+                raise GppError(f"omega must be a contiguous vector of {M} weights (got {tuple(omega.shape)})")
+        if Gsum is not None:
+            self.ensure_workspace(OP_POINT_GRAM, 0, M, nd, 0)
+        self._stream()
+        status = self.lib.gpp_point_gram(self.h, Q.data_ptr(), ld, M, nd, N, _ptr(omega), _ptr(G), _ptr(Gsum))
+        if status == NO_WORKSPACE:
+            raise GppError("gpp_point_gram: the handle's scratch workspace is missing or too small")
+        check(status, "gpp_point_gram")
+        return G, Gsum
 
 
 

@@ -249,6 +249,7 @@ struct PostCrossMinArgs {
 };
 hipError_t gpp_launch_post_cross_min(hipStream_t s, int variant, const GemmArgs& p, const PostCrossMinArgs& e);
 size_t gpp_post_cross_min_ws_bytes(int64_t Mc, int64_t Mr, int Q);  // gpp_alc.hip
+size_t gpp_point_gram_ws_bytes(int64_t M, int nd);                  // gpp_dgrad.hip
 
 // one-wave kernels on a stream (gpp_gemm.hip): wait until counters[id] >= target — a wait that exceeds `budget` ticks of the 100 MHz
 // clock sets the abort word counters[0] and *info = GPP_INFO_EXEC_TIMEOUT + ms —, and counters[id] += 1 behind a release fence

@@ -21,7 +21,8 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .backend import KIND_RBF, UPLO_FULL, UPLO_UPPER, GppContext, get_context, rows_buffer, square_buffer
+from .backend import (KIND_MATERN32, KIND_RBF, UPLO_FULL, UPLO_UPPER, GppContext, get_context, row_stride, rows_buffer,
+                      square_buffer)
 from .psd_safe import inputs_nan_probe, psd_safe
 from . import settings
 
@@ -842,6 +843,133 @@ def variance_reduction(cache: FactorCache, Uc, tau_c, Ur, omega=None, q: int = 1
             with _stage("alc_append"):
                 var_c = _append_pick_coordinate(cache, Ucr, Uc, j, s[j], Vc, Vr, K, var_c, transposed)
         return first, torch.tensor(picks, dtype=torch.int64, device=dev), torch.stack(gains)
+
+
+#: Most bytes the derivative cross block Dk and the product Q = Dk^T Linv^T of ONE chunk of ``gradient_from_cache`` may take, each:
+#: the test points go in chunks of as many points as fit (at least one).  At N = 20 000 and nd = 8 that is 209 points per chunk.
+GRAD_CHUNK_BYTES = 256 << 20
+
+
+def gradient_prior_curvature(spec: KernelSpec, d0: int, nd: int) -> torch.Tensor:
+    """kappa_j = d^2 (sf2 k) / du_j du'_j at u' = u for the features d0 .. d0 + nd - 1: c_j w_j sf2 with c_j = 2 on a feature of
+    the RBF factor, 6 on a Matern-3/2 and 10 / 3 on a Matern-5/2 feature (h'(0) = -3 and -5 / 3 of the Matern factor h(r),
+    r^2 = 2 nu 2 sum_d w_d delta_d^2): the prior variance of the gradient's components, which are uncorrelated a priori."""
+    D = spec.w.numel()
+    split = D if spec.kind == KIND_RBF else int(spec.d_split)
+    c = torch.full((D,), 2.0, dtype=torch.float64, device=spec.w.device)
+    if spec.kind != KIND_RBF:
+        c[split:] = 6.0 if spec.kind == KIND_MATERN32 else 10.0 / 3.0
+    return (c * spec.w.reshape(-1) * spec.sf2.reshape(()))[d0:d0 + nd]
+
+
+def _gradient_chunk_points(N: int, nd: int) -> int:
+    per_point = 8 * nd * row_stride(N)
+    mc = max(1, GRAD_CHUNK_BYTES // per_point)
+    while mc > 1 and 8 * N * row_stride(mc * nd) > GRAD_CHUNK_BYTES:
+        mc -= 1
+    return mc
+
+
+@torch.no_grad()
+def gradient_from_cache(cache: FactorCache, Us, d0: int, nd: int, want: str, omega=None):
+    """Posterior of the gradient of the latent f with respect to the features d0 .. d0 + nd - 1 at the feature rows ``Us`` (M x D):
+    grad f(x_a) | data ~ N(g_a, S_a) with, for Dk[n, (a, j)] = d/du_{d0+j} sf2 k(u_a, U_n) and Q = Dk^T Linv^T,
+        g_a = Q_a z = Dk_a^T alpha,        S_a = diag(kappa) - Q_a Q_a^T        (kappa: ``gradient_prior_curvature``).
+    No observation noise enters: noise has no derivative.  ``want``:
+      "mean"  g (M x nd) alone, by ONE gpp_kernel_apply_grad call (C = alpha, Gbar = 1), O(M N): no block is formed;
+      "std"   (g, var): the diagonal of S (M x nd), unclamped;
+      "cov"   (g, S): M x nd x nd, bitwise symmetric;
+      "sum"   (sum_a omega_a g_a g_a^T, sum_a omega_a S_a), nd x nd each: the two parts of the active-subspace matrix, without
+              storing per-point matrices; ``omega``: M weights, None for 1 / M each.
+    For the last three the points go in chunks whose Dk and Q stay within ``GRAD_CHUNK_BYTES`` each; per chunk gpp_cross_kernel_dx
+    writes Dk, gpp_predict_tn (kss = kappa tiled per point) gives Q, g and the variance diagonal from the product every prediction
+    uses, and gpp_point_gram reduces Q to the per-point Gram matrices or their weighted sum; the sums of "sum" add up in chunk
+    order.  For nd > 16 (beyond gpp_point_gram) the Gram matrices come from ``torch.bmm`` on the chunk's Q.  Everything is in the
+    cache's (scaled-target) units.  The cache is only read (and refreshed when another model has taken the shared workspace).
+    Refused under ``settings.sharded_evaluation`` and inside a graph capture, like ``variance_reduction``."""
+    if want not in ("mean", "std", "cov", "sum"):
+        raise ValueError(f"want must be 'mean', 'std', 'cov' or 'sum' (got {want!r})")
+    if settings.sharded_evaluation.value() is not None:
+        raise NotImplementedError("gradient_from_cache is not available under settings.sharded_evaluation")
+    dev = cache.U.device
+    gctx = cache.gctx
+    on_gpu = dev.type == "cuda"  # (anything else only under a stand-in context: the library itself has no CPU path)
+    with torch.cuda.device(dev) if on_gpu else nullcontext():
+        if on_gpu and torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("gradient_from_cache is not available inside a graph capture")
+        Us = _as_f64(Us.detach(), dev).contiguous()
+        N, D = cache.U.shape
+        d0, nd = int(d0), int(nd)
+        if Us.dim() != 2 or Us.shape[0] < 1 or Us.shape[1] != D:
+            raise ValueError(f"the test points must be at least one row of {D} features (got {tuple(Us.shape)})")
+        if nd < 1 or d0 < 0 or d0 + nd > D:
+            raise ValueError(f"the differentiated features [{d0}, {d0 + nd}) must be a non-empty range of the {D} features")
+        M = Us.shape[0]
+        if want == "sum":
+            if omega is None:
+                omega = torch.full((M,), 1.0 / M, dtype=torch.float64, device=dev)
+            else:
+                omega = _as_f64(omega.detach().reshape(-1), dev).contiguous()
+                if omega.numel() != M:
+                    raise ValueError(f"{omega.numel()} weights for {M} test points")
+        cache.refresh()  # (a cache of the shared workspace that another model has factored into since)
+        spec = cache.spec
+        w, sf2 = spec.w, spec.sf2.reshape(1)
+        if want == "mean":
+            g = torch.empty((M, D), dtype=torch.float64, device=dev)
+            with _stage("grad_mean"):
+                gctx.kernel_apply_grad(Us, cache.U, w, sf2, cache.alpha.reshape(-1, 1), torch.ones((M, 1), dtype=torch.float64, device=dev),
+                                       g, kind=spec.kind, d_split=spec.d_split)
+            return g[:, d0:d0 + nd].contiguous()
+        kappa = gradient_prior_curvature(spec, d0, nd)
+        mean = torch.empty((M, nd), dtype=torch.float64, device=dev)
+        var = torch.empty((M, nd), dtype=torch.float64, device=dev) if want == "std" else None
+        cov = torch.empty((M, nd, nd), dtype=torch.float64, device=dev) if want == "cov" else None
+        if want == "sum":
+            mean_part = torch.zeros((nd, nd), dtype=torch.float64, device=dev)
+            cov_part = torch.zeros((nd, nd), dtype=torch.float64, device=dev)
+        step = _gradient_chunk_points(N, nd)
+        for a0 in range(0, M, step):
+            mc = min(step, M - a0)
+            Dk = rows_buffer(N, mc * nd, dev)
+            Q = rows_buffer(mc * nd, N, dev)
+            g_c = torch.empty(mc * nd, dtype=torch.float64, device=dev)
+            v_c = torch.empty(mc * nd, dtype=torch.float64, device=dev)
+            with _stage("cross_kernel_dx"):
+                gctx.cross_kernel_dx(Us[a0:a0 + mc], cache.U, w, sf2, d0, nd, Dk, kind=spec.kind, d_split=spec.d_split)
+            with _stage("grad_predict_tn"):
+                gctx.predict_tn(cache.Linv, cache.z, Dk, kappa.repeat(mc), Q, g_c, v_c)
+            del Dk
+            g_c = g_c.view(mc, nd)
+            mean[a0:a0 + mc] = g_c
+            if want == "std":
+                var[a0:a0 + mc] = v_c.view(mc, nd)
+                continue
+            with _stage("point_gram"):
+                if nd <= 16:
+                    if want == "cov":
+                        G = torch.empty((mc, nd, nd), dtype=torch.float64, device=dev)
+                        gctx.point_gram(Q, nd, G=G)
+                    else:
+                        Gsum = torch.empty((nd, nd), dtype=torch.float64, device=dev)
+                        gctx.point_gram(Q, nd, Gsum=Gsum, omega=omega[a0:a0 + mc])
+                else:
+                    Q3 = Q.unflatten(0, (mc, nd))
+                    G = torch.bmm(Q3, Q3.transpose(1, 2))
+                    G = 0.5 * (G + G.transpose(1, 2))
+                    if want == "sum":
+                        Gsum = (omega[a0:a0 + mc, None, None] * G).sum(0)
+            if want == "cov":
+                cov[a0:a0 + mc] = torch.diag(kappa) - G
+            else:
+                om = omega[a0:a0 + mc]
+                mean_part += (g_c * om[:, None]).T @ g_c
+                cov_part += om.sum() * torch.diag(kappa) - Gsum
+        if want == "std":
+            return mean, var
+        if want == "cov":
+            return mean, cov
+        return 0.5 * (mean_part + mean_part.T), cov_part
 
 
 #: Scratch one gpp_post_cross_min launch of ``knowledge_gradient`` may ask for: above it the reference rows go in column chunks

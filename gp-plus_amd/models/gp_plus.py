@@ -36,6 +36,19 @@ from .gpregression import GPR
 _QUANT_CLASSES = ['Rough_RBF', 'RBFKernel', 'Matern32Kernel', 'Matern12Kernel', 'Matern52Kernel']  # gp_plus.py:150
 
 
+class ActiveSubspace:
+    """What ``GP_Plus.active_subspace`` returns: the matrix C = sum_a w_a (g_a g_a^T + S_a), its eigen-decomposition (eigenvalues
+    descending, eigenvectors as columns), its two parts and its diagonal (the derivative-based sensitivity measures)."""
+    __slots__ = ("matrix", "eigenvalues", "eigenvectors", "mean_part", "cov_part", "sensitivity")
+
+    def __init__(self, matrix, eigenvalues, eigenvectors, mean_part, cov_part, sensitivity):
+        self.matrix, self.eigenvalues, self.eigenvectors = matrix, eigenvalues, eigenvectors
+        self.mean_part, self.cov_part, self.sensitivity = mean_part, cov_part, sensitivity
+
+    def __repr__(self):
+        return f"ActiveSubspace(p={self.matrix.shape[0]}, eigenvalues={self.eigenvalues.tolist()})"
+
+
 def _rough_transform(x):
     return 2.0 ** (-0.5) * torch.pow(10, -x / 2)
 
@@ -439,6 +452,94 @@ class GP_Plus(GPR):
             object.__setattr__(enc, '_owner', weakref.ref(child))
         child._cat_cache = {}
         child.__dict__.pop('_seen_levels', None)
+
+    # ---- posterior of the gradient -------------------------------------------------------------------
+    def _gradient_rows(self, X, what: str):
+        """The rows of ``predict_gradient`` / ``active_subspace``, validated on the host."""
+        X = self._alc_rows(X, "Xtest" if what == "predict_gradient" else "X", what)
+        if int(self.quant_index.numel()) == 0:
+            raise ValueError(f"{what}: the model has no quantitative input column to differentiate")
+        return X
+
+    def _gradient_operands(self, X, what: str):
+        """(cache, feature rows, first differentiated feature, their count) for the validated rows ``X``."""
+        from .. import settings as gpp_settings
+        from ..backend import get_context
+        from ..gpcore.module import Module
+
+        p = int(self.quant_index.numel())
+        if gpp_settings.sharded_evaluation.value() is not None:
+            raise NotImplementedError(f"{what} is not available under settings.sharded_evaluation")
+        train_x = self.train_inputs[0]
+        get_context(train_x.device)  # (raises for anything but a GPU: there is no CPU path)
+        self.eval()
+        with torch.no_grad():
+            cache = self._ensure_prediction_cache()
+            Us = Module.__call__(self, X.to(train_x)).lazy_covariance_matrix.U1
+        return cache, Us, Us.shape[1] - p, p
+
+    def predict_gradient(self, Xtest, return_std=True, return_cov=False):
+        """Posterior of the gradient of the latent f with respect to the quantitative input columns at the rows of ``Xtest``:
+        grad f(x) | data ~ N(g(x), S(x)), closed form for a GP.  Returns the mean (M, p) — and the std (M, p) of its components
+        with ``return_std``, or instead the covariance (M, p, p) with ``return_cov`` — in the units of y per unit of the model's
+        input column, columns in ``quant_index`` order.  The categorical columns are not differentiated and do not appear in the
+        output.  This is the distribution ``predict_with_grad`` has no access to (autograd gives the slope of the posterior mean
+        and std, not the spread of the slope).  Observation noise has no derivative and is never added; every supported prior
+        mean has zero gradient in these columns.  std = sqrt(max(var, 0)) |y_std|; the covariance is returned unclamped, times
+        y_std^2, bitwise symmetric.  The outputs carry no autograd graph.
+
+        Nothing is factorised: the mean alone is one gpp_kernel_apply_grad call against the cached alpha, O(M N); the spread costs
+        one product of the derivative cross block (gpp_cross_kernel_dx) with the cached inverse factor, O(N^2 M p), in chunks of
+        ``linalg.GRAD_CHUNK_BYTES``, and gpp_point_gram for the covariance.  The model is put in eval mode and is otherwise
+        untouched; a warm cache is reused, a model returned by ``condition_on`` included.  No reference counterpart.
+
+        ``ValueError`` before any device work: wrong column count, an empty set, NaN / inf, a categorical level or source the model
+        has not seen, a model without a quantitative column.  ``NotImplementedError`` under ``settings.sharded_evaluation`` or a
+        graph capture."""
+        from ..linalg import gradient_from_cache
+
+        cache, Us, d0, p = self._gradient_operands(self._gradient_rows(Xtest, "predict_gradient"), "predict_gradient")
+        scale = self.y_std.detach().to(torch.float64)
+        with torch.no_grad():
+            if return_cov:
+                mean, cov = gradient_from_cache(cache, Us, d0, p, "cov")
+                return mean * scale, cov * scale ** 2
+            if return_std:
+                mean, var = gradient_from_cache(cache, Us, d0, p, "std")
+                return mean * scale, var.clamp_min(0.0).sqrt() * scale.abs()
+            return gradient_from_cache(cache, Us, d0, p, "mean") * scale
+
+    def active_subspace(self, X, weights=None):
+        """Active-subspace matrix C = E_x[grad f grad f^T] = sum_a w_a (g_a g_a^T + S_a) of the posterior over the rows of ``X``
+        (``weights``: non-negative, not all zero, one per row; default 1 / M each), with (g_a, S_a) the gradient's posterior mean
+        and covariance of ``predict_gradient``: the posterior expectation of the matrix, not the matrix of the posterior mean.
+        Its leading eigenvectors are the directions of the quantitative inputs the response varies along; its diagonal holds the
+        derivative-based global sensitivity measures nu_j.  Returns an ``ActiveSubspace`` with ``matrix`` (p x p, symmetric),
+        ``eigenvalues`` (descending) and ``eigenvectors`` (columns) from ``torch.linalg.eigh``, ``mean_part`` = sum w g g^T,
+        ``cov_part`` = sum w S and ``sensitivity`` = diag(matrix), in y^2 per squared input unit, ``quant_index`` order.  The
+        per-point matrices are never stored (gpp_point_gram sums them).  Validation and refusals as in ``predict_gradient``, and
+        ``ValueError`` for weights that are negative, not finite, all zero or of the wrong length."""
+        from ..linalg import gradient_from_cache
+
+        X = self._gradient_rows(X, "active_subspace")
+        if weights is not None:
+            weights = data_type_check(weights).reshape(-1).to(torch.float64)
+            if weights.shape[0] != X.shape[0]:
+                raise ValueError(f"active_subspace: {weights.shape[0]} weights for {X.shape[0]} rows")
+            if not bool(torch.isfinite(weights).all()) or bool((weights < 0).any()):
+                raise ValueError("active_subspace: the weights must be finite and non-negative")
+            if not bool((weights > 0).any()):
+                raise ValueError("active_subspace: the weights are all zero")
+        cache, Us, d0, p = self._gradient_operands(X, "active_subspace")
+        with torch.no_grad():
+            mean_part, cov_part = gradient_from_cache(cache, Us, d0, p, "sum",
+                                                      omega=None if weights is None else weights.to(Us.device))
+            scale = self.y_std.detach().to(torch.float64) ** 2
+            mean_part, cov_part = mean_part * scale, cov_part * scale
+            matrix = mean_part + cov_part
+            evals, evecs = torch.linalg.eigh(matrix)
+            return ActiveSubspace(matrix=matrix, eigenvalues=evals.flip(0), eigenvectors=evecs.flip(1), mean_part=mean_part,
+                                  cov_part=cov_part, sensitivity=torch.diagonal(matrix).clone())
 
     def noise_value(self):
         return self.likelihood.noise_covar.noise.detach() * self.y_std ** 2

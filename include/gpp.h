@@ -56,6 +56,7 @@ typedef struct gpp_handle_s* gpp_handle_t;
 #define GPP_OP_APPEND 5     /* gpp_chol_append: N cached points, M = q appended points (D and S are not read) */
 #define GPP_OP_POST_CROSS 6 /* gpp_post_cross_sq: N = M_r reference points, M = M_c candidates (D and S are not read) */
 #define GPP_OP_POST_CROSS_MIN 7 /* gpp_post_cross_min: N = M_r reference points, M = M_c candidates, S = Q nodes (D is not read) */
+#define GPP_OP_POINT_GRAM 8 /* gpp_point_gram with a weighted sum: M points, D = nd rows per point (N and S are not read) */
 
 const char* gpp_version(void);
 
@@ -623,6 +624,37 @@ int gpp_post_cross_sq(gpp_handle_t h, const double* Uc, int64_t Mc, const double
 int gpp_post_cross_min(gpp_handle_t h, const double* Uc, int64_t Mc, const double* Ur, int64_t Mr, int D, const double* w,
                        const double* sf2, int kind, int d_split, const double* Vc, int64_t ldc, const double* Vr, int64_t ldr,
                        int64_t K, int vt, const double* m, const double* scale, const double* nodes, int Q, double* out);
+
+/*
+ * Derivative cross block, for the posterior of the gradient (models/gp_plus.py predict_gradient; no reference counterpart):
+ *   Dk[n, a nd + j] = d/du_{d0+j} ( sf2 k(u, Ub_n; w) ) at u = Ua_a = 2 w_{d0+j} (Ua[a,d0+j] - Ub[n,d0+j]) m_f(a, n)
+ * with the multipliers of gpp_kernel_apply_grad: m_0 = -sf2 k on a feature of the RBF factor, m_1 = sf2 e1 h' on one of the Matern
+ * factor, h' formed without a division by r.  Ua: M x D, Ub: N x D row-major and contiguous; kind / d_split as in gpp_cross_kernel;
+ * D <= 64, nd >= 1, 0 <= d0, d0 + nd <= D.  Dk: N x (M nd) row-major — training points as rows, the operand Kns of gpp_predict_tn —
+ * ld >= M nd, ld even, 16-byte aligned.  The multiplier (one exp, plus the Matern polynomial) is computed once per pair (a, n) and
+ * serves its nd directions.  A feature with w_d == 0 gives an exact 0; a row of Ua that equals a row of Ub gives finite values for
+ * the Matern kinds too, and exact zeros in that pair's entries.  The columns [M nd, ld) are never written and nothing outside the
+ * stated extents is read.  One plain launch on the handle's stream, no workspace; every entry is a function of its own pair alone,
+ * so two launches agree bit for bit.
+ */
+int gpp_cross_kernel_dx(gpp_handle_t h, const double* Ua, int64_t M, const double* Ub, int64_t N, int D, const double* w,
+                        const double* sf2, int kind, int d_split, int d0, int nd, double* Dk, int64_t ld);
+
+/*
+ * Gram matrices of consecutive groups of nd rows, the explained part of the gradient's posterior covariance (Q = Dk^T Linv^T as
+ * gpp_predict_tn leaves it, rows = points x directions):
+ *   G[a][j][j'] = sum_{n < N} Q[a nd + j][n] Q[a nd + j'][n],          Gsum[j][j'] = sum_{a < M} omega_a G[a][j][j']
+ * Q: (M nd) x N row-major, ldq >= N, ldq even, 16-byte aligned; the columns [N, ldq) are never read.  1 <= nd <= 16.  G: M x nd x nd,
+ * contiguous, both triangles written and bitwise symmetric; NULL when only the sum is wanted.  Gsum: nd x nd, or NULL; omega: M
+ * weights, or NULL for all ones.  G and Gsum may not both be NULL.  A point's matrix is a sum in an order fixed by (N, nd) alone:
+ * bit for bit it does not depend on M, on the point's index or on the other points.  Gsum adds the points in index order in two
+ * further launches (groups of 32 points, then the groups), whose partial sums — and the points' matrices when G is NULL — go
+ * through the handle workspace: gpp_workspace_bytes(h, GPP_OP_POINT_GRAM, 0, M, nd, 0) bytes, needed only with Gsum;
+ * GPP_NO_WORKSPACE with nothing enqueued when it is missing.  Plain launches on the handle's stream, no float atomics: two calls
+ * agree bit for bit.
+ */
+int gpp_point_gram(gpp_handle_t h, const double* Q, int64_t ldq, int64_t M, int nd, int64_t N, const double* omega, double* G,
+                   double* Gsum);
 
 #ifdef __cplusplus
 }
