@@ -140,6 +140,8 @@ _SIGNATURES = {
     "gpp_cross_kernel_dx": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                     c_int, c_void_p, c_int64]),
     "gpp_point_gram": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    "gpp_kernel_dxdx": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                c_int, c_void_p, c_int64]),
 }
 
 _lib = None

@@ -1030,20 +1030,17 @@ class GppContext:
         return out
 
     # -- posterior of the gradient -----------------------------------------------------------------------------------------------
-    @_on_own_device
-    def cross_kernel_dx(self, Ua, Ub, w, sf2, d0, nd, out, *, kind=KIND_RBF, d_split=0):
-        """out[n, a nd + j] = d/du_{d0+j} sf2 k(u, Ub_n; w) at u = Ua_a: the derivative cross block with the training points as rows,
-        the operand ``predict_tn`` takes (gpp_cross_kernel_dx).  ``out``: an N x (M nd) window of a row-major buffer with an even
-        leading dimension, 16-byte aligned; what lies beyond column M nd is not written.  Everything is checked before the launch."""
-        d0, nd = int(d0), int(nd)
-        for t, n in ((Ua, "Ua"), (Ub, "Ub"), (w, "w"), (sf2, "sf2"), (out, "Dk")):
+    @staticmethod
+    def _dx_checks(what, sizes, Ua, Ub, w, sf2, d0, nd, kind, d_split):
+        """The operand checks ``cross_kernel_dx`` and ``kernel_dxdx`` share; returns the two row counts."""
+        for t, n in ((Ua, "Ua"), (Ub, "Ub"), (w, "w"), (sf2, "sf2")):
             _need(t, torch.float64, n)
         if Ua.dim() != 2 or Ub.dim() != 2 or Ua.shape[1] != Ub.shape[1]:
             raise GppError(f"Ua and Ub must be matrices with the same feature count (got {tuple(Ua.shape)}, {tuple(Ub.shape)})")
-        (M, D), N = Ua.shape, Ub.shape[0]
+        (Ma, D), Mb = Ua.shape, Ub.shape[0]
         _check_features(D)
-        if min(M, N) < 1:
-            raise GppError(f"cross_kernel_dx takes M, N >= 1 (got {M}, {N})")
+        if min(Ma, Mb) < 1:
+            raise GppError(f"{what} takes {sizes} >= 1 (got {Ma}, {Mb})")
         if not (Ua.is_contiguous() and Ub.is_contiguous()):
             raise GppError("Ua and Ub must be contiguous")
         if w.numel() != D or not w.is_contiguous():
@@ -1054,13 +1051,29 @@ class GppContext:
             raise GppError(f"bad kernel kind / d_split ({kind}, {d_split}) for {D} features")
         if nd < 1 or d0 < 0 or d0 + nd > D:
             raise GppError(f"the differentiated columns [{d0}, {d0 + nd}) must be a non-empty range of the {D} features")
-        if out.dim() != 2 or out.stride(1) != 1 or out.shape != (N, M * nd):
-            raise GppError(f"Dk must be {N} x {M * nd} with unit column stride (got {tuple(out.shape)})")
+        return Ma, Mb
+
+    @staticmethod
+    def _dx_window(name, out, rows, cols):
+        """The output window's checks of the same two; returns its leading dimension."""
+        _need(out, torch.float64, name)
+        if out.dim() != 2 or out.stride(1) != 1 or out.shape != (rows, cols):
+            raise GppError(f"{name} must be {rows} x {cols} with unit column stride (got {tuple(out.shape)})")
         ld = _ld(out)
-        if ld & 1 or ld < M * nd:
-            raise GppError(f"Dk: the leading dimension ({ld}) must be even and at least {M * nd}")
+        if ld & 1 or ld < cols:
+            raise GppError(f"{name}: the leading dimension ({ld}) must be even and at least {cols}")
         if out.data_ptr() & 15:
-            raise GppError("Dk must be 16-byte aligned")
+            raise GppError(f"{name} must be 16-byte aligned")
+        return ld
+
+    @_on_own_device
+    def cross_kernel_dx(self, Ua, Ub, w, sf2, d0, nd, out, *, kind=KIND_RBF, d_split=0):
+        """out[n, a nd + j] = d/du_{d0+j} sf2 k(u, Ub_n; w) at u = Ua_a: the derivative cross block with the training points as rows,
+        the operand ``predict_tn`` takes (gpp_cross_kernel_dx).  ``out``: an N x (M nd) window of a row-major buffer with an even
+        leading dimension, 16-byte aligned; what lies beyond column M nd is not written.  Everything is checked before the launch."""
+        d0, nd = int(d0), int(nd)
+        M, N = self._dx_checks("cross_kernel_dx", "M, N", Ua, Ub, w, sf2, d0, nd, kind, d_split)
+        ld, D = self._dx_window("Dk", out, N, M * nd), Ua.shape[1]
         self._stream()
         check(self.lib.gpp_cross_kernel_dx(self.h, Ua.data_ptr(), M, Ub.data_ptr(), N, D, w.data_ptr(), sf2.data_ptr(), int(kind),
                                            int(d_split), d0, nd, out.data_ptr(), ld), "gpp_cross_kernel_dx")
@@ -1106,6 +1119,20 @@ class GppContext:
             raise GppError("gpp_point_gram: the handle's scratch workspace is missing or too small")
         check(status, "gpp_point_gram")
         return G, Gsum
+
+    # -- conditioning on gradient observations -----------------------------------------------------------------------------------
+    @_on_own_device
+    def kernel_dxdx(self, Ua, Ub, w, sf2, d0, nd, out, *, kind=KIND_RBF, d_split=0):
+        """out[a nd + j, b nd + l] = d^2/du_{d0+j} dv_{d0+l} sf2 k(u, v; w) at u = Ua_a, v = Ub_b: the covariance of two gradient
+        observations (gpp_kernel_dxdx).  ``out``: an (Ma nd) x (Mb nd) window of a row-major buffer with an even leading dimension,
+        16-byte aligned; what lies beyond column Mb nd is not written.  Everything is checked before the launch."""
+        d0, nd = int(d0), int(nd)
+        Ma, Mb = self._dx_checks("kernel_dxdx", "Ma, Mb", Ua, Ub, w, sf2, d0, nd, kind, d_split)
+        ld, D = self._dx_window("H", out, Ma * nd, Mb * nd), Ua.shape[1]
+        self._stream()
+        check(self.lib.gpp_kernel_dxdx(self.h, Ua.data_ptr(), Ma, Ub.data_ptr(), Mb, D, w.data_ptr(), sf2.data_ptr(), int(kind),
+                                       int(d_split), d0, nd, out.data_ptr(), ld), "gpp_kernel_dxdx")
+        return out
 
 
 

@@ -1,4 +1,5 @@
-// gpp_dgrad.hip — the two kernels behind the posterior of the gradient (GP_Plus.predict_gradient / active_subspace).
+// gpp_dgrad.hip — the two kernels behind the posterior of the gradient (GP_Plus.predict_gradient / active_subspace) and the
+// second-derivative block behind conditioning on gradient observations (GP_Plus.condition_on_gradients).
 //
 // gpp_cross_kernel_dx (gpp.h): the derivative cross block Dk[n, a nd + j] = d/du_{d0+j} sf2 k(Ua_a, Ub_n; w), training points as rows —
 // the orientation gpp_predict_tn takes, so that Q = Dk^T Linv^T, the gradient's mean Q z and its variance diagonal come from the
@@ -14,6 +15,14 @@
 // sum.  The order of a point's additions depends on (N, nd) alone.  The weighted sum over the points takes two more launches (groups
 // of PG_GROUP points in index order, then the groups in index order) through the handle workspace.  No atomics.  No reference
 // counterpart: the reference has no gradient posterior.
+//
+// gpp_kernel_dxdx (gpp.h): the second-derivative block H[a nd + j][b nd + l] = d^2/du_{d0+j} dv_{d0+l} sf2 k(Ua_a, Ub_b; w), the covariance
+// of two gradient observations (GP_Plus.condition_on_gradients).  One work-group per tile of HX_TA x HX_TB pairs: the multipliers
+// m_0 = -sf2 e1 h, m_1 = sf2 e1 h' and m_2 = -sf2 e1 h'' are computed once per pair by the staged arithmetic above and left in LDS; an
+// entry is then (p_j p_l) m_{f(j) + f(l)} - delta_jl g_j m_{f(j)} with g = 2 w, p_j = g_j (ua_j - vb_j) from the RAW features and f = 0 on
+// a feature of the RBF factor, 1 on one of the Matern factor.  The product p_j p_l and the one fused multiply-add are the same
+// operations on the same numbers for the entries (a, j), (b, l) and (b, l), (a, j): with Ua = Ub the block is bitwise symmetric.
+// 16-byte stores along the contiguous (b, l) axis.  Bandwidth-bound: Ma nd Mb nd doubles written once.
 #include "../../include/gpp.h"
 #include "gpp_internal.h"
 
@@ -299,5 +308,180 @@ extern "C" int gpp_point_gram(gpp_handle_t h, const double* Q, int64_t ldq, int6
     hipLaunchKernelGGL(gpp_point_gram_group, dim3((unsigned)groups), dim3(256), 0, h->stream, G, omega, m, nn, part);
     hipLaunchKernelGGL(gpp_point_gram_total, dim3(1), dim3(256), 0, h->stream, part, groups, nn, Gsum);
   }
+  return dg_rc(hipGetLastError());
+}
+
+// ---- gpp_kernel_dxdx ----------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int HX_TA = 16;          // row points per tile
+constexpr int HX_TB = 16;          // column points per tile (even: a tile's first column b0 nd is even, the 16-byte stores stay aligned)
+constexpr int HX_TBP = HX_TB + 1;  // row stride of the multiplier tiles
+constexpr int HX_THREADS = 256;    // one pair per thread in the multiplier phase
+
+struct HxArgs {
+  const double* Ua;
+  const double* Ub;
+  const double* w;
+  const double* sf2;
+  double* H;
+  int64_t ld;
+  int Ma, Mb, D, kind, d_split, d0, nd, tiles_b;
+};
+
+// doubles of dynamic LDS: staged rows (odd stride D | 1), raw direction columns of both sides, 2 w and sqrt(w), the multiplier tiles
+inline size_t hx_lds_doubles(int D, int nd, int nf) {
+  return (size_t)(HX_TA + HX_TB) * (D | 1) + (size_t)(HX_TA + HX_TB) * (nd | 1) + nd + D + (size_t)nf * HX_TA * HX_TBP;
+}
+
+// (p_j p_l) m_F - [j == l] g_j m_f: one product, one fused multiply-add
+__device__ __forceinline__ double hx_entry(double pj, double pl, double mF, bool diag, double gj, double mf) {
+  return fma(pj * pl, mF, diag ? -(gj * mf) : 0.0);
+}
+
+template <bool MAT>
+__global__ __launch_bounds__(HX_THREADS) void gpp_kernel_dxdx_f64(HxArgs p) {
+  extern __shared__ __attribute__((aligned(16))) double hx_lds[];
+  constexpr int NF = MAT ? 3 : 1;
+  constexpr int MT = HX_TA * HX_TBP;  // doubles of one multiplier tile
+  const int D = p.D, nd = p.nd, Dp = D | 1, ndp = nd | 1;
+  double* sA = hx_lds;                   // [HX_TA][Dp]  sqrt(w_d) ua_d
+  double* sB = sA + HX_TA * Dp;          // [HX_TB][Dp]  sqrt(w_d) vb_d
+  double* rA = sB + HX_TB * Dp;          // [HX_TA][ndp] ua_{d0+j}
+  double* rB = rA + HX_TA * ndp;         // [HX_TB][ndp] vb_{d0+j}
+  double* w2 = rB + HX_TB * ndp;         // [nd]         2 w_{d0+j}
+  double* sw = w2 + nd;                  // [D]          sqrt(w_d)
+  double* sM = sw + D;                   // [NF][HX_TA][HX_TBP] multipliers
+  const int t = (int)threadIdx.x;
+  const int tb = (int)(blockIdx.x % (unsigned)p.tiles_b), ta = (int)(blockIdx.x / (unsigned)p.tiles_b);
+  const int a0 = ta * HX_TA, b0 = tb * HX_TB;
+  const int na = min(HX_TA, p.Ma - a0), nb = min(HX_TB, p.Mb - b0);
+  const int ds = (!MAT || p.kind == 0) ? D : p.d_split;  // dims below ds belong to the RBF factor
+
+  for (int d = t; d < D; d += HX_THREADS) sw[d] = sqrt(p.w[d]);
+  for (int j = t; j < nd; j += HX_THREADS) w2[j] = 2.0 * p.w[p.d0 + j];
+  __syncthreads();
+  // rows beyond the matrices' ends are staged as zeros and never read from memory; their pairs are computed and never stored
+  for (int i = t; i < (HX_TA + HX_TB) * D; i += HX_THREADS) {
+    const int r = i / D, d = i - r * D;
+    if (r < HX_TA) {
+      const double u = r < na ? p.Ua[(int64_t)(a0 + r) * D + d] : 0.0;
+      sA[r * Dp + d] = sw[d] * u;
+      if (d >= p.d0 && d < p.d0 + nd) rA[r * ndp + (d - p.d0)] = u;
+    } else {
+      const int rb = r - HX_TA;
+      const double u = rb < nb ? p.Ub[(int64_t)(b0 + rb) * D + d] : 0.0;
+      sB[rb * Dp + d] = sw[d] * u;
+      if (d >= p.d0 && d < p.d0 + nd) rB[rb * ndp + (d - p.d0)] = u;
+    }
+  }
+  __syncthreads();
+
+  // the multipliers, once per pair (the staged arithmetic of gpp_cross_kernel_dx, operation for operation, plus h'')
+  {
+    const GppExpConsts ec = gpp_exp_consts();
+    const double sf2 = *p.sf2;
+    const int bl = t & (HX_TB - 1), al = t / HX_TB;
+    const double* ua = sA + al * Dp;
+    const double* ub = sB + bl * Dp;
+    double q1 = 0.0;
+    for (int d = 0; d < ds; ++d) {
+      const double df = ua[d] - ub[d];
+      q1 = fma(df, df, q1);
+    }
+    const double e1 = sf2 * gpp_exp_nonpos(-q1, ec);
+    if constexpr (MAT) {
+      double q2 = 0.0;
+      for (int d = ds; d < D; ++d) {
+        const double df = ua[d] - ub[d];
+        q2 = fma(df, df, q2);
+      }
+      double h, hp, hpp;  // h' without a division by r; h'' of the Matern 3/2 factor divides by r and is an exact 0 where r == 0
+      if (p.kind == 1) {
+        const double r = sqrt(3.0 * 2.0 * q2);
+        const double er = gpp_exp_nonpos(-r, ec);
+        h = (1.0 + r) * er;
+        hp = -3.0 * er;
+        hpp = r > 0.0 ? (9.0 * er) / r : 0.0;
+      } else {
+        const double r = sqrt(5.0 * 2.0 * q2);
+        const double er = gpp_exp_nonpos(-r, ec);
+        h = (1.0 + r + r * r * (1.0 / 3.0)) * er;
+        hp = (-5.0 / 3.0) * (1.0 + r) * er;
+        hpp = (25.0 / 3.0) * er;
+      }
+      sM[al * HX_TBP + bl] = -(e1 * h);
+      sM[MT + al * HX_TBP + bl] = e1 * hp;
+      sM[2 * MT + al * HX_TBP + bl] = -(e1 * hpp);
+    } else {
+      sM[al * HX_TBP + bl] = -e1;
+    }
+  }
+  __syncthreads();
+
+  // the tile's na nd rows of cw = nb nd contiguous columns, two columns per lane: consecutive lanes write consecutive 16 bytes
+  const int rows = na * nd, cw = nb * nd, hp2 = (cw + 1) >> 1;
+  int ct = 1;
+  while (ct < hp2 && ct < HX_THREADS) ct <<= 1;
+  const int rt = HX_THREADS / ct;
+  double* out = p.H + (int64_t)a0 * nd * p.ld + (int64_t)b0 * nd;
+  for (int pc = t % ct; pc < hp2; pc += ct) {
+    const int c0 = 2 * pc;
+    const bool two = c0 + 1 < cw;
+    const int bl0 = c0 / nd, l0 = c0 - bl0 * nd;
+    int bl1 = bl0, l1 = l0 + 1;
+    if (l1 == nd) { l1 = 0; bl1 = bl0 + 1; }
+    if (!two) { bl1 = bl0; l1 = l0; }
+    const int f0 = (NF == 3 && p.d0 + l0 >= ds) ? 1 : 0;
+    const int f1 = (NF == 3 && p.d0 + l1 >= ds) ? 1 : 0;
+    const double y0 = rB[bl0 * ndp + l0], y1 = rB[bl1 * ndp + l1];
+    const double g0 = w2[l0], g1 = w2[l1];
+    for (int row = t / ct; row < rows; row += rt) {
+      const int al = row / nd, j = row - al * nd;
+      const int fj = (NF == 3 && p.d0 + j >= ds) ? 1 : 0;
+      const double* xa = rA + al * ndp;
+      const double gj = w2[j], xj = xa[j];
+      const double* m0 = sM + al * HX_TBP + bl0;
+      const double v0 = hx_entry(gj * (xj - rB[bl0 * ndp + j]), g0 * (xa[l0] - y0), m0[(fj + f0) * MT], j == l0, gj, m0[fj * MT]);
+      double* dst = out + (int64_t)row * p.ld + c0;
+      if (two) {
+        const double* m1 = sM + al * HX_TBP + bl1;
+        const double v1 = hx_entry(gj * (xj - rB[bl1 * ndp + j]), g1 * (xa[l1] - y1), m1[(fj + f1) * MT], j == l1, gj, m1[fj * MT]);
+        *reinterpret_cast<double2*>(dst) = make_double2(v0, v1);
+      } else {
+        *dst = v0;
+      }
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int gpp_kernel_dxdx(gpp_handle_t h, const double* Ua, int64_t Ma, const double* Ub, int64_t Mb, int D, const double* w,
+                               const double* sf2, int kind, int d_split, int d0, int nd, double* H, int64_t ld) {
+  if (!h) return -1;
+  if (!Ua) return -2;
+  if (Ma < 1 || Ma > 0x7ffffff0) return -3;
+  if (!Ub) return -4;
+  if (Mb < 1 || Mb > 0x7ffffff0) return -5;
+  if (D < 1 || D > 64) return -6;
+  if (!w) return -7;
+  if (!sf2) return -8;
+  if (kind < 0 || kind > 2) return -9;
+  if (d_split < 0 || d_split > D) return -10;
+  if (d0 < 0 || d0 >= D) return -11;
+  if (nd < 1 || d0 + nd > D) return -12;
+  if (Ma * nd > 0x7ffffff0) return -3;
+  if (Mb * nd > 0x7ffffff0) return -5;
+  if (!H || !dg_aligned16(H)) return -13;
+  if ((ld & 1) || ld < Mb * nd) return -14;
+  const int64_t tiles_a = (Ma + HX_TA - 1) / HX_TA, tiles_b = (Mb + HX_TB - 1) / HX_TB;
+  if (tiles_a * tiles_b >= ((int64_t)1 << 31)) return -3;
+  HxArgs p{Ua, Ub, w, sf2, H, ld, (int)Ma, (int)Mb, D, kind, d_split, d0, nd, (int)tiles_b};
+  const dim3 grid((unsigned)(tiles_a * tiles_b)), block(HX_THREADS);
+  if (kind == GPP_KIND_RBF)
+    hipLaunchKernelGGL(gpp_kernel_dxdx_f64<false>, grid, block, hx_lds_doubles(D, nd, 1) * sizeof(double), h->stream, p);
+  else
+    hipLaunchKernelGGL(gpp_kernel_dxdx_f64<true>, grid, block, hx_lds_doubles(D, nd, 3) * sizeof(double), h->stream, p);
   return dg_rc(hipGetLastError());
 }

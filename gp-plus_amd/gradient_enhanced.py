@@ -1,0 +1,138 @@
+"""Gradient-enhanced Kriging on a fitted model: ``GP_Plus.condition_on_gradients`` borders the cached factorisation with observed
+gradients (``linalg.append_gradients_to_cache``: gpp_cross_kernel_dx for the function / gradient block, gpp_kernel_dxdx for the
+gradient / gradient block, gpp_chol_append for the border) and returns a ``GradientEnhancedPosterior``.  No reference counterpart."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .gpcore.distributions import DenseCovariance, MultivariateNormal
+from .gpcore.module import Module
+from .utils import data_type_check
+
+__all__ = ["GRADIENT_NUGGET_REL", "GradientEnhancedPosterior", "condition_on_gradients"]
+
+#: ``noise=None``: the variance given to a gradient observation, as a fraction of the prior curvature of its direction (the prior
+#: variance of that component of the gradient, ``linalg.gradient_prior_curvature``).
+GRADIENT_NUGGET_REL = 1e-6
+
+
+class GradientEnhancedPosterior:
+    """The posterior of a fitted model conditioned on its own training data AND on gradient observations, as returned by
+    ``GP_Plus.condition_on_gradients``.  It offers ``predict`` and ``predict_gradient`` with the conventions of the model's own, and
+    the attributes ``num_function_rows`` (N) and ``num_gradient_points`` (Mg).  Nothing else: no further conditioning, no sampling,
+    no leave-one-out or cross-validation, no acquisition scores, no joint covariance, no hyperparameter training on the gradient
+    data.  It holds a detached copy of the model (parameters, training inputs, no N x N factors) for the features, prior means and
+    noise of test rows: refitting or modifying the model it came from does not change it."""
+
+    def __init__(self, model, gcache):
+        self._model, self._cache = model, gcache
+
+    @property
+    def num_function_rows(self) -> int:
+        return int(self._cache.U.shape[0])
+
+    @property
+    def num_gradient_points(self) -> int:
+        return int(self._cache.Ug.shape[0])
+
+    def __repr__(self):
+        return (f"GradientEnhancedPosterior(function rows={self.num_function_rows}, gradient points={self.num_gradient_points}, "
+                f"directions={self._cache.nd})")
+
+    def _prior(self, Xtest, what: str):
+        m = self._model
+        X = m._alc_rows(Xtest, "Xtest", what).to(m.train_inputs[0])
+        out = Module.__call__(m, X)
+        return X, out, out.lazy_covariance_matrix.U1
+
+    def predict(self, Xtest, return_std=True, include_noise=True):
+        """Mean (and std) at the rows of ``Xtest`` in the units of the training targets, with the return convention of
+        ``GP_Plus.predict``: the std includes the noise of each test row's own source unless ``include_noise=False``."""
+        from .linalg import predict_from_gradient_cache
+
+        m = self._model
+        with torch.no_grad():
+            X, out, Us = self._prior(Xtest, "GradientEnhancedPosterior.predict")
+            mean_c, var = predict_from_gradient_cache(self._cache, Us, "function")
+            post = MultivariateNormal(out.mean.to(torch.float64) + mean_c, DenseCovariance(var, n=var.shape[0]))
+            if return_std and include_noise:
+                m.likelihood.fidel_indices = X[:, -1]  # noise of the test points' own sources
+                post = m.likelihood(post)
+            mean = m.y_min + m.y_std * post.mean
+            if return_std:
+                return mean, post.variance.sqrt() * m.y_std
+            return mean
+
+    def predict_gradient(self, Xtest, return_std=True):
+        """Posterior mean (M, p) — and with ``return_std`` the std (M, p) — of the gradient of the latent f with respect to the
+        quantitative input columns, in y per input unit, ``quant_index`` order, as ``GP_Plus.predict_gradient`` returns them."""
+        from .linalg import predict_from_gradient_cache
+
+        m = self._model
+        with torch.no_grad():
+            _, _, Us = self._prior(Xtest, "GradientEnhancedPosterior.predict_gradient")
+            mean, var = predict_from_gradient_cache(self._cache, Us, "gradient")
+            scale = m.y_std.detach().to(torch.float64)
+            if return_std:
+                return mean * scale, var.clamp_min(0.0).sqrt() * scale.abs()
+            return mean * scale
+
+
+def condition_on_gradients(model, X, dY, noise=None) -> GradientEnhancedPosterior:
+    """The work behind ``GP_Plus.condition_on_gradients`` (documented there)."""
+    from . import settings as gpp_settings
+    from .backend import get_context
+    from .linalg import APPEND_MAX_Q, append_gradients_to_cache, gradient_prior_curvature
+
+    what = "condition_on_gradients"
+    X, dY = data_type_check(X), data_type_check(dY)
+    train_x = model.train_inputs[0]
+    p = int(model.quant_index.numel())
+    if X.dim() != 2 or X.shape[1] != train_x.shape[1]:
+        raise ValueError(f"{what}: X must be (q, {train_x.shape[1]}) like the training inputs (got {tuple(X.shape)})")
+    if p == 0:
+        raise ValueError(f"{what}: the model has no quantitative input column to differentiate")
+    if dY.dim() == 1 and p == 1:
+        dY = dY.reshape(-1, 1)
+    if dY.dim() != 2 or dY.shape[1] != p:
+        raise ValueError(f"{what}: dY must be (q, {p}): one column per quantitative input column (got {tuple(dY.shape)})")
+    if dY.shape[0] != X.shape[0]:
+        raise ValueError(f"{what}: {X.shape[0]} rows of X for {dY.shape[0]} gradients")
+    if X.shape[0] == 0:
+        raise ValueError(f"{what}: no observation given (q = 0)")
+    if not (bool(torch.isfinite(X).all()) and bool(torch.isfinite(dY).all())):
+        raise ValueError(f"{what}: X and dY must be finite (NaN or inf found)")
+    model._check_new_rows(X)
+    Mg = X.shape[0]
+    if noise is not None:
+        # (a Python or numpy number straight to fp64: ``data_type_check`` would round a float to the default dtype first)
+        noise = noise.detach().to(torch.float64) if torch.is_tensor(noise) else torch.as_tensor(np.asarray(noise, dtype=np.float64))
+        try:
+            noise = torch.broadcast_to(noise, (Mg, p))
+        except RuntimeError:
+            raise ValueError(f"{what}: noise must be a scalar or broadcast to ({Mg}, {p}) (got {tuple(noise.shape)})") from None
+        if not bool(torch.isfinite(noise).all()) or bool((noise < 0).any()):
+            raise ValueError(f"{what}: the noise variances must be finite and not negative")
+    N = int(train_x.shape[0])
+    if Mg * p > min(N, APPEND_MAX_Q):
+        raise ValueError(f"{what}: {Mg} points x {p} directions = {Mg * p} gradient observations exceed min(N = {N}, {APPEND_MAX_Q})")
+    if gpp_settings.sharded_evaluation.value() is not None:
+        raise NotImplementedError(f"{what} is not available under settings.sharded_evaluation")
+    get_context(train_x.device)  # (raises for anything but a GPU: there is no CPU path)
+
+    model.eval()
+    with torch.no_grad():
+        cache = model._ensure_prediction_cache()
+        Ug = Module.__call__(model, X.to(train_x)).lazy_covariance_matrix.U1
+        d0 = Ug.shape[1] - p
+        y_std = model.y_std.detach().to(torch.float64)
+        r_g = dY.to(device=Ug.device, dtype=torch.float64) / y_std
+        if noise is None:
+            noise_diag = (GRADIENT_NUGGET_REL * gradient_prior_curvature(cache.spec, d0, p)).expand(Mg, p)
+        else:
+            noise_diag = noise.to(Ug.device) / y_std ** 2
+        gcache = append_gradients_to_cache(cache, Ug, d0, p, r_g, noise_diag.contiguous())
+        child = model._copy_without_factors()
+        child.eval()
+    return GradientEnhancedPosterior(child, gcache)

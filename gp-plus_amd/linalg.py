@@ -28,7 +28,8 @@ from . import settings
 
 __all__ = ["KernelSpec", "exact_mll", "ExactMLLFunction", "exact_loo", "ExactLOOFunction", "loo_moments", "exact_cv", "ExactCVFunction",
            "cv_moments", "EvalWorkspace", "dense_kernel", "cross_kernel",
-           "FactorCache", "factorize", "append_to_cache", "dense_log_prob", "predict_mean", "predict_var", "predictive_cov_upper",
+           "FactorCache", "factorize", "append_to_cache", "GradientFactorCache", "append_gradients_to_cache",
+           "predict_from_gradient_cache", "dense_log_prob", "predict_mean", "predict_var", "predictive_cov_upper",
            "train_post_cov_upper", "mvn_root", "mvn_draw"]
 
 
@@ -970,6 +971,152 @@ def gradient_from_cache(cache: FactorCache, Us, d0: int, nd: int, want: str, ome
         if want == "cov":
             return mean, cov
         return 0.5 * (mean_part + mean_part.T), cov_part
+
+
+class GradientFactorCache:
+    """Factor, inverse factor, z and alpha of the N function rows of a ``FactorCache`` bordered with q = Mg nd gradient observations
+    (``append_gradients_to_cache``): row N + a nd + j is d f / du_{d0+j} at the feature row ``Ug[a]``.  It owns its matrices (never
+    stale) and is deliberately NOT a ``FactorCache``: its last q rows are not function values, so nothing that reads a
+    ``FactorCache`` (prediction, appends, scores, sampling) may take it.  ``predict_from_gradient_cache`` is its only consumer."""
+
+    def __init__(self, gctx, own, n, q, z, alpha, U, Ug, d0, nd, spec, jitter):
+        self.gctx, self._own = gctx, own
+        self.L, self.Linv = own.A[:n + q, :n + q], own.Linv[:n + q, :n + q]
+        self.z, self.alpha, self.U, self.Ug, self.d0, self.nd, self.spec, self.jitter = z, alpha, U, Ug, d0, nd, spec, jitter
+
+
+def _gradient_cache_refusals(what: str, dev=None):
+    if settings.sharded_evaluation.value() is not None:
+        raise NotImplementedError(f"{what} is not available under settings.sharded_evaluation")
+    if dev is not None and dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+        raise NotImplementedError(f"{what} is not available inside a graph capture")
+
+
+@torch.no_grad()
+def append_gradients_to_cache(cache: FactorCache, Ug, d0: int, nd: int, r_g, noise_diag) -> GradientFactorCache:
+    """A ``GradientFactorCache`` of the N cached rows plus q = Mg nd observations of the gradient of the latent f with respect to
+    the features d0 .. d0 + nd - 1 at the feature rows ``Ug`` (Mg x D), in O(N^2 q) by bordering the cached factor (gpp_chol_append):
+    the cross block is cov(f(x_n), d_j f(ug_a)) = gpp_cross_kernel_dx(Ua = Ug, Ub = U) (N x q), the corner
+    cov(d_j f(ug_a), d_l f(ug_b)) = gpp_kernel_dxdx(Ug, Ug) plus diag(noise_diag + the cache's jitter).  ``r_g``: the q observed
+    gradients, point-major (a nd + j), in the cache's scaled units — every supported mean is constant, so their prior mean is 0;
+    ``noise_diag``: their q noise variances, same units squared.  The windows are always copied into a new pair of capacity
+    N + q: ``cache`` stays valid and bitwise unchanged (it is refreshed first when another model has taken the shared workspace).
+
+    ``ValueError`` for q > min(N, APPEND_MAX_Q): there is no from-scratch route, since no build kernel forms the mixed matrix.
+    ``errors.NotPSDError`` when the Schur complement is not positive definite (duplicate gradient points without noise).
+    Refused under ``settings.sharded_evaluation`` and inside a graph capture, like ``append_to_cache``."""
+    from .errors import NotPSDError
+
+    _gradient_cache_refusals("appending gradients to a factor cache")
+    dev = cache.U.device
+    gctx = cache.gctx
+    on_gpu = dev.type == "cuda"  # (anything else only under a stand-in context: the library itself has no CPU path)
+    with torch.cuda.device(dev) if on_gpu else nullcontext():
+        _gradient_cache_refusals("appending gradients to a factor cache", dev)
+        n, D = cache.U.shape
+        d0, nd = int(d0), int(nd)
+        Ug = _as_f64(Ug.detach(), dev).contiguous()
+        if Ug.dim() != 2 or Ug.shape[0] < 1 or Ug.shape[1] != D:
+            raise ValueError(f"the gradient points must be at least one row of {D} features (got {tuple(Ug.shape)})")
+        if nd < 1 or d0 < 0 or d0 + nd > D:
+            raise ValueError(f"the differentiated features [{d0}, {d0 + nd}) must be a non-empty range of the {D} features")
+        q = Ug.shape[0] * nd
+        r_g = _as_f64(r_g.detach().reshape(-1), dev).contiguous()
+        noise_diag = _as_f64(noise_diag.detach().reshape(-1), dev)
+        if r_g.numel() != q or noise_diag.numel() != q:
+            raise ValueError(f"{r_g.numel()} gradients / {noise_diag.numel()} noise variances for {q} gradient observations")
+        if q > min(n, APPEND_MAX_Q):
+            raise ValueError(f"{q} gradient observations exceed min(N = {n}, {APPEND_MAX_Q}): the factor can only be bordered, "
+                             "no build kernel forms the mixed function / gradient matrix from scratch")
+        cache.refresh()  # (a cache of the shared workspace that another model has factored into since)
+        own = _owned_copy(cache, n, n + q)
+        spec = cache.spec
+        w, sf2 = spec.w, spec.sf2.reshape(1)
+        with _stage("append_gradient_operands"):
+            k = gctx.cross_kernel_dx(Ug, cache.U, w, sf2, d0, nd, rows_buffer(n, q, dev), kind=spec.kind, d_split=spec.d_split)
+            C = gctx.kernel_dxdx(Ug, Ug, w, sf2, d0, nd, square_buffer(q, dev), kind=spec.kind, d_split=spec.d_split)
+            C.diagonal().add_(noise_diag + cache.jitter)
+        z = torch.empty(n + q, dtype=torch.float64, device=dev)
+        alpha = torch.empty(n + q, dtype=torch.float64, device=dev)
+        z[:n].copy_(cache.z)
+        alpha[:n].copy_(cache.alpha)
+        info = torch.zeros(1, dtype=torch.int32, device=dev)
+        with _stage("chol_append"):
+            gctx.chol_append(own.A, own.Linv, n, q, k, C, r_g, z, alpha, info)
+        minor = int(info.item())
+        if minor == 0:
+            # A Schur complement that is singular in exact arithmetic (the same gradient observed twice without noise) may still
+            # factor, on a pivot that is rounding noise of either sign.  S_kk = C_kk - |V_k|^2 is formed from N + q products of size
+            # up to C_kk: a squared pivot within 4 (N + q) u of C_kk has no digit left and counts as not positive.  (The default
+            # nugget keeps S_kk >= 1e-6 C_kk / (1 + 1e-6), five orders above this at N + q = 22 048.)
+            piv = own.A[n:n + q, n:n + q].diagonal()
+            lost = piv * piv <= (4.0 * (n + q) * 2.0 ** -53) * C.diagonal()
+            if bool(lost.any()):
+                minor = int(lost.to(torch.int32).argmax().item()) + 1
+        if minor != 0:
+            raise NotPSDError(f"conditioning on gradients: leading minor {minor} of the Schur complement of the {q} gradient "
+                              f"observations is not positive definite (gradient point {(minor - 1) // nd}, direction "
+                              f"{(minor - 1) % nd}); pass a larger noise")
+        own.filled = n + q
+        return GradientFactorCache(gctx, own, n, q, z, alpha, cache.U, Ug, d0, nd, spec, cache.jitter)
+
+
+@torch.no_grad()
+def predict_from_gradient_cache(gcache: GradientFactorCache, Us, want: str = "function"):
+    """Posterior at the feature rows ``Us`` (M x D) from a ``GradientFactorCache``, in the cache's scaled units, by gpp_predict_tn on
+    an (N + q)-row operand whose first N rows are what a ``FactorCache`` prediction uses and whose last q rows are the covariances
+    with the gradient observations.  ``want``:
+      "function"  (mean contribution, variance) of the latent f, M each: rows [0, N) = gpp_cross_kernel(U, Us), rows [N, N + q) =
+                  gpp_cross_kernel_dx(Ua = Ug, Ub = Us) (M x q) transposed; the prior mean is not added and the variance is unclamped;
+      "gradient"  (mean, variance diagonal) of the gradient with respect to the cache's differentiated features, M x nd each, in
+                  chunks of ``GRAD_CHUNK_BYTES`` like ``gradient_from_cache``: rows [0, N) = gpp_cross_kernel_dx(Ua = Us, Ub = U), rows
+                  [N, N + q) = gpp_kernel_dxdx(Ug, Us); the prior diagonal is ``gradient_prior_curvature``.
+    Refused under ``settings.sharded_evaluation`` and inside a graph capture."""
+    if want not in ("function", "gradient"):
+        raise ValueError(f"want must be 'function' or 'gradient' (got {want!r})")
+    _gradient_cache_refusals("predicting from a gradient cache")
+    dev = gcache.U.device
+    gctx = gcache.gctx
+    on_gpu = dev.type == "cuda"
+    with torch.cuda.device(dev) if on_gpu else nullcontext():
+        _gradient_cache_refusals("predicting from a gradient cache", dev)
+        Us = _as_f64(Us.detach(), dev).contiguous()
+        N, D = gcache.U.shape
+        if Us.dim() != 2 or Us.shape[0] < 1 or Us.shape[1] != D:
+            raise ValueError(f"the test points must be at least one row of {D} features (got {tuple(Us.shape)})")
+        M, d0, nd = Us.shape[0], gcache.d0, gcache.nd
+        q = gcache.Ug.shape[0] * nd
+        spec = gcache.spec
+        w, sf2 = spec.w, spec.sf2.reshape(1)
+        if want == "function":
+            op = rows_buffer(N + q, M, dev)
+            with _stage("gek_operands"):
+                gctx.cross_kernel(gcache.U, Us, w, sf2, op[:N], kind=spec.kind, d_split=spec.d_split)
+                Dsg = gctx.cross_kernel_dx(gcache.Ug, Us, w, sf2, d0, nd, rows_buffer(M, q, dev), kind=spec.kind, d_split=spec.d_split)
+                gctx.transpose(Dsg, op[N:])
+            mean = torch.empty(M, dtype=torch.float64, device=dev)
+            var = torch.empty(M, dtype=torch.float64, device=dev)
+            with _stage("gek_predict_tn"):
+                gctx.predict_tn(gcache.Linv, gcache.z, op, sf2.expand(M).contiguous(), rows_buffer(M, N + q, dev), mean, var)
+            return mean, var
+        kappa = gradient_prior_curvature(spec, d0, nd)
+        mean = torch.empty((M, nd), dtype=torch.float64, device=dev)
+        var = torch.empty((M, nd), dtype=torch.float64, device=dev)
+        step = _gradient_chunk_points(N + q, nd)
+        for a0 in range(0, M, step):
+            mc = min(step, M - a0)
+            op = rows_buffer(N + q, mc * nd, dev)
+            g_c = torch.empty(mc * nd, dtype=torch.float64, device=dev)
+            v_c = torch.empty(mc * nd, dtype=torch.float64, device=dev)
+            with _stage("gek_operands"):
+                gctx.cross_kernel_dx(Us[a0:a0 + mc], gcache.U, w, sf2, d0, nd, op[:N], kind=spec.kind, d_split=spec.d_split)
+                gctx.kernel_dxdx(gcache.Ug, Us[a0:a0 + mc], w, sf2, d0, nd, op[N:], kind=spec.kind, d_split=spec.d_split)
+            with _stage("gek_predict_tn"):
+                gctx.predict_tn(gcache.Linv, gcache.z, op, kappa.repeat(mc), rows_buffer(mc * nd, N + q, dev), g_c, v_c)
+            del op
+            mean[a0:a0 + mc] = g_c.view(mc, nd)
+            var[a0:a0 + mc] = v_c.view(mc, nd)
+        return mean, var
 
 
 #: Scratch one gpp_post_cross_min launch of ``knowledge_gradient`` may ask for: above it the reference rows go in column chunks

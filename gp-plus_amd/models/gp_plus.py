@@ -541,6 +541,32 @@ class GP_Plus(GPR):
             return ActiveSubspace(matrix=matrix, eigenvalues=evals.flip(0), eigenvectors=evecs.flip(1), mean_part=mean_part,
                                   cov_part=cov_part, sensitivity=torch.diagonal(matrix).clone())
 
+    def condition_on_gradients(self, X, dY, noise=None):
+        """Gradient-enhanced Kriging on the fitted model: a ``GradientEnhancedPosterior`` of this model's training data plus observed
+        gradients, made by bordering the cached factorisation in O(N^2 q), q = Mg p, without refactorising
+        (``linalg.append_gradients_to_cache``: gpp_cross_kernel_dx, gpp_kernel_dxdx, gpp_chol_append).  ``X``: (Mg, columns of the
+        training inputs), the points the gradients were observed at — rows of any source: gradients of a cheap source inform the
+        others through the latent map like any other row.  ``dY``: (Mg, p), d y / d x over the quantitative columns in
+        ``quant_index`` order, in y per input unit, as ``predict_gradient`` returns them; every supported prior mean is constant,
+        so the gradients' prior mean is 0.  ``noise``: the variance of those observations in (y per input unit)^2, a scalar or
+        anything that broadcasts to (Mg, p); ``None`` takes ``gradient_enhanced.GRADIENT_NUGGET_REL`` = 1e-6 times the prior
+        curvature of each direction (the prior variance of that gradient component).
+
+        The receiver's data, parameters and cache are not modified (it is put in eval mode, as by ``predict``; without a cache it
+        is factorised first).  The returned object holds a detached copy of the model without the N x N factors and offers
+        ``predict(Xtest, return_std=True, include_noise=True)`` and ``predict_gradient(Xtest, return_std=True)`` in this model's
+        conventions and units, ``num_function_rows`` and ``num_gradient_points`` — nothing else: no partial gradients, no further
+        appends, no sampling, LOO / CV, acquisition scores or ``return_cov``, no training on the gradient data.  No reference
+        counterpart.
+
+        ``ValueError`` before any kernel runs: wrong column count or shapes, NaN / inf, Mg = 0, a categorical level or source the
+        model has not seen, negative noise, a model without a quantitative column, Mg p > min(N, 2048).  ``errors.NotPSDError``
+        when the gradient observations' Schur complement is not positive definite (duplicate points without noise): pass a larger
+        ``noise``; the receiver stays usable.  ``NotImplementedError`` under ``settings.sharded_evaluation`` or a graph capture."""
+        from ..gradient_enhanced import condition_on_gradients
+
+        return condition_on_gradients(self, X, dY, noise)
+
     def noise_value(self):
         return self.likelihood.noise_covar.noise.detach() * self.y_std ** 2
 

@@ -110,6 +110,23 @@ class GPR(ExactGP):
     def _after_copy(self, child) -> None:
         """Hook of ``condition_on``: mend whatever a deep copy of the model leaves pointing at the original."""
 
+    def _copy_without_factors(self):
+        """A deep copy of this model without its prediction cache (the N x N factors are not part of the copy): the copy route of
+        ``condition_on`` and ``condition_on_gradients``."""
+        import copy
+
+        held, self.prediction_strategy = self.prediction_strategy, None
+        # (predict_with_grad leaves ``fidel_indices`` — a slice of its differentiable input — on the model and the likelihood:
+        #  such non-leaf attributes are copied detached)
+        memo = {id(v): v.detach().clone() for mod in self.modules() for v in vars(mod).values()
+                if torch.is_tensor(v) and not v.is_leaf}
+        try:
+            child = copy.deepcopy(self, memo)
+        finally:
+            self.prediction_strategy = held
+        self._after_copy(child)
+        return child
+
     def condition_on(self, X, y, reserve: int = 256):
         """A NEW model, in eval mode, that has the q observations (X, y) beside this model's training data, made by bordering
         the cached factorisation in O(N^2 q) (``linalg.append_to_cache``, gpp_chol_append) instead of factorising N + q rows in
@@ -128,8 +145,6 @@ class GPR(ExactGP):
 
         ``ValueError`` before any kernel runs: wrong column count, length mismatch, NaN / inf, q = 0, a categorical level or a
         source the model has not seen.  ``NotImplementedError`` under ``settings.sharded_evaluation`` or a graph capture."""
-        import copy
-
         from .. import settings as gpp_settings
         from ..backend import get_context
         from ..gpcore.module import Module
@@ -170,16 +185,7 @@ class GPR(ExactGP):
                     lik.fidel_indices = saved
             new_cache = append_to_cache(cache, cov_q.U1, noisy.tau, noisy.grp, out_q.mean, yq, reserve)
 
-            held, self.prediction_strategy = self.prediction_strategy, None  # (the N x N factors are not part of the copy)
-            # (predict_with_grad leaves ``fidel_indices`` — a slice of its differentiable input — on the model and the likelihood:
-            #  such non-leaf attributes are copied detached)
-            memo = {id(v): v.detach().clone() for mod in self.modules() for v in vars(mod).values()
-                    if torch.is_tensor(v) and not v.is_leaf}
-            try:
-                child = copy.deepcopy(self, memo)
-            finally:
-                self.prediction_strategy = held
-            self._after_copy(child)
+            child = self._copy_without_factors()
             child.train_inputs = (torch.cat([train_x, Xq]),)
             targets = torch.cat([self.train_targets, yq])
             child.train_targets = targets

@@ -656,6 +656,26 @@ int gpp_cross_kernel_dx(gpp_handle_t h, const double* Ua, int64_t M, const doubl
 int gpp_point_gram(gpp_handle_t h, const double* Q, int64_t ldq, int64_t M, int nd, int64_t N, const double* omega, double* G,
                    double* Gsum);
 
+/*
+ * Second-derivative block, the covariance of two gradient observations and of a gradient observation with a predicted gradient
+ * (models/gp_plus.py condition_on_gradients; no reference counterpart):
+ *   H[a nd + j][b nd + l] = d^2/du_{d0+j} dv_{d0+l} ( sf2 k(u, v; w) ) at u = Ua_a, v = Ub_b
+ *                         = g_j g_l D_j D_l m_{f(j)+f(l)} - [j == l] g_j m_{f(j)},      g = 2 w,  D_d = Ua[a,d] - Ub[b,d],
+ * f = 0 on a feature of the RBF factor and 1 on one of the Matern factor, m_0 and m_1 the multipliers of gpp_cross_kernel_dx and
+ * m_2 = -sf2 e1 h'' with h'' = (25/3) e^-r (Matern 5/2) or 9 e^-r / r (Matern 3/2: the only division; |sqrt(w_j) D_j| <= r / sqrt(6)
+ * bounds the term by a multiple of r, and where r == 0 the multiplier is an exact 0, so a pair of equal points keeps the finite
+ * prior curvature 6 w_j sf2 e1 on its diagonal and nothing else).  Ua: Ma x D, Ub: Mb x D row-major and contiguous; kind / d_split as
+ * in gpp_cross_kernel; D <= 64, nd >= 1, 0 <= d0, d0 + nd <= D.  H: (Ma nd) x (Mb nd) row-major, ld >= Mb nd, ld even, 16-byte
+ * aligned.  The multipliers (one exp, plus the Matern polynomial) are computed once per pair (a, b) by the staged arithmetic of
+ * gpp_cross_kernel_dx and serve its nd^2 entries; D_d comes from the raw features.  A feature with w_d == 0 gives exact zeros in its
+ * whole row and column of every pair's block.  The columns [Mb nd, ld) are never written and nothing outside the stated extents is
+ * read.  One plain launch on the handle's stream, no workspace, no atomics; every entry is a function of its own pair alone, so two
+ * launches agree bit for bit, and the entries (a, j), (b, l) and (b, l), (a, j) are the same operations on the same numbers: with
+ * Ua and Ub the same rows H is bitwise symmetric.
+ */
+int gpp_kernel_dxdx(gpp_handle_t h, const double* Ua, int64_t Ma, const double* Ub, int64_t Mb, int D, const double* w,
+                    const double* sf2, int kind, int d_split, int d0, int nd, double* H, int64_t ld);
+
 #ifdef __cplusplus
 }
 #endif
