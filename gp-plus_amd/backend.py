@@ -589,6 +589,40 @@ class GppContext:
                                            g_sf2.data_ptr(), g_tau.data_ptr(), _ptr(g_U)), "gpp_loo_grad_reduce")
 
     @_on_own_device
+    def calib_grad_reduce(self, U, w, sf2, alpha, Kinv, member, cols, g_theta, *, kind=KIND_RBF, d_split=0):
+        """g_theta[k] = d MLL / d theta_k for calibration parameters written into feature column ``cols[k]`` of the rows with
+        ``member[i] != 0``: the sum of ``grad_reduce``'s g_U[i, cols[k]] over those rows without the N x D block
+        (gpp_calib_grad_reduce).  ``member`` (N,) and ``cols`` (C,) int32 on the GPU, ``Kinv`` as the LAUUM leaves it."""
+        N, D = U.shape
+        _check_features(D)
+        C = int(cols.numel())
+        for t, n, size in ((U, "U", N * D), (w, "w", D), (sf2, "sf2", 1), (alpha, "alpha", N), (g_theta, "g_theta", C)):
+            _need(t, torch.float64, n)
+            if t.numel() != size or not t.is_contiguous():
+                raise GppError(f"{n} must be contiguous with {size} doubles")
+        _need(Kinv, torch.float64, "Kinv")
+        if Kinv.dim() != 2 or Kinv.shape[0] != N or Kinv.shape[1] != N:
+            raise GppError(f"Kinv must be {N} x {N}")
+        for t, n, size in ((member, "member", N), (cols, "cols", C)):
+            _need(t, torch.int32, n)
+            if t.dim() != 1 or t.numel() != size:
+                raise GppError(f"{n} must be a vector of {size} int32")
+        if C < 1 or C > D:
+            raise GppError(f"1 <= C <= D calibrated columns (got C = {C}, D = {D})")
+        # the value range costs a device read: once per index tensor, as for the noise groups
+        seen = getattr(self, "_cols_ok", None)
+        if seen is None or seen[0]() is not cols or seen[1:] != (cols._version, D):
+            lo, hi = int(cols.min()), int(cols.max())
+            if lo < 0 or hi >= D:
+                raise GppError(f"calibrated feature column out of range: values in [{lo}, {hi}] for {D} feature columns")
+            self._cols_ok = (weakref.ref(cols), cols._version, D)
+        self.ensure_workspace(OP_MLL_EVAL, N, 0, D, 1)
+        self._stream()
+        check(self.lib.gpp_calib_grad_reduce(self.h, U.data_ptr(), N, D, w.data_ptr(), sf2.data_ptr(), kind, d_split,
+                                             alpha.data_ptr(), Kinv.data_ptr(), _ld(Kinv), member.data_ptr(), cols.data_ptr(), C,
+                                             g_theta.data_ptr()), "gpp_calib_grad_reduce")
+
+    @_on_own_device
     def grad_reduce_rows(self, U, w, sf2, grp, S, alpha, Kinv, dU, nb, rank, nranks, g_w, g_sf2, g_tau, g_U, *,
                          kind=KIND_RBF, d_split=0):
         """Partial sums over the block rows of Kinv owned by ``rank`` (block-cyclic, block height ``nb``)."""

@@ -1768,6 +1768,29 @@ int gpp_loo_grad_reduce(gpp_handle_t h, const double* U, int64_t N, int D, const
   return 0;
 }
 
+int gpp_calib_grad_reduce(gpp_handle_t h, const double* U, int64_t N, int D, const double* w, const double* sf2, int kind,
+                          int d_split, const double* alpha, const double* Kinv, int64_t ldk, const int32_t* member,
+                          const int32_t* cols, int C, double* g_theta) {
+  if (!h) return -1;
+  if (!U) return -2;
+  if (N < 0) return -3;
+  if (D < 1 || D > 64) return -4;
+  if (!w) return -5;
+  if (!sf2) return -6;
+  if (kind < 0 || kind > 2) return -7;
+  if (d_split < 0 || d_split > D) return -8;
+  if (!alpha) return -9;
+  if (int q = check_mat(Kinv, ldk, N, 10)) return q;
+  if (!member) return -12;
+  if (!cols) return -13;
+  if (C < 1 || C > D) return -14;
+  if (!g_theta) return -15;
+  if (N > 1 && (!h->ws || h->ws_bytes < gpp_calib_ws_bytes(C))) return -1;
+  GPP_TRY(gpp_launch_calib_grad_reduce(h->stream, U, N, D, w, sf2, kind, d_split, alpha, Kinv, ldk, member, cols, C, g_theta, h->ws,
+                                       h->ws_bytes));
+  return 0;
+}
+
 int gpp_grad_reduce_rows(gpp_handle_t h, const double* U, int64_t N, int D, const double* w, const double* sf2,
                          const int32_t* grp, int S, int kind, int d_split, const double* alpha, const double* Kinv,
                          int64_t ldk, int dU, int64_t nb, int rank, int nranks, double* g_w, double* g_sf2, double* g_tau,

@@ -435,6 +435,11 @@ hipError_t gpp_launch_loo_scalars(hipStream_t s, const double* Linv, int64_t ldi
 hipError_t gpp_launch_loo_scalars_batched(hipStream_t s, const double* Linv, int64_t ldi, int64_t N, const double* alpha,
                                           const double* y, double* d, double* mu, double* s2, double* a, double* sb, double* loo,
                                           int batch, int64_t sLi, int64_t sv);
+// g_theta[k] = sum over the member rows i of gpp_grad_reduce's g_U[i, cols[k]] (gpp_calib_grad_reduce in gpp.h): G_WGS records of C sums
+size_t gpp_calib_ws_bytes(int C);
+hipError_t gpp_launch_calib_grad_reduce(hipStream_t s, const double* U, int64_t N, int D, const double* w, const double* sf2, int kind,
+                                        int d_split, const double* alpha, const double* Kinv, int64_t ldk, const int32_t* member,
+                                        const int32_t* cols, int C, double* g_theta, void* ws, size_t ws_bytes);
 // the finish of gpp_launch_grad_reduce alone, over `nrec` records of D + 1 sums (gpp_lauum_grad: one per 128 x 128 tile)
 size_t gpp_lauum_grad_ws_bytes(int64_t N, int D);
 hipError_t gpp_launch_grad_finish(hipStream_t s, const double* rec, int64_t nrec, int D, int S, const double* wdiag,

@@ -1048,3 +1048,202 @@ hipError_t gpp_launch_transpose(hipStream_t s, const double* src, int64_t lds, i
   hipLaunchKernelGGL(gpp_transpose_tile, grid, dim3(256), 0, s, src, lds, rows, cols, dst, ldd);
   return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------------
+// gradient by calibration parameters (gpp_calib_grad_reduce).  theta_k is written into feature column cols[k] of every row of the
+// calibrated source (member[i] != 0), so with m_i the membership and W = 0.5 (alpha alpha' - Kinv)
+//    g_theta[k] = sum_ij W_ij (m_i - m_j) dK_ij/du_{i,c}   =   2 sum_{i > j} (m_i - m_j) W_ij sf2 k'_ij (-2 w_c) (u_ic - u_jc),   c = cols[k]
+// (k' = k on an RBF dimension, the Matern factor's derivative for c >= d_split, as in gpp_grad_tiles): the sum of gpp_grad_reduce's
+// g_U[i, c] over the member rows, without the N x dU block and its T x N x dU partials.  Pairs of one source contribute an exact
+// zero and are never evaluated: a 64 x 64 tile of Kinv's lower triangle whose rows and columns all share one membership is skipped
+// before any of it is read, so rows sorted by source cost the cross-source rectangle only.
+// Work-groups grid-stride over the tiles (the tile -> work-group map and so every sum's order depend on N alone); a thread holds
+// 4 rows x the column pairs {2 tx, 2 tx + 1}, {32 + 2 tx, 33 + 2 tx} (the LDS and Kinv access shapes of gpp_grad_tiles); per tile and
+// parameter the wave's sum goes to one LDS accumulator per wave, the work-group writes one record of C sums, and the finish kernel
+// adds the records in index order.  No atomics.
+namespace {
+
+template <int DT, bool MAT>
+__global__ __launch_bounds__(256) void gpp_calib_tiles(const double* __restrict__ U, int64_t N, int D, const double* __restrict__ w,
+                                                       const double* __restrict__ sf2p, int kind, int d_split,
+                                                       const double* __restrict__ alpha, const double* __restrict__ Kinv, int64_t ldk,
+                                                       const int32_t* __restrict__ member, const int32_t* __restrict__ cols, int C,
+                                                       int64_t ntiles, double* __restrict__ rec /* [gridDim.x][C] */) {
+  __shared__ __attribute__((aligned(16))) double sa[DT * GT];  // raw U rows of tile-row ti, [d][r]
+  __shared__ __attribute__((aligned(16))) double sb[DT * GT];
+  __shared__ double sal_a[GT], sal_b[GT];
+  __shared__ int sm_a[GT], sm_b[GT];
+  __shared__ double sw[DT];
+  __shared__ int scol[GD_MAX];
+  __shared__ double wacc[4 * GD_MAX];
+  const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15, wave = tid >> 6, lane = tid & 63;
+  const double sf2 = *sf2p;
+  const GppExpConsts ec = gpp_exp_consts();
+  const int dsp = MAT ? d_split : DT;
+  if (tid < DT) sw[tid] = (tid < D) ? w[tid] : 0.0;
+  if (tid < GD_MAX) {
+    const int c = (tid < C) ? cols[tid] : -1;
+    scol[tid] = (c >= 0 && c < D) ? c : -1;  // (the wrappers refuse a column outside [0, D); here it would add nothing)
+  }
+  for (int e = tid; e < 4 * GD_MAX; e += 256) wacc[e] = 0.0;
+  __syncthreads();
+
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    int64_t ti, tj;
+    tile_from_index(t, ti, tj);
+    const int64_t i0 = ti * GT, j0 = tj * GT;
+    // the tile's memberships: threads 0..63 look at its rows, 64..127 at its columns
+    int mine = 0, p1 = 0, p0 = 0;
+    if (tid < 2 * GT) {
+      const int64_t r = (tid < GT) ? i0 + tid : j0 + (tid - GT);
+      if (r < N) {
+        mine = member[r] != 0;
+        p1 = mine;
+        p0 = !mine;
+      }
+    }
+    // (both are barriers: every thread is done with the previous tile's LDS before anything below is overwritten)
+    const int any1 = __syncthreads_or(p1), any0 = __syncthreads_or(p0);
+    if (!(any1 && any0)) continue;  // one membership throughout: every pair contributes an exact zero
+    for (int e = tid; e < DT * GT; e += 256) {
+      const int d = e / GT, r = e - d * GT;
+      sa[e] = (d < D && i0 + r < N) ? U[(i0 + r) * D + d] : 0.0;
+      sb[e] = (d < D && j0 + r < N) ? U[(j0 + r) * D + d] : 0.0;
+    }
+    if (tid < GT) {
+      sal_a[tid] = (i0 + tid < N) ? alpha[i0 + tid] : 0.0;
+      sm_a[tid] = mine;
+    } else if (tid < 2 * GT) {
+      sal_b[tid - GT] = (j0 + tid - GT < N) ? alpha[j0 + tid - GT] : 0.0;
+      sm_b[tid - GT] = mine;
+    }
+    __syncthreads();
+
+    // this thread's 4 x 4 entries of Kinv: two 16-byte loads per row, issued before the arithmetic (lower triangle only is used)
+    double kin[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const int64_t i = i0 + 4 * ty + a, jb = j0 + 2 * tx;
+      const double* src = Kinv + (i < N ? i : N - 1) * ldk + jb;
+      if (jb + 34 <= ldk) {
+        const v2d q0 = *reinterpret_cast<const v2d*>(src), q1 = *reinterpret_cast<const v2d*>(src + 32);
+        kin[a][0] = q0.x; kin[a][1] = q0.y; kin[a][2] = q1.x; kin[a][3] = q1.y;
+      } else {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) kin[a][b] = (jb + (b & 1) + ((b >> 1) << 5) < N) ? src[(b & 1) + ((b >> 1) << 5)] : 0.0;
+      }
+    }
+    double r2[4][4], r2m[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) r2[a][b] = r2m[a][b] = 0.0;
+#pragma unroll 4
+    for (int d = 0; d < DT; ++d) {
+      const v2d u01 = *reinterpret_cast<const v2d*>(sa + d * GT + 4 * ty), u23 = *reinterpret_cast<const v2d*>(sa + d * GT + 4 * ty + 2);
+      const v2d b01 = *reinterpret_cast<const v2d*>(sb + d * GT + 2 * tx), b23 = *reinterpret_cast<const v2d*>(sb + d * GT + 32 + 2 * tx);
+      const double ua[4] = {u01.x, u01.y, u23.x, u23.y}, ub[4] = {b01.x, b01.y, b23.x, b23.y};
+      const double wd = sw[d];
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const double df = ua[a] - ub[b];
+          if (!MAT || d < dsp) r2[a][b] = fma(wd * df, df, r2[a][b]);
+          else r2m[a][b] = fma(wd * df, df, r2m[a][b]);
+        }
+    }
+    // g = (m_i - m_j) 2 W_ij sf2 k_ij, gm the same with the Matern factor's derivative by -r2_mat (gpp_grad_tiles); 0 where the pair
+    // shares a membership, lies on or above the diagonal or outside the matrix
+    double g[4][4], gm[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const int64_t i = i0 + 4 * ty + a;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const int cb = 2 * tx + (b & 1) + ((b >> 1) << 5);
+        const int64_t j = j0 + cb;
+        double gg = 0.0, gmm = 0.0;
+        const int sgn = sm_a[4 * ty + a] - sm_b[cb];
+        if (i < N && j < i && sgn != 0) {
+          const double er = gpp_exp_nonpos(-r2[a][b], ec);
+          double kv = er, kd = 0.0;
+          if (MAT && kind == 1) {
+            const double aa = sqrt(6.0 * r2m[a][b]), ea = gpp_exp_nonpos(-aa, ec);
+            kv = er * (1.0 + aa) * ea;
+            kd = er * 3.0 * ea;
+          } else if (MAT && kind == 2) {
+            const double aa = sqrt(10.0 * r2m[a][b]), ea = gpp_exp_nonpos(-aa, ec);
+            kv = er * (1.0 + aa + aa * aa * (1.0 / 3.0)) * ea;
+            kd = er * (5.0 / 3.0) * (1.0 + aa) * ea;
+          }
+          const double Wij = 0.5 * (sal_a[4 * ty + a] * sal_b[cb] - kin[a][b]);
+          const double s2w = (sgn > 0 ? 2.0 : -2.0) * Wij * sf2;
+          gg = s2w * kv;
+          gmm = s2w * kd;
+        }
+        g[a][b] = gg;
+        gm[a][b] = gmm;
+      }
+    }
+    for (int k = 0; k < C; ++k) {
+      const int c = scol[k];
+      if (c < 0) continue;
+      const bool rbf_dim = !MAT || c < dsp;
+      const double* pa = sa + c * GT + 4 * ty;
+      const double* pb = sb + c * GT + 2 * tx;
+      const double ub[4] = {pb[0], pb[1], pb[32], pb[33]};
+      double s = 0.0;
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) s = fma(rbf_dim ? g[a][b] : gm[a][b], pa[a] - ub[b], s);
+      s = wave_sum(s);
+      if (lane == 0) wacc[wave * GD_MAX + k] += -2.0 * sw[c] * s;
+    }
+  }
+  __syncthreads();
+  if (tid < C) rec[(int64_t)blockIdx.x * C + tid] = (wacc[tid] + wacc[GD_MAX + tid]) + (wacc[2 * GD_MAX + tid] + wacc[3 * GD_MAX + tid]);
+}
+
+// g_theta[k] = the records' k-th sums, added in work-group order
+__global__ __launch_bounds__(256) void gpp_calib_finish(const double* __restrict__ rec, int nwg, int C, double* __restrict__ g_theta) {
+  __shared__ double red[256];
+  const int k = blockIdx.x, tid = threadIdx.x;
+  double v = 0.0;
+  for (int b = tid; b < nwg; b += 256) v += rec[(int64_t)b * C + k];
+  red[tid] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) g_theta[k] = red[0];
+}
+
+}  // namespace
+
+size_t gpp_calib_ws_bytes(int C) { return (size_t)G_WGS * (size_t)(C > 0 ? C : 0) * sizeof(double); }
+
+hipError_t gpp_launch_calib_grad_reduce(hipStream_t s, const double* U, int64_t N, int D, const double* w, const double* sf2, int kind,
+                                        int d_split, const double* alpha, const double* Kinv, int64_t ldk, const int32_t* member,
+                                        const int32_t* cols, int C, double* g_theta, void* ws, size_t ws_bytes) {
+  if (kind < 0 || kind > 2 || D < 1 || D > GD_MAX || C < 1 || C > D) return hipErrorInvalidValue;
+  if (N <= 1) return hipMemsetAsync(g_theta, 0, (size_t)C * sizeof(double), s);  // no pair of distinct rows: an empty sum
+  if (!ws || ws_bytes < gpp_calib_ws_bytes(C)) return hipErrorInvalidValue;
+  const int64_t T = (N + GT - 1) / GT, ntiles = T * (T + 1) / 2;
+  const int nwg = (int)(ntiles < G_WGS ? ntiles : G_WGS);
+  double* rec = reinterpret_cast<double*>(ws);
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), 0, s, U, N, D, w, sf2, kind, d_split, alpha, Kinv, ldk, member, cols, C, ntiles, rec);
+  };
+  const bool mat = kind != 0;
+#define GPP_CT(DT) (mat ? launch(gpp_calib_tiles<DT, true>) : launch(gpp_calib_tiles<DT, false>))
+  if (D <= 8) GPP_CT(8);
+  else if (D <= 16) GPP_CT(16);
+  else if (D <= 32) GPP_CT(32);
+  else GPP_CT(64);
+#undef GPP_CT
+  hipLaunchKernelGGL(gpp_calib_finish, dim3(C), dim3(256), 0, s, rec, nwg, C, g_theta);
+  return hipGetLastError();
+}

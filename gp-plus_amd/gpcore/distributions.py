@@ -165,7 +165,7 @@ class MultivariateNormal:
                 raise RuntimeError("log_prob of a noise-free kernel matrix: apply the likelihood first")
             from ..linalg import exact_mll
 
-            return exact_mll(cov.U1, cov.spec, cov.tau, self.loc, value, cov.grp, cov.n_grad_dims)
+            return exact_mll(cov.U1, cov.spec, cov.tau, self.loc, value, cov.grp, cov.n_grad_dims, calib=cov.calib)
         from ..linalg import dense_log_prob
 
         dense = cov if torch.is_tensor(cov) else cov.evaluate()
@@ -181,6 +181,8 @@ class MultivariateNormal:
             raise RuntimeError("loo_log_prob needs a square covariance")
         if cov.tau is None:
             raise RuntimeError("loo_log_prob of a noise-free kernel matrix: apply the likelihood first")
+        if cov.calib is not None:
+            raise NotImplementedError("loo_log_prob: the objective has no gradient by calibration parameters")
         from ..linalg import exact_loo
 
         return exact_loo(cov.U1, cov.spec, cov.tau, self.loc, value, cov.grp, cov.n_grad_dims)
@@ -196,6 +198,8 @@ class MultivariateNormal:
             raise RuntimeError("cv_log_prob needs a square covariance")
         if cov.tau is None:
             raise RuntimeError("cv_log_prob of a noise-free kernel matrix: apply the likelihood first")
+        if cov.calib is not None:
+            raise NotImplementedError("cv_log_prob: the objective has no gradient by calibration parameters")
         from ..linalg import exact_cv
 
         return exact_cv(cov.U1, cov.spec, cov.tau, self.loc, value, folds, cov.grp, cov.n_grad_dims)

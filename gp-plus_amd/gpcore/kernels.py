@@ -33,9 +33,12 @@ class LazyKernelMatrix:
     """sf2*k(U1,U2;w) (+ diag(tau[grp]) when square) held symbolically."""
 
     def __init__(self, U1: torch.Tensor, U2: Optional[torch.Tensor], spec: KernelSpec,
-                 tau: Optional[torch.Tensor] = None, grp: Optional[torch.Tensor] = None, n_grad_dims: Optional[int] = None):
+                 tau: Optional[torch.Tensor] = None, grp: Optional[torch.Tensor] = None, n_grad_dims: Optional[int] = None,
+                 calib=None):
         self.U1, self.U2, self.spec, self.tau, self.grp = U1, U2, spec, tau, grp
         self.n_grad_dims = n_grad_dims
+        #: ``linalg.Calibration`` of a training evaluation whose U1 holds calibration parameters (models/gp_plus.py), else None
+        self.calib = calib
 
     @property
     def is_square(self) -> bool:
@@ -62,7 +65,7 @@ class LazyKernelMatrix:
             raise RuntimeError("diagonal noise needs a square covariance")
         if self.tau is not None:
             raise RuntimeError("noise was already added to this covariance")
-        return LazyKernelMatrix(self.U1, None, self.spec, tau, grp, self.n_grad_dims)
+        return LazyKernelMatrix(self.U1, None, self.spec, tau, grp, self.n_grad_dims, self.calib)
 
     def noise_vector(self) -> Optional[torch.Tensor]:
         if self.tau is None:

@@ -26,7 +26,8 @@ from .backend import (KIND_MATERN32, KIND_RBF, UPLO_FULL, UPLO_UPPER, GppContext
 from .psd_safe import inputs_nan_probe, psd_safe
 from . import settings
 
-__all__ = ["KernelSpec", "exact_mll", "ExactMLLFunction", "exact_loo", "ExactLOOFunction", "loo_moments", "exact_cv", "ExactCVFunction",
+__all__ = ["KernelSpec", "exact_mll", "ExactMLLFunction", "CalibratedMLLFunction", "Calibration", "exact_loo", "ExactLOOFunction",
+           "loo_moments", "exact_cv", "ExactCVFunction",
            "cv_moments", "EvalWorkspace", "dense_kernel", "cross_kernel",
            "FactorCache", "factorize", "append_to_cache", "GradientFactorCache", "append_gradients_to_cache",
            "predict_from_gradient_cache", "dense_log_prob", "predict_mean", "predict_var", "predictive_cov_upper",
@@ -244,6 +245,7 @@ def _exact_forward(fn, ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slo
         dev = U.device
         N, D = U.shape
         Ud, wd, sd, td, grp, S, need_grad, need_U = _eval_operands(ctx, U, w, sf2, tau, mean, y, grp, dU)
+        need_grad = need_grad or getattr(fn, "wants_grad", False)  # (an input of the objective's own: the calibration parameters)
         ws = get_workspace(gctx, N, slot)
         ws.epoch += 1
         torch.sub(_as_f64(y.detach(), dev), _as_f64(mean.detach(), dev), out=ws.r)
@@ -315,18 +317,85 @@ class ExactMLLFunction(torch.autograd.Function):
 
 
 def exact_mll(U: torch.Tensor, spec: KernelSpec, tau: torch.Tensor, mean: torch.Tensor, y: torch.Tensor,
-              grp: Optional[torch.Tensor] = None, n_grad_dims: Optional[int] = None, slot: Optional[int] = None) -> torch.Tensor:
-    """log N(y | mean, Ky) on the GPU; differentiable w.r.t. U[:, :n_grad_dims], spec.w, spec.sf2, tau, mean, y."""
+              grp: Optional[torch.Tensor] = None, n_grad_dims: Optional[int] = None, slot: Optional[int] = None,
+              calib: Optional["Calibration"] = None) -> torch.Tensor:
+    """log N(y | mean, Ky) on the GPU; differentiable w.r.t. U[:, :n_grad_dims], spec.w, spec.sf2, tau, mean, y — and, with
+    ``calib``, w.r.t. the calibration parameters ``calib.theta`` whose values ``U`` holds (CalibratedMLLFunction)."""
     if slot is None:
         slot = current_slot()
     if n_grad_dims is None:
         n_grad_dims = U.shape[1] if U.requires_grad else 0
     shard = settings.sharded_evaluation.value()
+    if calib is not None:
+        if shard is not None:
+            raise NotImplementedError("calibration parameters are not available under settings.sharded_evaluation")
+        return CalibratedMLLFunction.apply(U, spec.w, spec.sf2, tau, mean, y, grp, spec.kind, spec.d_split, int(n_grad_dims), slot,
+                                           calib.theta, calib.member, calib.cols)
     if shard is not None:
         from .sharded import sharded_mll
         return sharded_mll(U, spec.w, spec.sf2, tau, mean, y, grp, spec.kind, spec.d_split, int(n_grad_dims),
                            group=shard.get("group"), nb=int(shard.get("nb", 1024)))
     return ExactMLLFunction.apply(U, spec.w, spec.sf2, tau, mean, y, grp, spec.kind, spec.d_split, int(n_grad_dims), slot)
+
+
+class _CalibratedEvaluation:
+    """What ``_exact_forward`` asks of an objective, for ONE evaluation of the marginal likelihood of a model with calibration
+    parameters: ExactMLLFunction's sequence on the dense route (plain LAUUM, Ky^-1 in memory: the LAUUM-fused reduction has no
+    feature gradients) followed by gpp_calib_grad_reduce on the same alpha and Ky^-1."""
+
+    capturable, value_needs_alpha, what = False, False, "the marginal likelihood of a model with calibration parameters"
+
+    def __init__(self, member, cols, wants_grad):
+        self.member, self.cols, self.wants_grad, self.g_theta = member, cols, wants_grad, None
+
+    def tail(self, gctx, ws, need_grad, ops, grads, kind, d_split):
+        if not need_grad:
+            return
+        with _stage("lauum"):
+            gctx.lauum(ws.Li, ws.Ki)
+        with _stage("grad_reduce"):
+            gctx.grad_reduce(*ops, ws.alpha, ws.Ki, *grads, kind=kind, d_split=d_split)
+        if self.wants_grad:
+            with _stage("calib_grad_reduce"):
+                self.g_theta = torch.empty(self.cols.numel(), dtype=torch.float64, device=ws.A.device)
+                gctx.calib_grad_reduce(*ops[:3], ws.alpha, ws.Ki, self.member, self.cols, self.g_theta, kind=kind, d_split=d_split)
+
+    @staticmethod
+    def result(ws, need_grad):
+        return ExactMLLFunction.result(ws, need_grad)
+
+
+class CalibratedMLLFunction(torch.autograd.Function):
+    """:class:`ExactMLLFunction` with one more differentiable input, the calibration parameters ``theta`` (C,): theta[k] stands in
+    feature column ``cols[k]`` of the rows with ``member[i] != 0`` (reference models/gp_plus.py:439-461).  ``U`` already holds the
+    values — as constants: those columns are past ``dU`` — and
+        d mll / d theta_k = sum_ij W_ij (m_i - m_j) dK_ij/du_{i,cols[k]},   W = (alpha alpha^T - Ky^-1) / 2
+    comes from gpp_calib_grad_reduce, a scalar reduction per parameter: no N x D feature gradient exists on this route.  A sibling
+    of ExactMLLFunction, so a model without calibration parameters enqueues exactly what it did before."""
+
+    @staticmethod
+    def forward(ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slot, theta, member, cols):
+        ev = _CalibratedEvaluation(member, cols, ctx.needs_input_grad[11])
+        ctx.theta_dtype = theta.dtype
+        value = _exact_forward(ev, ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slot)
+        ctx.g_theta = ev.g_theta
+        return value
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        g_theta = None
+        if ctx.needs_input_grad[11]:
+            g_theta = (grad_out.to(torch.float64) * ctx.g_theta).to(ctx.theta_dtype)
+        return _eval_backward(ctx, grad_out, *ctx.saved) + (None,) * 5 + (g_theta, None, None)
+
+
+@dataclass
+class Calibration:
+    """The calibration parameters of a lazy covariance: ``theta`` (C,) autograd-connected to the model's ``Theta_<n>.constant``,
+    ``member`` (N,) int32 (1 on the rows of the calibrated source) and ``cols`` (C,) int32 (feature column of each parameter)."""
+    theta: torch.Tensor
+    member: torch.Tensor
+    cols: torch.Tensor
 
 
 class ExactLOOFunction(torch.autograd.Function):

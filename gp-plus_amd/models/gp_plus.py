@@ -125,7 +125,19 @@ class GP_Plus(GPR):
             raise NotImplementedError("probabilistic embedding/calibration (stochastic multi-pass ensembles, "
                                       "gp_plus.py:387-392,414-461) is outside the exact-GP hot path of this build")
         if len(calibration_id) > 0:
-            raise NotImplementedError("calibration parameters (gp_plus.py:311-320,440-461) are outside this build's scope")
+            # deterministic calibration (gp_plus.py:311-320,440-461): every id names a quantitative column of train_x
+            ncol = train_x.shape[-1]
+            for n in calibration_id:
+                if n < 0 or n >= ncol or n in qual_dict:
+                    raise ValueError(f"calibration_id: column {n} is not a quantitative column of train_x "
+                                     "(a calibration parameter stands in a quantitative input)")
+            if len(set(calibration_id)) != len(calibration_id):
+                raise ValueError("calibration_id: a column is listed twice")
+            if (ncol - 1) not in qual_dict or qual_dict[ncol - 1] < 2:
+                raise ValueError("calibration needs the data source as the last, categorical column of train_x "
+                                 "(the calibrated rows are those of source 0)")
+            if len(self.mean_prior_cal) != len(calibration_id) or len(self.std_prior_cal) != len(calibration_id):
+                raise ValueError("mean_prior_cal and std_prior_cal need one entry per calibration_id")
         if len(separate_embedding) > 0:
             raise NotImplementedError("separate_embedding is effectively broken in the reference (SURVEY.md B-5)")
         if m_gp not in ('single_constant', 'single_zero', 'multiple_constant'):
@@ -137,6 +149,12 @@ class GP_Plus(GPR):
         self.calibration_id = calibration_id
         self.calibration_source_index = 0
         self.calibration_type = calibration_type
+        if len(calibration_id) > 0:
+            # gp_plus.py:318-320: the calibrated source's entries in the calibrated columns are unknown (NaN is the expected way to
+            # say so; fill_nan_with_mean has put the column mean there) and are zeroed: theta stands there in every forward
+            rows = torch.where(train_x[:, -1] == self.calibration_source_index)[0]
+            for n in calibration_id:
+                train_x[rows, n] = torch.zeros_like(train_x[rows, n])
         # index bookkeeping: gp_plus.py:190-217
         qual_dict_list = list(qual_dict.keys())
         all_index = set(range(train_x.shape[-1]))
@@ -206,6 +224,13 @@ class GP_Plus(GPR):
         self.count = train_x.size()[0]
         self.num_pass_train, self.num_pass_pred = num_pass_train, num_pass_pred
         self._cat_cache = {}
+        # calibration parameters (gp_plus.py:311-320): Theta_<n>.constant with a NormalPrior of its own; feature column of the k-th one
+        # = embedding dims + position of column n among the quantitative columns (the reference's embeddings.size(1) + n whenever
+        # the categorical columns come last, which it assumes)
+        self._calib_pos = [quant_index.index(n) for n in calibration_id]
+        self._calib_cache, self._calib_cols = None, {}
+        for n, mean_prior, std_prior in zip(calibration_id, self.mean_prior_cal, self.std_prior_cal):
+            setattr(self, 'Theta_' + str(n), ConstantMean(prior=NormalPrior(float(mean_prior), float(std_prior))))
         if len(qual_kernel_columns) > 0:
             for i in range(len(qual_kernel_columns)):
                 if type(qual_kernel_columns[i]) == int:
@@ -239,6 +264,7 @@ class GP_Plus(GPR):
     def _apply(self, fn, *args, **kwargs):
         out = super()._apply(fn, *args, **kwargs)  # encoder weights are registered on this module, so they move too
         self._cat_cache = {}
+        self._calib_cache, self._calib_cols = None, {}
         if hasattr(self, 'likelihood') and hasattr(self.likelihood, 'fidel_indices') and torch.is_tensor(self.likelihood.fidel_indices):
             self.likelihood.fidel_indices = fn(self.likelihood.fidel_indices)
         return out
@@ -261,8 +287,61 @@ class GP_Plus(GPR):
             if key is not None:
                 self._cat_cache = {key: zeta_rows}
         emb = self.A_matrix[i](zeta_rows)
-        x_new = torch.cat([emb, x[..., self.quant_index.long()].to(**self.tkwargs)], dim=-1)
+        xq = x[..., self.quant_index.long()].to(**self.tkwargs)
+        if len(self.calibration_id) > 0:
+            # gp_plus.py:439-461: theta_k into the rows of the calibrated source, in training and in eval mode, for any x (the
+            # membership comes from THIS x's last column).  The values enter as constants: the gradient by theta is
+            # CalibratedMLLFunction's own (``_calibration``), not a feature gradient
+            member = self._calibration_rows(x)[0]
+            pos = self._calib_pos
+            xq[:, pos] = torch.where(member.unsqueeze(1), self._theta_vector().detach().unsqueeze(0), xq[:, pos])
+        x_new = torch.cat([emb, xq], dim=-1)
         return x_new, emb.shape[-1]
+
+    def _theta_vector(self):
+        """The calibration parameters (C,), autograd-connected to ``Theta_<n>.constant``, in ``calibration_id`` order."""
+        return torch.cat([getattr(self, 'Theta_' + str(n)).constant.reshape(1) for n in self.calibration_id]).to(**self.tkwargs)
+
+    def _calibration(self, x, dz):
+        """What the training objective needs besides the features of ``x`` (``linalg.Calibration``): theta, the membership of the
+        rows and the feature column of each parameter."""
+        from ..linalg import Calibration
+
+        cols = self._calib_cols.get(dz)
+        if cols is None:
+            cols = torch.tensor([dz + pos for pos in self._calib_pos], dtype=torch.int32, device=self.tkwargs['device'])
+            self._calib_cols[dz] = cols
+        return Calibration(self._theta_vector(), self._calibration_rows(x)[1], cols)
+
+    def _calibration_rows(self, x):
+        """(membership of ``x``'s rows in the calibrated source as bool, the same as int32) on the model's device; computed once for
+        the training inputs (the same tensor object in every forward of a fit), every time for anything else."""
+        dev = self.tkwargs['device']
+        is_train = self.train_inputs is not None and len(self.train_inputs) > 0 and x is self.train_inputs[0]
+        cached = getattr(self, '_calib_cache', None)
+        if is_train and cached is not None and cached[0] is x and cached[1] == x._version:
+            return cached[2]
+        member = (x[:, -1] == self.calibration_source_index).to(dev)
+        out = (member, member.to(torch.int32).contiguous())
+        if is_train:
+            self._calib_cache = (x, x._version, out)
+        return out
+
+    def _refuse_calibrated(self, what: str, why: str):
+        if len(self.calibration_id) > 0:
+            raise NotImplementedError(f"{what} is not available for a model with calibration parameters: {why}")
+
+    def calibration_result(self, mean_train=None, std_train=None):
+        """gp_plus.py:934-956: the estimated calibration parameters ``{n: theta_n}``, a float per id.  With the column means and
+        standard deviations the inputs were standardised by, ``theta_n * std_train[n] + mean_train[n]``: the parameter in the units
+        of the data."""
+        if (mean_train is None) != (std_train is None):
+            raise ValueError("calibration_result: give both mean_train and std_train, or neither")
+        out = {}
+        for n in self.calibration_id:
+            theta = float(getattr(self, 'Theta_' + str(n)).constant.detach().reshape(-1)[0])
+            out[n] = theta if mean_train is None else theta * float(std_train[n]) + float(mean_train[n])
+        return out
 
     def forward(self, x: torch.Tensor) -> MultivariateNormal:
         """gp_plus.py:386-484 (deterministic single pass)."""
@@ -276,6 +355,8 @@ class GP_Plus(GPR):
             mean_x = self.single_mean(x_new).to(**self.tkwargs)
         covar_x = self.covar_module(x_new)
         covar_x.n_grad_dims = dz if x_new.requires_grad else 0
+        if len(self.calibration_id) > 0 and self.training:
+            covar_x.calib = self._calibration(x, dz)
         return MultivariateNormal(mean_x, covar_x)
 
     # ---- mean functions ------------------------------------------------------------------------------
@@ -323,6 +404,10 @@ class GP_Plus(GPR):
         eager route."""
         from ..optim.mll_torch import check_objective_folds
         folds = check_objective_folds(objective, folds, int(self.train_targets.shape[0]))
+        if objective != "mll":
+            self._refuse_calibrated(f'objective="{objective}"', "only the exact marginal likelihood has a gradient by theta")
+        if optim_type == 'adam_torch_batched':
+            self._refuse_calibrated("optim_type='adam_torch_batched'", "the batched restarts have no gradient by theta")
         print("## Learning the model's parameters has started ##")
         if self.tkwargs['device'].type != 'cuda':
             raise RuntimeError("this build evaluates the marginal likelihood only on an MI355X (device='cuda'); "
@@ -357,8 +442,8 @@ class GP_Plus(GPR):
         from ..backend import row_stride
         from ..optim.mll_batched import BATCHED_MAX_N
 
-        if not gpp_settings.batched_restarts.value():
-            return False
+        if not gpp_settings.batched_restarts.value() or len(self.calibration_id) > 0:
+            return False  # (calibration parameters: the batched evaluation has no gradient by theta)
         N = int(self.train_targets.shape[0])
         if N > BATCHED_MAX_N:
             return False
@@ -368,7 +453,10 @@ class GP_Plus(GPR):
 
     def fill_nan_with_mean(self, train_x, cal_ID):
         if torch.isnan(train_x).any():
-            print("There are NaN values in the data, which will be filled with column-wise mean values.")
+            if len(cal_ID) == 0:
+                print("There are NaN values in the data, which will be filled with column-wise mean values.")
+            else:
+                print("There are NaN values in the data, which will be estimated in calibration process")
             col_means = torch.nanmean(train_x, dim=0)
             nan_indices = torch.isnan(train_x)
             train_x[nan_indices] = col_means.repeat(train_x.shape[0], 1)[nan_indices]
@@ -452,6 +540,7 @@ class GP_Plus(GPR):
             object.__setattr__(enc, '_owner', weakref.ref(child))
         child._cat_cache = {}
         child.__dict__.pop('_seen_levels', None)
+        child._calib_cache, child._calib_cols = None, {}
 
     # ---- posterior of the gradient -------------------------------------------------------------------
     def _gradient_rows(self, X, what: str):
@@ -498,6 +587,7 @@ class GP_Plus(GPR):
         graph capture."""
         from ..linalg import gradient_from_cache
 
+        self._refuse_calibrated("predict_gradient", "the gradient by a calibrated column has no meaning on the calibrated source")
         cache, Us, d0, p = self._gradient_operands(self._gradient_rows(Xtest, "predict_gradient"), "predict_gradient")
         scale = self.y_std.detach().to(torch.float64)
         with torch.no_grad():
@@ -521,6 +611,7 @@ class GP_Plus(GPR):
         ``ValueError`` for weights that are negative, not finite, all zero or of the wrong length."""
         from ..linalg import gradient_from_cache
 
+        self._refuse_calibrated("active_subspace", "the gradient by a calibrated column has no meaning on the calibrated source")
         X = self._gradient_rows(X, "active_subspace")
         if weights is not None:
             weights = data_type_check(weights).reshape(-1).to(torch.float64)
@@ -565,6 +656,7 @@ class GP_Plus(GPR):
         ``noise``; the receiver stays usable.  ``NotImplementedError`` under ``settings.sharded_evaluation`` or a graph capture."""
         from ..gradient_enhanced import condition_on_gradients
 
+        self._refuse_calibrated("condition_on_gradients", "gradient observations by a calibrated column are not defined")
         return condition_on_gradients(self, X, dY, noise)
 
     def noise_value(self):

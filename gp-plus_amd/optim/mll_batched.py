@@ -190,6 +190,8 @@ def fit_model_torch_batched(model, lr_default: float = 0.01, num_iter: int = 100
     leave-one-out log pseudo-likelihood (plus the priors) in the same way: batched, and replayed as a HIP graph."""
     N = int(model.train_targets.shape[0])
     folds = check_objective_folds(objective, folds, N)
+    if getattr(model, "calibration_id", None):
+        raise NotImplementedError("the batched restarts have no gradient by calibration parameters: use fit_model_torch")
     if objective == "cv":  # the cross-validation objective has no batched form: the sequential, eager driver
         from .mll_torch import fit_model_torch
         return fit_model_torch(model, None, lr_default, num_iter, num_restarts, break_steps, verbose=verbose, objective=objective,

@@ -97,7 +97,8 @@ class MLLObjective:
             dev = params[0].device if params else torch.device("cpu")
             n_points = self.model.train_inputs[0].shape[0]
             ok = (self.objective == "mll" and settings.graphed_objective.value() and dev.type == "cuda" and n_points < LOOKAHEAD_MIN_N
-                  and settings.sharded_evaluation.value() is None and not getattr(self.model, "interval_score", False))
+                  and settings.sharded_evaluation.value() is None and not getattr(self.model, "interval_score", False)
+                  and not getattr(self.model, "calibration_id", None))  # (calibrated models: the eager evaluation)
             if not ok:
                 self._graph_failed = True
                 return None
@@ -151,6 +152,8 @@ def get_bounds(likobj: MLLObjective, theta: np.ndarray):
             a, b = -10.0, 3.0
         elif name.startswith('mean'):
             a, b = -1.5, 1.5
+        elif name.startswith('Theta_'):  # calibration parameters (optim/mll_scipy.py:173-175)
+            a, b = -15.0, 15.0
         else:
             a, b = -np.inf, np.inf
         lo += [a] * n

@@ -62,6 +62,8 @@ def _graphed_step(model, mll, params, evaluations: int):
     dev, n = plist[0].device, int(model.train_targets.shape[0])
     if dev.type != "cuda" or n >= LOOKAHEAD_MIN_N or settings.sharded_evaluation.value() is not None:
         return None
+    if getattr(model, "calibration_id", None):  # calibration parameters: the eager evaluation (CalibratedMLLFunction is not captured)
+        return None
     from ..graphed import GraphedLossAndGrad
 
     def closure():

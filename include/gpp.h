@@ -429,6 +429,21 @@ int gpp_loo_grad_reduce(gpp_handle_t h, const double* U, int64_t N, int D, const
                         const double* C, int64_t ldc, int dU, double* g_w, double* g_sf2, double* g_tau, double* g_U);
 
 /*
+ * Gradient of the MLL by calibration parameters (reference models/gp_plus.py:439-461 writes theta_k into input column k of every
+ * row of the calibrated source and leaves the derivative to autograd).  With member[i] != 0 for the rows that carry theta, cols[k]
+ * the feature column of theta_k (0 <= cols[k] < D, 1 <= C <= D) and W = 0.5 (alpha alpha' - Kinv):
+ *   g_theta[k] = sum_ij W_ij (m_i - m_j) dK_ij/du_{i,cols[k]}  =  sum_{i: member[i] != 0} g_U[i, cols[k]] of gpp_grad_reduce
+ * without an N x D block of feature gradients.  The noise diagonal does not depend on theta; pairs of one source contribute an exact
+ * zero (all rows members, or none: g_theta = 0.0), and 64 x 64 tiles with one membership throughout are skipped unread.  Only the
+ * LOWER triangle of Kinv is read (as gpp_lauum leaves it); all three kinds, cols[k] on either side of d_split.  One record per
+ * work-group in the handle workspace (gpp_workspace_bytes(GPP_OP_MLL_EVAL) covers it), added in index order: no atomics, the result
+ * depends on the sizes alone, bit for bit.
+ */
+int gpp_calib_grad_reduce(gpp_handle_t h, const double* U, int64_t N, int D, const double* w, const double* sf2, int kind,
+                          int d_split, const double* alpha, const double* Kinv, int64_t ldk, const int32_t* member,
+                          const int32_t* cols, int C, double* g_theta);
+
+/*
  * The same reduction restricted to the block rows of Kinv this rank owns in a sharded evaluation (SURVEY.md §8(e) mode 2;
  * BASELINE config 5): rows [b*nb, (b+1)*nb) with b % nranks == rank (nb a multiple of 64).  Only those rows of Kinv are
  * read; the outputs are this rank's PARTIAL sums (the caller all-reduces them).  nranks == 1 is gpp_grad_reduce.
