@@ -120,37 +120,17 @@ struct KernelGen {
   }
   __device__ __forceinline__ bool second(int d) const { return MAT && kind != 0 && d >= d_split; }
   __device__ __forceinline__ double value(const double (&acc)[NACC]) const {
-    double v = gpp_exp_nonpos(-acc[0], ec);
-    if constexpr (MAT) {  // the factors of kfun (gpp_build.hip)
-      if (kind == 1) {
-        const double r = sqrt(3.0 * 2.0 * acc[1]);
-        v *= (1.0 + r) * gpp_exp_nonpos(-r, ec);
-      } else if (kind == 2) {
-        const double r = sqrt(5.0 * 2.0 * acc[1]);
-        v *= (1.0 + r + r * r * (1.0 / 3.0)) * gpp_exp_nonpos(-r, ec);
-      }
-    }
-    return sf2 * v;
+    if constexpr (MAT) return sf2 * gpp_kernel_value(kind, acc[0], acc[1], ec);
+    else return sf2 * gpp_exp_nonpos(-acc[0], ec);
   }
   // gradient: one ones-column per factor gives the row sums of W_f; m_f as in the file header
   static constexpr int NROWSUM = NACC;
   __device__ __forceinline__ void dvalue(const double (&acc)[NACC], double (&m)[NACC]) const {
     const double e1 = sf2 * gpp_exp_nonpos(-acc[0], ec);
     if constexpr (MAT) {
-      double h, hp;
-      if (kind == 1) {
-        const double r = sqrt(3.0 * 2.0 * acc[1]);
-        const double er = gpp_exp_nonpos(-r, ec);
-        h = (1.0 + r) * er;
-        hp = -3.0 * er;
-      } else {
-        const double r = sqrt(5.0 * 2.0 * acc[1]);
-        const double er = gpp_exp_nonpos(-r, ec);
-        h = (1.0 + r + r * r * (1.0 / 3.0)) * er;
-        hp = (-5.0 / 3.0) * (1.0 + r) * er;
-      }
-      m[0] = -(e1 * h);
-      m[1] = e1 * hp;
+      const GppMatern h = gpp_matern(kind, acc[1], ec);
+      m[0] = -(e1 * (h.p * h.er));
+      m[1] = e1 * (h.dp * h.er);
     } else {
       m[0] = -e1;
     }

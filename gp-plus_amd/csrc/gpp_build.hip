@@ -24,18 +24,6 @@ namespace {
 constexpr int TB = 64;
 constexpr int DMAX = 64;
 
-__device__ __forceinline__ double kfun(double r2_rbf, double r2_mat, int kind, const GppExpConsts& ec) {
-  double v = gpp_exp_nonpos(-r2_rbf, ec);
-  if (kind == 1) {  // Matern 3/2 in the scaled distance r = sqrt(2 * r2_mat)  (gpytorch MaternKernel nu=1.5)
-    const double r = sqrt(3.0 * 2.0 * r2_mat);
-    v *= (1.0 + r) * gpp_exp_nonpos(-r, ec);
-  } else if (kind == 2) {  // Matern 5/2
-    const double r = sqrt(5.0 * 2.0 * r2_mat);
-    v *= (1.0 + r + r * r * (1.0 / 3.0)) * gpp_exp_nonpos(-r, ec);
-  }
-  return v;
-}
-
 // grid.x = tile id.  lower = 1 / 2: only the tiles of the lower / upper triangle of a square problem are written.
 // MAT = false: pure RBF product (kind 0) — no second set of distance accumulators (32 VGPRs: four instead of three waves per
 // SIMD behind the loads and the exp chains) and no Matern code.
@@ -136,8 +124,8 @@ __global__ __launch_bounds__(256) void gpp_cov_tile(const double* __restrict__ U
     double v[4];
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-      const int64_t j = j0 + 2 * tx + (b & 1) + ((b >> 1) << 5);
-      double x = sf2 * (MAT ? kfun(r2a[a][b], r2b[MAT ? a : 0][MAT ? b : 0], kind, ec) : gpp_exp_nonpos(-r2a[a][b], ec));
+      const int64_t j = j0 + gpp_tile_col(2 * tx, b);
+      double x = sf2 * (MAT ? gpp_kernel_value(kind, r2a[a][b], r2b[MAT ? a : 0][MAT ? b : 0], ec) : gpp_exp_nonpos(-r2a[a][b], ec));
       if (add_diag && i == j) x += (tau ? tau[grp ? grp[i] : 0] : 0.0) + jitter;
       v[b] = x;
     }

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(DX_THREADS) void gpp_cross_dx_f64(DxArgs p) {
   }
   __syncthreads();
 
-  // the multipliers, once per pair (KernelGen::dvalue of gpp_apply.hip, operation for operation)
+  // the multipliers, once per pair: m_0 = -(e1 h), m_1 = e1 h' from gpp_matern's pieces, as KernelGen::dvalue of gpp_apply.hip forms them
   const GppExpConsts ec = gpp_exp_consts();
   const double sf2 = *p.sf2;
   for (int pr = t; pr < DX_TA * DX_TN; pr += DX_THREADS) {
@@ -108,17 +108,17 @@ __global__ __launch_bounds__(DX_THREADS) void gpp_cross_dx_f64(DxArgs p) {
         const double df = ua[d] - ub[d];
         q2 = fma(df, df, q2);
       }
-      double h, hp;  // h' without a division by r: finite where the two points agree
+      // (one call per kind, the products inside the branches: with a single call the two exp chains of a pair meet in one block,
+      //  the scheduler interleaves them and the kernel takes 50 registers instead of 48)
+      double h, hp;
       if (p.kind == 1) {
-        const double r = sqrt(3.0 * 2.0 * q2);
-        const double er = gpp_exp_nonpos(-r, ec);
-        h = (1.0 + r) * er;
-        hp = -3.0 * er;
+        const GppMatern m = gpp_matern(1, q2, ec);
+        h = m.p * m.er;
+        hp = m.dp * m.er;
       } else {
-        const double r = sqrt(5.0 * 2.0 * q2);
-        const double er = gpp_exp_nonpos(-r, ec);
-        h = (1.0 + r + r * r * (1.0 / 3.0)) * er;
-        hp = (-5.0 / 3.0) * (1.0 + r) * er;
+        const GppMatern m = gpp_matern(2, q2, ec);
+        h = m.p * m.er;
+        hp = m.dp * m.er;
       }
       sM[nl * DX_TAP + al] = -(e1 * h);
       sM[DX_TN * DX_TAP + nl * DX_TAP + al] = e1 * hp;
@@ -377,7 +377,7 @@ __global__ __launch_bounds__(HX_THREADS) void gpp_kernel_dxdx_f64(HxArgs p) {
   }
   __syncthreads();
 
-  // the multipliers, once per pair (the staged arithmetic of gpp_cross_kernel_dx, operation for operation, plus h'')
+  // the multipliers, once per pair: those of gpp_cross_kernel_dx and m_2 = -(e1 h'') (gpp_matern_d2)
   {
     const GppExpConsts ec = gpp_exp_consts();
     const double sf2 = *p.sf2;
@@ -396,23 +396,10 @@ __global__ __launch_bounds__(HX_THREADS) void gpp_kernel_dxdx_f64(HxArgs p) {
         const double df = ua[d] - ub[d];
         q2 = fma(df, df, q2);
       }
-      double h, hp, hpp;  // h' without a division by r; h'' of the Matern 3/2 factor divides by r and is an exact 0 where r == 0
-      if (p.kind == 1) {
-        const double r = sqrt(3.0 * 2.0 * q2);
-        const double er = gpp_exp_nonpos(-r, ec);
-        h = (1.0 + r) * er;
-        hp = -3.0 * er;
-        hpp = r > 0.0 ? (9.0 * er) / r : 0.0;
-      } else {
-        const double r = sqrt(5.0 * 2.0 * q2);
-        const double er = gpp_exp_nonpos(-r, ec);
-        h = (1.0 + r + r * r * (1.0 / 3.0)) * er;
-        hp = (-5.0 / 3.0) * (1.0 + r) * er;
-        hpp = (25.0 / 3.0) * er;
-      }
-      sM[al * HX_TBP + bl] = -(e1 * h);
-      sM[MT + al * HX_TBP + bl] = e1 * hp;
-      sM[2 * MT + al * HX_TBP + bl] = -(e1 * hpp);
+      const GppMatern h = gpp_matern(p.kind, q2, ec);
+      sM[al * HX_TBP + bl] = -(e1 * (h.p * h.er));
+      sM[MT + al * HX_TBP + bl] = e1 * (h.dp * h.er);
+      sM[2 * MT + al * HX_TBP + bl] = -(e1 * gpp_matern_d2(p.kind, h));
     } else {
       sM[al * HX_TBP + bl] = -e1;
     }

@@ -650,7 +650,7 @@ __global__ __launch_bounds__(256, 2) void gpp_lauum_grad_f64(GemmArgs p, GradEpi
 
 // ---- Vc Vr^T with the weighted squared posterior cross-covariance as its epilogue (gpp_post_cross_sq in gpp.h) -------------------
 // Entry (c, r) of a 128 x 128 tile of Vc Vr^T never reaches memory: the epilogue regenerates g = sf2 k(Uc_c, Ur_r; w) with the
-// arithmetic of gpp_cov_tile (features staged times sqrt(w_d), r2 summed by fma in the order of d, kfun's factors), forms
+// arithmetic of gpp_cov_tile (features staged times sqrt(w_d), r2 summed by fma in the order of d, gpp_kernel_value), forms
 // omega_r (g - acc)^2 and sums it along the tile's columns.  The slab idiom of GradEpilogue: the 16 values of slab a4 pass through
 // lane-private LDS slots, the arithmetic runs in a rolled loop over half-slabs of 2 rows x 4 columns per lane.  The features are
 // staged DC dims at a time: D <= DC once for the whole tile; above, every half-slab walks the chunks (two barriers per chunk — the
@@ -751,16 +751,7 @@ struct PostCrossEpilogue {
           double s = 0.0;
 #pragma unroll
           for (int b = 0; b < 4; ++b) {
-            double kv = gpp_exp_nonpos(-r2[a][b], ec);
-            if constexpr (MAT) {  // the factors of kfun (gpp_build.hip)
-              if (kind == 1) {
-                const double r = sqrt(3.0 * 2.0 * r2m[MAT ? a : 0][MAT ? b : 0]);
-                kv *= (1.0 + r) * gpp_exp_nonpos(-r, ec);
-              } else if (kind == 2) {
-                const double r = sqrt(5.0 * 2.0 * r2m[MAT ? a : 0][MAT ? b : 0]);
-                kv *= (1.0 + r + r * r * (1.0 / 3.0)) * gpp_exp_nonpos(-r, ec);
-              }
-            }
+            const double kv = MAT ? gpp_kernel_value(kind, r2[a][b], r2m[MAT ? a : 0][MAT ? b : 0], ec) : gpp_exp_nonpos(-r2[a][b], ec);
             const double c = sf2 * kv - slab[((2 * h + a) * 4 + b) * 256 + tid];
             double t = c * c;
             t = (cb + 16 * b < clim) ? t : 0.0;  // (a select: whatever a column beyond M_r holds never reaches a sum)
@@ -894,16 +885,7 @@ struct PostCrossMinEpilogue {
         for (int a = 0; a < 2; ++a)
 #pragma unroll
           for (int b = 0; b < 4; ++b) {
-            double kv = gpp_exp_nonpos(-r2[a][b], ec);
-            if constexpr (MAT) {  // the factors of kfun (gpp_build.hip)
-              if (kind == 1) {
-                const double r = sqrt(3.0 * 2.0 * r2m[MAT ? a : 0][MAT ? b : 0]);
-                kv *= (1.0 + r) * gpp_exp_nonpos(-r, ec);
-              } else if (kind == 2) {
-                const double r = sqrt(5.0 * 2.0 * r2m[MAT ? a : 0][MAT ? b : 0]);
-                kv *= (1.0 + r + r * r * (1.0 / 3.0)) * gpp_exp_nonpos(-r, ec);
-              }
-            }
+            const double kv = MAT ? gpp_kernel_value(kind, r2[a][b], r2m[MAT ? a : 0][MAT ? b : 0], ec) : gpp_exp_nonpos(-r2[a][b], ec);
             const double c = sf2 * kv - slab[((2 * h + a) * 4 + b) * 256 + tid];
             cv[a][b] = (cb + 16 * b < clim) ? c : 0.0;  // (a select: whatever a column beyond M_r holds never reaches a minimum)
           }

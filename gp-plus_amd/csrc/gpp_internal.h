@@ -147,6 +147,55 @@ __device__ __forceinline__ double gpp_exp_nonpos(double x, const GppExpConsts& k
   p = __builtin_fma(p, r, 1.0);
   return __builtin_ldexp(p, (int)n);
 }
+
+// ---- the Matern factor of the covariance kernels ---------------------------------------------
+// k = sf2 exp(-r2_rbf) h(r2_mat), h the Matern factor in the scaled distance r = sqrt(2 nu r2_mat) (gpytorch MaternKernel):
+//   kind 1, nu = 3/2:  h = (1 + r) e^-r            dh/d r2_mat = -3 e^-r               d2h/d r2_mat^2 = 9 e^-r / r
+//   kind 2, nu = 5/2:  h = (1 + r + r^2 / 3) e^-r  dh/d r2_mat = -(5/3)(1 + r) e^-r    d2h/d r2_mat^2 = (25/3) e^-r
+// (the first derivative without a division by r: finite where the two points agree).  The ONE definition every kernel of the library
+// uses — the error bounds of the tests assume that all of them round alike.  It returns the pieces h = p er and dh/d r2_mat = dp er,
+// not the products: a caller multiplies them into its own chain in its own order, and the pieces it does not read cost nothing.
+// Callers reach it with kind 1 or 2 only (kind 0 has no Matern factor; the launchers refuse everything else).
+struct GppMatern {
+  double r, er, p, dp;
+};
+__device__ __forceinline__ GppMatern gpp_matern(int kind, double r2_mat, const GppExpConsts& k) {
+  GppMatern m;
+  if (kind == 1) {
+    m.r = sqrt(3.0 * 2.0 * r2_mat);
+    m.p = 1.0 + m.r;
+    m.dp = -3.0;
+  } else {
+    m.r = sqrt(5.0 * 2.0 * r2_mat);
+    m.p = 1.0 + m.r + m.r * m.r * (1.0 / 3.0);
+    m.dp = (-5.0 / 3.0) * (1.0 + m.r);
+  }
+  m.er = gpp_exp_nonpos(-m.r, k);
+  return m;
+}
+// exp(-r2_rbf) h(r2_mat), the covariance without its scale sf2, in the one order of multiplication of every kernel that generates
+// VALUES (gpp_cov_tile, KernelGen::value, the post-cross epilogues): their entries agree to the bit (tests/test_gpu_kernel_sites.py)
+__device__ __forceinline__ double gpp_kernel_value(int kind, double r2_rbf, double r2_mat, const GppExpConsts& k) {
+  double v = gpp_exp_nonpos(-r2_rbf, k);
+  if (kind != 0) {
+    const GppMatern m = gpp_matern(kind, r2_mat, k);
+    v *= m.p * m.er;
+  }
+  return v;
+}
+// d2h/d r2_mat^2 (the second-derivative block of gpp_dgrad.hip alone); nu = 3/2 divides by r and is an exact 0 where r == 0
+__device__ __forceinline__ double gpp_matern_d2(int kind, const GppMatern& m) {
+  if (kind == 1) return m.r > 0.0 ? (9.0 * m.er) / m.r : 0.0;
+  return (25.0 / 3.0) * m.er;
+}
+
+// The 64 x 64 tile kernels (gpp_build.hip, gpp_reduce.hip) give thread tx of a row of 16 the column PAIRS {2 tx, 2 tx + 1} and
+// {32 + 2 tx, 33 + 2 tx}, so that the 16 lanes of a ds_read_b128 cover 256 contiguous bytes: the thread's column b = 0..3, counted
+// from `first`, the index of its column 0 (2 tx inside the tile; with j0 or an LDS row's offset added, that of the matrix or of LDS)
+template <class T>
+__device__ __forceinline__ T gpp_tile_col(T first, int b) {
+  return first + (b & 1) + ((b >> 1) << 5);
+}
 #endif
 
 // ---- fp64 MFMA GEMM (gpp_gemm.hip) ------------------------------------------------------------

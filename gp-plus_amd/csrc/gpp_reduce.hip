@@ -20,6 +20,20 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
+// red[0] = the sum of v over the 256 threads of a work-group, through the LDS array red[256]: a fixed tree, so a sum's order never
+// depends on the run.  The finish kernels' sum.  (The pointer carries the LDS address space: through a generic one the compiler forms
+// the tree's last step differently.  The record loops that end gpp_grad_tiles and gpp_pgrad_tiles write the same tree out: called
+// inside a loop the helper's comparisons are hoisted out of it, which changes the code of the RBF instantiations.)
+typedef __attribute__((address_space(3))) double lds_double;
+__device__ __forceinline__ void block_sum(int tid, double v, lds_double* red) {
+  red[tid] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+}
+
 // y_i = sum_{k<=i} T[i][k] x_k : one wave per row, rows interleaved over waves so long and short rows mix.
 __global__ __launch_bounds__(256) void gpp_trmv_lower(const double* __restrict__ T, int64_t ldt, int64_t N,
                                                       const double* __restrict__ x, double* __restrict__ y, int64_t sT,
@@ -270,6 +284,26 @@ __device__ __forceinline__ void tile_from_index(int64_t t, int64_t& ti, int64_t&
   tj = t - r * (r + 1) / 2;
 }
 
+// kv = exp(-r2_rbf) h(r2_mat) and kd = its derivative by -r2_mat, from er = exp(-r2_rbf), for the three gradient reductions; kind 0 and
+// the RBF instantiations: kv = er, kd = 0.  Their products take er first and e^-r last, (er 3) e^-r and ((er (5/3)) (1 + r)) e^-r:
+// gpp_matern's dp, the rounded product -(5/3)(1 + r), cannot give the second, so -dp is written out here in that order (with dp the
+// nu = 5/2 sums change in the last bit, gpp_grad_reduce with feature gradients runs 2 % slower and gpp_pgrad_tiles<8, true> takes 224
+// registers instead of 220).  One call per kind, as the branches were: the code of every instantiation stays as it was.
+template <bool MAT>
+__device__ __forceinline__ void kernel_and_dmat(int kind, double er, double r2_mat, const GppExpConsts& ec, double& kv, double& kd) {
+  kv = er;
+  kd = 0.0;
+  if (MAT && kind == 1) {
+    const GppMatern m = gpp_matern(1, r2_mat, ec);
+    kv = er * m.p * m.er;
+    kd = er * 3.0 * m.er;
+  } else if (MAT && kind == 2) {
+    const GppMatern m = gpp_matern(2, r2_mat, ec);
+    kv = er * m.p * m.er;
+    kd = er * (5.0 / 3.0) * (1.0 + m.r) * m.er;
+  }
+}
+
 // MAT = false: pure RBF product (kind 0): no Matern distance / derivative registers, two waves per SIMD
 // HASU = false: no gradient w.r.t. feature columns (dU = 0): the 4 x 4 blocks of G are never materialised
 // LOO = true: the leave-one-out pseudo-likelihood's weights W_ij = -0.5 (alpha_i beta_j + beta_i alpha_j) - C_ij (gpp_loo_grad_reduce:
@@ -347,9 +381,7 @@ __global__ __launch_bounds__(256) void gpp_grad_tiles(const double* __restrict__
     __syncthreads();
 
     // G  = mult * W_ij * dK_ij/d(-r2_rbf)  (= mult W K for the RBF dims)
-    // GM = mult * W_ij * dK_ij/d(-r2_mat)  for the Matern dims (d >= d_split), with K = sf2 e^{-r2_rbf} m(a):
-    //      nu = 3/2: a = sqrt(6 r2_mat), m = (1+a)e^{-a},          dm/d(-r2_mat) = 3 e^{-a}
-    //      nu = 5/2: a = sqrt(10 r2_mat), m = (1+a+a^2/3)e^{-a},   dm/d(-r2_mat) = (5/3)(1+a) e^{-a}
+    // GM = mult * W_ij * dK_ij/d(-r2_mat)  for the Matern dims (d >= d_split), with K = sf2 e^{-r2_rbf} h(r2_mat) (gpp_matern)
     const int dsp = MAT ? d_split : DT;
     typedef double v2d __attribute__((ext_vector_type(2)));
     double G[4][4], GM[4][4];  // (GM only lives in the Matern instantiation; G / GM feed the g_U part below)
@@ -374,7 +406,7 @@ __global__ __launch_bounds__(256) void gpp_grad_tiles(const double* __restrict__
           kin[a][0] = p0.x; kin[a][1] = p0.y; kin[a][2] = p1.x; kin[a][3] = p1.y;
         } else {
 #pragma unroll
-          for (int b = 0; b < 4; ++b) kin[a][b] = (jb + (b & 1) + ((b >> 1) << 5) < N) ? src[(b & 1) + ((b >> 1) << 5)] : 0.0;
+          for (int b = 0; b < 4; ++b) kin[a][b] = (gpp_tile_col(jb, b) < N) ? src[gpp_tile_col(0, b)] : 0.0;
         }
       }
       double r2[2][4], r2m[2][4];
@@ -406,27 +438,15 @@ __global__ __launch_bounds__(256) void gpp_grad_tiles(const double* __restrict__
         const int64_t i = i0 + ra + a;
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
-          const int64_t j = j0 + 2 * tx + (b & 1) + ((b >> 1) << 5);
+          const int cb = gpp_tile_col(2 * tx, b);
+          const int64_t j = j0 + cb;
           double g = 0.0, gm = 0.0;
           if (i < N && j <= i) {
-            const double er = gpp_exp_nonpos(-r2[a][b], ec);
-            double kv = er, kd = 0.0;
-            if (MAT && kind == 1) {
-              const double aa = sqrt(6.0 * r2m[a][b]), ea = gpp_exp_nonpos(-aa, ec);
-              kv = er * (1.0 + aa) * ea;
-              kd = er * 3.0 * ea;
-            } else if (MAT && kind == 2) {
-              const double aa = sqrt(10.0 * r2m[a][b]), ea = gpp_exp_nonpos(-aa, ec);
-              kv = er * (1.0 + aa + aa * aa * (1.0 / 3.0)) * ea;
-              kd = er * (5.0 / 3.0) * (1.0 + aa) * ea;
-            }
+            double kv, kd;
+            kernel_and_dmat<MAT>(kind, gpp_exp_nonpos(-r2[a][b], ec), r2m[a][b], ec, kv, kd);
             double Wij;
-            if constexpr (LOO) {
-              const int cb = 2 * tx + (b & 1) + ((b >> 1) << 5);
-              Wij = -0.5 * (sal_a[ra + a] * sbe_b[cb] + sbe_a[ra + a] * sal_b[cb]) - kin[a][b];
-            } else {
-              Wij = 0.5 * (sal_a[ra + a] * sal_b[2 * tx + (b & 1) + ((b >> 1) << 5)] - kin[a][b]);
-            }
+            if constexpr (LOO) Wij = -0.5 * (sal_a[ra + a] * sbe_b[cb] + sbe_a[ra + a] * sal_b[cb]) - kin[a][b];
+            else Wij = 0.5 * (sal_a[ra + a] * sal_b[cb] - kin[a][b]);
             const double mult = (i == j) ? 1.0 : 2.0;
             my_sf2 = fma(mult * Wij, kv, my_sf2);
             g = mult * Wij * sf2 * kv;
@@ -476,7 +496,7 @@ __global__ __launch_bounds__(256) void gpp_grad_tiles(const double* __restrict__
         double s = 0.0;
 #pragma unroll
         for (int b = 0; b < 4; ++b)
-          s = fma(rbf_dim ? G[a][b] : GM[a][b], sa[d * GT + 4 * ty + a] - sb[d * GT + 2 * tx + (b & 1) + ((b >> 1) << 5)], s);
+          s = fma(rbf_dim ? G[a][b] : GM[a][b], sa[d * GT + 4 * ty + a] - sb[gpp_tile_col(d * GT + 2 * tx, b)], s);
         rs[a] = s;
       }
 #pragma unroll
@@ -484,7 +504,7 @@ __global__ __launch_bounds__(256) void gpp_grad_tiles(const double* __restrict__
         double s = 0.0;
 #pragma unroll
         for (int a = 0; a < 4; ++a)
-          s = fma(rbf_dim ? G[a][b] : GM[a][b], sb[d * GT + 2 * tx + (b & 1) + ((b >> 1) << 5)] - sa[d * GT + 4 * ty + a], s);
+          s = fma(rbf_dim ? G[a][b] : GM[a][b], sb[gpp_tile_col(d * GT + 2 * tx, b)] - sa[d * GT + 4 * ty + a], s);
         cs[b] = s;
       }
       __syncthreads();
@@ -496,7 +516,7 @@ __global__ __launch_bounds__(256) void gpp_grad_tiles(const double* __restrict__
         for (int q = 0; q < 16; ++q) rsum += rowpart[tid * 16 + q];
       __syncthreads();
 #pragma unroll
-      for (int b = 0; b < 4; ++b) rowpart[(2 * tx + (b & 1) + ((b >> 1) << 5)) * 16 + ty] = cs[b];
+      for (int b = 0; b < 4; ++b) rowpart[gpp_tile_col(2 * tx, b) * 16 + ty] = cs[b];
       __syncthreads();
       if (tid < GT) {
         double csum = 0.0;
@@ -554,12 +574,7 @@ __global__ __launch_bounds__(256) void gpp_grad_finish(const double* __restrict_
     for (int64_t i = tid; i < N; i += 256)
       if ((grp ? grp[i] : 0) == s) v += wdiag[i];
   }
-  red[tid] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
+  block_sum(tid, v, (lds_double*)red);
   if (tid == 0) {
     if (q < D) g_w[q] = red[0];
     else if (q == D) g_sf2[0] = red[0];
@@ -673,7 +688,7 @@ __global__ __launch_bounds__(256) void gpp_pgrad_tiles(const double* __restrict_
           bv[a][0] = p0.x; bv[a][1] = p0.y; bv[a][2] = p1.x; bv[a][3] = p1.y;
         } else {
 #pragma unroll
-          for (int b = 0; b < 4; ++b) bv[a][b] = (jb + (b & 1) + ((b >> 1) << 5) < N) ? src[(b & 1) + ((b >> 1) << 5)] : 0.0;
+          for (int b = 0; b < 4; ++b) bv[a][b] = (gpp_tile_col(jb, b) < N) ? src[gpp_tile_col(0, b)] : 0.0;
         }
       }
     }
@@ -707,20 +722,11 @@ __global__ __launch_bounds__(256) void gpp_pgrad_tiles(const double* __restrict_
       const int64_t i = i0 + 4 * ty + a;
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
-        const int cb = 2 * tx + (b & 1) + ((b >> 1) << 5);
+        const int cb = gpp_tile_col(2 * tx, b);
         double gg = 0.0, gmm = 0.0;
         if (i < M && j0 + cb < N) {
-          const double er = gpp_exp_nonpos(-r2[a][b], ec);
-          double kv = er, kd = 0.0;
-          if (MAT && kind == 1) {
-            const double aa = sqrt(6.0 * r2m[a][b]), ea = gpp_exp_nonpos(-aa, ec);
-            kv = er * (1.0 + aa) * ea;
-            kd = er * 3.0 * ea;
-          } else if (MAT && kind == 2) {
-            const double aa = sqrt(10.0 * r2m[a][b]), ea = gpp_exp_nonpos(-aa, ec);
-            kv = er * (1.0 + aa + aa * aa * (1.0 / 3.0)) * ea;
-            kd = er * (5.0 / 3.0) * (1.0 + aa) * ea;
-          }
+          double kv, kd;
+          kernel_and_dmat<MAT>(kind, gpp_exp_nonpos(-r2[a][b], ec), r2m[a][b], ec, kv, kd);
           const double G = fma(s_gm[4 * ty + a], s_al[cb], s_gv[4 * ty + a] * bv[a][b]);
           my_sf2 = fma(G, kv, my_sf2);
           gg = G * sf2 * kv;
@@ -770,7 +776,7 @@ __global__ __launch_bounds__(256) void gpp_pgrad_tiles(const double* __restrict_
           double v = cs[b];
           v += __shfl_xor(v, 16);
           v += __shfl_xor(v, 32);
-          if (lane < 16) colred[wave * GT + 2 * tx + (b & 1) + ((b >> 1) << 5)] = v;
+          if (lane < 16) colred[gpp_tile_col(wave * GT + 2 * tx, b)] = v;
         }
         __syncthreads();
         if (tid < GT && j0 + tid < N)
@@ -808,12 +814,7 @@ __global__ __launch_bounds__(256) void gpp_pgrad_finish(const double* __restrict
   const int q = blockIdx.x, nrec = D + 1, tid = threadIdx.x;
   double v = 0.0;
   for (int b = tid; b < nwg; b += 256) v += rec[(int64_t)b * nrec + q];
-  red[tid] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
+  block_sum(tid, v, (lds_double*)red);
   if (tid == 0) {
     if (q < D && g_w) g_w[q] = red[0];
     else if (q == D && g_sf2) g_sf2[0] = red[0];
@@ -1130,7 +1131,7 @@ __global__ __launch_bounds__(256) void gpp_calib_tiles(const double* __restrict_
         kin[a][0] = q0.x; kin[a][1] = q0.y; kin[a][2] = q1.x; kin[a][3] = q1.y;
       } else {
 #pragma unroll
-        for (int b = 0; b < 4; ++b) kin[a][b] = (jb + (b & 1) + ((b >> 1) << 5) < N) ? src[(b & 1) + ((b >> 1) << 5)] : 0.0;
+        for (int b = 0; b < 4; ++b) kin[a][b] = (gpp_tile_col(jb, b) < N) ? src[gpp_tile_col(0, b)] : 0.0;
       }
     }
     double r2[4][4], r2m[4][4];
@@ -1161,22 +1162,13 @@ __global__ __launch_bounds__(256) void gpp_calib_tiles(const double* __restrict_
       const int64_t i = i0 + 4 * ty + a;
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
-        const int cb = 2 * tx + (b & 1) + ((b >> 1) << 5);
+        const int cb = gpp_tile_col(2 * tx, b);
         const int64_t j = j0 + cb;
         double gg = 0.0, gmm = 0.0;
         const int sgn = sm_a[4 * ty + a] - sm_b[cb];
         if (i < N && j < i && sgn != 0) {
-          const double er = gpp_exp_nonpos(-r2[a][b], ec);
-          double kv = er, kd = 0.0;
-          if (MAT && kind == 1) {
-            const double aa = sqrt(6.0 * r2m[a][b]), ea = gpp_exp_nonpos(-aa, ec);
-            kv = er * (1.0 + aa) * ea;
-            kd = er * 3.0 * ea;
-          } else if (MAT && kind == 2) {
-            const double aa = sqrt(10.0 * r2m[a][b]), ea = gpp_exp_nonpos(-aa, ec);
-            kv = er * (1.0 + aa + aa * aa * (1.0 / 3.0)) * ea;
-            kd = er * (5.0 / 3.0) * (1.0 + aa) * ea;
-          }
+          double kv, kd;
+          kernel_and_dmat<MAT>(kind, gpp_exp_nonpos(-r2[a][b], ec), r2m[a][b], ec, kv, kd);
           const double Wij = 0.5 * (sal_a[4 * ty + a] * sal_b[cb] - kin[a][b]);
           const double s2w = (sgn > 0 ? 2.0 : -2.0) * Wij * sf2;
           gg = s2w * kv;
@@ -1212,12 +1204,7 @@ __global__ __launch_bounds__(256) void gpp_calib_finish(const double* __restrict
   const int k = blockIdx.x, tid = threadIdx.x;
   double v = 0.0;
   for (int b = tid; b < nwg; b += 256) v += rec[(int64_t)b * C + k];
-  red[tid] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
+  block_sum(tid, v, (lds_double*)red);
   if (tid == 0) g_theta[k] = red[0];
 }
 
