@@ -144,6 +144,8 @@ _SIGNATURES = {
     "gpp_point_gram": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
     "gpp_kernel_dxdx": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                 c_int, c_void_p, c_int64]),
+    "gpp_gek_grad_reduce": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                    c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -30,6 +30,7 @@ OP_APPEND = 5  # gpp_chol_append: N cached points, M carries the appended count 
 OP_POST_CROSS = 6  # gpp_post_cross_sq: N carries the reference count M_r, M the candidate count M_c
 OP_POST_CROSS_MIN = 7  # gpp_post_cross_min: N carries M_r, M carries M_c, S the node count Q
 OP_POINT_GRAM = 8  # gpp_point_gram with a weighted sum: M points, D carries the rows per point
+OP_GEK_GRAD = 9  # gpp_gek_grad_reduce: N function points, M carries the gradient points Mg, S the feature columns with a gradient
 #: most quadrature nodes gpp_post_cross_min takes (gpp_gemm.hip PostCrossMinEpilogue::QMAX)
 MAX_NODES = 64
 #: longest contraction gpp_kernel_apply / gpp_rff_apply run without scratch (gpp_apply.hip AP_SPLIT)
@@ -1167,6 +1168,40 @@ class GppContext:
         check(self.lib.gpp_kernel_dxdx(self.h, Ua.data_ptr(), Ma, Ub.data_ptr(), Mb, D, w.data_ptr(), sf2.data_ptr(), int(kind),
                                        int(d_split), d0, nd, out.data_ptr(), ld), "gpp_kernel_dxdx")
         return out
+
+    # -- training on gradient observations ---------------------------------------------------------------------------------------
+    @_on_own_device
+    def gek_grad_reduce(self, U, Ug, w, sf2, d0, nd, alpha, Kinv, dU, g_w, g_sf2, g_U=None, g_Ug=None, *, kind=KIND_RBF, d_split=0):
+        """The gradient of the joint log-likelihood of [y; grad y] through the function / gradient and gradient / gradient blocks
+        (gpp_gek_grad_reduce): ADDS to ``g_w`` (D), ``g_sf2`` (1) and ``g_U`` (N x dU), WRITES ``g_Ug`` (Mg x dU).  ``alpha``: the
+        n = N + Mg nd solved residuals; ``Kinv``: n x n as the LAUUM leaves it (lower triangle), an even leading dimension, 16-byte
+        aligned.  ``dU`` <= d0, and <= d_split on the Matern kinds.  Everything is checked before the launch."""
+        d0, nd, dU = int(d0), int(nd), int(dU)
+        Mg, N = self._dx_checks("gek_grad_reduce", "Mg, N", Ug, U, w, sf2, d0, nd, kind, d_split)
+        D, n = U.shape[1], N + Mg * nd
+        if dU < 0 or dU > d0 or (kind != KIND_RBF and dU > int(d_split)):
+            raise GppError(f"gek_grad_reduce: the {dU} feature columns with a gradient must lie in front of the differentiated ones "
+                           f"(d0 = {d0}) and, on a Matern kind, inside the RBF factor (d_split = {d_split})")
+        _need(alpha, torch.float64, "alpha")
+        if alpha.dim() != 1 or alpha.numel() != n or not alpha.is_contiguous():
+            raise GppError(f"alpha must be a contiguous vector of {n} doubles (got {tuple(alpha.shape)})")
+        ld = self._dx_window("Kinv", Kinv, n, n)
+        for t, name, shape in ((g_w, "g_w", (D,)), (g_sf2, "g_sf2", (1,)), (g_U, "g_U", (N, dU)), (g_Ug, "g_Ug", (Mg, dU))):
+            if t is None:
+                if dU > 0 or name in ("g_w", "g_sf2"):
+                    raise GppError(f"gek_grad_reduce: {name} is missing")
+                continue
+            _need(t, torch.float64, name)
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise GppError(f"{name} must be a contiguous {shape} tensor (got {tuple(t.shape)})")
+        self.ensure_workspace(OP_GEK_GRAD, N, Mg, D, dU)
+        self._stream()
+        status = self.lib.gpp_gek_grad_reduce(self.h, U.data_ptr(), N, Ug.data_ptr(), Mg, D, w.data_ptr(), sf2.data_ptr(), int(kind),
+                                              int(d_split), d0, nd, alpha.data_ptr(), Kinv.data_ptr(), ld, dU, g_w.data_ptr(),
+                                              g_sf2.data_ptr(), _ptr(g_U) if dU else None, _ptr(g_Ug) if dU else None)
+        if status == NO_WORKSPACE:
+            raise GppError("gpp_gek_grad_reduce: the handle's scratch workspace is missing or too small")
+        check(status, "gpp_gek_grad_reduce")
 
 
 

@@ -1,5 +1,6 @@
 // gpp_dgrad.hip — the two kernels behind the posterior of the gradient (GP_Plus.predict_gradient / active_subspace) and the
-// second-derivative block behind conditioning on gradient observations (GP_Plus.condition_on_gradients).
+// second-derivative block behind conditioning on gradient observations (GP_Plus.condition_on_gradients), and the gradient of the
+// joint log-likelihood through both derivative blocks (gpp_gek_grad_reduce, described in front of its code at the end of the file).
 //
 // gpp_cross_kernel_dx (gpp.h): the derivative cross block Dk[n, a nd + j] = d/du_{d0+j} sf2 k(Ua_a, Ub_n; w), training points as rows —
 // the orientation gpp_predict_tn takes, so that Q = Dk^T Linv^T, the gradient's mean Q z and its variance diagonal come from the
@@ -470,5 +471,383 @@ extern "C" int gpp_kernel_dxdx(gpp_handle_t h, const double* Ua, int64_t Ma, con
     hipLaunchKernelGGL(gpp_kernel_dxdx_f64<false>, grid, block, hx_lds_doubles(D, nd, 1) * sizeof(double), h->stream, p);
   else
     hipLaunchKernelGGL(gpp_kernel_dxdx_f64<true>, grid, block, hx_lds_doubles(D, nd, 3) * sizeof(double), h->stream, p);
+  return dg_rc(hipGetLastError());
+}
+
+// ---- gpp_gek_grad_reduce ------------------------------------------------------------------------------------------------------------
+// The gradient of the joint log-likelihood of [y; grad y] through the two derivative blocks of
+//   Kj = [[Kff, Kfg], [Kfg^T, Kgg]],   Kfg[i, a nd + j] = gpp_cross_kernel_dx(Ua = Ug, Ub = U),   Kgg = gpp_kernel_dxdx(Ug, Ug):
+// sum over their entries of W dKj / dtheta with W = (alpha alpha^T - Kinv) / 2, the Kfg block counted for both triangles, theta in
+// {w (all D), sf2, U[:, :dU], Ug[:, :dU]}.  Only the lower triangle of Kinv is read: the rows N + a nd + j against the columns i < N
+// (Kfg^T) and, of Kgg, the pairs of points a >= b (twice for a > b; the block of a point with itself through max / min indices).
+//
+// Chain rule (tests/gek_reference.py's header one order further).  An entry is a derivative of F(q1, q2) = sf2 e^-q1 H(q2) in
+// delta = u - v with dq / dw_d = delta_d^2 and dq / du_d = 2 w_d delta_d; a derivative of F by q1 is -F, so with A_k = e^-q1 H^(k)(q2) a
+// partial of F of order n with k Matern indices is (-1)^(n - k) sf2 A_k.  With p_j = 2 w_j delta_j and f(j) the factor of feature j:
+//   Kfg entry  E_j  = F_f(j) p_j                                      Kgg entry  E_jl = -F_f(j)f(l) p_j p_l - [j == l] 2 w_j F_f(j)
+// One set of sums per PAIR of points serves all its nd or nd^2 entries:
+//   Kfg:  P_k = sum_{j in k} W_j p_j;                         s0 = A_1 P_1 - A_0 P_0;                    r1 = A_2 P_1 - A_1 P_0
+//   Kgg:  Q_m = sum_{f(j) + f(l) = m} W_jl p_j p_l,  D_k = sum_{j in k} W_jj 2 w_j;
+//         s0 = -A_0 Q_0 + A_1 Q_1 - A_2 Q_2 + A_0 D_0 - A_1 D_1;      r1 = -A_1 Q_0 + A_2 Q_1 - A_3 Q_2 + A_1 D_0 - A_2 D_1
+//   g_sf2 += s0;    g_w[d] += sf2 delta_d^2 (d in the RBF factor ? -s0 : r1);    g_u[d] -= 2 w_d delta_d sf2 s0,  g_v[d] += the same (d < dU)
+// and, through the explicit weights of p_j and of the diagonal term, per differentiated feature
+//   Kfg:  g_w[d0 + j] += 2 delta_j F_f(j) W_j
+//   Kgg:  g_w[d0 + j] += -2 delta_j sum_l W_jl F_f(j)f(l) p_l - 2 F_f(j) W_jj        g_w[d0 + l] += -2 delta_l sum_j W_jl F_f(j)f(l) p_j
+// dU <= d0 (and <= d_split on a Matern kind): a feature with a gradient is none of the differentiated ones and sits in the RBF
+// factor, which is what makes its derivative the entry itself times -2 w_d delta_d.  A_3 Q_2 is gpp_matern_d3_times: Q_2 carries two
+// factors delta of the Matern features, nothing divides by r = 0 and the term is an exact 0 there (as are A_2's, gpp_matern_d2).
+//
+// One work-group per tile of GK_T x GK_T pairs, thread (al, bl) = one pair: the A_k are computed once per pair and left in LDS; the
+// pair's entries of Kinv are read once (Kfg: 16 consecutive lanes read 16 consecutive columns of one row; Kgg: nd consecutive columns
+// per lane, 16 nd per row over the 16 lanes).  Every sum of a tile is added over each wave by a butterfly, the four waves' sums in
+// wave order, and written as one record per tile to the handle workspace; g_U / g_Ug rows go to one slot per (tile row or column,
+// point), each written exactly once.  Two finish kernels add records and slots in index order: no atomics, two calls agree bitwise.
+namespace {
+
+constexpr int GK_T = 16;            // points per tile side
+constexpr int GK_TP = GK_T + 1;     // row stride of the per-pair tiles in LDS
+constexpr int GK_THREADS = 256;     // one pair per thread
+constexpr int GK_MT = GK_T * GK_TP;
+
+struct GkArgs {
+  const double* U;
+  const double* Ug;
+  const double* w;
+  const double* sf2;
+  const double* alpha;
+  const double* Kinv;
+  int64_t ldk, N, Mg, tiles_a, n_fg;
+  int D, kind, d_split, d0, nd, dU;
+  double* rec;    // [tiles][D + 1]
+  double* partA;  // [tiles_i][Mg][dU]   g_Ug rows from the Kfg tiles, slot = the tile of function points
+  double* partI;  // [tiles_a][N][dU]    g_U rows from the Kfg tiles, slot = the tile of gradient points
+  double* partG;  // [tiles_a][Mg][dU]   g_Ug rows from the Kgg tiles, slot = the other tile of the pair
+};
+
+__device__ __forceinline__ double gk_wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// tile t of the lower triangle in row-major order: (ti, tj), tj <= ti
+__device__ __forceinline__ void gk_tile_from_index(int64_t t, int64_t& ti, int64_t& tj) {
+  int64_t r = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+  while ((r + 1) * (r + 2) / 2 <= t) ++r;
+  while (r * (r + 1) / 2 > t) --r;
+  ti = r;
+  tj = t - r * (r + 1) / 2;
+}
+
+inline size_t gk_lds_doubles(int D, int nm) {
+  return (size_t)2 * GK_T * (D | 1) + D + (size_t)(nm + 1) * GK_MT + (size_t)4 * (D + 1);
+}
+
+// CH: columns of a Kgg pair's block taken per pass (their column sums stay in registers)
+template <bool MAT, int CH>
+__global__ __launch_bounds__(GK_THREADS) void gpp_gek_grad_tiles(GkArgs p) {
+  extern __shared__ __attribute__((aligned(16))) double gk_lds[];
+  constexpr int NM = MAT ? 5 : 1;
+  const int D = p.D, nd = p.nd, d0 = p.d0, dU = p.dU, Dp = D | 1, nrec = D + 1;
+  double* rA = gk_lds;              // [GK_T][Dp] raw rows of the gradient points a
+  double* rB = rA + GK_T * Dp;      // [GK_T][Dp] raw rows of the other side: function points (Kfg) or gradient points b (Kgg)
+  double* sw = rB + GK_T * Dp;      // [D]
+  double* sM = sw + D;              // [NM][GK_T][GK_TP]: A_0 (, A_1, A_2, r, e^-q1 e^-r)
+  double* sG = sM + NM * GK_MT;     // [GK_T][GK_TP] sf2 s0 of every pair
+  double* wred = sG + GK_MT;        // [4][nrec] the waves' sums
+  const int t = (int)threadIdx.x, wave = t >> 6, lane = t & 63;
+  const int al = t >> 4, bl = t & 15;
+  const int64_t blk = blockIdx.x;
+  const bool gg = blk >= p.n_fg;
+  int64_t ta, tb;
+  if (!gg) {
+    ta = blk % p.tiles_a;
+    tb = blk / p.tiles_a;
+  } else {
+    gk_tile_from_index(blk - p.n_fg, ta, tb);
+  }
+  const int64_t a0 = ta * GK_T, b0 = tb * GK_T;
+  const double* Ub = gg ? p.Ug : p.U;
+  const int64_t nbt = gg ? p.Mg : p.N;
+  const int na = (int)min((int64_t)GK_T, p.Mg - a0), nb = (int)min((int64_t)GK_T, nbt - b0);
+  const int ds = MAT ? p.d_split : D;  // features below ds belong to the RBF factor
+  const double sf2 = *p.sf2;
+
+  for (int d = t; d < D; d += GK_THREADS) sw[d] = p.w[d];
+  for (int e = t; e < 4 * nrec; e += GK_THREADS) wred[e] = 0.0;
+  // rows beyond the ends are staged as zeros and never read from memory; their pairs are not valid and add nothing
+  for (int e = t; e < 2 * GK_T * D; e += GK_THREADS) {
+    const int r = e / D, d = e - r * D;
+    if (r < GK_T) {
+      rA[r * Dp + d] = r < na ? p.Ug[(a0 + r) * D + d] : 0.0;
+    } else {
+      const int rb = r - GK_T;
+      rB[rb * Dp + d] = rb < nb ? Ub[(b0 + rb) * D + d] : 0.0;
+    }
+  }
+  __syncthreads();
+
+  const double* xa = rA + al * Dp;
+  const double* xb = rB + bl * Dp;
+  const int64_t a = a0 + al, b = b0 + bl;
+  const bool valid = al < na && bl < nb && (!gg || a >= b);
+  double* mine = sM + al * GK_TP + bl;
+  {
+    const GppExpConsts ec = gpp_exp_consts();
+    double q1 = 0.0;
+    for (int d = 0; d < ds; ++d) {
+      const double df = xa[d] - xb[d];
+      q1 = fma(sw[d] * df, df, q1);
+    }
+    const double e1 = gpp_exp_nonpos(-q1, ec);
+    if constexpr (MAT) {
+      double q2 = 0.0;
+      for (int d = ds; d < D; ++d) {
+        const double df = xa[d] - xb[d];
+        q2 = fma(sw[d] * df, df, q2);
+      }
+      const GppMatern h = gpp_matern(p.kind, q2, ec);
+      mine[0] = e1 * (h.p * h.er);
+      mine[GK_MT] = e1 * (h.dp * h.er);
+      mine[2 * GK_MT] = e1 * gpp_matern_d2(p.kind, h);
+      mine[3 * GK_MT] = h.r;
+      mine[4 * GK_MT] = e1 * h.er;
+    } else {
+      mine[0] = e1;
+    }
+  }
+  __syncthreads();
+  const double A0 = mine[0];
+  const double A1 = MAT ? mine[GK_MT] : 0.0, A2 = MAT ? mine[2 * GK_MT] : 0.0;
+
+  const double* __restrict__ alpha = p.alpha;
+  const double* __restrict__ Kinv = p.Kinv;
+  const double* da = xa + d0;
+  const double* db = xb + d0;
+  const double* wd = sw + d0;
+  double s0 = 0.0, r1 = 0.0;  // per unit sf2
+  if (!gg) {
+    double P0 = 0.0, P1 = 0.0;
+    const double ab = valid ? alpha[b] : 0.0;
+    for (int j = 0; j < nd; ++j) {
+      double dir = 0.0;
+      if (valid) {
+        const int64_t r = p.N + a * nd + j;
+        const double W = alpha[r] * ab - Kinv[r * p.ldk + b];  // both triangles: 2 x 1/2
+        const double dj = da[j] - db[j];
+        const double pj = (2.0 * wd[j]) * dj;
+        const bool fj = MAT && d0 + j >= ds;
+        if (fj) P1 = fma(W, pj, P1);
+        else P0 = fma(W, pj, P0);
+        dir = (2.0 * dj) * ((fj ? A1 : -A0) * W);
+      }
+      dir = gk_wave_sum(dir);
+      if (lane == 0) wred[wave * nrec + d0 + j] += dir;
+    }
+    s0 = A1 * P1 - A0 * P0;
+    r1 = A2 * P1 - A1 * P0;
+  } else {
+    double Q0 = 0.0, Q1 = 0.0, Q2 = 0.0, D0 = 0.0, D1 = 0.0;
+    const bool self = a == b;
+    const double hm = self ? 0.5 : 1.0;  // (1 or 2 triangles) x 1/2
+    for (int l0 = 0; l0 < nd; l0 += CH) {
+      double cF[CH];
+#pragma unroll
+      for (int ll = 0; ll < CH; ++ll) cF[ll] = 0.0;
+      for (int j = 0; j < nd; ++j) {
+        double dir = 0.0;
+        if (valid) {
+          const int64_t r = p.N + a * nd + j;
+          const double ar = alpha[r];
+          const double dj = da[j] - db[j];
+          const double wj2 = 2.0 * wd[j];
+          const double pj = wj2 * dj;
+          const int fj = (MAT && d0 + j >= ds) ? 1 : 0;
+          double rF = 0.0;
+#pragma unroll
+          for (int ll = 0; ll < CH; ++ll) {
+            const int l = l0 + ll;
+            if (l < nd) {
+              const int64_t c = p.N + b * nd + l;
+              const bool flip = self && c > r;  // a point with itself: the block straddles the diagonal
+              const double W = hm * (ar * alpha[c] - Kinv[(flip ? c : r) * p.ldk + (flip ? r : c)]);
+              const double pl = (2.0 * wd[l]) * (da[l] - db[l]);
+              const int m = fj + ((MAT && d0 + l >= ds) ? 1 : 0);
+              const double F = m == 0 ? A0 : (m == 1 ? -A1 : A2);
+              const double x = W * F;
+              rF = fma(x, pl, rF);
+              cF[ll] = fma(x, pj, cF[ll]);
+              const double wpp = W * (pj * pl);
+              if (m == 0) Q0 += wpp;
+              else if (m == 1) Q1 += wpp;
+              else Q2 += wpp;
+              if (l == j) {
+                if (fj) D1 = fma(W, wj2, D1);
+                else D0 = fma(W, wj2, D0);
+                dir = -2.0 * ((fj ? A1 : -A0) * W);
+              }
+            }
+          }
+          dir = fma(-2.0 * dj, rF, dir);
+        }
+        dir = gk_wave_sum(dir);
+        if (lane == 0) wred[wave * nrec + d0 + j] += dir;
+      }
+#pragma unroll
+      for (int ll = 0; ll < CH; ++ll) {
+        const int l = l0 + ll;
+        if (l < nd) {  // (wave-uniform)
+          const double v = gk_wave_sum(valid ? (-2.0 * (da[l] - db[l])) * cF[ll] : 0.0);
+          if (lane == 0) wred[wave * nrec + d0 + l] += v;
+        }
+      }
+    }
+    s0 = -A0 * Q0 + A1 * Q1 - A2 * Q2 + A0 * D0 - A1 * D1;
+    if constexpr (MAT) {
+      GppMatern h3;
+      h3.r = mine[3 * GK_MT];
+      h3.er = mine[4 * GK_MT];
+      h3.p = h3.dp = 0.0;
+      r1 = -A1 * Q0 + A2 * Q1 - gpp_matern_d3_times(p.kind, h3, Q2) + A1 * D0 - A2 * D1;
+    }
+  }
+  if (!valid) s0 = r1 = 0.0;
+
+  for (int d = 0; d < D; ++d) {
+    const double df = xa[d] - xb[d];
+    const double v = gk_wave_sum((df * df) * ((MAT && d >= ds) ? r1 : -s0));
+    if (lane == 0) wred[wave * nrec + d] += v;
+  }
+  {
+    const double v = gk_wave_sum(s0);
+    if (lane == 0) wred[wave * nrec + D] += v;
+  }
+  sG[al * GK_TP + bl] = sf2 * s0;
+  __syncthreads();
+  if (t < nrec) {
+    const double s = ((wred[t] + wred[nrec + t]) + wred[2 * nrec + t]) + wred[3 * nrec + t];
+    p.rec[blk * nrec + t] = t < D ? sf2 * s : s;
+  }
+  for (int e = t; e < GK_T * dU; e += GK_THREADS) {
+    const int x = e & (GK_T - 1), d = e / GK_T;
+    double rs = 0.0, cs = 0.0;
+    for (int k = 0; k < GK_T; ++k) {
+      rs = fma(sG[x * GK_TP + k], rA[x * Dp + d] - rB[k * Dp + d], rs);
+      cs = fma(sG[k * GK_TP + x], rA[k * Dp + d] - rB[x * Dp + d], cs);
+    }
+    const double w2 = 2.0 * sw[d];
+    const double ga = -(w2 * rs), gb = w2 * cs;
+    if (!gg) {
+      if (x < na) p.partA[(tb * p.Mg + a0 + x) * dU + d] = ga;
+      if (x < nb) p.partI[(ta * p.N + b0 + x) * dU + d] = gb;
+    } else if (ta == tb) {
+      if (x < na) p.partG[(ta * p.Mg + a0 + x) * dU + d] = ga + gb;
+    } else {
+      if (x < na) p.partG[(tb * p.Mg + a0 + x) * dU + d] = ga;
+      if (x < nb) p.partG[(ta * p.Mg + b0 + x) * dU + d] = gb;
+    }
+  }
+}
+
+// g_w[q] (q < D) or g_sf2 (q == D) += the tiles' records in index order
+__global__ __launch_bounds__(256) void gpp_gek_finish(const double* __restrict__ rec, int64_t ntiles, int D, double* __restrict__ g_w,
+                                                      double* __restrict__ g_sf2) {
+  __shared__ double red[256];
+  const int q = (int)blockIdx.x, nrec = D + 1, tid = (int)threadIdx.x;
+  double v = 0.0;
+  for (int64_t b = tid; b < ntiles; b += 256) v += rec[b * nrec + q];
+  red[tid] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    if (q < D) g_w[q] += red[0];
+    else g_sf2[0] += red[0];
+  }
+}
+
+// g_Ug[e] = the slots of partA, then of partG, in slot order (written); g_U[e] += the slots of partI in slot order
+__global__ __launch_bounds__(256) void gpp_gek_gU_finish(const double* __restrict__ partA, int64_t tiles_i, const double* __restrict__ partG,
+                                                         const double* __restrict__ partI, int64_t tiles_a, int64_t N, int64_t Mg, int dU,
+                                                         double* __restrict__ g_U, double* __restrict__ g_Ug) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e < Mg * dU) {
+    double s = 0.0;
+    for (int64_t k = 0; k < tiles_i; ++k) s += partA[k * Mg * dU + e];
+    for (int64_t k = 0; k < tiles_a; ++k) s += partG[k * Mg * dU + e];
+    g_Ug[e] = s;
+  }
+  if (e < N * dU) {
+    double s = 0.0;
+    for (int64_t k = 0; k < tiles_a; ++k) s += partI[k * N * dU + e];
+    g_U[e] += s;
+  }
+}
+
+inline int64_t gk_tiles(int64_t n) { return (n + GK_T - 1) / GK_T; }
+
+template <bool MAT>
+void gk_launch(hipStream_t s, const GkArgs& p, int64_t ntiles) {
+  const dim3 grid((unsigned)ntiles), block(GK_THREADS);
+  const size_t lds = gk_lds_doubles(p.D, MAT ? 5 : 1) * sizeof(double);
+  if (p.nd <= 4) hipLaunchKernelGGL((gpp_gek_grad_tiles<MAT, 4>), grid, block, lds, s, p);
+  else if (p.nd <= 8) hipLaunchKernelGGL((gpp_gek_grad_tiles<MAT, 8>), grid, block, lds, s, p);
+  else hipLaunchKernelGGL((gpp_gek_grad_tiles<MAT, 16>), grid, block, lds, s, p);
+}
+
+}  // namespace
+
+size_t gpp_gek_grad_ws_bytes(int64_t N, int64_t Mg, int D, int dU) {
+  if (N < 1 || Mg < 1 || D < 1 || dU < 0) return 0;
+  const int64_t ta = gk_tiles(Mg), ti = gk_tiles(N);
+  const int64_t ntiles = ta * ti + ta * (ta + 1) / 2;
+  return (size_t)(ntiles * (D + 1) + (int64_t)dU * (ti * Mg + ta * N + ta * Mg)) * sizeof(double);
+}
+
+extern "C" int gpp_gek_grad_reduce(gpp_handle_t h, const double* U, int64_t N, const double* Ug, int64_t Mg, int D, const double* w,
+                                   const double* sf2, int kind, int d_split, int d0, int nd, const double* alpha, const double* Kinv,
+                                   int64_t ldk, int dU, double* g_w, double* g_sf2, double* g_U, double* g_Ug) {
+  if (!h) return -1;
+  if (!U) return -2;
+  if (N < 1 || N > 0x7ffffff0) return -3;
+  if (!Ug) return -4;
+  if (Mg < 1 || Mg > 0x7ffffff0) return -5;
+  if (D < 1 || D > 64) return -6;
+  if (!w) return -7;
+  if (!sf2) return -8;
+  if (kind < 0 || kind > 2) return -9;
+  if (d_split < 0 || d_split > D) return -10;
+  if (d0 < 0 || d0 >= D) return -11;
+  if (nd < 1 || d0 + nd > D) return -12;
+  if (Mg * nd > 0x7ffffff0) return -5;
+  if (!alpha) return -13;
+  if (!Kinv || !dg_aligned16(Kinv)) return -14;
+  if ((ldk & 1) || ldk < N + Mg * nd) return -15;
+  // a feature with a gradient is none of the differentiated ones and, on a Matern kind, belongs to the RBF factor
+  if (dU < 0 || dU > d0 || (kind != GPP_KIND_RBF && dU > d_split)) return -16;
+  if (!g_w) return -17;
+  if (!g_sf2) return -18;
+  if (dU > 0 && !g_U) return -19;
+  if (dU > 0 && !g_Ug) return -20;
+  const int64_t ta = gk_tiles(Mg), ti = gk_tiles(N);
+  const int64_t n_fg = ta * ti, ntiles = n_fg + ta * (ta + 1) / 2;
+  if (ntiles >= ((int64_t)1 << 31)) return -3;
+  if (!h->ws || h->ws_bytes < gpp_gek_grad_ws_bytes(N, Mg, D, dU)) return GPP_NO_WORKSPACE;
+  double* rec = reinterpret_cast<double*>(h->ws);
+  double* partA = rec + ntiles * (D + 1);
+  double* partI = partA + (int64_t)dU * ti * Mg;
+  double* partG = partI + (int64_t)dU * ta * N;
+  GkArgs p{U, Ug, w, sf2, alpha, Kinv, ldk, N, Mg, ta, n_fg, D, kind, d_split, d0, nd, dU, rec, partA, partI, partG};
+  if (kind == GPP_KIND_RBF) gk_launch<false>(h->stream, p, ntiles);
+  else gk_launch<true>(h->stream, p, ntiles);
+  if (hipError_t r = hipGetLastError(); r != hipSuccess) return dg_rc(r);
+  hipLaunchKernelGGL(gpp_gek_finish, dim3((unsigned)(D + 1)), dim3(256), 0, h->stream, rec, ntiles, D, g_w, g_sf2);
+  if (dU > 0) {
+    const int64_t rows = (Mg > N ? Mg : N) * dU;
+    hipLaunchKernelGGL(gpp_gek_gU_finish, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, h->stream, partA, ti, partG, partI, ta, N, Mg,
+                       dU, g_U, g_Ug);
+  }
   return dg_rc(hipGetLastError());
 }

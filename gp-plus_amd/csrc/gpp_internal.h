@@ -188,6 +188,19 @@ __device__ __forceinline__ double gpp_matern_d2(int kind, const GppMatern& m) {
   if (kind == 1) return m.r > 0.0 ? (9.0 * m.er) / m.r : 0.0;
   return (25.0 / 3.0) * m.er;
 }
+// d3h/d r2_mat^3 times x (the gradient of the second-derivative block, gpp_gek_grad_reduce alone):
+//   nu = 3/2:  -27 e^-r (1 / r^2 + 1 / r^3) x          nu = 5/2:  -(125 / 3) e^-r x / r
+// for an x that carries two or more factors delta of the Matern features (|x| = O(r^2)): formed as ((x / r) / r)(1 + 1 / r), so
+// that no power of r under- or overflows on the way, and an exact 0 where r == 0.  Only m.r and m.er are read.
+__device__ __forceinline__ double gpp_matern_d3_times(int kind, const GppMatern& m, double x) {
+  if (m.r == 0.0) return 0.0;
+  const double rho = 1.0 / m.r;
+  if (kind == 1) {
+    const double y = (x * rho) * rho;
+    return (-27.0 * m.er) * __builtin_fma(y, rho, y);
+  }
+  return ((-125.0 / 3.0) * m.er) * (x * rho);
+}
 
 // The 64 x 64 tile kernels (gpp_build.hip, gpp_reduce.hip) give thread tx of a row of 16 the column PAIRS {2 tx, 2 tx + 1} and
 // {32 + 2 tx, 33 + 2 tx}, so that the 16 lanes of a ds_read_b128 cover 256 contiguous bytes: the thread's column b = 0..3, counted
@@ -299,6 +312,7 @@ struct PostCrossMinArgs {
 hipError_t gpp_launch_post_cross_min(hipStream_t s, int variant, const GemmArgs& p, const PostCrossMinArgs& e);
 size_t gpp_post_cross_min_ws_bytes(int64_t Mc, int64_t Mr, int Q);  // gpp_alc.hip
 size_t gpp_point_gram_ws_bytes(int64_t M, int nd);                  // gpp_dgrad.hip
+size_t gpp_gek_grad_ws_bytes(int64_t N, int64_t Mg, int D, int dU);  // gpp_dgrad.hip: per-tile records of gpp_gek_grad_reduce
 
 // one-wave kernels on a stream (gpp_gemm.hip): wait until counters[id] >= target — a wait that exceeds `budget` ticks of the 100 MHz
 // clock sets the abort word counters[0] and *info = GPP_INFO_EXEC_TIMEOUT + ms —, and counters[id] += 1 behind a release fence

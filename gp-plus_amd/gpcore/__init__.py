@@ -8,4 +8,5 @@ from .distributions import DenseCovariance, MultivariateNormal  # noqa: F401
 from .means import ConstantMean, Mean, ZeroMean  # noqa: F401
 from .likelihoods import GaussianLikelihood, HomoskedasticNoise, _GaussianLikelihoodBase  # noqa: F401
 from .models import ExactGP, GP  # noqa: F401
-from .mlls import CrossValidationPseudoLikelihood, ExactMarginalLogLikelihood, LeaveOneOutPseudoLikelihood  # noqa: F401
+from .mlls import (CrossValidationPseudoLikelihood, ExactMarginalLogLikelihood,  # noqa: F401
+                   GradientEnhancedMarginalLogLikelihood, LeaveOneOutPseudoLikelihood)

@@ -204,6 +204,28 @@ class MultivariateNormal:
 
         return exact_cv(cov.U1, cov.spec, cov.tau, self.loc, value, folds, cov.grp, cov.n_grad_dims)
 
+    def gek_log_prob(self, value: torch.Tensor, gradient_data) -> torch.Tensor:
+        """Joint log-density log N([value - mean; r_g] | 0, Kj) of ``value`` and of observed gradients, for a (noisy) lazy kernel
+        covariance (``linalg.exact_gek_mll``).  ``gradient_data`` = (Ug, r_g, noise, d0, nd): the feature rows of the gradient points
+        from the same ``forward`` of the model, the Mg x nd gradients in scaled units, their variances in scaled units squared or
+        None for the default nugget, and the range of differentiated features."""
+        cov = self._covar
+        if not isinstance(cov, LazyKernelMatrix):
+            raise NotImplementedError("gek_log_prob needs the lazy kernel covariance of a training evaluation")
+        if not cov.is_square:
+            raise RuntimeError("gek_log_prob needs a square covariance")
+        if cov.tau is None:
+            raise RuntimeError("gek_log_prob of a noise-free kernel matrix: apply the likelihood first")
+        if cov.calib is not None:
+            raise NotImplementedError("gek_log_prob: the objective has no gradient by calibration parameters")
+        from ..linalg import exact_gek_mll
+
+        Ug, r_g, noise, d0, nd = gradient_data
+        dU = cov.n_grad_dims
+        if dU is None:
+            dU = int(d0) if (cov.U1.requires_grad or Ug.requires_grad) else 0
+        return exact_gek_mll(cov.U1, Ug, cov.spec, cov.tau, self.loc, value, r_g, noise, cov.grp, d0, nd, min(int(dU), int(d0)))
+
     # -- sampling --------------------------------------------------------------------------------
     def root_factor(self) -> torch.Tensor:
         """Upper Cholesky factor U of the covariance (U^T U = Sigma; an M x M view whose strict lower triangle is not part of

@@ -79,3 +79,47 @@ class CrossValidationPseudoLikelihood(ExactMarginalLogLikelihood):
         if prior_sum is not None:
             res = res + prior_sum
         return res / num_data
+
+
+class GradientEnhancedMarginalLogLikelihood(ExactMarginalLogLikelihood):
+    """The joint marginal log-likelihood of the training targets AND of gradients observed at the rows ``Xg`` — gradient-enhanced
+    Kriging as a training criterion — in the scaling of :class:`ExactMarginalLogLikelihood` with n = N + Mg p observations:
+        (log N([y - mean; dY / y_std] | 0, Kj) + sum of prior log-densities) / n
+    (``MultivariateNormal.gek_log_prob``, ``linalg.exact_gek_mll``).  ``Xg``: (Mg, columns of the training inputs); ``dY``: (Mg, p),
+    d y / d x over the quantitative columns in ``quant_index`` order, y per input unit; ``noise``: their variances in (y per input
+    unit)^2, a scalar or anything that broadcasts to (Mg, p), constant during the fit — None takes
+    ``gradient_enhanced.GRADIENT_NUGGET_REL`` times the prior curvature at the current hyperparameters.  The data are validated
+    once, here, as ``GP_Plus.condition_on_gradients`` validates them (the number of observations is limited by memory alone)."""
+
+    def __init__(self, likelihood, model, Xg, dY, noise=None):
+        super().__init__(likelihood, model)
+        from ..gradient_enhanced import check_gradient_observations
+
+        if len(getattr(model, "calibration_id", ())) > 0:
+            raise NotImplementedError("the gradient-enhanced objective is not available for a model with calibration parameters: "
+                                      "gradient observations by a calibrated column are not defined")
+        Xg, dY, noise = check_gradient_observations(model, Xg, dY, noise, "GradientEnhancedMarginalLogLikelihood")
+        train_x = model.train_inputs[0]
+        y_std = model.y_std.detach().to(device=train_x.device, dtype=torch.float64)
+        self.Xg = Xg.to(train_x)
+        self.r_g = (dY.to(device=train_x.device, dtype=torch.float64) / y_std).contiguous()
+        self.noise = None if noise is None else (noise.to(train_x.device) / y_std ** 2).contiguous()
+        self.num_directions = int(model.quant_index.numel())
+
+    def joint_log_prob(self, output: MultivariateNormal, target: torch.Tensor) -> torch.Tensor:
+        """log N([target - mean; dY / y_std] | 0, Kj) for the noisy training distribution ``output``: neither normalised nor with
+        the priors (what the scipy driver adds its own terms to).  The gradient points go through the model's ``forward`` here,
+        at the current parameters: their latent columns carry the categorical map's graph."""
+        p = self.num_directions
+        Ug = Module.__call__(self.model, self.Xg).lazy_covariance_matrix.U1
+        return output.gek_log_prob(target, (Ug, self.r_g, self.noise, Ug.shape[1] - p, p))
+
+    def forward(self, function_dist: MultivariateNormal, target: torch.Tensor, *params):
+        if not isinstance(function_dist, MultivariateNormal):
+            raise RuntimeError("GradientEnhancedMarginalLogLikelihood can only operate on Gaussian random variables")
+        num_data = function_dist.event_shape.numel() + self.r_g.numel()
+        res = self.joint_log_prob(self.likelihood(function_dist, *params), target)
+        prior_sum = self._prior_sum(res.dtype)
+        if prior_sum is not None:
+            res = res + prior_sum
+        return res / num_data

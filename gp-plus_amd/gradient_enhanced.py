@@ -10,7 +10,7 @@ from .gpcore.distributions import DenseCovariance, MultivariateNormal
 from .gpcore.module import Module
 from .utils import data_type_check
 
-__all__ = ["GRADIENT_NUGGET_REL", "GradientEnhancedPosterior", "condition_on_gradients"]
+__all__ = ["GRADIENT_NUGGET_REL", "GradientEnhancedPosterior", "condition_on_gradients", "check_gradient_observations"]
 
 #: ``noise=None``: the variance given to a gradient observation, as a fraction of the prior curvature of its direction (the prior
 #: variance of that component of the gradient, ``linalg.gradient_prior_curvature``).
@@ -79,13 +79,10 @@ class GradientEnhancedPosterior:
             return mean * scale
 
 
-def condition_on_gradients(model, X, dY, noise=None) -> GradientEnhancedPosterior:
-    """The work behind ``GP_Plus.condition_on_gradients`` (documented there)."""
-    from . import settings as gpp_settings
-    from .backend import get_context
-    from .linalg import APPEND_MAX_Q, append_gradients_to_cache, gradient_prior_curvature
-
-    what = "condition_on_gradients"
+def check_gradient_observations(model, X, dY, noise, what: str):
+    """The host-side validation ``condition_on_gradients`` and the ``"gek"`` training objective share: returns (X, dY, noise) with
+    dY as (Mg, p) and ``noise`` as an fp64 (Mg, p) tensor or None.  ``ValueError`` for wrong shapes, NaN / inf, Mg = 0, rows the model
+    cannot take, negative noise or a model without a quantitative column."""
     X, dY = data_type_check(X), data_type_check(dY)
     train_x = model.train_inputs[0]
     p = int(model.quant_index.numel())
@@ -114,6 +111,20 @@ def condition_on_gradients(model, X, dY, noise=None) -> GradientEnhancedPosterio
             raise ValueError(f"{what}: noise must be a scalar or broadcast to ({Mg}, {p}) (got {tuple(noise.shape)})") from None
         if not bool(torch.isfinite(noise).all()) or bool((noise < 0).any()):
             raise ValueError(f"{what}: the noise variances must be finite and not negative")
+    return X, dY, noise
+
+
+def condition_on_gradients(model, X, dY, noise=None) -> GradientEnhancedPosterior:
+    """The work behind ``GP_Plus.condition_on_gradients`` (documented there)."""
+    from . import settings as gpp_settings
+    from .backend import get_context
+    from .linalg import APPEND_MAX_Q, append_gradients_to_cache, gradient_prior_curvature
+
+    what = "condition_on_gradients"
+    X, dY, noise = check_gradient_observations(model, X, dY, noise, what)
+    train_x = model.train_inputs[0]
+    p = int(model.quant_index.numel())
+    Mg = X.shape[0]
     N = int(train_x.shape[0])
     if Mg * p > min(N, APPEND_MAX_Q):
         raise ValueError(f"{what}: {Mg} points x {p} directions = {Mg * p} gradient observations exceed min(N = {N}, {APPEND_MAX_Q})")

@@ -27,7 +27,7 @@ from .psd_safe import inputs_nan_probe, psd_safe
 from . import settings
 
 __all__ = ["KernelSpec", "exact_mll", "ExactMLLFunction", "CalibratedMLLFunction", "Calibration", "exact_loo", "ExactLOOFunction",
-           "loo_moments", "exact_cv", "ExactCVFunction",
+           "loo_moments", "exact_cv", "ExactCVFunction", "exact_gek_mll", "ExactGEKFunction",
            "cv_moments", "EvalWorkspace", "dense_kernel", "cross_kernel",
            "FactorCache", "factorize", "append_to_cache", "GradientFactorCache", "append_gradients_to_cache",
            "predict_from_gradient_cache", "dense_log_prob", "predict_mean", "predict_var", "predictive_cov_upper",
@@ -920,16 +920,21 @@ def variance_reduction(cache: FactorCache, Uc, tau_c, Ur, omega=None, q: int = 1
 GRAD_CHUNK_BYTES = 256 << 20
 
 
-def gradient_prior_curvature(spec: KernelSpec, d0: int, nd: int) -> torch.Tensor:
-    """kappa_j = d^2 (sf2 k) / du_j du'_j at u' = u for the features d0 .. d0 + nd - 1: c_j w_j sf2 with c_j = 2 on a feature of
-    the RBF factor, 6 on a Matern-3/2 and 10 / 3 on a Matern-5/2 feature (h'(0) = -3 and -5 / 3 of the Matern factor h(r),
-    r^2 = 2 nu 2 sum_d w_d delta_d^2): the prior variance of the gradient's components, which are uncorrelated a priori."""
+def _curvature_coefficients(spec: KernelSpec) -> torch.Tensor:
+    """c_d of ``gradient_prior_curvature`` for all D features: 2 on the RBF factor, 6 (Matern 3/2) or 10 / 3 (Matern 5/2) behind."""
     D = spec.w.numel()
     split = D if spec.kind == KIND_RBF else int(spec.d_split)
     c = torch.full((D,), 2.0, dtype=torch.float64, device=spec.w.device)
     if spec.kind != KIND_RBF:
         c[split:] = 6.0 if spec.kind == KIND_MATERN32 else 10.0 / 3.0
-    return (c * spec.w.reshape(-1) * spec.sf2.reshape(()))[d0:d0 + nd]
+    return c
+
+
+def gradient_prior_curvature(spec: KernelSpec, d0: int, nd: int) -> torch.Tensor:
+    """kappa_j = d^2 (sf2 k) / du_j du'_j at u' = u for the features d0 .. d0 + nd - 1: c_j w_j sf2 with c_j = 2 on a feature of
+    the RBF factor, 6 on a Matern-3/2 and 10 / 3 on a Matern-5/2 feature (h'(0) = -3 and -5 / 3 of the Matern factor h(r),
+    r^2 = 2 nu 2 sum_d w_d delta_d^2): the prior variance of the gradient's components, which are uncorrelated a priori."""
+    return (_curvature_coefficients(spec) * spec.w.reshape(-1) * spec.sf2.reshape(()))[d0:d0 + nd]
 
 
 def _gradient_chunk_points(N: int, nd: int) -> int:
@@ -1186,6 +1191,168 @@ def predict_from_gradient_cache(gcache: GradientFactorCache, Us, want: str = "fu
             mean[a0:a0 + mc] = g_c.view(mc, nd)
             var[a0:a0 + mc] = v_c.view(mc, nd)
         return mean, var
+
+
+# ---------------------------------------------------------------------------------------------------
+# training on gradient observations: the joint log-likelihood of [y; grad y], factored from scratch
+# ---------------------------------------------------------------------------------------------------
+class ExactGEKFunction(torch.autograd.Function):
+    """log N([y - mean; r_g] | 0, Kj) of N function rows U and q = Mg nd gradient observations at the rows Ug,
+        Kj = [[sf2 k(U, U) + diag(tau[grp]), Kfg], [Kfg^T, Kgg + diag(nu)]],
+    Kfg = gpp_cross_kernel_dx(Ua = Ug, Ub = U) (N x q), Kgg = gpp_kernel_dxdx(Ug, Ug), rows point-major as in
+    ``append_gradients_to_cache``; with gradients for U[:, :dU], Ug[:, :dU], w, sf2, tau, mean and y.  ``nu``: the q noise variances
+    of the gradient observations (constant), or None for ``nugget_rel`` times ``gradient_prior_curvature`` at the CURRENT w and sf2,
+    whose derivative by w and sf2 is added on the host from the diagonal of the gradient rows' block of Kj^-1 - alpha alpha^T.
+
+    As in ExactMLLFunction the whole evaluation is enqueued in ``forward``: the three blocks into the triangle gpp_potrf reads
+    (nu and the jitter on the diagonal, the jitter-retry policy of ``_factor``), potrf, trtri, z, alpha, the dense LAUUM,
+    gpp_grad_reduce on the leading N x N view and gpp_gek_grad_reduce on the other two blocks; ``backward`` scales."""
+
+    @staticmethod
+    def forward(ctx, U, Ug, w, sf2, tau, mean, y, r_g, nu, grp, kind, d_split, d0, nd, dU, nugget_rel, slot):
+        gctx = get_context(U.device)  # raises GppError for anything but a GPU: there is no CPU path
+        with torch.cuda.device(U.device):
+            if torch.cuda.is_current_stream_capturing():
+                raise NotImplementedError("the gradient-enhanced objective is not available inside a graph capture")
+            dev = U.device
+            (N, D), Mg = U.shape, Ug.shape[0]
+            q = Mg * nd
+            n = N + q
+            Ud, wd, sd, td, grp = _operands(U, w, sf2, tau, grp)
+            Ugd = _as_f64(Ug.detach(), dev)
+            S = td.numel()
+            need = ctx.needs_input_grad
+            ctx.in_dtypes = (U.dtype, Ug.dtype, w.dtype, sf2.dtype, tau.dtype, mean.dtype, y.dtype)
+            ctx.shapes = (sf2.shape, tau.shape)
+            ctx.n_grad_points = Mg
+            need_grad = any(need[:7])
+            need_U = (need[0] or need[1]) and dU > 0
+            dUk = dU if need_U else 0
+            spec = KernelSpec(wd, sd, kind, d_split)
+            if nu is None:
+                nu_d = (float(nugget_rel) * gradient_prior_curvature(spec, d0, nd)).repeat(Mg)
+            else:
+                nu_d = _as_f64(nu.detach().reshape(-1), dev)
+            ws = get_workspace(gctx, n, slot)
+            ws.epoch += 1
+            torch.sub(_as_f64(y.detach(), dev), _as_f64(mean.detach(), dev), out=ws.r[:N])
+            ws.r[N:].copy_(_as_f64(r_g.detach().reshape(-1), dev))
+            g_w = g_s = g_t = g_Ud = g_Ugd = None
+            if need_grad:
+                g_w = torch.empty(D, dtype=torch.float64, device=dev)
+                g_s = torch.empty(1, dtype=torch.float64, device=dev)
+                g_t = torch.empty(S, dtype=torch.float64, device=dev)
+                if need_U:
+                    g_Ud = torch.empty(N, dU, dtype=torch.float64, device=dev)
+                    g_Ugd = torch.empty(Mg, dU, dtype=torch.float64, device=dev)
+            # gpp_cross_kernel_dx / gpp_kernel_dxdx write 16-byte pairs: a window that starts at an odd column N is built aside
+            aligned = N % 2 == 0
+            Kfg_out = ws.A[:N, N:n] if aligned else rows_buffer(N, q, dev)
+            Kgg_out = ws.A[N:n, N:n] if aligned else square_buffer(q, dev)
+
+            def rest():
+                with _stage("trtri"):
+                    gctx.trtri(ws.A, ws.Li, ws.Ki)
+                with _stage("mll_reduce"):
+                    gctx.mll_reduce(ws.A, ws.Li, ws.r, ws.z, ws.out3)
+                if not need_grad:
+                    return
+                with _stage("alpha"):
+                    gctx.alpha(ws.Li, ws.z, ws.alpha)
+                with _stage("lauum"):
+                    gctx.lauum(ws.Li, ws.Ki)
+                with _stage("grad_reduce"):
+                    gctx.grad_reduce(Ud, wd, sd, grp, S, ws.alpha[:N], ws.Ki[:N, :N], dUk, g_w, g_s, g_t, g_Ud, kind=kind,
+                                     d_split=d_split)
+                with _stage("gek_grad_reduce"):
+                    gctx.gek_grad_reduce(Ud, Ugd, wd, sd, d0, nd, ws.alpha, ws.Ki, dUk, g_w, g_s, g_Ud, g_Ugd, kind=kind,
+                                         d_split=d_split)
+                    if nu is None:
+                        # d nu_k / dw_j = rel c_j sf2, d nu_k / dsf2 = rel c_j w_j on the rows k = (a, j), times W_kk
+                        a_g = ws.alpha[N:]
+                        Wd = (0.5 * (a_g * a_g - ws.Ki[N:n, N:n].diagonal())).view(Mg, nd).sum(0)
+                        c = float(nugget_rel) * _curvature_coefficients(spec)[d0:d0 + nd]
+                        g_w[d0:d0 + nd].add_(c * sd * Wd)
+                        g_s.add_((c * wd[d0:d0 + nd] * Wd).sum())
+
+            def attempt(jit):
+                if n >= LOOKAHEAD_MIN_N:  # (as in ``_factor``: the factorisation's launches go to an idle device)
+                    torch.cuda.current_stream(gctx.index).synchronize()
+                with _stage("gek_build"):
+                    gctx.kernel_build(Ud, wd, sd, td, grp, ws.A[:N, :N], jitter=jit, kind=kind, d_split=d_split, uplo=UPLO_UPPER)
+                    gctx.cross_kernel_dx(Ugd, Ud, wd, sd, d0, nd, Kfg_out, kind=kind, d_split=d_split)
+                    gctx.kernel_dxdx(Ugd, Ugd, wd, sd, d0, nd, Kgg_out, kind=kind, d_split=d_split)
+                    if not aligned:
+                        ws.A[:N, N:n].copy_(Kfg_out)
+                        ws.A[N:n, N:n].copy_(Kgg_out)
+                    ws.A[N:n, N:n].diagonal().add_(nu_d + jit)
+                with _stage("potrf"):
+                    gctx.potrf(ws.A, ws.Li, ws.info, ws.Ki)
+                ws.info_host.copy_(ws.info, non_blocking=True)
+                ws.info_event.record(torch.cuda.current_stream(gctx.index))
+                rest()
+                ws.info_event.synchronize()
+                return int(ws.info_host[0])
+
+            psd_safe(gctx, attempt, inputs_nan_probe(torch.cat([Ud.reshape(-1), Ugd.reshape(-1), ws.r]), wd, sd,
+                                                     torch.cat([td, nu_d])))
+            ctx.saved = (g_w, g_s, g_t, g_Ud, g_Ugd, ws.alpha[:N].clone() if need_grad else None)
+            return ws.out3[2].clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        g_w, g_s, g_t, g_Ud, g_Ugd, g_mean = ctx.saved
+        need = ctx.needs_input_grad
+        go = grad_out.to(torch.float64)
+        dt = ctx.in_dtypes
+        sf2_shape, tau_shape = ctx.shapes
+
+        def rows(g_d, rows_n):
+            g = torch.zeros(rows_n, g_w.shape[0], dtype=torch.float64, device=g_w.device)
+            if g_d is not None:
+                g[:, :g_d.shape[1]] = g_d
+            return go * g
+
+        return (rows(g_Ud, g_mean.shape[0]).to(dt[0]) if need[0] else None,
+                rows(g_Ugd, ctx.n_grad_points).to(dt[1]) if need[1] else None,
+                (go * g_w).to(dt[2]) if need[2] else None,
+                (go * g_s).reshape(sf2_shape).to(dt[3]) if need[3] else None,
+                (go * g_t).reshape(tau_shape).to(dt[4]) if need[4] else None,
+                (go * g_mean).to(dt[5]) if need[5] else None,
+                (-go * g_mean).to(dt[6]) if need[6] else None) + (None,) * 10
+
+
+def exact_gek_mll(U: torch.Tensor, Ug: torch.Tensor, spec: KernelSpec, tau: torch.Tensor, mean: torch.Tensor, y: torch.Tensor,
+                  r_g: torch.Tensor, noise: Optional[torch.Tensor], grp: Optional[torch.Tensor], d0: int, nd: int,
+                  n_grad_dims: Optional[int] = None, slot: Optional[int] = None) -> torch.Tensor:
+    """log N([y - mean; r_g] | 0, Kj) on the GPU (``ExactGEKFunction``): the joint density of the N function rows ``U`` and the
+    q = Mg nd observed gradients ``r_g`` (point-major, scaled units; prior mean 0) with respect to the features d0 .. d0 + nd - 1 at
+    the rows ``Ug``.  ``noise``: their q variances (scaled units squared, constant during a fit), or None for
+    ``gradient_enhanced.GRADIENT_NUGGET_REL`` times the prior curvature at the current hyperparameters.  Differentiable with respect
+    to U[:, :n_grad_dims], Ug[:, :n_grad_dims], spec.w, spec.sf2, tau, mean and y; n_grad_dims <= d0.  The matrix is factored from
+    scratch in a workspace of N + q rows: q is limited by memory alone.  Refused under ``settings.sharded_evaluation`` and inside a
+    graph capture."""
+    from .gradient_enhanced import GRADIENT_NUGGET_REL
+
+    _gradient_cache_refusals("the gradient-enhanced objective")
+    if slot is None:
+        slot = current_slot()
+    if n_grad_dims is None:
+        n_grad_dims = min(U.shape[1], int(d0)) if (U.requires_grad or Ug.requires_grad) else 0
+    d0, nd, dU = int(d0), int(nd), int(n_grad_dims)
+    D = U.shape[1]
+    if Ug.dim() != 2 or Ug.shape[0] < 1 or Ug.shape[1] != D:
+        raise ValueError(f"the gradient points must be at least one row of {D} features (got {tuple(Ug.shape)})")
+    if nd < 1 or d0 < 0 or d0 + nd > D:
+        raise ValueError(f"the differentiated features [{d0}, {d0 + nd}) must be a non-empty range of the {D} features")
+    q = Ug.shape[0] * nd
+    if r_g.numel() != q or (noise is not None and noise.numel() != q):
+        raise ValueError(f"{r_g.numel()} gradients / {None if noise is None else noise.numel()} noise variances for {q} gradient "
+                         "observations")
+    if dU > d0:
+        raise ValueError(f"the {dU} feature columns with a gradient must lie in front of the differentiated ones (d0 = {d0})")
+    return ExactGEKFunction.apply(U, Ug, spec.w, spec.sf2, tau, mean, y, r_g, noise, grp, spec.kind, spec.d_split, d0, nd, dU,
+                                  GRADIENT_NUGGET_REL, slot)
 
 
 #: Scratch one gpp_post_cross_min launch of ``knowledge_gradient`` may ask for: above it the reference rows go in column chunks

@@ -391,7 +391,8 @@ class GP_Plus(GPR):
     # ---- fit -----------------------------------------------------------------------------------------
     def fit(self, add_prior: bool = True, num_restarts: int = 64, theta0_list: Optional[List[np.ndarray]] = None,
             jac: bool = True, options: Dict = {}, n_jobs: int = -1, method='L-BFGS-B', constraint=False, bounds=False,
-            regularization_parameter: List[int] = [0, 0], optim_type='scipy', objective: str = "mll", folds=None):
+            regularization_parameter: List[int] = [0, 0], optim_type='scipy', objective: str = "mll", folds=None,
+            gradients=None):
         """gp_plus.py:547-599.  On a GPU device the reference always ends in ``fit_model_torch`` (64 restarts for
         'adam_torch', otherwise a warning and 4 restarts) — reproduced here.  The CPU branches
         (scipy / continuation drivers) do not exist in this build: the exact-GP path only runs on the MI355X.
@@ -401,9 +402,13 @@ class GP_Plus(GPR):
         the restarts run one after the other, the leave-one-out objective then with every evaluation eager.
         ``objective="cv"`` with ``folds=`` (an int k, one integer label per training row — ``cv.group_labels`` makes them from
         columns of X — or a ``cv.FoldIndex``) maximises the grouped cross-validation log pseudo-likelihood: always the sequential,
-        eager route."""
-        from ..optim.mll_torch import check_objective_folds
+        eager route.  ``objective="gek"`` with ``gradients=(Xg, dY)`` or ``(Xg, dY, noise)`` — the arguments of
+        ``condition_on_gradients`` — trains on the joint marginal likelihood of the targets and of the observed gradients
+        (``gpcore.GradientEnhancedMarginalLogLikelihood``): sequential and eager as well; afterwards ``condition_on_gradients`` on
+        the same data gives the gradient-enhanced posterior at the fitted hyperparameters."""
+        from ..optim.mll_torch import check_objective_folds, check_objective_gradients
         folds = check_objective_folds(objective, folds, int(self.train_targets.shape[0]))
+        gradients = check_objective_gradients(objective, gradients)
         if objective != "mll":
             self._refuse_calibrated(f'objective="{objective}"', "only the exact marginal likelihood has a gradient by theta")
         if optim_type == 'adam_torch_batched':
@@ -425,6 +430,9 @@ class GP_Plus(GPR):
         if objective == "cv":
             out = fit_model_torch(model=self, model_param_groups=None, lr_default=0.01, num_iter=100,
                                   num_restarts=restarts, break_steps=50, objective=objective, folds=folds)
+        elif objective == "gek":
+            out = fit_model_torch(model=self, model_param_groups=None, lr_default=0.01, num_iter=100,
+                                  num_restarts=restarts, break_steps=50, objective=objective, gradients=gradients)
         elif optim_type == 'adam_torch_batched' or self._restarts_fit_one_batch(restarts + 1):
             from ..optim import fit_model_torch_batched
             out = fit_model_torch_batched(self, lr_default=0.01, num_iter=100, num_restarts=restarts, break_steps=50,

@@ -26,7 +26,7 @@ from torch.func import functional_call
 from ..batched import batched_loo, batched_mll
 from ..gpcore.kernels import LazyKernelMatrix
 from ..gpcore.mlls import ExactMarginalLogLikelihood
-from .mll_torch import check_objective, check_objective_folds
+from .mll_torch import check_objective, check_objective_folds, check_objective_gradients
 
 __all__ = ["BatchedObjective", "fit_model_torch_batched", "BATCHED_MAX_N"]
 
@@ -185,17 +185,23 @@ class _GraphedLossAndGrad:
 
 def fit_model_torch_batched(model, lr_default: float = 0.01, num_iter: int = 100, num_restarts: int = 0,
                             break_steps: int = 50, verbose: bool = False, objective: str = "mll",
-                            folds=None) -> Tuple[float, List[List[float]]]:
+                            folds=None, gradients=None) -> Tuple[float, List[List[float]]]:
     """Drop-in for ``fit_model_torch`` (same return value) that advances all restarts together.  ``objective="loo"`` maximises the
-    leave-one-out log pseudo-likelihood (plus the priors) in the same way: batched, and replayed as a HIP graph."""
+    leave-one-out log pseudo-likelihood (plus the priors) in the same way: batched, and replayed as a HIP graph.  ``"cv"`` and
+    ``"gek"`` have no batched form and go to the sequential driver."""
     N = int(model.train_targets.shape[0])
     folds = check_objective_folds(objective, folds, N)
+    gradients = check_objective_gradients(objective, gradients)
     if getattr(model, "calibration_id", None):
         raise NotImplementedError("the batched restarts have no gradient by calibration parameters: use fit_model_torch")
     if objective == "cv":  # the cross-validation objective has no batched form: the sequential, eager driver
         from .mll_torch import fit_model_torch
         return fit_model_torch(model, None, lr_default, num_iter, num_restarts, break_steps, verbose=verbose, objective=objective,
                                folds=folds)
+    if objective == "gek":  # neither has the gradient-enhanced objective
+        from .mll_torch import fit_model_torch
+        return fit_model_torch(model, None, lr_default, num_iter, num_restarts, break_steps, verbose=verbose, objective=objective,
+                               gradients=gradients)
     B = num_restarts + 1
     if N > BATCHED_MAX_N:
         # gpp_potrf_batched factors each problem right-looking in leaf steps and rejects larger matrices; at these sizes

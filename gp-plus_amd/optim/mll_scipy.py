@@ -25,15 +25,22 @@ from scipy.optimize import Bounds, OptimizeResult, minimize
 from ..errors import NanError, NotPSDError
 
 
-def marginal_log_likelihood(model, add_prior: bool, regularization_parameter=[0, 0], objective: str = "mll", folds=None):
+def marginal_log_likelihood(model, add_prior: bool, regularization_parameter=[0, 0], objective: str = "mll", folds=None,
+                            gradients=None):
     """optim/mll_scipy.py:37-60 (exact log-marginal + priors, un-normalised).  ``objective="loo"``: the leave-one-out log
-    pseudo-likelihood in place of the log-marginal; ``objective="cv"``: the grouped cross-validation one over ``folds``."""
+    pseudo-likelihood in place of the log-marginal; ``objective="cv"``: the grouped cross-validation one over ``folds``;
+    ``objective="gek"``: the joint log-marginal of the targets and of observed gradients, ``gradients`` a
+    ``GradientEnhancedMarginalLogLikelihood`` that holds the validated data."""
     from .mll_torch import check_objective_folds
 
     folds = check_objective_folds(objective, folds, int(model.train_targets.shape[0]))
+    if (objective == "gek") != (gradients is not None):
+        raise ValueError('objective="gek" and gradients= go together')
     output = model(*model.train_inputs)
     noisy = model.likelihood(output)
-    if objective == "cv":
+    if objective == "gek":
+        out = gradients.joint_log_prob(noisy, model.train_targets)
+    elif objective == "cv":
         out = noisy.cv_log_prob(model.train_targets, folds)
     else:
         out = noisy.loo_log_prob(model.train_targets) if objective == "loo" else noisy.log_prob(model.train_targets)
@@ -48,12 +55,18 @@ def marginal_log_likelihood(model, add_prior: bool, regularization_parameter=[0,
 class MLLObjective:
     """optim/mll_scipy.py:63-127."""
 
-    def __init__(self, model, add_prior, regularization_parameter, objective: str = "mll", folds=None):
-        from .mll_torch import check_objective, check_objective_folds
+    def __init__(self, model, add_prior, regularization_parameter, objective: str = "mll", folds=None, gradients=None):
+        from .mll_torch import check_objective, check_objective_folds, check_objective_gradients
 
         self.model, self.add_prior, self.regularization_parameter = model, add_prior, regularization_parameter
         self.objective = check_objective(objective)
         self.folds = check_objective_folds(objective, folds, int(model.train_targets.shape[0]))  # normalised once per fit
+        gradients = check_objective_gradients(objective, gradients)
+        self.gradients = None
+        if gradients is not None:  # validated and scaled once per fit
+            from ..gpcore.mlls import GradientEnhancedMarginalLogLikelihood
+
+            self.gradients = GradientEnhancedMarginalLogLikelihood(model.likelihood, model, *gradients)
         self.param_shapes = OrderedDict()
         for n, p in self.model.named_parameters():
             if p.requires_grad:
@@ -134,7 +147,8 @@ class MLLObjective:
         old.update(self.unpack_parameters(x))
         self.model.load_state_dict(old)
         self.model.zero_grad()
-        obj = -marginal_log_likelihood(self.model, self.add_prior, self.regularization_parameter, self.objective, self.folds)
+        obj = -marginal_log_likelihood(self.model, self.add_prior, self.regularization_parameter, self.objective, self.folds,
+                                       self.gradients)
         if return_grad:
             obj.backward()
             return obj.item(), self.pack_grads()
@@ -180,11 +194,13 @@ def _fit_model_from_state(likobj, theta0, jac, options, method='L-BFGS-B', const
 def fit_model_scipy(model, add_prior: bool = True, num_restarts: int = 1, theta0_list: Optional[List[np.ndarray]] = None,
                     jac: bool = True, options: Dict = {}, n_jobs: int = -1, method='L-BFGS-B', constraint=False,
                     bounds=False, regularization_parameter: List[int] = [0, 0],
-                    objective: str = "mll", folds=None) -> Tuple[List[OptimizeResult], float]:
-    from .mll_torch import check_objective_folds
+                    objective: str = "mll", folds=None, gradients=None) -> Tuple[List[OptimizeResult], float]:
+    from .mll_torch import check_objective_folds, check_objective_gradients
 
-    # "loo" / "cv": the leave-one-out / grouped cross-validation log pseudo-likelihood (+ priors), evaluated eagerly
+    # "loo" / "cv": the leave-one-out / grouped cross-validation log pseudo-likelihood (+ priors), evaluated eagerly;
+    # "gek" with gradients=(Xg, dY[, noise]): the joint log-marginal of the targets and the observed gradients, eagerly too
     folds = check_objective_folds(objective, folds, int(model.train_targets.shape[0]))
+    check_objective_gradients(objective, gradients)
     if method == 'L-BFGS-B':
         defaults = {'ftol': 1e-6, 'gtol': 1e-5, 'maxfun': 5000, 'maxiter': 2000}
     elif method == 'trust-constr':
@@ -205,7 +221,7 @@ def fit_model_scipy(model, add_prior: bool = True, num_restarts: int = 1, theta0
         defaults[key] = options[key]
 
     model.train()
-    likobj = MLLObjective(model, add_prior, regularization_parameter, objective, folds)
+    likobj = MLLObjective(model, add_prior, regularization_parameter, objective, folds, gradients)
     if theta0_list is None:
         theta0_list = [likobj.pack_parameters()]
         if num_restarts > -1:

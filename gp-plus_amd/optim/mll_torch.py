@@ -9,7 +9,8 @@ import torch
 from tqdm import tqdm
 
 from ..backend import INFO_PANEL_TIMEOUT
-from ..gpcore.mlls import CrossValidationPseudoLikelihood, ExactMarginalLogLikelihood, LeaveOneOutPseudoLikelihood
+from ..gpcore.mlls import (CrossValidationPseudoLikelihood, ExactMarginalLogLikelihood, GradientEnhancedMarginalLogLikelihood,
+                           LeaveOneOutPseudoLikelihood)
 
 #: what the fit drivers maximise (per datum, priors included): the exact marginal log-likelihood, or the leave-one-out log
 #: pseudo-likelihood (Rasmussen & Williams 5.4.2).  In THIS driver and in fit_model_scipy the latter is always the eager evaluation,
@@ -17,11 +18,14 @@ from ..gpcore.mlls import CrossValidationPseudoLikelihood, ExactMarginalLogLikel
 #: "cv" is the grouped cross-validation log pseudo-likelihood over the ``folds`` the caller gives (gp-plus_amd/cv.py): always the
 #: sequential, eager route (fit_model_torch_batched hands it to fit_model_torch)
 OBJECTIVES = ("mll", "loo", "cv")
+#: the objectives that train on observed gradients as well, given as ``gradients=(Xg, dY)`` or ``(Xg, dY, noise)``: "gek" is the joint
+#: marginal log-likelihood of the targets and of those gradients (gpcore.GradientEnhancedMarginalLogLikelihood), sequential and eager
+GRADIENT_OBJECTIVES = ("gek",)
 
 
 def check_objective(objective: str) -> str:
-    if objective not in OBJECTIVES:
-        raise ValueError(f"objective must be one of {OBJECTIVES} (got {objective!r})")
+    if objective not in OBJECTIVES + GRADIENT_OBJECTIVES:
+        raise ValueError(f"objective must be one of {OBJECTIVES + GRADIENT_OBJECTIVES} (got {objective!r})")
     return objective
 
 
@@ -36,6 +40,21 @@ def check_objective_folds(objective: str, folds, n_points: int):
         return FoldIndex.make(folds, n_points)
     if folds is not None:
         raise ValueError(f'folds= belongs to objective="cv" (got objective={objective!r})')
+    return None
+
+
+def check_objective_gradients(objective: str, gradients):
+    """The pairing of ``objective`` and ``gradients``: "gek" needs them, no other objective takes them.  Returns (Xg, dY, noise) or
+    None.  Host work only; the data themselves are validated by ``GradientEnhancedMarginalLogLikelihood``."""
+    check_objective(objective)
+    if objective in GRADIENT_OBJECTIVES:
+        if gradients is None:
+            raise ValueError('objective="gek" needs gradients=(Xg, dY) or (Xg, dY, noise)')
+        if not isinstance(gradients, (tuple, list)) or len(gradients) not in (2, 3):
+            raise ValueError("gradients= must be (Xg, dY) or (Xg, dY, noise)")
+        return (gradients[0], gradients[1], gradients[2] if len(gradients) == 3 else None)
+    if gradients is not None:
+        raise ValueError(f'gradients= belongs to objective="gek" (got objective={objective!r})')
     return None
 
 
@@ -118,20 +137,26 @@ def _adam_run(model, mll, params, lr: float, num_iter: int, break_steps: int, ve
 
 
 def fit_model_torch(model, model_param_groups: Optional[List] = None, lr_default: float = 0.01, num_iter: int = 100,
-                    num_restarts: int = 0, break_steps: int = 50, verbose: bool = True, objective: str = "mll", folds=None) -> float:
+                    num_restarts: int = 0, break_steps: int = 50, verbose: bool = True, objective: str = "mll", folds=None,
+                    gradients=None) -> float:
     """Optimize the log-posterior of a GP+ model with ``torch.optim.Adam`` (optim/mll_torch.py:56-141).
 
     ``objective="loo"`` maximises the leave-one-out log pseudo-likelihood (plus the priors) instead of the marginal likelihood;
     every evaluation is then the eager one.  ``objective="cv"`` with ``folds=`` (an int k, one integer label per training row, or a
-    ``cv.FoldIndex``) maximises the grouped cross-validation log pseudo-likelihood, eagerly as well.
+    ``cv.FoldIndex``) maximises the grouped cross-validation log pseudo-likelihood, eagerly as well.  ``objective="gek"`` with
+    ``gradients=(Xg, dY)`` or ``(Xg, dY, noise)`` maximises the joint marginal log-likelihood of the targets and of the gradients
+    ``dY`` observed at the rows ``Xg`` (``GradientEnhancedMarginalLogLikelihood``), eagerly as well.
 
     :returns: ``(f_inc, loss_hist_total)`` — best (negative, per-datum) log-posterior found and the loss histories.
     """
     folds = check_objective_folds(objective, folds, int(model.train_targets.shape[0]))
-    loo = objective != "mll"  # (neither pseudo-likelihood is captured)
+    gradients = check_objective_gradients(objective, gradients)
+    loo = objective != "mll"  # (neither pseudo-likelihood nor the gradient-enhanced objective is captured)
     model.train()
     if objective == "cv":
         mll = CrossValidationPseudoLikelihood(model.likelihood, model, folds)
+    elif objective == "gek":
+        mll = GradientEnhancedMarginalLogLikelihood(model.likelihood, model, *gradients)
     else:
         mll = (LeaveOneOutPseudoLikelihood if loo else ExactMarginalLogLikelihood)(model.likelihood, model)
     best_loss, best_state = math.inf, model.state_dict()

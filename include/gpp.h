@@ -57,6 +57,7 @@ typedef struct gpp_handle_s* gpp_handle_t;
 #define GPP_OP_POST_CROSS 6 /* gpp_post_cross_sq: N = M_r reference points, M = M_c candidates (D and S are not read) */
 #define GPP_OP_POST_CROSS_MIN 7 /* gpp_post_cross_min: N = M_r reference points, M = M_c candidates, S = Q nodes (D is not read) */
 #define GPP_OP_POINT_GRAM 8 /* gpp_point_gram with a weighted sum: M points, D = nd rows per point (N and S are not read) */
+#define GPP_OP_GEK_GRAD 9   /* gpp_gek_grad_reduce: N function points, M = Mg gradient points, D features, S carries dU */
 
 const char* gpp_version(void);
 
@@ -690,6 +691,28 @@ int gpp_point_gram(gpp_handle_t h, const double* Q, int64_t ldq, int64_t M, int 
  */
 int gpp_kernel_dxdx(gpp_handle_t h, const double* Ua, int64_t Ma, const double* Ub, int64_t Mb, int D, const double* w,
                     const double* sf2, int kind, int d_split, int d0, int nd, double* H, int64_t ld);
+
+/*
+ * Gradient of the joint log-likelihood of function values and gradient observations through the two derivative blocks of
+ *   Kj = [[Kff, Kfg], [Kfg^T, Kgg]],  Kfg = gpp_cross_kernel_dx(Ua = Ug, Ub = U) (N x q),  Kgg = gpp_kernel_dxdx(Ug, Ug),  q = Mg nd
+ * (linalg.py exact_gek_mll; no reference counterpart).  With W = 0.5 (alpha alpha' - Kinv), the convention of gpp_grad_reduce, the
+ * call ADDS to g_w (D), g_sf2 (1) and g_U (N x dU) and WRITES g_Ug (Mg x dU):
+ *   sum over the entries of Kfg (counted for both triangles) and of Kgg of W_rc dKj_rc/dtheta,   theta = w_d, sf2, U[i, d], Ug[a, d]
+ * (g_sf2 as in gpp_grad_reduce: the sum of W_rc Kj_rc / sf2).  The caller adds gpp_grad_reduce on the leading N x N view (ld = n,
+ * alpha[:N]) for the Kff block and its own noise terms.  alpha: n = N + q doubles; Kinv: n x n, ld >= n, ld even, 16-byte aligned,
+ * LOWER triangle read (as gpp_lauum leaves it), rows N + a nd + j = the gradient observations, point-major.  kind / d_split as in
+ * gpp_cross_kernel; D <= 64, nd >= 1, 0 <= d0, d0 + nd <= D; 0 <= dU <= d0, and dU <= d_split on the Matern kinds (a feature with a
+ * gradient is none of the differentiated ones and belongs to the RBF factor), -16 otherwise; g_U and g_Ug may be NULL when dU == 0.
+ * The Matern kinds need the third derivative of the factor, h''' = -(125/3) e^-r / r (5/2) or -27 e^-r (1/r^2 + 1/r^3) (3/2): it
+ * only appears times products of features' differences that vanish faster, which are formed without a division by r == 0; pairs
+ * of equal points give finite results and an exact 0 in those terms.  Tiles of 16 x 16 pairs of points, one record of sums per tile
+ * and one slot per (tile, point) of the feature gradients in the handle workspace (gpp_workspace_bytes(h, GPP_OP_GEK_GRAD, N, Mg, D,
+ * dU) bytes; GPP_NO_WORKSPACE with nothing enqueued when it is missing), added in index order by two finish launches: no float
+ * atomics, two calls agree bit for bit.
+ */
+int gpp_gek_grad_reduce(gpp_handle_t h, const double* U, int64_t N, const double* Ug, int64_t Mg, int D, const double* w,
+                        const double* sf2, int kind, int d_split, int d0, int nd, const double* alpha, const double* Kinv,
+                        int64_t ldk, int dU, double* g_w, double* g_sf2, double* g_U, double* g_Ug);
 
 #ifdef __cplusplus
 }
