@@ -146,6 +146,13 @@ _SIGNATURES = {
                                 c_int, c_void_p, c_int64]),
     "gpp_gek_grad_reduce": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                     c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gpp_cross_kernel_dx_sel": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                        c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64]),
+    "gpp_kernel_dxdx_sel": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                    c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64]),
+    "gpp_gek_grad_reduce_sel": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                        c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -126,6 +126,40 @@ def _ld(m: torch.Tensor) -> int:
     return m.stride(0) if m.shape[0] > 1 else max(m.shape[1], m.stride(0))
 
 
+class GradientSelection:
+    """Which (point, direction) entries of ``Mg`` gradient points with ``nd`` directions each are observed, in the form the
+    ``_sel`` entry points of gpp.h take.  Built once per call from a bool mask (Mg, nd) — the ONLY producer of these arrays, whose
+    contents the C layer does not check:
+      ``first``  device int32 (Mg + 1): first[a] = the number of observed entries of the points before a;
+      ``dir``    device int32 (q): the direction of observation k, strictly increasing within a point;
+      ``q``      the number of observations, a Python int (the mask is read on the host once: one sync for a device mask);
+      ``flat``   device int64 (q): a nd + j of observation k, the gather of a dense point-major (Mg nd) vector;
+      ``mask``   a bool copy of the mask on the device.
+    Observation k is row (or column) k of every compact block, point-major."""
+
+    def __init__(self, mask, device=None):
+        if not torch.is_tensor(mask) or mask.dtype != torch.bool or mask.dim() != 2 or mask.shape[1] < 1:
+            raise GppError("a gradient selection is built from a bool mask (points, directions)")
+        dev = mask.device if device is None else torch.device(device)
+        host = mask.detach().cpu().contiguous()
+        self.num_points, self.nd = int(host.shape[0]), int(host.shape[1])
+        first = torch.zeros(self.num_points + 1, dtype=torch.int64)
+        torch.cumsum(host.sum(1), 0, out=first[1:])
+        flat = host.reshape(-1).nonzero().reshape(-1)  # (row-major: point-major, directions increasing within a point)
+        self.q = int(flat.numel())
+        if self.q < 1 or self.num_points * self.nd > 0x7ffffff0:
+            raise GppError(f"a gradient selection needs at least one observed entry (mask {tuple(host.shape)}, {self.q} observed)")
+        self.first = first.to(torch.int32).to(dev)
+        self.dir = (flat % self.nd).to(torch.int32).to(dev)
+        self.flat = flat.to(dev)
+        self.mask = host.to(dev)
+
+    def _check(self, name, M, nd, device):
+        if self.num_points != M or self.nd != nd or self.first.device != device:
+            raise GppError(f"{name}: the selection is for {self.num_points} points x {self.nd} directions on {self.first.device}, the "
+                           f"call has {M} x {nd} on {device}")
+
+
 def _on_own_device(fn):
     """Run a GppContext operator with the context's GPU as the CURRENT device.  The library enqueues on the stream it is
     handed; PyTorch's default stream is the null handle, which HIP resolves against the calling thread's current device —
@@ -1102,12 +1136,22 @@ class GppContext:
         return ld
 
     @_on_own_device
-    def cross_kernel_dx(self, Ua, Ub, w, sf2, d0, nd, out, *, kind=KIND_RBF, d_split=0):
+    def cross_kernel_dx(self, Ua, Ub, w, sf2, d0, nd, out, *, kind=KIND_RBF, d_split=0, sel=None):
         """out[n, a nd + j] = d/du_{d0+j} sf2 k(u, Ub_n; w) at u = Ua_a: the derivative cross block with the training points as rows,
         the operand ``predict_tn`` takes (gpp_cross_kernel_dx).  ``out``: an N x (M nd) window of a row-major buffer with an even
-        leading dimension, 16-byte aligned; what lies beyond column M nd is not written.  Everything is checked before the launch."""
+        leading dimension, 16-byte aligned; what lies beyond column M nd is not written.  Everything is checked before the launch.
+        ``sel``: a ``GradientSelection`` of the points ``Ua``: ``out`` is then N x sel.q, column k the selected entry k
+        (gpp_cross_kernel_dx_sel)."""
         d0, nd = int(d0), int(nd)
         M, N = self._dx_checks("cross_kernel_dx", "M, N", Ua, Ub, w, sf2, d0, nd, kind, d_split)
+        if sel is not None:
+            sel._check("cross_kernel_dx", M, nd, Ua.device)
+            ld, D = self._dx_window("Dk", out, N, sel.q), Ua.shape[1]
+            self._stream()
+            check(self.lib.gpp_cross_kernel_dx_sel(self.h, Ua.data_ptr(), M, Ub.data_ptr(), N, D, w.data_ptr(), sf2.data_ptr(),
+                                                   int(kind), int(d_split), d0, nd, sel.first.data_ptr(), sel.dir.data_ptr(), sel.q,
+                                                   out.data_ptr(), ld), "gpp_cross_kernel_dx_sel")
+            return out
         ld, D = self._dx_window("Dk", out, N, M * nd), Ua.shape[1]
         self._stream()
         check(self.lib.gpp_cross_kernel_dx(self.h, Ua.data_ptr(), M, Ub.data_ptr(), N, D, w.data_ptr(), sf2.data_ptr(), int(kind),
@@ -1157,12 +1201,30 @@ class GppContext:
 
     # -- conditioning on gradient observations -----------------------------------------------------------------------------------
     @_on_own_device
-    def kernel_dxdx(self, Ua, Ub, w, sf2, d0, nd, out, *, kind=KIND_RBF, d_split=0):
+    def kernel_dxdx(self, Ua, Ub, w, sf2, d0, nd, out, *, kind=KIND_RBF, d_split=0, sel_a=None, sel_b=None):
         """out[a nd + j, b nd + l] = d^2/du_{d0+j} dv_{d0+l} sf2 k(u, v; w) at u = Ua_a, v = Ub_b: the covariance of two gradient
         observations (gpp_kernel_dxdx).  ``out``: an (Ma nd) x (Mb nd) window of a row-major buffer with an even leading dimension,
-        16-byte aligned; what lies beyond column Mb nd is not written.  Everything is checked before the launch."""
+        16-byte aligned; what lies beyond column Mb nd is not written.  Everything is checked before the launch.
+        ``sel_a`` / ``sel_b``: a ``GradientSelection`` of the points ``Ua`` / ``Ub``: the rows / columns of ``out`` are then its
+        selected entries (gpp_kernel_dxdx_sel)."""
         d0, nd = int(d0), int(nd)
         Ma, Mb = self._dx_checks("kernel_dxdx", "Ma, Mb", Ua, Ub, w, sf2, d0, nd, kind, d_split)
+        if sel_a is not None or sel_b is not None:
+            if sel_a is not None:
+                sel_a._check("kernel_dxdx (rows)", Ma, nd, Ua.device)
+            if sel_b is not None:
+                sel_b._check("kernel_dxdx (columns)", Mb, nd, Ua.device)
+            qa, qb = (Ma * nd if sel_a is None else sel_a.q), (Mb * nd if sel_b is None else sel_b.q)
+            ld, D = self._dx_window("H", out, qa, qb), Ua.shape[1]
+            self._stream()
+            check(self.lib.gpp_kernel_dxdx_sel(self.h, Ua.data_ptr(), Ma, Ub.data_ptr(), Mb, D, w.data_ptr(), sf2.data_ptr(),
+                                               int(kind), int(d_split), d0, nd,
+                                               None if sel_a is None else sel_a.first.data_ptr(),
+                                               None if sel_a is None else sel_a.dir.data_ptr(), qa,
+                                               None if sel_b is None else sel_b.first.data_ptr(),
+                                               None if sel_b is None else sel_b.dir.data_ptr(), qb, out.data_ptr(), ld),
+                  "gpp_kernel_dxdx_sel")
+            return out
         ld, D = self._dx_window("H", out, Ma * nd, Mb * nd), Ua.shape[1]
         self._stream()
         check(self.lib.gpp_kernel_dxdx(self.h, Ua.data_ptr(), Ma, Ub.data_ptr(), Mb, D, w.data_ptr(), sf2.data_ptr(), int(kind),
@@ -1171,14 +1233,19 @@ class GppContext:
 
     # -- training on gradient observations ---------------------------------------------------------------------------------------
     @_on_own_device
-    def gek_grad_reduce(self, U, Ug, w, sf2, d0, nd, alpha, Kinv, dU, g_w, g_sf2, g_U=None, g_Ug=None, *, kind=KIND_RBF, d_split=0):
+    def gek_grad_reduce(self, U, Ug, w, sf2, d0, nd, alpha, Kinv, dU, g_w, g_sf2, g_U=None, g_Ug=None, *, kind=KIND_RBF, d_split=0,
+                        sel=None):
         """The gradient of the joint log-likelihood of [y; grad y] through the function / gradient and gradient / gradient blocks
         (gpp_gek_grad_reduce): ADDS to ``g_w`` (D), ``g_sf2`` (1) and ``g_U`` (N x dU), WRITES ``g_Ug`` (Mg x dU).  ``alpha``: the
         n = N + Mg nd solved residuals; ``Kinv``: n x n as the LAUUM leaves it (lower triangle), an even leading dimension, 16-byte
-        aligned.  ``dU`` <= d0, and <= d_split on the Matern kinds.  Everything is checked before the launch."""
+        aligned.  ``dU`` <= d0, and <= d_split on the Matern kinds.  Everything is checked before the launch.
+        ``sel``: a ``GradientSelection`` of the points ``Ug``: n = N + sel.q, row N + k the selected entry k
+        (gpp_gek_grad_reduce_sel)."""
         d0, nd, dU = int(d0), int(nd), int(dU)
         Mg, N = self._dx_checks("gek_grad_reduce", "Mg, N", Ug, U, w, sf2, d0, nd, kind, d_split)
-        D, n = U.shape[1], N + Mg * nd
+        if sel is not None:
+            sel._check("gek_grad_reduce", Mg, nd, Ug.device)
+        D, n = U.shape[1], N + (Mg * nd if sel is None else sel.q)
         if dU < 0 or dU > d0 or (kind != KIND_RBF and dU > int(d_split)):
             raise GppError(f"gek_grad_reduce: the {dU} feature columns with a gradient must lie in front of the differentiated ones "
                            f"(d0 = {d0}) and, on a Matern kind, inside the RBF factor (d_split = {d_split})")
@@ -1196,6 +1263,15 @@ class GppContext:
                 raise GppError(f"{name} must be a contiguous {shape} tensor (got {tuple(t.shape)})")
         self.ensure_workspace(OP_GEK_GRAD, N, Mg, D, dU)
         self._stream()
+        if sel is not None:
+            status = self.lib.gpp_gek_grad_reduce_sel(self.h, U.data_ptr(), N, Ug.data_ptr(), Mg, D, w.data_ptr(), sf2.data_ptr(),
+                                                      int(kind), int(d_split), d0, nd, sel.first.data_ptr(), sel.dir.data_ptr(), sel.q,
+                                                      alpha.data_ptr(), Kinv.data_ptr(), ld, dU, g_w.data_ptr(), g_sf2.data_ptr(),
+                                                      _ptr(g_U) if dU else None, _ptr(g_Ug) if dU else None)
+            if status == NO_WORKSPACE:
+                raise GppError("gpp_gek_grad_reduce_sel: the handle's scratch workspace is missing or too small")
+            check(status, "gpp_gek_grad_reduce_sel")
+            return
         status = self.lib.gpp_gek_grad_reduce(self.h, U.data_ptr(), N, Ug.data_ptr(), Mg, D, w.data_ptr(), sf2.data_ptr(), int(kind),
                                               int(d_split), d0, nd, alpha.data_ptr(), Kinv.data_ptr(), ld, dU, g_w.data_ptr(),
                                               g_sf2.data_ptr(), _ptr(g_U) if dU else None, _ptr(g_Ug) if dU else None)

@@ -24,6 +24,10 @@
 // a feature of the RBF factor, 1 on one of the Matern factor.  The product p_j p_l and the one fused multiply-add are the same
 // operations on the same numbers for the entries (a, j), (b, l) and (b, l), (a, j): with Ua = Ub the block is bitwise symmetric.
 // 16-byte stores along the contiguous (b, l) axis.  Bandwidth-bound: Ma nd Mb nd doubles written once.
+//
+// Partial gradients (gpp.h: the three _sel entry points): the same kernels with a second instantiation (SEL) in which a tile's points
+// own the compact rows / columns first[a0] .. first[a0 + na) - 1 of a selection and the map from compact index to (point, direction)
+// is staged in LDS once per tile; pairs, multipliers and every entry's arithmetic are those of the dense instantiation.
 #include "../../include/gpp.h"
 #include "gpp_internal.h"
 
@@ -46,14 +50,38 @@ struct DxArgs {
   double* Dk;
   int64_t ld;
   int M, N, D, kind, d_split, d0, nd, tiles_a;
+  const int* first;  // SEL: the selection of the Ua side (gpp.h), device pointers; unread otherwise
+  const int* dir;
 };
 
 // doubles of dynamic LDS: staged rows (odd stride D | 1), raw direction columns, 2 w and sqrt(w), the multiplier tiles
 inline size_t dx_lds_doubles(int D, int nd, int nf) {
   return (size_t)(DX_TA + DX_TN) * (D | 1) + (size_t)DX_TA * nd + (size_t)DX_TN * (nd | 1) + nd + D + (size_t)nf * DX_TN * DX_TAP;
 }
+// SEL: plus the tile's column map, one int per entry of its points
+inline size_t dx_sel_lds_doubles(int D, int nd, int nf) { return dx_lds_doubles(D, nd, nf) + (size_t)(DX_TA * nd + 1) / 2; }
 
-template <bool MAT>
+// An entry of a selection as the tiles stage it: the point within the tile and the direction (nd <= 64)
+__device__ __forceinline__ int dg_pack(int point, int dir) { return (point << 8) | dir; }
+
+// One tile's slice of a selection into LDS: map[c - first[p0]] = (point - p0, direction) of the compact row or column c, for the
+// np points from p0 on.  A NULL selection is the dense layout, point-major.  One thread per point: each slot has one writer.
+__device__ __forceinline__ void dg_stage_selection(const int* __restrict__ first, const int* __restrict__ dir, int p0, int np, int nd,
+                                                   int* map, int t, int threads) {
+  if (first) {
+    const int c0 = first[p0];
+    for (int r = t; r < np; r += threads) {
+      const int k1 = first[p0 + r + 1];
+      for (int k = first[p0 + r]; k < k1; ++k) map[k - c0] = dg_pack(r, dir[k]);
+    }
+  } else {
+    for (int i = t; i < np * nd; i += threads) map[i] = dg_pack(i / nd, i % nd);
+  }
+}
+
+// SEL: the tile's points own the compact columns [first[a0], first[a0 + na)) and entry k of point a is the direction
+// dir[first[a] + k] (gpp_cross_kernel_dx_sel); the dense instantiation is the code it was.
+template <bool MAT, bool SEL>
 __global__ __launch_bounds__(DX_THREADS) void gpp_cross_dx_f64(DxArgs p) {
   extern __shared__ __attribute__((aligned(16))) double dx_lds[];
   constexpr int NF = MAT ? 2 : 1;
@@ -70,6 +98,14 @@ __global__ __launch_bounds__(DX_THREADS) void gpp_cross_dx_f64(DxArgs p) {
   const int a0 = ta * DX_TA, n0 = tn * DX_TN;
   const int na = min(DX_TA, p.M - a0), nn = min(DX_TN, p.N - n0);
   const int ds = (!MAT || p.kind == 0) ? D : p.d_split;  // dims below ds belong to the RBF factor
+  int cb = 0, ce = 0;  // SEL: the tile's compact columns [cb, ce)
+  int* cmap = reinterpret_cast<int*>(sM + NF * DX_TN * DX_TAP);  // SEL: [ce - cb] (point, direction) of each
+  if constexpr (SEL) {
+    cb = p.first[a0];
+    ce = p.first[a0 + na];
+    if (cb == ce) return;  // (the whole work-group: a tile of points without an entry owns no column)
+    dg_stage_selection(p.first, p.dir, a0, na, nd, cmap, t, DX_THREADS);
+  }
 
   for (int d = t; d < D; d += DX_THREADS) sw[d] = sqrt(p.w[d]);
   for (int j = t; j < nd; j += DX_THREADS) w2[j] = 2.0 * p.w[p.d0 + j];
@@ -129,6 +165,35 @@ __global__ __launch_bounds__(DX_THREADS) void gpp_cross_dx_f64(DxArgs p) {
   }
   __syncthreads();
 
+  if constexpr (SEL) {
+    // the tile's nn rows of its columns [cb, ce), paired on the ABSOLUTE column: a lane takes the even column c0 and c0 + 1, so a
+    // 16-byte store is aligned whatever the parity of cb; an odd head (c0 = cb - 1) and an odd tail (c0 + 1 = ce) store one double
+    // and leave the neighbouring tile's column alone
+    const int cs = cb & ~1, hp2 = (ce - cs + 1) >> 1;
+    int ct = 1;
+    while (ct < hp2 && ct < DX_THREADS) ct <<= 1;
+    const int rt = DX_THREADS / ct;
+    double* out = p.Dk + (int64_t)n0 * p.ld;
+    for (int pc = t % ct; pc < hp2; pc += ct) {
+      const int c0 = cs + 2 * pc;
+      const bool h0 = c0 >= cb, h1 = c0 + 1 < ce;  // (never both false: cb < ce)
+      const int e0 = cmap[(h0 ? c0 : c0 + 1) - cb], e1 = cmap[(h1 ? c0 + 1 : c0) - cb];
+      const int al0 = e0 >> 8, j0 = e0 & 255, al1 = e1 >> 8, j1 = e1 & 255;
+      const int f0 = (NF == 2 && p.d0 + j0 >= ds) ? DX_TN * DX_TAP : 0;
+      const int f1 = (NF == 2 && p.d0 + j1 >= ds) ? DX_TN * DX_TAP : 0;
+      const double x0 = rA[al0 * nd + j0], x1 = rA[al1 * nd + j1];
+      const double g0 = w2[j0], g1 = w2[j1];
+      for (int row = t / ct; row < nn; row += rt) {
+        const double v0 = (g0 * (x0 - rB[row * ndp + j0])) * sM[f0 + row * DX_TAP + al0];
+        const double v1 = (g1 * (x1 - rB[row * ndp + j1])) * sM[f1 + row * DX_TAP + al1];
+        double* dst = out + (int64_t)row * p.ld + c0;
+        if (h0 && h1) *reinterpret_cast<double2*>(dst) = make_double2(v0, v1);
+        else if (h0) dst[0] = v0;
+        else dst[1] = v1;
+      }
+    }
+    return;
+  }
   // the tile's nn rows of cw = na nd contiguous columns, two columns per lane: consecutive lanes write consecutive 16 bytes
   const int cw = na * nd, hp2 = (cw + 1) >> 1;
   int ct = 1;
@@ -252,13 +317,14 @@ size_t gpp_point_gram_ws_bytes(int64_t M, int nd) {
   return (size_t)((M + (M + PG_GROUP - 1) / PG_GROUP) * nd * nd) * sizeof(double);
 }
 
-extern "C" int gpp_cross_kernel_dx(gpp_handle_t h, const double* Ua, int64_t M, const double* Ub, int64_t N, int D, const double* w,
-                                   const double* sf2, int kind, int d_split, int d0, int nd, double* Dk, int64_t ld) {
+// the checks the derivative-block entry points share; 0 or the argument code
+static int dg_check_pair(gpp_handle_t h, const double* Ua, int64_t Ma, const double* Ub, int64_t Mb, int D, const double* w,
+                         const double* sf2, int kind, int d_split, int d0, int nd) {
   if (!h) return -1;
   if (!Ua) return -2;
-  if (M < 1 || M > 0x7ffffff0) return -3;
+  if (Ma < 1 || Ma > 0x7ffffff0) return -3;
   if (!Ub) return -4;
-  if (N < 1 || N > 0x7ffffff0) return -5;
+  if (Mb < 1 || Mb > 0x7ffffff0) return -5;
   if (D < 1 || D > 64) return -6;
   if (!w) return -7;
   if (!sf2) return -8;
@@ -266,18 +332,55 @@ extern "C" int gpp_cross_kernel_dx(gpp_handle_t h, const double* Ua, int64_t M, 
   if (d_split < 0 || d_split > D) return -10;
   if (d0 < 0 || d0 >= D) return -11;
   if (nd < 1 || d0 + nd > D) return -12;
+  return 0;
+}
+
+// a selection's pair of pointers and its count q for M points: 0, or 1 for a mismatched pair, 2 for q out of range
+static int dg_check_selection(const int* first, const int* dir, int64_t q, int64_t M, int nd) {
+  if ((first == nullptr) != (dir == nullptr)) return 1;
+  if (first ? (q < 1 || q > M * nd) : q != M * nd) return 2;
+  return 0;
+}
+
+// gpp_cross_kernel_dx (first == NULL, cols = M nd) and gpp_cross_kernel_dx_sel; `shift`: how far the latter's three extra arguments
+// move the codes of Dk and ld
+static int dx_run(gpp_handle_t h, const double* Ua, int64_t M, const double* Ub, int64_t N, int D, const double* w, const double* sf2,
+                  int kind, int d_split, int d0, int nd, const int* first, const int* dir, int64_t cols, double* Dk, int64_t ld,
+                  int shift) {
+  if (int rc = dg_check_pair(h, Ua, M, Ub, N, D, w, sf2, kind, d_split, d0, nd)) return rc;
   if (M * nd > 0x7ffffff0) return -3;
-  if (!Dk || !dg_aligned16(Dk)) return -13;
-  if ((ld & 1) || ld < M * nd) return -14;
+  if (!Dk || !dg_aligned16(Dk)) return -13 - shift;
+  if ((ld & 1) || ld < cols) return -14 - shift;
   const int64_t tiles_a = (M + DX_TA - 1) / DX_TA, tiles_n = (N + DX_TN - 1) / DX_TN;
   if (tiles_a * tiles_n >= ((int64_t)1 << 31)) return -3;
-  DxArgs p{Ua, Ub, w, sf2, Dk, ld, (int)M, (int)N, D, kind, d_split, d0, nd, (int)tiles_a};
+  DxArgs p{Ua, Ub, w, sf2, Dk, ld, (int)M, (int)N, D, kind, d_split, d0, nd, (int)tiles_a, first, dir};
   const dim3 grid((unsigned)(tiles_a * tiles_n)), block(DX_THREADS);
-  if (kind == GPP_KIND_RBF)
-    hipLaunchKernelGGL(gpp_cross_dx_f64<false>, grid, block, dx_lds_doubles(D, nd, 1) * sizeof(double), h->stream, p);
-  else
-    hipLaunchKernelGGL(gpp_cross_dx_f64<true>, grid, block, dx_lds_doubles(D, nd, 2) * sizeof(double), h->stream, p);
+  const bool mat = kind != GPP_KIND_RBF;
+  const int nf = mat ? 2 : 1;
+  if (!first) {
+    const size_t lds = dx_lds_doubles(D, nd, nf) * sizeof(double);
+    if (!mat) hipLaunchKernelGGL((gpp_cross_dx_f64<false, false>), grid, block, lds, h->stream, p);
+    else hipLaunchKernelGGL((gpp_cross_dx_f64<true, false>), grid, block, lds, h->stream, p);
+  } else {
+    const size_t lds = dx_sel_lds_doubles(D, nd, nf) * sizeof(double);
+    if (!mat) hipLaunchKernelGGL((gpp_cross_dx_f64<false, true>), grid, block, lds, h->stream, p);
+    else hipLaunchKernelGGL((gpp_cross_dx_f64<true, true>), grid, block, lds, h->stream, p);
+  }
   return dg_rc(hipGetLastError());
+}
+
+extern "C" int gpp_cross_kernel_dx(gpp_handle_t h, const double* Ua, int64_t M, const double* Ub, int64_t N, int D, const double* w,
+                                   const double* sf2, int kind, int d_split, int d0, int nd, double* Dk, int64_t ld) {
+  return dx_run(h, Ua, M, Ub, N, D, w, sf2, kind, d_split, d0, nd, nullptr, nullptr, M * nd, Dk, ld, 0);
+}
+
+extern "C" int gpp_cross_kernel_dx_sel(gpp_handle_t h, const double* Ua, int64_t M, const double* Ub, int64_t N, int D, const double* w,
+                                       const double* sf2, int kind, int d_split, int d0, int nd, const int* first_a, const int* dir_a,
+                                       int64_t qa, double* Dk, int64_t ld) {
+  if (int rc = dg_check_pair(h, Ua, M, Ub, N, D, w, sf2, kind, d_split, d0, nd)) return rc;
+  if (M * nd > 0x7ffffff0) return -3;
+  if (int rc = dg_check_selection(first_a, dir_a, qa, M, nd)) return rc == 1 ? -14 : -15;
+  return dx_run(h, Ua, M, Ub, N, D, w, sf2, kind, d_split, d0, nd, first_a, dir_a, qa, Dk, ld, 3);
 }
 
 extern "C" int gpp_point_gram(gpp_handle_t h, const double* Q, int64_t ldq, int64_t M, int nd, int64_t N, const double* omega, double* G,
@@ -328,6 +431,10 @@ struct HxArgs {
   double* H;
   int64_t ld;
   int Ma, Mb, D, kind, d_split, d0, nd, tiles_b;
+  const int* first_a;  // SEL: the selections of the two sides (gpp.h), device pointers, a NULL pair for a dense side
+  const int* dir_a;
+  const int* first_b;
+  const int* dir_b;
 };
 
 // doubles of dynamic LDS: staged rows (odd stride D | 1), raw direction columns of both sides, 2 w and sqrt(w), the multiplier tiles
@@ -340,7 +447,12 @@ __device__ __forceinline__ double hx_entry(double pj, double pl, double mF, bool
   return fma(pj * pl, mF, diag ? -(gj * mf) : 0.0);
 }
 
-template <bool MAT>
+// SEL: plus the tile's row and column maps, one int per entry of its points
+inline size_t hx_sel_lds_doubles(int D, int nd, int nf) { return hx_lds_doubles(D, nd, nf) + (size_t)(HX_TA + HX_TB) * nd / 2; }
+
+// SEL: rows and columns through the selections of gpp_kernel_dxdx_sel, either side dense where its pair is NULL; the dense
+// instantiation is the code it was.
+template <bool MAT, bool SEL>
 __global__ __launch_bounds__(HX_THREADS) void gpp_kernel_dxdx_f64(HxArgs p) {
   extern __shared__ __attribute__((aligned(16))) double hx_lds[];
   constexpr int NF = MAT ? 3 : 1;
@@ -358,6 +470,18 @@ __global__ __launch_bounds__(HX_THREADS) void gpp_kernel_dxdx_f64(HxArgs p) {
   const int a0 = ta * HX_TA, b0 = tb * HX_TB;
   const int na = min(HX_TA, p.Ma - a0), nb = min(HX_TB, p.Mb - b0);
   const int ds = (!MAT || p.kind == 0) ? D : p.d_split;  // dims below ds belong to the RBF factor
+  int rb = 0, re = 0, cb = 0, ce = 0;  // SEL: the tile's compact rows [rb, re) and columns [cb, ce)
+  int* rmap = reinterpret_cast<int*>(sM + NF * MT);  // SEL: [re - rb] (point, direction) of each row
+  int* cmap = rmap + HX_TA * nd;                     // SEL: [ce - cb] the same of each column
+  if constexpr (SEL) {
+    rb = p.first_a ? p.first_a[a0] : a0 * nd;
+    re = p.first_a ? p.first_a[a0 + na] : (a0 + na) * nd;
+    cb = p.first_b ? p.first_b[b0] : b0 * nd;
+    ce = p.first_b ? p.first_b[b0 + nb] : (b0 + nb) * nd;
+    if (rb == re || cb == ce) return;  // (the whole work-group: a tile of points without an entry owns no row or no column)
+    dg_stage_selection(p.first_a, p.dir_a, a0, na, nd, rmap, t, HX_THREADS);
+    dg_stage_selection(p.first_b, p.dir_b, b0, nb, nd, cmap, t, HX_THREADS);
+  }
 
   for (int d = t; d < D; d += HX_THREADS) sw[d] = sqrt(p.w[d]);
   for (int j = t; j < nd; j += HX_THREADS) w2[j] = 2.0 * p.w[p.d0 + j];
@@ -407,6 +531,40 @@ __global__ __launch_bounds__(HX_THREADS) void gpp_kernel_dxdx_f64(HxArgs p) {
   }
   __syncthreads();
 
+  if constexpr (SEL) {
+    // the tile's rows [rb, re) of its columns [cb, ce), paired on the ABSOLUTE column as in gpp_cross_dx_f64: an aligned 16-byte
+    // store on an even column, one double at an odd head or tail
+    const int rows = re - rb, cs = cb & ~1, hp2 = (ce - cs + 1) >> 1;
+    int ct = 1;
+    while (ct < hp2 && ct < HX_THREADS) ct <<= 1;
+    const int rt = HX_THREADS / ct;
+    double* out = p.H + (int64_t)rb * p.ld;
+    for (int pc = t % ct; pc < hp2; pc += ct) {
+      const int c0 = cs + 2 * pc;
+      const bool h0 = c0 >= cb, h1 = c0 + 1 < ce;  // (never both false: cb < ce)
+      const int e0 = cmap[(h0 ? c0 : c0 + 1) - cb], e1 = cmap[(h1 ? c0 + 1 : c0) - cb];
+      const int bl0 = e0 >> 8, l0 = e0 & 255, bl1 = e1 >> 8, l1 = e1 & 255;
+      const int f0 = (NF == 3 && p.d0 + l0 >= ds) ? 1 : 0;
+      const int f1 = (NF == 3 && p.d0 + l1 >= ds) ? 1 : 0;
+      const double y0 = rB[bl0 * ndp + l0], y1 = rB[bl1 * ndp + l1];
+      const double g0 = w2[l0], g1 = w2[l1];
+      for (int row = t / ct; row < rows; row += rt) {
+        const int er = rmap[row], al = er >> 8, j = er & 255;
+        const int fj = (NF == 3 && p.d0 + j >= ds) ? 1 : 0;
+        const double* xa = rA + al * ndp;
+        const double gj = w2[j], xj = xa[j];
+        const double* m0 = sM + al * HX_TBP + bl0;
+        const double* m1 = sM + al * HX_TBP + bl1;
+        const double v0 = hx_entry(gj * (xj - rB[bl0 * ndp + j]), g0 * (xa[l0] - y0), m0[(fj + f0) * MT], j == l0, gj, m0[fj * MT]);
+        const double v1 = hx_entry(gj * (xj - rB[bl1 * ndp + j]), g1 * (xa[l1] - y1), m1[(fj + f1) * MT], j == l1, gj, m1[fj * MT]);
+        double* dst = out + (int64_t)row * p.ld + c0;
+        if (h0 && h1) *reinterpret_cast<double2*>(dst) = make_double2(v0, v1);
+        else if (h0) dst[0] = v0;
+        else dst[1] = v1;
+      }
+    }
+    return;
+  }
   // the tile's na nd rows of cw = nb nd contiguous columns, two columns per lane: consecutive lanes write consecutive 16 bytes
   const int rows = na * nd, cw = nb * nd, hp2 = (cw + 1) >> 1;
   int ct = 1;
@@ -445,33 +603,48 @@ __global__ __launch_bounds__(HX_THREADS) void gpp_kernel_dxdx_f64(HxArgs p) {
 
 }  // namespace
 
-extern "C" int gpp_kernel_dxdx(gpp_handle_t h, const double* Ua, int64_t Ma, const double* Ub, int64_t Mb, int D, const double* w,
-                               const double* sf2, int kind, int d_split, int d0, int nd, double* H, int64_t ld) {
-  if (!h) return -1;
-  if (!Ua) return -2;
-  if (Ma < 1 || Ma > 0x7ffffff0) return -3;
-  if (!Ub) return -4;
-  if (Mb < 1 || Mb > 0x7ffffff0) return -5;
-  if (D < 1 || D > 64) return -6;
-  if (!w) return -7;
-  if (!sf2) return -8;
-  if (kind < 0 || kind > 2) return -9;
-  if (d_split < 0 || d_split > D) return -10;
-  if (d0 < 0 || d0 >= D) return -11;
-  if (nd < 1 || d0 + nd > D) return -12;
+// gpp_kernel_dxdx (both pairs NULL, cols = Mb nd) and gpp_kernel_dxdx_sel; `shift`: how far the latter's six extra arguments move the
+// codes of H and ld
+static int hx_run(gpp_handle_t h, const double* Ua, int64_t Ma, const double* Ub, int64_t Mb, int D, const double* w, const double* sf2,
+                  int kind, int d_split, int d0, int nd, const int* first_a, const int* dir_a, const int* first_b, const int* dir_b,
+                  int64_t cols, double* H, int64_t ld, int shift) {
+  if (int rc = dg_check_pair(h, Ua, Ma, Ub, Mb, D, w, sf2, kind, d_split, d0, nd)) return rc;
   if (Ma * nd > 0x7ffffff0) return -3;
   if (Mb * nd > 0x7ffffff0) return -5;
-  if (!H || !dg_aligned16(H)) return -13;
-  if ((ld & 1) || ld < Mb * nd) return -14;
+  if (!H || !dg_aligned16(H)) return -13 - shift;
+  if ((ld & 1) || ld < cols) return -14 - shift;
   const int64_t tiles_a = (Ma + HX_TA - 1) / HX_TA, tiles_b = (Mb + HX_TB - 1) / HX_TB;
   if (tiles_a * tiles_b >= ((int64_t)1 << 31)) return -3;
-  HxArgs p{Ua, Ub, w, sf2, H, ld, (int)Ma, (int)Mb, D, kind, d_split, d0, nd, (int)tiles_b};
+  HxArgs p{Ua, Ub, w, sf2, H, ld, (int)Ma, (int)Mb, D, kind, d_split, d0, nd, (int)tiles_b, first_a, dir_a, first_b, dir_b};
   const dim3 grid((unsigned)(tiles_a * tiles_b)), block(HX_THREADS);
-  if (kind == GPP_KIND_RBF)
-    hipLaunchKernelGGL(gpp_kernel_dxdx_f64<false>, grid, block, hx_lds_doubles(D, nd, 1) * sizeof(double), h->stream, p);
-  else
-    hipLaunchKernelGGL(gpp_kernel_dxdx_f64<true>, grid, block, hx_lds_doubles(D, nd, 3) * sizeof(double), h->stream, p);
+  const bool mat = kind != GPP_KIND_RBF;
+  const int nf = mat ? 3 : 1;
+  if (!first_a && !first_b) {
+    const size_t lds = hx_lds_doubles(D, nd, nf) * sizeof(double);
+    if (!mat) hipLaunchKernelGGL((gpp_kernel_dxdx_f64<false, false>), grid, block, lds, h->stream, p);
+    else hipLaunchKernelGGL((gpp_kernel_dxdx_f64<true, false>), grid, block, lds, h->stream, p);
+  } else {
+    const size_t lds = hx_sel_lds_doubles(D, nd, nf) * sizeof(double);
+    if (!mat) hipLaunchKernelGGL((gpp_kernel_dxdx_f64<false, true>), grid, block, lds, h->stream, p);
+    else hipLaunchKernelGGL((gpp_kernel_dxdx_f64<true, true>), grid, block, lds, h->stream, p);
+  }
   return dg_rc(hipGetLastError());
+}
+
+extern "C" int gpp_kernel_dxdx(gpp_handle_t h, const double* Ua, int64_t Ma, const double* Ub, int64_t Mb, int D, const double* w,
+                               const double* sf2, int kind, int d_split, int d0, int nd, double* H, int64_t ld) {
+  return hx_run(h, Ua, Ma, Ub, Mb, D, w, sf2, kind, d_split, d0, nd, nullptr, nullptr, nullptr, nullptr, Mb * nd, H, ld, 0);
+}
+
+extern "C" int gpp_kernel_dxdx_sel(gpp_handle_t h, const double* Ua, int64_t Ma, const double* Ub, int64_t Mb, int D, const double* w,
+                                   const double* sf2, int kind, int d_split, int d0, int nd, const int* first_a, const int* dir_a,
+                                   int64_t qa, const int* first_b, const int* dir_b, int64_t qb, double* H, int64_t ld) {
+  if (int rc = dg_check_pair(h, Ua, Ma, Ub, Mb, D, w, sf2, kind, d_split, d0, nd)) return rc;
+  if (Ma * nd > 0x7ffffff0) return -3;
+  if (Mb * nd > 0x7ffffff0) return -5;
+  if (int rc = dg_check_selection(first_a, dir_a, qa, Ma, nd)) return rc == 1 ? -14 : -15;
+  if (int rc = dg_check_selection(first_b, dir_b, qb, Mb, nd)) return rc == 1 ? -17 : -18;
+  return hx_run(h, Ua, Ma, Ub, Mb, D, w, sf2, kind, d_split, d0, nd, first_a, dir_a, first_b, dir_b, qb, H, ld, 6);
 }
 
 // ---- gpp_gek_grad_reduce ------------------------------------------------------------------------------------------------------------
@@ -522,6 +695,8 @@ struct GkArgs {
   double* partA;  // [tiles_i][Mg][dU]   g_Ug rows from the Kfg tiles, slot = the tile of function points
   double* partI;  // [tiles_a][N][dU]    g_U rows from the Kfg tiles, slot = the tile of gradient points
   double* partG;  // [tiles_a][Mg][dU]   g_Ug rows from the Kgg tiles, slot = the other tile of the pair
+  const int* first;  // SEL: the selection of the gradient points (gpp.h), device pointers; unread otherwise
+  const int* dir;
 };
 
 __device__ __forceinline__ double gk_wave_sum(double v) {
@@ -543,8 +718,16 @@ inline size_t gk_lds_doubles(int D, int nm) {
   return (size_t)2 * GK_T * (D | 1) + D + (size_t)(nm + 1) * GK_MT + (size_t)4 * (D + 1);
 }
 
+// SEL: plus, for the 2 GK_T points of a tile, the compact index of each of their nd directions
+inline size_t gk_sel_lds_doubles(int D, int nm, int nd) { return gk_lds_doubles(D, nm) + (size_t)GK_T * nd; }
+
 // CH: columns of a Kgg pair's block taken per pass (their column sums stay in registers)
-template <bool MAT, int CH>
+// SEL (gpp_gek_grad_reduce_sel): the rows of a point's observed directions are first[a] .. first[a + 1] - 1 of the gradient block.
+// The loops still walk the nd directions, in order and uniformly over a wave (every direction's term is summed over the wave and
+// lands in its own g_w slot), and a lane skips the directions its point lacks: cix[point][j] is the compact index of direction j
+// or -1, staged once per tile.  What is read of alpha and Kinv, and the sums P_k, Q_m, D_k, run over the observed directions alone,
+// in the order of k; with every direction observed the operations are those of the dense instantiation, which is the code it was.
+template <bool MAT, int CH, bool SEL>
 __global__ __launch_bounds__(GK_THREADS) void gpp_gek_grad_tiles(GkArgs p) {
   extern __shared__ __attribute__((aligned(16))) double gk_lds[];
   constexpr int NM = MAT ? 5 : 1;
@@ -555,6 +738,7 @@ __global__ __launch_bounds__(GK_THREADS) void gpp_gek_grad_tiles(GkArgs p) {
   double* sM = sw + D;              // [NM][GK_T][GK_TP]: A_0 (, A_1, A_2, r, e^-q1 e^-r)
   double* sG = sM + NM * GK_MT;     // [GK_T][GK_TP] sf2 s0 of every pair
   double* wred = sG + GK_MT;        // [4][nrec] the waves' sums
+  int* cix = reinterpret_cast<int*>(wred + 4 * nrec);  // SEL: [2 GK_T][nd], side a then side b
   const int t = (int)threadIdx.x, wave = t >> 6, lane = t & 63;
   const int al = t >> 4, bl = t & 15;
   const int64_t blk = blockIdx.x;
@@ -583,6 +767,24 @@ __global__ __launch_bounds__(GK_THREADS) void gpp_gek_grad_tiles(GkArgs p) {
     } else {
       const int rb = r - GK_T;
       rB[rb * Dp + d] = rb < nb ? Ub[(b0 + rb) * D + d] : 0.0;
+    }
+  }
+  if constexpr (SEL) {
+    // one thread per point (the b side only in a Kgg tile): dir is increasing within a point, so one pass fills its nd slots
+    if (t < (gg ? 2 * GK_T : GK_T)) {
+      const int r = t & (GK_T - 1);
+      const bool side_b = t >= GK_T;
+      const int64_t pt = (side_b ? b0 : a0) + r;
+      int k = 0, k1 = 0;
+      if (r < (side_b ? nb : na)) {
+        k = p.first[pt];
+        k1 = p.first[pt + 1];
+      }
+      for (int j = 0; j < nd; ++j) {
+        const bool has = k < k1 && p.dir[k] == j;
+        cix[t * nd + j] = has ? k : -1;
+        if (has) ++k;
+      }
     }
   }
   __syncthreads();
@@ -625,14 +827,17 @@ __global__ __launch_bounds__(GK_THREADS) void gpp_gek_grad_tiles(GkArgs p) {
   const double* da = xa + d0;
   const double* db = xb + d0;
   const double* wd = sw + d0;
+  const int* ca = cix + al * nd;            // SEL: compact indices of the directions of point a,
+  const int* cb = cix + (GK_T + bl) * nd;   //      and in a Kgg tile of point b
   double s0 = 0.0, r1 = 0.0;  // per unit sf2
   if (!gg) {
     double P0 = 0.0, P1 = 0.0;
     const double ab = valid ? alpha[b] : 0.0;
     for (int j = 0; j < nd; ++j) {
       double dir = 0.0;
-      if (valid) {
-        const int64_t r = p.N + a * nd + j;
+      const int ka = SEL ? ca[j] : 0;
+      if (valid && (!SEL || ka >= 0)) {
+        const int64_t r = SEL ? p.N + ka : p.N + a * nd + j;
         const double W = alpha[r] * ab - Kinv[r * p.ldk + b];  // both triangles: 2 x 1/2
         const double dj = da[j] - db[j];
         const double pj = (2.0 * wd[j]) * dj;
@@ -656,8 +861,9 @@ __global__ __launch_bounds__(GK_THREADS) void gpp_gek_grad_tiles(GkArgs p) {
       for (int ll = 0; ll < CH; ++ll) cF[ll] = 0.0;
       for (int j = 0; j < nd; ++j) {
         double dir = 0.0;
-        if (valid) {
-          const int64_t r = p.N + a * nd + j;
+        const int ka = SEL ? ca[j] : 0;
+        if (valid && (!SEL || ka >= 0)) {
+          const int64_t r = SEL ? p.N + ka : p.N + a * nd + j;
           const double ar = alpha[r];
           const double dj = da[j] - db[j];
           const double wj2 = 2.0 * wd[j];
@@ -667,8 +873,9 @@ __global__ __launch_bounds__(GK_THREADS) void gpp_gek_grad_tiles(GkArgs p) {
 #pragma unroll
           for (int ll = 0; ll < CH; ++ll) {
             const int l = l0 + ll;
-            if (l < nd) {
-              const int64_t c = p.N + b * nd + l;
+            const int kb = (SEL && l < nd) ? cb[l] : 0;
+            if (l < nd && (!SEL || kb >= 0)) {
+              const int64_t c = SEL ? p.N + kb : p.N + b * nd + l;
               const bool flip = self && c > r;  // a point with itself: the block straddles the diagonal
               const double W = hm * (ar * alpha[c] - Kinv[(flip ? c : r) * p.ldk + (flip ? r : c)]);
               const double pl = (2.0 * wd[l]) * (da[l] - db[l]);
@@ -791,10 +998,17 @@ inline int64_t gk_tiles(int64_t n) { return (n + GK_T - 1) / GK_T; }
 template <bool MAT>
 void gk_launch(hipStream_t s, const GkArgs& p, int64_t ntiles) {
   const dim3 grid((unsigned)ntiles), block(GK_THREADS);
-  const size_t lds = gk_lds_doubles(p.D, MAT ? 5 : 1) * sizeof(double);
-  if (p.nd <= 4) hipLaunchKernelGGL((gpp_gek_grad_tiles<MAT, 4>), grid, block, lds, s, p);
-  else if (p.nd <= 8) hipLaunchKernelGGL((gpp_gek_grad_tiles<MAT, 8>), grid, block, lds, s, p);
-  else hipLaunchKernelGGL((gpp_gek_grad_tiles<MAT, 16>), grid, block, lds, s, p);
+  if (!p.first) {
+    const size_t lds = gk_lds_doubles(p.D, MAT ? 5 : 1) * sizeof(double);
+    if (p.nd <= 4) hipLaunchKernelGGL((gpp_gek_grad_tiles<MAT, 4, false>), grid, block, lds, s, p);
+    else if (p.nd <= 8) hipLaunchKernelGGL((gpp_gek_grad_tiles<MAT, 8, false>), grid, block, lds, s, p);
+    else hipLaunchKernelGGL((gpp_gek_grad_tiles<MAT, 16, false>), grid, block, lds, s, p);
+  } else {
+    const size_t lds = gk_sel_lds_doubles(p.D, MAT ? 5 : 1, p.nd) * sizeof(double);
+    if (p.nd <= 4) hipLaunchKernelGGL((gpp_gek_grad_tiles<MAT, 4, true>), grid, block, lds, s, p);
+    else if (p.nd <= 8) hipLaunchKernelGGL((gpp_gek_grad_tiles<MAT, 8, true>), grid, block, lds, s, p);
+    else hipLaunchKernelGGL((gpp_gek_grad_tiles<MAT, 16, true>), grid, block, lds, s, p);
+  }
 }
 
 }  // namespace
@@ -806,31 +1020,22 @@ size_t gpp_gek_grad_ws_bytes(int64_t N, int64_t Mg, int D, int dU) {
   return (size_t)(ntiles * (D + 1) + (int64_t)dU * (ti * Mg + ta * N + ta * Mg)) * sizeof(double);
 }
 
-extern "C" int gpp_gek_grad_reduce(gpp_handle_t h, const double* U, int64_t N, const double* Ug, int64_t Mg, int D, const double* w,
-                                   const double* sf2, int kind, int d_split, int d0, int nd, const double* alpha, const double* Kinv,
-                                   int64_t ldk, int dU, double* g_w, double* g_sf2, double* g_U, double* g_Ug) {
-  if (!h) return -1;
-  if (!U) return -2;
-  if (N < 1 || N > 0x7ffffff0) return -3;
-  if (!Ug) return -4;
-  if (Mg < 1 || Mg > 0x7ffffff0) return -5;
-  if (D < 1 || D > 64) return -6;
-  if (!w) return -7;
-  if (!sf2) return -8;
-  if (kind < 0 || kind > 2) return -9;
-  if (d_split < 0 || d_split > D) return -10;
-  if (d0 < 0 || d0 >= D) return -11;
-  if (nd < 1 || d0 + nd > D) return -12;
+// gpp_gek_grad_reduce (first == NULL, q = Mg nd) and gpp_gek_grad_reduce_sel; `shift`: how far the latter's three extra arguments move
+// the codes from alpha on
+static int gk_run(gpp_handle_t h, const double* U, int64_t N, const double* Ug, int64_t Mg, int D, const double* w, const double* sf2,
+                  int kind, int d_split, int d0, int nd, const int* first, const int* dir, int64_t q, const double* alpha,
+                  const double* Kinv, int64_t ldk, int dU, double* g_w, double* g_sf2, double* g_U, double* g_Ug, int shift) {
+  if (int rc = dg_check_pair(h, U, N, Ug, Mg, D, w, sf2, kind, d_split, d0, nd)) return rc;
   if (Mg * nd > 0x7ffffff0) return -5;
-  if (!alpha) return -13;
-  if (!Kinv || !dg_aligned16(Kinv)) return -14;
-  if ((ldk & 1) || ldk < N + Mg * nd) return -15;
+  if (!alpha) return -13 - shift;
+  if (!Kinv || !dg_aligned16(Kinv)) return -14 - shift;
+  if ((ldk & 1) || ldk < N + q) return -15 - shift;
   // a feature with a gradient is none of the differentiated ones and, on a Matern kind, belongs to the RBF factor
-  if (dU < 0 || dU > d0 || (kind != GPP_KIND_RBF && dU > d_split)) return -16;
-  if (!g_w) return -17;
-  if (!g_sf2) return -18;
-  if (dU > 0 && !g_U) return -19;
-  if (dU > 0 && !g_Ug) return -20;
+  if (dU < 0 || dU > d0 || (kind != GPP_KIND_RBF && dU > d_split)) return -16 - shift;
+  if (!g_w) return -17 - shift;
+  if (!g_sf2) return -18 - shift;
+  if (dU > 0 && !g_U) return -19 - shift;
+  if (dU > 0 && !g_Ug) return -20 - shift;
   const int64_t ta = gk_tiles(Mg), ti = gk_tiles(N);
   const int64_t n_fg = ta * ti, ntiles = n_fg + ta * (ta + 1) / 2;
   if (ntiles >= ((int64_t)1 << 31)) return -3;
@@ -839,7 +1044,7 @@ extern "C" int gpp_gek_grad_reduce(gpp_handle_t h, const double* U, int64_t N, c
   double* partA = rec + ntiles * (D + 1);
   double* partI = partA + (int64_t)dU * ti * Mg;
   double* partG = partI + (int64_t)dU * ta * N;
-  GkArgs p{U, Ug, w, sf2, alpha, Kinv, ldk, N, Mg, ta, n_fg, D, kind, d_split, d0, nd, dU, rec, partA, partI, partG};
+  GkArgs p{U, Ug, w, sf2, alpha, Kinv, ldk, N, Mg, ta, n_fg, D, kind, d_split, d0, nd, dU, rec, partA, partI, partG, first, dir};
   if (kind == GPP_KIND_RBF) gk_launch<false>(h->stream, p, ntiles);
   else gk_launch<true>(h->stream, p, ntiles);
   if (hipError_t r = hipGetLastError(); r != hipSuccess) return dg_rc(r);
@@ -850,4 +1055,21 @@ extern "C" int gpp_gek_grad_reduce(gpp_handle_t h, const double* U, int64_t N, c
                        dU, g_U, g_Ug);
   }
   return dg_rc(hipGetLastError());
+}
+
+extern "C" int gpp_gek_grad_reduce(gpp_handle_t h, const double* U, int64_t N, const double* Ug, int64_t Mg, int D, const double* w,
+                                   const double* sf2, int kind, int d_split, int d0, int nd, const double* alpha, const double* Kinv,
+                                   int64_t ldk, int dU, double* g_w, double* g_sf2, double* g_U, double* g_Ug) {
+  return gk_run(h, U, N, Ug, Mg, D, w, sf2, kind, d_split, d0, nd, nullptr, nullptr, Mg * nd, alpha, Kinv, ldk, dU, g_w, g_sf2, g_U,
+                g_Ug, 0);
+}
+
+extern "C" int gpp_gek_grad_reduce_sel(gpp_handle_t h, const double* U, int64_t N, const double* Ug, int64_t Mg, int D, const double* w,
+                                       const double* sf2, int kind, int d_split, int d0, int nd, const int* first, const int* dir,
+                                       int64_t q, const double* alpha, const double* Kinv, int64_t ldk, int dU, double* g_w,
+                                       double* g_sf2, double* g_U, double* g_Ug) {
+  if (int rc = dg_check_pair(h, U, N, Ug, Mg, D, w, sf2, kind, d_split, d0, nd)) return rc;
+  if (Mg * nd > 0x7ffffff0) return -5;
+  if (int rc = dg_check_selection(first, dir, q, Mg, nd)) return rc == 1 ? -14 : -15;
+  return gk_run(h, U, N, Ug, Mg, D, w, sf2, kind, d_split, d0, nd, first, dir, q, alpha, Kinv, ldk, dU, g_w, g_sf2, g_U, g_Ug, 3);
 }

@@ -208,7 +208,8 @@ class MultivariateNormal:
         """Joint log-density log N([value - mean; r_g] | 0, Kj) of ``value`` and of observed gradients, for a (noisy) lazy kernel
         covariance (``linalg.exact_gek_mll``).  ``gradient_data`` = (Ug, r_g, noise, d0, nd): the feature rows of the gradient points
         from the same ``forward`` of the model, the Mg x nd gradients in scaled units, their variances in scaled units squared or
-        None for the default nugget, and the range of differentiated features."""
+        None for the default nugget, and the range of differentiated features; optionally a sixth entry, the
+        ``backend.GradientSelection`` of the observed entries, with r_g and noise holding those q entries alone."""
         cov = self._covar
         if not isinstance(cov, LazyKernelMatrix):
             raise NotImplementedError("gek_log_prob needs the lazy kernel covariance of a training evaluation")
@@ -220,11 +221,13 @@ class MultivariateNormal:
             raise NotImplementedError("gek_log_prob: the objective has no gradient by calibration parameters")
         from ..linalg import exact_gek_mll
 
-        Ug, r_g, noise, d0, nd = gradient_data
+        Ug, r_g, noise, d0, nd = gradient_data[:5]
+        sel = gradient_data[5] if len(gradient_data) > 5 else None
         dU = cov.n_grad_dims
         if dU is None:
             dU = int(d0) if (cov.U1.requires_grad or Ug.requires_grad) else 0
-        return exact_gek_mll(cov.U1, Ug, cov.spec, cov.tau, self.loc, value, r_g, noise, cov.grp, d0, nd, min(int(dU), int(d0)))
+        return exact_gek_mll(cov.U1, Ug, cov.spec, cov.tau, self.loc, value, r_g, noise, cov.grp, d0, nd, min(int(dU), int(d0)),
+                             sel=sel)
 
     # -- sampling --------------------------------------------------------------------------------
     def root_factor(self) -> torch.Tensor:

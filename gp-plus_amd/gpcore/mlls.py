@@ -83,28 +83,37 @@ class CrossValidationPseudoLikelihood(ExactMarginalLogLikelihood):
 
 class GradientEnhancedMarginalLogLikelihood(ExactMarginalLogLikelihood):
     """The joint marginal log-likelihood of the training targets AND of gradients observed at the rows ``Xg`` — gradient-enhanced
-    Kriging as a training criterion — in the scaling of :class:`ExactMarginalLogLikelihood` with n = N + Mg p observations:
+    Kriging as a training criterion — in the scaling of :class:`ExactMarginalLogLikelihood` with n = N + q observations, q = Mg p:
         (log N([y - mean; dY / y_std] | 0, Kj) + sum of prior log-densities) / n
     (``MultivariateNormal.gek_log_prob``, ``linalg.exact_gek_mll``).  ``Xg``: (Mg, columns of the training inputs); ``dY``: (Mg, p),
     d y / d x over the quantitative columns in ``quant_index`` order, y per input unit; ``noise``: their variances in (y per input
     unit)^2, a scalar or anything that broadcasts to (Mg, p), constant during the fit — None takes
-    ``gradient_enhanced.GRADIENT_NUGGET_REL`` times the prior curvature at the current hyperparameters.  The data are validated
-    once, here, as ``GP_Plus.condition_on_gradients`` validates them (the number of observations is limited by memory alone)."""
+    ``gradient_enhanced.GRADIENT_NUGGET_REL`` times the prior curvature at the current hyperparameters.  ``observed``: a bool mask
+    that broadcasts to (Mg, p), for partial gradients: only its True entries of ``dY`` (and of ``noise``) are observations, the rest
+    is not read, and q is their number.  The data are validated once, here, as ``GP_Plus.condition_on_gradients`` validates them
+    (the number of observations is limited by memory alone)."""
 
-    def __init__(self, likelihood, model, Xg, dY, noise=None):
+    def __init__(self, likelihood, model, Xg, dY, noise=None, observed=None):
         super().__init__(likelihood, model)
         from ..gradient_enhanced import check_gradient_observations
 
         if len(getattr(model, "calibration_id", ())) > 0:
             raise NotImplementedError("the gradient-enhanced objective is not available for a model with calibration parameters: "
                                       "gradient observations by a calibrated column are not defined")
-        Xg, dY, noise = check_gradient_observations(model, Xg, dY, noise, "GradientEnhancedMarginalLogLikelihood")
+        Xg, dY, noise, observed = check_gradient_observations(model, Xg, dY, noise, "GradientEnhancedMarginalLogLikelihood", observed)
         train_x = model.train_inputs[0]
         y_std = model.y_std.detach().to(device=train_x.device, dtype=torch.float64)
         self.Xg = Xg.to(train_x)
         self.r_g = (dY.to(device=train_x.device, dtype=torch.float64) / y_std).contiguous()
         self.noise = None if noise is None else (noise.to(train_x.device) / y_std ** 2).contiguous()
         self.num_directions = int(model.quant_index.numel())
+        self.selection = None
+        if observed is not None:  # the q observed entries alone, in the selection's order
+            from ..backend import GradientSelection
+
+            self.selection = sel = GradientSelection(observed, train_x.device)
+            self.r_g = self.r_g.reshape(-1)[sel.flat].contiguous()
+            self.noise = None if self.noise is None else self.noise.reshape(-1)[sel.flat].contiguous()
 
     def joint_log_prob(self, output: MultivariateNormal, target: torch.Tensor) -> torch.Tensor:
         """log N([target - mean; dY / y_std] | 0, Kj) for the noisy training distribution ``output``: neither normalised nor with
@@ -112,7 +121,7 @@ class GradientEnhancedMarginalLogLikelihood(ExactMarginalLogLikelihood):
         at the current parameters: their latent columns carry the categorical map's graph."""
         p = self.num_directions
         Ug = Module.__call__(self.model, self.Xg).lazy_covariance_matrix.U1
-        return output.gek_log_prob(target, (Ug, self.r_g, self.noise, Ug.shape[1] - p, p))
+        return output.gek_log_prob(target, (Ug, self.r_g, self.noise, Ug.shape[1] - p, p, self.selection))
 
     def forward(self, function_dist: MultivariateNormal, target: torch.Tensor, *params):
         if not isinstance(function_dist, MultivariateNormal):

@@ -20,9 +20,10 @@ GRADIENT_NUGGET_REL = 1e-6
 class GradientEnhancedPosterior:
     """The posterior of a fitted model conditioned on its own training data AND on gradient observations, as returned by
     ``GP_Plus.condition_on_gradients``.  It offers ``predict`` and ``predict_gradient`` with the conventions of the model's own, and
-    the attributes ``num_function_rows`` (N) and ``num_gradient_points`` (Mg).  Nothing else: no further conditioning, no sampling,
-    no leave-one-out or cross-validation, no acquisition scores, no joint covariance, no hyperparameter training on the gradient
-    data.  It holds a detached copy of the model (parameters, training inputs, no N x N factors) for the features, prior means and
+    the attributes ``num_function_rows`` (N), ``num_gradient_points`` (Mg), ``num_gradient_observations`` (q: Mg p, or the number of
+    observed components when an ``observed=`` mask was given) and ``observed`` (the (Mg, p) bool mask).  Nothing else: no further
+    conditioning, no sampling, no leave-one-out or cross-validation, no acquisition scores, no joint covariance, no hyperparameter
+    training on the gradient data.  It holds a detached copy of the model (parameters, training inputs, no N x N factors) for the features, prior means and
     noise of test rows: refitting or modifying the model it came from does not change it."""
 
     def __init__(self, model, gcache):
@@ -36,9 +37,21 @@ class GradientEnhancedPosterior:
     def num_gradient_points(self) -> int:
         return int(self._cache.Ug.shape[0])
 
+    @property
+    def num_gradient_observations(self) -> int:
+        return int(self._cache.q)
+
+    @property
+    def observed(self) -> torch.Tensor:
+        """A copy of the (Mg, p) bool mask of the observed gradient components (all True without ``observed=``)."""
+        sel = self._cache.sel
+        if sel is None:
+            return torch.ones(self.num_gradient_points, self._cache.nd, dtype=torch.bool, device=self._cache.Ug.device)
+        return sel.mask.clone()
+
     def __repr__(self):
         return (f"GradientEnhancedPosterior(function rows={self.num_function_rows}, gradient points={self.num_gradient_points}, "
-                f"directions={self._cache.nd})")
+                f"directions={self._cache.nd}, gradient observations={self.num_gradient_observations})")
 
     def _prior(self, Xtest, what: str):
         m = self._model
@@ -79,10 +92,33 @@ class GradientEnhancedPosterior:
             return mean * scale
 
 
-def check_gradient_observations(model, X, dY, noise, what: str):
-    """The host-side validation ``condition_on_gradients`` and the ``"gek"`` training objective share: returns (X, dY, noise) with
-    dY as (Mg, p) and ``noise`` as an fp64 (Mg, p) tensor or None.  ``ValueError`` for wrong shapes, NaN / inf, Mg = 0, rows the model
-    cannot take, negative noise or a model without a quantitative column."""
+def _check_observed_mask(observed, Mg: int, p: int, what: str):
+    """``observed`` as a host bool (Mg, p) tensor: a bool (or 0 / 1 valued) mask that broadcasts to (Mg, p), every row with at
+    least one True.  ``ValueError`` otherwise."""
+    m = observed.detach().cpu() if torch.is_tensor(observed) else torch.as_tensor(np.asarray(observed))
+    if m.dtype != torch.bool:
+        if m.is_complex() or not bool(((m == 0) | (m == 1)).all()):
+            raise ValueError(f"{what}: observed must be a bool mask (or hold only 0 and 1)")
+        m = m != 0
+    if m.dim() > 2:
+        raise ValueError(f"{what}: observed must broadcast to ({Mg}, {p}) (got {tuple(m.shape)})")
+    try:
+        m = torch.broadcast_to(m, (Mg, p)).contiguous()
+    except RuntimeError:
+        raise ValueError(f"{what}: observed must broadcast to ({Mg}, {p}) (got {tuple(m.shape)})") from None
+    empty = ~m.any(1)
+    if bool(empty.any()):
+        raise ValueError(f"{what}: gradient point {int(empty.to(torch.int32).argmax())} has no observed component under the "
+                         "observed= mask: drop the row")
+    return m
+
+
+def check_gradient_observations(model, X, dY, noise, what: str, observed=None):
+    """The host-side validation ``condition_on_gradients`` and the ``"gek"`` training objective share: returns (X, dY, noise,
+    observed) with dY as (Mg, p), ``noise`` as an fp64 (Mg, p) tensor or None and ``observed`` as a host bool (Mg, p) tensor or None.
+    ``ValueError`` for wrong shapes, NaN / inf, Mg = 0, rows the model cannot take, negative noise, a model without a quantitative
+    column, or a mask that is not one (``_check_observed_mask``).  With a mask the entries of ``dY`` and ``noise`` under its False
+    entries are not read: they may be NaN or inf, and come back as zeros.  Without one NaN is refused: it never means "missing"."""
     X, dY = data_type_check(X), data_type_check(dY)
     train_x = model.train_inputs[0]
     p = int(model.quant_index.numel())
@@ -98,10 +134,13 @@ def check_gradient_observations(model, X, dY, noise, what: str):
         raise ValueError(f"{what}: {X.shape[0]} rows of X for {dY.shape[0]} gradients")
     if X.shape[0] == 0:
         raise ValueError(f"{what}: no observation given (q = 0)")
+    Mg = X.shape[0]
+    if observed is not None:
+        observed = _check_observed_mask(observed, Mg, p, what)
+        dY = torch.where(observed.to(dY.device), dY, torch.zeros((), dtype=dY.dtype, device=dY.device))
     if not (bool(torch.isfinite(X).all()) and bool(torch.isfinite(dY).all())):
         raise ValueError(f"{what}: X and dY must be finite (NaN or inf found)")
     model._check_new_rows(X)
-    Mg = X.shape[0]
     if noise is not None:
         # (a Python or numpy number straight to fp64: ``data_type_check`` would round a float to the default dtype first)
         noise = noise.detach().to(torch.float64) if torch.is_tensor(noise) else torch.as_tensor(np.asarray(noise, dtype=np.float64))
@@ -109,25 +148,34 @@ def check_gradient_observations(model, X, dY, noise, what: str):
             noise = torch.broadcast_to(noise, (Mg, p))
         except RuntimeError:
             raise ValueError(f"{what}: noise must be a scalar or broadcast to ({Mg}, {p}) (got {tuple(noise.shape)})") from None
+        if observed is not None:
+            noise = torch.where(observed.to(noise.device), noise, torch.zeros((), dtype=noise.dtype, device=noise.device))
         if not bool(torch.isfinite(noise).all()) or bool((noise < 0).any()):
             raise ValueError(f"{what}: the noise variances must be finite and not negative")
-    return X, dY, noise
+    return X, dY, noise, observed
 
 
-def condition_on_gradients(model, X, dY, noise=None) -> GradientEnhancedPosterior:
+def condition_on_gradients(model, X, dY, noise=None, observed=None) -> GradientEnhancedPosterior:
     """The work behind ``GP_Plus.condition_on_gradients`` (documented there)."""
     from . import settings as gpp_settings
-    from .backend import get_context
+    from .backend import GradientSelection, get_context
     from .linalg import APPEND_MAX_Q, append_gradients_to_cache, gradient_prior_curvature
 
     what = "condition_on_gradients"
-    X, dY, noise = check_gradient_observations(model, X, dY, noise, what)
+    X, dY, noise, observed = check_gradient_observations(model, X, dY, noise, what, observed)
     train_x = model.train_inputs[0]
     p = int(model.quant_index.numel())
     Mg = X.shape[0]
     N = int(train_x.shape[0])
-    if Mg * p > min(N, APPEND_MAX_Q):
-        raise ValueError(f"{what}: {Mg} points x {p} directions = {Mg * p} gradient observations exceed min(N = {N}, {APPEND_MAX_Q})")
+    if observed is None:
+        if Mg * p > min(N, APPEND_MAX_Q):
+            raise ValueError(f"{what}: {Mg} points x {p} directions = {Mg * p} gradient observations exceed "
+                             f"min(N = {N}, {APPEND_MAX_Q})")
+    else:
+        q = int(observed.sum())
+        if q > min(N, APPEND_MAX_Q):
+            raise ValueError(f"{what}: {q} gradient observations (the True entries of observed, at {Mg} points x {p} directions) "
+                             f"exceed min(N = {N}, {APPEND_MAX_Q})")
     if gpp_settings.sharded_evaluation.value() is not None:
         raise NotImplementedError(f"{what} is not available under settings.sharded_evaluation")
     get_context(train_x.device)  # (raises for anything but a GPU: there is no CPU path)
@@ -143,7 +191,11 @@ def condition_on_gradients(model, X, dY, noise=None) -> GradientEnhancedPosterio
             noise_diag = (GRADIENT_NUGGET_REL * gradient_prior_curvature(cache.spec, d0, p)).expand(Mg, p)
         else:
             noise_diag = noise.to(Ug.device) / y_std ** 2
-        gcache = append_gradients_to_cache(cache, Ug, d0, p, r_g, noise_diag.contiguous())
+        if observed is None:
+            gcache = append_gradients_to_cache(cache, Ug, d0, p, r_g, noise_diag.contiguous())
+        else:
+            sel = GradientSelection(observed, Ug.device)
+            gcache = append_gradients_to_cache(cache, Ug, d0, p, r_g.reshape(-1)[sel.flat], noise_diag.reshape(-1)[sel.flat], sel)
         child = model._copy_without_factors()
         child.eval()
     return GradientEnhancedPosterior(child, gcache)

@@ -1049,14 +1049,17 @@ def gradient_from_cache(cache: FactorCache, Us, d0: int, nd: int, want: str, ome
 
 class GradientFactorCache:
     """Factor, inverse factor, z and alpha of the N function rows of a ``FactorCache`` bordered with q = Mg nd gradient observations
-    (``append_gradients_to_cache``): row N + a nd + j is d f / du_{d0+j} at the feature row ``Ug[a]``.  It owns its matrices (never
-    stale) and is deliberately NOT a ``FactorCache``: its last q rows are not function values, so nothing that reads a
-    ``FactorCache`` (prediction, appends, scores, sampling) may take it.  ``predict_from_gradient_cache`` is its only consumer."""
+    (``append_gradients_to_cache``): row N + a nd + j is d f / du_{d0+j} at the feature row ``Ug[a]``.  With a selection ``sel``
+    (``backend.GradientSelection``: partial gradients) q = sel.q and row N + k is its observation k, the direction sel.dir[k] at the
+    point that owns k.  It owns its matrices (never stale) and is deliberately NOT a ``FactorCache``: its last q rows are not
+    function values, so nothing that reads a ``FactorCache`` (prediction, appends, scores, sampling) may take it.
+    ``predict_from_gradient_cache`` is its only consumer."""
 
-    def __init__(self, gctx, own, n, q, z, alpha, U, Ug, d0, nd, spec, jitter):
+    def __init__(self, gctx, own, n, q, z, alpha, U, Ug, d0, nd, spec, jitter, sel=None):
         self.gctx, self._own = gctx, own
         self.L, self.Linv = own.A[:n + q, :n + q], own.Linv[:n + q, :n + q]
         self.z, self.alpha, self.U, self.Ug, self.d0, self.nd, self.spec, self.jitter = z, alpha, U, Ug, d0, nd, spec, jitter
+        self.q, self.sel = q, sel
 
 
 def _gradient_cache_refusals(what: str, dev=None):
@@ -1067,7 +1070,7 @@ def _gradient_cache_refusals(what: str, dev=None):
 
 
 @torch.no_grad()
-def append_gradients_to_cache(cache: FactorCache, Ug, d0: int, nd: int, r_g, noise_diag) -> GradientFactorCache:
+def append_gradients_to_cache(cache: FactorCache, Ug, d0: int, nd: int, r_g, noise_diag, sel=None) -> GradientFactorCache:
     """A ``GradientFactorCache`` of the N cached rows plus q = Mg nd observations of the gradient of the latent f with respect to
     the features d0 .. d0 + nd - 1 at the feature rows ``Ug`` (Mg x D), in O(N^2 q) by bordering the cached factor (gpp_chol_append):
     the cross block is cov(f(x_n), d_j f(ug_a)) = gpp_cross_kernel_dx(Ua = Ug, Ub = U) (N x q), the corner
@@ -1075,6 +1078,8 @@ def append_gradients_to_cache(cache: FactorCache, Ug, d0: int, nd: int, r_g, noi
     gradients, point-major (a nd + j), in the cache's scaled units — every supported mean is constant, so their prior mean is 0;
     ``noise_diag``: their q noise variances, same units squared.  The windows are always copied into a new pair of capacity
     N + q: ``cache`` stays valid and bitwise unchanged (it is refreshed first when another model has taken the shared workspace).
+    ``sel``: a ``backend.GradientSelection`` of the (point, direction) entries that were observed; q = sel.q, ``r_g`` and
+    ``noise_diag`` hold those q entries in its order, and both blocks are built at their compact size by the ``_sel`` kernels.
 
     ``ValueError`` for q > min(N, APPEND_MAX_Q): there is no from-scratch route, since no build kernel forms the mixed matrix.
     ``errors.NotPSDError`` when the Schur complement is not positive definite (duplicate gradient points without noise).
@@ -1094,7 +1099,9 @@ def append_gradients_to_cache(cache: FactorCache, Ug, d0: int, nd: int, r_g, noi
             raise ValueError(f"the gradient points must be at least one row of {D} features (got {tuple(Ug.shape)})")
         if nd < 1 or d0 < 0 or d0 + nd > D:
             raise ValueError(f"the differentiated features [{d0}, {d0 + nd}) must be a non-empty range of the {D} features")
-        q = Ug.shape[0] * nd
+        if sel is not None and (sel.num_points, sel.nd) != (Ug.shape[0], nd):
+            raise ValueError(f"a selection of {sel.num_points} points x {sel.nd} directions for {Ug.shape[0]} x {nd}")
+        q = Ug.shape[0] * nd if sel is None else sel.q
         r_g = _as_f64(r_g.detach().reshape(-1), dev).contiguous()
         noise_diag = _as_f64(noise_diag.detach().reshape(-1), dev)
         if r_g.numel() != q or noise_diag.numel() != q:
@@ -1107,8 +1114,10 @@ def append_gradients_to_cache(cache: FactorCache, Ug, d0: int, nd: int, r_g, noi
         spec = cache.spec
         w, sf2 = spec.w, spec.sf2.reshape(1)
         with _stage("append_gradient_operands"):
-            k = gctx.cross_kernel_dx(Ug, cache.U, w, sf2, d0, nd, rows_buffer(n, q, dev), kind=spec.kind, d_split=spec.d_split)
-            C = gctx.kernel_dxdx(Ug, Ug, w, sf2, d0, nd, square_buffer(q, dev), kind=spec.kind, d_split=spec.d_split)
+            k = gctx.cross_kernel_dx(Ug, cache.U, w, sf2, d0, nd, rows_buffer(n, q, dev), kind=spec.kind, d_split=spec.d_split,
+                                     sel=sel)
+            C = gctx.kernel_dxdx(Ug, Ug, w, sf2, d0, nd, square_buffer(q, dev), kind=spec.kind, d_split=spec.d_split, sel_a=sel,
+                                 sel_b=sel)
             C.diagonal().add_(noise_diag + cache.jitter)
         z = torch.empty(n + q, dtype=torch.float64, device=dev)
         alpha = torch.empty(n + q, dtype=torch.float64, device=dev)
@@ -1128,11 +1137,12 @@ def append_gradients_to_cache(cache: FactorCache, Ug, d0: int, nd: int, r_g, noi
             if bool(lost.any()):
                 minor = int(lost.to(torch.int32).argmax().item()) + 1
         if minor != 0:
+            entry = minor - 1 if sel is None else int(sel.flat[minor - 1])  # a nd + j of the failing observation
             raise NotPSDError(f"conditioning on gradients: leading minor {minor} of the Schur complement of the {q} gradient "
-                              f"observations is not positive definite (gradient point {(minor - 1) // nd}, direction "
-                              f"{(minor - 1) % nd}); pass a larger noise")
+                              f"observations is not positive definite (gradient point {entry // nd}, direction "
+                              f"{entry % nd}); pass a larger noise")
         own.filled = n + q
-        return GradientFactorCache(gctx, own, n, q, z, alpha, cache.U, Ug, d0, nd, spec, cache.jitter)
+        return GradientFactorCache(gctx, own, n, q, z, alpha, cache.U, Ug, d0, nd, spec, cache.jitter, sel)
 
 
 @torch.no_grad()
@@ -1159,14 +1169,15 @@ def predict_from_gradient_cache(gcache: GradientFactorCache, Us, want: str = "fu
         if Us.dim() != 2 or Us.shape[0] < 1 or Us.shape[1] != D:
             raise ValueError(f"the test points must be at least one row of {D} features (got {tuple(Us.shape)})")
         M, d0, nd = Us.shape[0], gcache.d0, gcache.nd
-        q = gcache.Ug.shape[0] * nd
+        q, sel = gcache.q, gcache.sel  # (the test side stays dense: all nd directions at every test point)
         spec = gcache.spec
         w, sf2 = spec.w, spec.sf2.reshape(1)
         if want == "function":
             op = rows_buffer(N + q, M, dev)
             with _stage("gek_operands"):
                 gctx.cross_kernel(gcache.U, Us, w, sf2, op[:N], kind=spec.kind, d_split=spec.d_split)
-                Dsg = gctx.cross_kernel_dx(gcache.Ug, Us, w, sf2, d0, nd, rows_buffer(M, q, dev), kind=spec.kind, d_split=spec.d_split)
+                Dsg = gctx.cross_kernel_dx(gcache.Ug, Us, w, sf2, d0, nd, rows_buffer(M, q, dev), kind=spec.kind, d_split=spec.d_split,
+                                           sel=sel)
                 gctx.transpose(Dsg, op[N:])
             mean = torch.empty(M, dtype=torch.float64, device=dev)
             var = torch.empty(M, dtype=torch.float64, device=dev)
@@ -1184,7 +1195,7 @@ def predict_from_gradient_cache(gcache: GradientFactorCache, Us, want: str = "fu
             v_c = torch.empty(mc * nd, dtype=torch.float64, device=dev)
             with _stage("gek_operands"):
                 gctx.cross_kernel_dx(Us[a0:a0 + mc], gcache.U, w, sf2, d0, nd, op[:N], kind=spec.kind, d_split=spec.d_split)
-                gctx.kernel_dxdx(gcache.Ug, Us[a0:a0 + mc], w, sf2, d0, nd, op[N:], kind=spec.kind, d_split=spec.d_split)
+                gctx.kernel_dxdx(gcache.Ug, Us[a0:a0 + mc], w, sf2, d0, nd, op[N:], kind=spec.kind, d_split=spec.d_split, sel_a=sel)
             with _stage("gek_predict_tn"):
                 gctx.predict_tn(gcache.Linv, gcache.z, op, kappa.repeat(mc), rows_buffer(mc * nd, N + q, dev), g_c, v_c)
             del op
@@ -1209,14 +1220,14 @@ class ExactGEKFunction(torch.autograd.Function):
     gpp_grad_reduce on the leading N x N view and gpp_gek_grad_reduce on the other two blocks; ``backward`` scales."""
 
     @staticmethod
-    def forward(ctx, U, Ug, w, sf2, tau, mean, y, r_g, nu, grp, kind, d_split, d0, nd, dU, nugget_rel, slot):
+    def forward(ctx, U, Ug, w, sf2, tau, mean, y, r_g, nu, grp, kind, d_split, d0, nd, dU, nugget_rel, slot, sel=None):
         gctx = get_context(U.device)  # raises GppError for anything but a GPU: there is no CPU path
         with torch.cuda.device(U.device):
             if torch.cuda.is_current_stream_capturing():
                 raise NotImplementedError("the gradient-enhanced objective is not available inside a graph capture")
             dev = U.device
             (N, D), Mg = U.shape, Ug.shape[0]
-            q = Mg * nd
+            q = Mg * nd if sel is None else sel.q
             n = N + q
             Ud, wd, sd, td, grp = _operands(U, w, sf2, tau, grp)
             Ugd = _as_f64(Ug.detach(), dev)
@@ -1230,7 +1241,8 @@ class ExactGEKFunction(torch.autograd.Function):
             dUk = dU if need_U else 0
             spec = KernelSpec(wd, sd, kind, d_split)
             if nu is None:
-                nu_d = (float(nugget_rel) * gradient_prior_curvature(spec, d0, nd)).repeat(Mg)
+                nu_d = float(nugget_rel) * gradient_prior_curvature(spec, d0, nd)
+                nu_d = nu_d.repeat(Mg) if sel is None else nu_d[sel.flat % nd]
             else:
                 nu_d = _as_f64(nu.detach().reshape(-1), dev)
             ws = get_workspace(gctx, n, slot)
@@ -1266,11 +1278,14 @@ class ExactGEKFunction(torch.autograd.Function):
                                      d_split=d_split)
                 with _stage("gek_grad_reduce"):
                     gctx.gek_grad_reduce(Ud, Ugd, wd, sd, d0, nd, ws.alpha, ws.Ki, dUk, g_w, g_s, g_Ud, g_Ugd, kind=kind,
-                                         d_split=d_split)
+                                         d_split=d_split, sel=sel)
                     if nu is None:
                         # d nu_k / dw_j = rel c_j sf2, d nu_k / dsf2 = rel c_j w_j on the rows k = (a, j), times W_kk
                         a_g = ws.alpha[N:]
-                        Wd = (0.5 * (a_g * a_g - ws.Ki[N:n, N:n].diagonal())).view(Mg, nd).sum(0)
+                        Wd = 0.5 * (a_g * a_g - ws.Ki[N:n, N:n].diagonal())
+                        if sel is not None:  # (scattered into the dense layout, zeros elsewhere: the same ordered sum, no atomics)
+                            Wd = torch.zeros(Mg * nd, dtype=torch.float64, device=dev).index_put_((sel.flat,), Wd)
+                        Wd = Wd.view(Mg, nd).sum(0)
                         c = float(nugget_rel) * _curvature_coefficients(spec)[d0:d0 + nd]
                         g_w[d0:d0 + nd].add_(c * sd * Wd)
                         g_s.add_((c * wd[d0:d0 + nd] * Wd).sum())
@@ -1280,8 +1295,8 @@ class ExactGEKFunction(torch.autograd.Function):
                     torch.cuda.current_stream(gctx.index).synchronize()
                 with _stage("gek_build"):
                     gctx.kernel_build(Ud, wd, sd, td, grp, ws.A[:N, :N], jitter=jit, kind=kind, d_split=d_split, uplo=UPLO_UPPER)
-                    gctx.cross_kernel_dx(Ugd, Ud, wd, sd, d0, nd, Kfg_out, kind=kind, d_split=d_split)
-                    gctx.kernel_dxdx(Ugd, Ugd, wd, sd, d0, nd, Kgg_out, kind=kind, d_split=d_split)
+                    gctx.cross_kernel_dx(Ugd, Ud, wd, sd, d0, nd, Kfg_out, kind=kind, d_split=d_split, sel=sel)
+                    gctx.kernel_dxdx(Ugd, Ugd, wd, sd, d0, nd, Kgg_out, kind=kind, d_split=d_split, sel_a=sel, sel_b=sel)
                     if not aligned:
                         ws.A[:N, N:n].copy_(Kfg_out)
                         ws.A[N:n, N:n].copy_(Kgg_out)
@@ -1319,19 +1334,20 @@ class ExactGEKFunction(torch.autograd.Function):
                 (go * g_s).reshape(sf2_shape).to(dt[3]) if need[3] else None,
                 (go * g_t).reshape(tau_shape).to(dt[4]) if need[4] else None,
                 (go * g_mean).to(dt[5]) if need[5] else None,
-                (-go * g_mean).to(dt[6]) if need[6] else None) + (None,) * 10
+                (-go * g_mean).to(dt[6]) if need[6] else None) + (None,) * 11
 
 
 def exact_gek_mll(U: torch.Tensor, Ug: torch.Tensor, spec: KernelSpec, tau: torch.Tensor, mean: torch.Tensor, y: torch.Tensor,
                   r_g: torch.Tensor, noise: Optional[torch.Tensor], grp: Optional[torch.Tensor], d0: int, nd: int,
-                  n_grad_dims: Optional[int] = None, slot: Optional[int] = None) -> torch.Tensor:
+                  n_grad_dims: Optional[int] = None, slot: Optional[int] = None, sel=None) -> torch.Tensor:
     """log N([y - mean; r_g] | 0, Kj) on the GPU (``ExactGEKFunction``): the joint density of the N function rows ``U`` and the
     q = Mg nd observed gradients ``r_g`` (point-major, scaled units; prior mean 0) with respect to the features d0 .. d0 + nd - 1 at
     the rows ``Ug``.  ``noise``: their q variances (scaled units squared, constant during a fit), or None for
     ``gradient_enhanced.GRADIENT_NUGGET_REL`` times the prior curvature at the current hyperparameters.  Differentiable with respect
     to U[:, :n_grad_dims], Ug[:, :n_grad_dims], spec.w, spec.sf2, tau, mean and y; n_grad_dims <= d0.  The matrix is factored from
-    scratch in a workspace of N + q rows: q is limited by memory alone.  Refused under ``settings.sharded_evaluation`` and inside a
-    graph capture."""
+    scratch in a workspace of N + q rows: q is limited by memory alone.  ``sel``: a ``backend.GradientSelection`` of the observed
+    (point, direction) entries (partial gradients): q = sel.q, ``r_g`` and ``noise`` hold those entries in its order, and the
+    density is that of the selected rows alone.  Refused under ``settings.sharded_evaluation`` and inside a graph capture."""
     from .gradient_enhanced import GRADIENT_NUGGET_REL
 
     _gradient_cache_refusals("the gradient-enhanced objective")
@@ -1345,14 +1361,16 @@ def exact_gek_mll(U: torch.Tensor, Ug: torch.Tensor, spec: KernelSpec, tau: torc
         raise ValueError(f"the gradient points must be at least one row of {D} features (got {tuple(Ug.shape)})")
     if nd < 1 or d0 < 0 or d0 + nd > D:
         raise ValueError(f"the differentiated features [{d0}, {d0 + nd}) must be a non-empty range of the {D} features")
-    q = Ug.shape[0] * nd
+    if sel is not None and (sel.num_points, sel.nd) != (Ug.shape[0], nd):
+        raise ValueError(f"a selection of {sel.num_points} points x {sel.nd} directions for {Ug.shape[0]} x {nd}")
+    q = Ug.shape[0] * nd if sel is None else sel.q
     if r_g.numel() != q or (noise is not None and noise.numel() != q):
         raise ValueError(f"{r_g.numel()} gradients / {None if noise is None else noise.numel()} noise variances for {q} gradient "
                          "observations")
     if dU > d0:
         raise ValueError(f"the {dU} feature columns with a gradient must lie in front of the differentiated ones (d0 = {d0})")
     return ExactGEKFunction.apply(U, Ug, spec.w, spec.sf2, tau, mean, y, r_g, noise, grp, spec.kind, spec.d_split, d0, nd, dU,
-                                  GRADIENT_NUGGET_REL, slot)
+                                  GRADIENT_NUGGET_REL, slot, sel)
 
 
 #: Scratch one gpp_post_cross_min launch of ``knowledge_gradient`` may ask for: above it the reference rows go in column chunks

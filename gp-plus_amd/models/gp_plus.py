@@ -402,10 +402,10 @@ class GP_Plus(GPR):
         the restarts run one after the other, the leave-one-out objective then with every evaluation eager.
         ``objective="cv"`` with ``folds=`` (an int k, one integer label per training row — ``cv.group_labels`` makes them from
         columns of X — or a ``cv.FoldIndex``) maximises the grouped cross-validation log pseudo-likelihood: always the sequential,
-        eager route.  ``objective="gek"`` with ``gradients=(Xg, dY)`` or ``(Xg, dY, noise)`` — the arguments of
-        ``condition_on_gradients`` — trains on the joint marginal likelihood of the targets and of the observed gradients
-        (``gpcore.GradientEnhancedMarginalLogLikelihood``): sequential and eager as well; afterwards ``condition_on_gradients`` on
-        the same data gives the gradient-enhanced posterior at the fitted hyperparameters."""
+        eager route.  ``objective="gek"`` with ``gradients=(Xg, dY)``, ``(Xg, dY, noise)`` or ``(Xg, dY, noise, observed)`` —
+        the arguments of ``condition_on_gradients`` — trains on the joint marginal likelihood of the targets and of the observed
+        gradients (``gpcore.GradientEnhancedMarginalLogLikelihood``): sequential and eager as well; afterwards
+        ``condition_on_gradients`` on the same data gives the gradient-enhanced posterior at the fitted hyperparameters."""
         from ..optim.mll_torch import check_objective_folds, check_objective_gradients
         folds = check_objective_folds(objective, folds, int(self.train_targets.shape[0]))
         gradients = check_objective_gradients(objective, gradients)
@@ -640,7 +640,7 @@ class GP_Plus(GPR):
             return ActiveSubspace(matrix=matrix, eigenvalues=evals.flip(0), eigenvectors=evecs.flip(1), mean_part=mean_part,
                                   cov_part=cov_part, sensitivity=torch.diagonal(matrix).clone())
 
-    def condition_on_gradients(self, X, dY, noise=None):
+    def condition_on_gradients(self, X, dY, noise=None, observed=None):
         """Gradient-enhanced Kriging on the fitted model: a ``GradientEnhancedPosterior`` of this model's training data plus observed
         gradients, made by bordering the cached factorisation in O(N^2 q), q = Mg p, without refactorising
         (``linalg.append_gradients_to_cache``: gpp_cross_kernel_dx, gpp_kernel_dxdx, gpp_chol_append).  ``X``: (Mg, columns of the
@@ -649,23 +649,29 @@ class GP_Plus(GPR):
         ``quant_index`` order, in y per input unit, as ``predict_gradient`` returns them; every supported prior mean is constant,
         so the gradients' prior mean is 0.  ``noise``: the variance of those observations in (y per input unit)^2, a scalar or
         anything that broadcasts to (Mg, p); ``None`` takes ``gradient_enhanced.GRADIENT_NUGGET_REL`` = 1e-6 times the prior
-        curvature of each direction (the prior variance of that gradient component).
+        curvature of each direction (the prior variance of that gradient component).  ``observed``: partial gradients — a bool
+        mask that broadcasts to (Mg, p) (a length-p row: the same directions at every point) of the components of ``dY`` that were
+        observed, as an adjoint gives them for the design variables only.  Entries of ``dY`` and ``noise`` under a False are not
+        read and may be NaN or inf; q is then the number of True entries, every limit counts q, and both derivative blocks are
+        built at that size (gpp_cross_kernel_dx_sel, gpp_kernel_dxdx_sel).  A point without an observed component is a
+        ``ValueError``: drop the row.  Without a mask NaN is refused — it never means "missing".
 
         The receiver's data, parameters and cache are not modified (it is put in eval mode, as by ``predict``; without a cache it
         is factorised first).  The returned object holds a detached copy of the model without the N x N factors and offers
         ``predict(Xtest, return_std=True, include_noise=True)`` and ``predict_gradient(Xtest, return_std=True)`` in this model's
-        conventions and units, ``num_function_rows`` and ``num_gradient_points`` — nothing else: no partial gradients, no further
-        appends, no sampling, LOO / CV, acquisition scores or ``return_cov``, no training on the gradient data.  No reference
+        conventions and units, ``num_function_rows``, ``num_gradient_points``, ``num_gradient_observations`` (q) and ``observed``
+        — nothing else: no further appends, no sampling, LOO / CV, acquisition scores or ``return_cov``, no training on the gradient data.  No reference
         counterpart.
 
         ``ValueError`` before any kernel runs: wrong column count or shapes, NaN / inf, Mg = 0, a categorical level or source the
-        model has not seen, negative noise, a model without a quantitative column, Mg p > min(N, 2048).  ``errors.NotPSDError``
+        model has not seen, negative noise, a model without a quantitative column, a mask of the wrong shape or type or with an empty
+        row, q > min(N, 2048).  ``errors.NotPSDError``
         when the gradient observations' Schur complement is not positive definite (duplicate points without noise): pass a larger
         ``noise``; the receiver stays usable.  ``NotImplementedError`` under ``settings.sharded_evaluation`` or a graph capture."""
         from ..gradient_enhanced import condition_on_gradients
 
         self._refuse_calibrated("condition_on_gradients", "gradient observations by a calibrated column are not defined")
-        return condition_on_gradients(self, X, dY, noise)
+        return condition_on_gradients(self, X, dY, noise, observed)
 
     def noise_value(self):
         return self.likelihood.noise_covar.noise.detach() * self.y_std ** 2

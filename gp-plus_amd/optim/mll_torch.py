@@ -18,7 +18,8 @@ from ..gpcore.mlls import (CrossValidationPseudoLikelihood, ExactMarginalLogLike
 #: "cv" is the grouped cross-validation log pseudo-likelihood over the ``folds`` the caller gives (gp-plus_amd/cv.py): always the
 #: sequential, eager route (fit_model_torch_batched hands it to fit_model_torch)
 OBJECTIVES = ("mll", "loo", "cv")
-#: the objectives that train on observed gradients as well, given as ``gradients=(Xg, dY)`` or ``(Xg, dY, noise)``: "gek" is the joint
+#: the objectives that train on observed gradients as well, given as ``gradients=(Xg, dY)``, ``(Xg, dY, noise)`` or, for partial
+#: gradients, ``(Xg, dY, noise, observed)``: "gek" is the joint
 #: marginal log-likelihood of the targets and of those gradients (gpcore.GradientEnhancedMarginalLogLikelihood), sequential and eager
 GRADIENT_OBJECTIVES = ("gek",)
 
@@ -44,14 +45,17 @@ def check_objective_folds(objective: str, folds, n_points: int):
 
 
 def check_objective_gradients(objective: str, gradients):
-    """The pairing of ``objective`` and ``gradients``: "gek" needs them, no other objective takes them.  Returns (Xg, dY, noise) or
-    None.  Host work only; the data themselves are validated by ``GradientEnhancedMarginalLogLikelihood``."""
+    """The pairing of ``objective`` and ``gradients``: "gek" needs them, no other objective takes them.  Returns (Xg, dY, noise), or
+    (Xg, dY, noise, observed) for the 4-tuple of partial gradients, or None.  Host work only; the data themselves are validated by
+    ``GradientEnhancedMarginalLogLikelihood``."""
     check_objective(objective)
     if objective in GRADIENT_OBJECTIVES:
         if gradients is None:
-            raise ValueError('objective="gek" needs gradients=(Xg, dY) or (Xg, dY, noise)')
-        if not isinstance(gradients, (tuple, list)) or len(gradients) not in (2, 3):
-            raise ValueError("gradients= must be (Xg, dY) or (Xg, dY, noise)")
+            raise ValueError('objective="gek" needs gradients=(Xg, dY), (Xg, dY, noise) or (Xg, dY, noise, observed)')
+        if not isinstance(gradients, (tuple, list)) or len(gradients) not in (2, 3, 4):
+            raise ValueError("gradients= must be (Xg, dY), (Xg, dY, noise) or (Xg, dY, noise, observed)")
+        if len(gradients) == 4:
+            return tuple(gradients)
         return (gradients[0], gradients[1], gradients[2] if len(gradients) == 3 else None)
     if gradients is not None:
         raise ValueError(f'gradients= belongs to objective="gek" (got objective={objective!r})')
@@ -144,7 +148,7 @@ def fit_model_torch(model, model_param_groups: Optional[List] = None, lr_default
     ``objective="loo"`` maximises the leave-one-out log pseudo-likelihood (plus the priors) instead of the marginal likelihood;
     every evaluation is then the eager one.  ``objective="cv"`` with ``folds=`` (an int k, one integer label per training row, or a
     ``cv.FoldIndex``) maximises the grouped cross-validation log pseudo-likelihood, eagerly as well.  ``objective="gek"`` with
-    ``gradients=(Xg, dY)`` or ``(Xg, dY, noise)`` maximises the joint marginal log-likelihood of the targets and of the gradients
+    ``gradients=(Xg, dY)``, ``(Xg, dY, noise)`` or ``(Xg, dY, noise, observed)`` maximises the joint marginal log-likelihood of the targets and of the gradients
     ``dY`` observed at the rows ``Xg`` (``GradientEnhancedMarginalLogLikelihood``), eagerly as well.
 
     :returns: ``(f_inc, loss_hist_total)`` — best (negative, per-datum) log-posterior found and the loss histories.

@@ -714,6 +714,52 @@ int gpp_gek_grad_reduce(gpp_handle_t h, const double* U, int64_t N, const double
                         const double* sf2, int kind, int d_split, int d0, int nd, const double* alpha, const double* Kinv,
                         int64_t ldk, int dU, double* g_w, double* g_sf2, double* g_U, double* g_Ug);
 
+/*
+ * Partial gradients: the three calls above on a SELECTION of the (point, direction) entries (models/gp_plus.py
+ * condition_on_gradients(observed=...); no reference counterpart).  A selection of M points with nd directions each is two DEVICE
+ * arrays of int and a count q:
+ *   first[M + 1]  first[a] = the number of selected entries of the points before a (first[0] = 0, first[M] = q, non-decreasing;
+ *                 a point may have none);
+ *   dir[q]        dir[first[a] + k] in [0, nd) = the direction of entry k of point a, strictly increasing within a point.
+ * The selected entries are numbered point-major, 0 .. q - 1: entry first[a] + k is row (or column) N-or-0 + first[a] + k wherever the
+ * dense calls have a nd + j.  A NULL pair first / dir means "dense on this side": its q must then be M nd, and with every pair NULL
+ * the call IS the one above.  Checked on the host, with argument codes: a pair of which one pointer is NULL (the code of dir), q
+ * outside [1, M nd] (or != M nd for a NULL pair), the leading dimension against q, the alignment, and everything the dense calls
+ * check.  NOT checked — the caller's contract, backend.GradientSelection being the only producer: the arrays' contents as stated
+ * above.  Every call writes the compact extents alone (the columns [q, ld) stay untouched), reads nothing outside the stated
+ * extents, uses no workspace beyond the dense call's and no float atomics; two calls agree bit for bit, every entry is the dense
+ * entry it selects bit for bit, and a selection of all M nd entries gives the bits of the dense call.
+ *
+ * gpp_cross_kernel_dx_sel: Dk[n, first_a[a] + k] = the dense Dk[n, a nd + dir_a[first_a[a] + k]].  Dk: N x qa, ld >= qa, ld even,
+ * 16-byte aligned.  Two columns per lane are paired on the ABSOLUTE compact column, so the 16-byte stores stay aligned where a tile
+ * of 16 points starts at an odd column; an odd head or tail is one 8-byte store.
+ */
+int gpp_cross_kernel_dx_sel(gpp_handle_t h, const double* Ua, int64_t M, const double* Ub, int64_t N, int D, const double* w,
+                            const double* sf2, int kind, int d_split, int d0, int nd, const int* first_a, const int* dir_a, int64_t qa,
+                            double* Dk, int64_t ld);
+
+/*
+ * gpp_kernel_dxdx on a selection of the rows (first_a, dir_a, qa: Ma points) and / or of the columns (first_b, dir_b, qb: Mb
+ * points), as described at gpp_cross_kernel_dx_sel: H: qa x qb row-major, ld >= qb, ld even, 16-byte aligned;
+ *   H[first_a[a] + k][first_b[b] + m] = the dense H[a nd + dir_a[first_a[a] + k]][b nd + dir_b[first_b[b] + m]].
+ * With Ua and Ub the same rows and the same selection on both sides H is bitwise symmetric.
+ */
+int gpp_kernel_dxdx_sel(gpp_handle_t h, const double* Ua, int64_t Ma, const double* Ub, int64_t Mb, int D, const double* w,
+                        const double* sf2, int kind, int d_split, int d0, int nd, const int* first_a, const int* dir_a, int64_t qa,
+                        const int* first_b, const int* dir_b, int64_t qb, double* H, int64_t ld);
+
+/*
+ * gpp_gek_grad_reduce for q selected gradient observations (first, dir, q: Mg points; described at gpp_cross_kernel_dx_sel):
+ * n = N + q, alpha: n doubles, Kinv: n x n with ld >= n, the gradient observations in the rows N + first[a] + k.  The sums of a pair
+ * of points run over the selected directions of its points in the order of k; the explicit-weight terms of entry k go to
+ * g_w[d0 + dir[first[a] + k]]; g_Ug of a point without an entry is an exact 0.  Workspace, finish launches and the codes from dU on
+ * (moved by the three arguments) as gpp_gek_grad_reduce: gpp_workspace_bytes(h, GPP_OP_GEK_GRAD, N, Mg, D, dU) bytes.
+ */
+int gpp_gek_grad_reduce_sel(gpp_handle_t h, const double* U, int64_t N, const double* Ug, int64_t Mg, int D, const double* w,
+                            const double* sf2, int kind, int d_split, int d0, int nd, const int* first, const int* dir, int64_t q,
+                            const double* alpha, const double* Kinv, int64_t ldk, int dU, double* g_w, double* g_sf2, double* g_U,
+                            double* g_Ug);
+
 #ifdef __cplusplus
 }
 #endif
