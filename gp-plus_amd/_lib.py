@@ -137,6 +137,9 @@ _SIGNATURES = {
                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "gpp_post_cross_sq": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                   c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "gpp_post_cross_lin_sq": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                      c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p,
+                                      c_void_p]),
     "gpp_post_cross_min": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                    c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "gpp_cross_kernel_dx": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int,

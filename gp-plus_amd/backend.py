@@ -31,6 +31,7 @@ OP_POST_CROSS = 6  # gpp_post_cross_sq: N carries the reference count M_r, M the
 OP_POST_CROSS_MIN = 7  # gpp_post_cross_min: N carries M_r, M carries M_c, S the node count Q
 OP_POINT_GRAM = 8  # gpp_point_gram with a weighted sum: M points, D carries the rows per point
 OP_GEK_GRAD = 9  # gpp_gek_grad_reduce: N function points, M carries the gradient points Mg, S the feature columns with a gradient
+OP_POST_CROSS_LIN = 10  # gpp_post_cross_lin_sq: N carries the reference count M_r, M the functional count M_f
 #: most quadrature nodes gpp_post_cross_min takes (gpp_gemm.hip PostCrossMinEpilogue::QMAX)
 MAX_NODES = 64
 #: longest contraction gpp_kernel_apply / gpp_rff_apply run without scratch (gpp_apply.hip AP_SPLIT)
@@ -1041,6 +1042,63 @@ class GppContext:
         if status == NO_WORKSPACE:
             raise GppError("gpp_post_cross_sq: the handle's scratch workspace is missing or too small")
         check(status, "gpp_post_cross_sq")
+        return out
+
+    @_on_own_device
+    def post_cross_lin_sq(self, Uf, Ur, w, sf2, A, d0, nd, Vf, Vr, K, out, *, omega=None, kind=KIND_RBF, d_split=0, transposed=False):
+        """``post_cross_sq`` for rows that observe a linear functional of f at their point (gpp_post_cross_lin_sq): row i is
+        A[i, 0] f + sum_{j < nd} A[i, 1 + j] df/du_{d0 + j} at Uf_i, and out[i] = sum_r omega_r (its prior covariance with f(Ur_r)
+        - sum_{n < K} Vf[i, n] Vr[r, n])^2.  ``A``: M_f x (>= 1 + nd) window of a row-major buffer; what lies beyond 1 + nd is not
+        read.  ``Vf`` / ``Vr``, ``transposed`` and ``omega`` as in ``post_cross_sq``.  Everything is checked before any launch."""
+        K, d0, nd = int(K), int(d0), int(nd)
+        for t, n in ((Uf, "Uf"), (Ur, "Ur"), (w, "w"), (sf2, "sf2"), (A, "A"), (Vf, "Vf"), (Vr, "Vr"), (out, "out")):
+            _need(t, torch.float64, n)
+        if Uf.dim() != 2 or Ur.dim() != 2 or Uf.shape[1] != Ur.shape[1]:
+            raise GppError(f"Uf and Ur must be matrices with the same feature count (got {tuple(Uf.shape)}, {tuple(Ur.shape)})")
+        (Mf, D), Mr = Uf.shape, Ur.shape[0]
+        _check_features(D)
+        if min(Mf, Mr, K) < 1:
+            raise GppError(f"post_cross_lin_sq takes M_f, M_r, K >= 1 (got {Mf}, {Mr}, {K})")
+        if not (Uf.is_contiguous() and Ur.is_contiguous()):
+            raise GppError("Uf and Ur must be contiguous")
+        if w.numel() != D or not w.is_contiguous():
+            raise GppError(f"w must be a contiguous vector of {D} weights (got {w.numel()})")
+        if sf2.numel() < 1:
+            raise GppError("sf2 must hold one value")
+        if not (0 <= int(d_split) <= D) or kind not in (KIND_RBF, KIND_MATERN32, KIND_MATERN52):
+            raise GppError(f"bad kernel kind / d_split ({kind}, {d_split}) for {D} features")
+        if d0 < 0 or nd < 1 or d0 + nd > D:
+            raise GppError(f"the observed directions [{d0}, {d0 + nd}) must be a non-empty range inside the {D} features")
+        if A.dim() != 2 or A.stride(1) != 1 or A.shape[0] != Mf or A.shape[1] < 1 + nd or (Mf > 1 and _ld(A) < 1 + nd):
+            raise GppError(f"A is {tuple(A.shape)}: {Mf} functionals of {nd} directions need {Mf} x at least {1 + nd}, "
+                           "unit column stride")
+        for t, n, pts in ((Vf, "Vf", Mf), (Vr, "Vr", Mr)):
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise GppError(f"{n} must be 2-D with unit column stride")
+            rows, cols = (K, pts) if transposed else (pts, K)
+            if t.shape[0] < rows or t.shape[1] < cols or (t.shape[1 if transposed else 0] != pts):
+                raise GppError(f"{n} is {tuple(t.shape)}: post_cross_lin_sq with {pts} points and K = {K} needs "
+                               f"{'at least ' + str(K) + ' x ' + str(pts) if transposed else str(pts) + ' x at least ' + str(K)}")
+            ld = _ld(t)
+            if ld & 1 or ld < cols:
+                raise GppError(f"{n}: the leading dimension ({ld}) must be even and at least {cols}")
+            if t.data_ptr() & 15:
+                raise GppError(f"{n} must be 16-byte aligned")
+        if omega is not None:
+            _need(omega, torch.float64, "omega")
+            if omega.dim() != 1 or omega.numel() != Mr or not omega.is_contiguous():
+                raise GppError(f"omega must be a contiguous vector of {Mr} weights (got {tuple(omega.shape)})")
+        if out.dim() != 1 or out.numel() < Mf or not out.is_contiguous():
+            raise GppError(f"out must be a contiguous vector with room for {Mf} doubles (got {out.numel()})")
+        self.ensure_workspace(OP_POST_CROSS_LIN, Mr, Mf, 0, 0)
+        self._stream()
+        status = self.lib.gpp_post_cross_lin_sq(self.h, Uf.data_ptr(), Mf, Ur.data_ptr(), Mr, D, w.data_ptr(), sf2.data_ptr(),
+                                                int(kind), int(d_split), d0, nd, A.data_ptr(), max(_ld(A), 1 + nd), Vf.data_ptr(),
+                                                _ld(Vf), Vr.data_ptr(), _ld(Vr), K, 1 if transposed else 0, _ptr(omega),
+                                                out.data_ptr())
+        if status == NO_WORKSPACE:
+            raise GppError("gpp_post_cross_lin_sq: the handle's scratch workspace is missing or too small")
+        check(status, "gpp_post_cross_lin_sq")
         return out
 
     # -- knowledge gradient ------------------------------------------------------------------------------------------------------

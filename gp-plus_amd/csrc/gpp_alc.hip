@@ -9,6 +9,9 @@
 // gpp_post_cross_min (gpp.h): out[c][k] = min_r (m_r + nodes_k scale_c c(x_r, x_c)), the reduction of the knowledge gradient's
 // Gauss-Hermite form, by the same product with PostCrossMinEpilogue (gpp_gemm.hip): Q minima per row and column half of a tile go to
 // the workspace, the finish kernel below takes the minimum of a row's records.
+//
+// gpp_post_cross_lin_sq (gpp.h): gpp_post_cross_sq for rows that observe a linear functional of f, a value plus gradient components
+// (the score of a run that returns y and its gradient), by the same product with PostCrossLinEpilogue and the same records and finish.
 #include "../../include/gpp.h"
 #include "gpp_internal.h"
 
@@ -78,6 +81,47 @@ extern "C" int gpp_post_cross_sq(gpp_handle_t h, const double* Uc, int64_t Mc, c
   e.dk = D | (kind << 8) | (d_split << 16);
   if (hipError_t r = gpp_launch_post_cross(h->stream, vt ? 2 : 0, g, e); r != hipSuccess) return alc_rc(r);
   hipLaunchKernelGGL(gpp_post_cross_finish, dim3((unsigned)((Mc + 255) / 256)), dim3(256), 0, h->stream, e.rec, (int)tiles_n, (int)Mc, out);
+  return alc_rc(hipGetLastError());
+}
+
+// rows that are linear functionals of f (value and gradient components at Uf_i): the tiles, records and finish of gpp_post_cross_sq
+extern "C" int gpp_post_cross_lin_sq(gpp_handle_t h, const double* Uf, int64_t Mf, const double* Ur, int64_t Mr, int D, const double* w,
+                                     const double* sf2, int kind, int d_split, int d0, int nd, const double* A, int64_t lda,
+                                     const double* Vf, int64_t ldf, const double* Vr, int64_t ldr, int64_t K, int vt,
+                                     const double* omega, double* out) {
+  if (!h) return -1;
+  if (!Uf) return -2;
+  if (Mf < 1 || Mf > 0x7ffffff0) return -3;
+  if (!Ur) return -4;
+  if (Mr < 1 || Mr > 0x7ffffff0) return -5;
+  if (D < 1 || D > 64) return -6;
+  if (!w) return -7;
+  if (!sf2) return -8;
+  if (kind < 0 || kind > 2) return -9;
+  if (d_split < 0 || d_split > D) return -10;
+  if (d0 < 0 || d0 >= D) return -11;
+  if (nd < 1 || d0 + nd > D) return -12;
+  if (!A) return -13;
+  if (lda < 1 + nd) return -14;
+  if (K < 1 || K > 0x7ffffff0) return -19;
+  if (vt != 0 && vt != 1) return -20;
+  if (!Vf || !alc_aligned16(Vf) || (ldf & 1) || ldf < (vt ? Mf : K)) return -15;
+  if (!Vr || !alc_aligned16(Vr) || (ldr & 1) || ldr < (vt ? Mr : K)) return -17;
+  if (!out) return -22;
+  const int64_t tiles_m = (Mf + 127) / 128, tiles_n = (Mr + 127) / 128;
+  if (tiles_m * tiles_n >= ((int64_t)1 << 31)) return -3;
+  if (!h->ws || h->ws_bytes < gpp_post_cross_ws_bytes(Mf, Mr)) return GPP_NO_WORKSPACE;
+  GemmArgs g{};
+  g.A = Vf; g.B = Vr; g.C = nullptr;
+  g.lda = ldf; g.ldb = ldr;
+  g.M = (int)Mf; g.N = (int)Mr; g.K = (int)K;
+  PostCrossLinArgs e{};
+  e.Uf = Uf; e.Ur = Ur; e.w = w; e.sf2 = sf2; e.omega = omega; e.A = A; e.lda = lda;
+  e.rec = reinterpret_cast<double*>(h->ws);
+  e.dk = D | (kind << 8) | (d_split << 16);
+  e.dn = d0 | (nd << 8);
+  if (hipError_t r = gpp_launch_post_cross_lin(h->stream, vt ? 2 : 0, g, e); r != hipSuccess) return alc_rc(r);
+  hipLaunchKernelGGL(gpp_post_cross_finish, dim3((unsigned)((Mf + 255) / 256)), dim3(256), 0, h->stream, e.rec, (int)tiles_n, (int)Mf, out);
   return alc_rc(hipGetLastError());
 }
 

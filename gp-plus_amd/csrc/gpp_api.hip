@@ -1237,7 +1237,7 @@ size_t gpp_workspace_bytes(gpp_handle_t h, int op, int64_t N, int64_t M, int D, 
   if (op == GPP_OP_APPLY) return gpp_apply_ws_bytes(N, M, S) + 256;
   if (op == GPP_OP_APPLY_GRAD) return gpp_apply_ws_bytes(N, M, D) + 256;
   if (op == GPP_OP_APPEND) return gpp_append_ws_bytes(N, M) + 256;
-  if (op == GPP_OP_POST_CROSS) return gpp_post_cross_ws_bytes(M, N) + 256;
+  if (op == GPP_OP_POST_CROSS || op == GPP_OP_POST_CROSS_LIN) return gpp_post_cross_ws_bytes(M, N) + 256;
   if (op == GPP_OP_POST_CROSS_MIN) return gpp_post_cross_min_ws_bytes(M, N, S) + 256;
   if (op == GPP_OP_POINT_GRAM) return gpp_point_gram_ws_bytes(M, D) + 256;
   if (op == GPP_OP_GEK_GRAD) return gpp_gek_grad_ws_bytes(N, M, D, S) + 256;

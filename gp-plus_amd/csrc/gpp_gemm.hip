@@ -777,6 +777,171 @@ __global__ __launch_bounds__(256, VAR == 2 ? 2 : 1) void gpp_post_cross_f64(Gemm
   gemm_tile<VAR, 64, 64, 2, 16, 2, 2>(p, tm, tn, p.A, p.B, nullptr, nullptr, smem, GemmNoHook(), PostCrossEpilogue<MAT>{e, t, p.N});
 }
 
+// ---- Vf Vr^T whose rows are linear functionals of f: value and gradient components (gpp_post_cross_lin_sq in gpp.h) -------------
+// PostCrossEpilogue with a richer generator: row i observes a_0 f + sum_j a_j df/du_{dlo + j} at Uf_i, a = A[i][0 .. nd], so its
+// prior covariance with f(Ur_r) is a_0 sf2 k + m_0 lin_0 + m_1 lin_1 with the multipliers of gpp_cross_kernel_dx (m_0 = -(e1 h),
+// m_1 = e1 h', e1 = sf2 exp(-r2_rbf), h and h' from the ONE gpp_matern call that also gives k) and, per kernel factor f,
+//   lin_f = sum over the observed dims d of factor f of (a_d g_d) (sa_d - sb_d),   g_d = 2 sqrt(w_d),
+// one rounded product a_d g_d per row and dim and one fma per entry, inside the loop over the staged dims that sums r2 (same
+// staging, same r2 order, same slab idiom, same record).  The entry is
+//   c = fma(a_0 sf2, k, -acc);  c = fma(m_0, lin_0, c);  c = fma(m_1, lin_1, c)
+// in this order: with a = (1, 0, ..., 0) the product a_0 sf2 is sf2, every lin is an exact +0 and adding a zero changes no bit of
+// c^2 — such a row is bit for bit PostCrossEpilogue's (which the compiler contracts to fma(sf2, k, -acc) as well).  A feature with
+// w_d == 0 has g_d == 0 and staged zeros; a row of Uf equal to a row of Ur has sa == sb in every dim: lin is an exact 0 either way.
+// The coefficients do not fit beside the slab (a 128 x 17 table at two work-groups per CU): g_d is staged (DC doubles), a lane
+// reads its two rows' a_d from global memory as the dims come by — M_f (1 + nd) doubles, L2-resident, 16 lanes per address.
+template <bool MAT>
+struct PostCrossLinEpilogue {
+  PostCrossLinArgs e;
+  int tile, Mr;
+  static constexpr int T = 128, DC = 16;
+  static constexpr int SLAB = 2 * DC * T + T + 2 * T + DC;  // doubles in front of the slab
+  static_assert((SLAB & 1) == 0 && (SLAB + 16 * 256) * sizeof(double) <= 2 * 2 * BK16 * ldt_mc(T) * sizeof(double) &&
+                    (SLAB + 16 * 256) * sizeof(double) <= 2 * 2 * T * LDK * sizeof(double),
+                "the epilogue lives in the main loop's LDS");
+  __device__ __forceinline__ void operator()(const v4d (&acc4)[4][4], int row0, int col0, int Mf, double* __restrict__ smem) const {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64, li = lane & 15, lk = lane >> 4;
+    const int D = e.dk & 255, kind = (e.dk >> 8) & 255;
+    const int dsp = (!MAT || kind == 0) ? D : (e.dk >> 16);  // dims below go to the RBF factor, the others to the Matern factor
+    const int dlo = e.dn & 255, dhi = dlo + (e.dn >> 8);     // the observed directions [dlo, dhi)
+    double* __restrict__ sa = smem;           // staged features of the tile's rows (functionals), [d][r], times sqrt(w_d)
+    double* __restrict__ sb = sa + DC * T;    // ... of its columns (reference points)
+    double* __restrict__ som = sb + DC * T;   // omega of the columns, 0 beyond M_r
+    double* __restrict__ rs = som + T;        // [2 column halves][T] row sums
+    double* __restrict__ sg = rs + 2 * T;     // g_d = 2 sqrt(w_d) of the staged dims
+    double* __restrict__ slab = smem + SLAB;  // [16 values][256 lanes]
+    // (parked in VGPRs as in PostCrossEpilogue)
+    const double* __restrict__ Uf = e.Uf;
+    const double* __restrict__ Ur = e.Ur;
+    const double* __restrict__ wp = e.w;
+    const double* __restrict__ Ap = e.A + (int64_t)row0 * e.lda;
+    double* __restrict__ rec = e.rec + (int64_t)tile * T;
+    Uf += (int64_t)row0 * (e.dk & 255);
+    Ur += (int64_t)col0 * (e.dk & 255);
+    int rlim = Mf - row0, clim = Mr - col0;  // rows / columns of the tile inside the block
+    int64_t lda = e.lda;
+    asm volatile("" : "+v"(Uf), "+v"(Ur), "+v"(wp), "+v"(Ap), "+v"(lda), "+v"(rec), "+v"(rlim), "+v"(clim));
+    auto stage = [&](int d0) {
+      for (int x = tid; x < DC * T; x += 256) {
+        const int dd = x / T, r = x - dd * T, d = d0 + dd;
+        const bool okd = d < D;
+        const double sw = okd ? sqrt(wp[okd ? d : 0]) : 0.0;
+        sa[x] = (okd && r < rlim) ? Uf[r * D + d] * sw : 0.0;
+        sb[x] = (okd && r < clim) ? Ur[r * D + d] * sw : 0.0;
+        if (r == 0) sg[dd] = 2.0 * sw;
+      }
+    };
+    if (tid < T) som[tid] = (tid < clim) ? (e.omega ? e.omega[col0 + tid] : 1.0) : 0.0;
+    const bool one = (D <= DC);  // work-group uniform
+    if (one) stage(0);
+    __syncthreads();
+
+    const double sf2 = *e.sf2;
+    const GppExpConsts ec = gpp_exp_consts();
+#pragma unroll
+    for (int a4 = 0; a4 < 4; ++a4) {
+#pragma unroll
+      for (int v = 0; v < 4; ++v)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) slab[(v * 4 + b) * 256 + tid] = acc4[a4][b][v];
+#pragma unroll 1
+      for (int h = 0; h < 2; ++h) {
+        const int ra = wm + 16 * a4 + 8 * h + lk;  // this half's rows inside the tile: ra and ra + 4
+        const int cb = wn + li;                    // its columns: cb + 16 b
+        // the two rows' coefficients; a row beyond M_f has none (never read) and counts as all zeros
+        const bool okr[2] = {ra < rlim, ra + 4 < rlim};
+        const double* __restrict__ pa[2] = {Ap + (okr[0] ? ra : 0) * lda, Ap + (okr[1] ? ra + 4 : 0) * lda};
+        double r2[2][4], r2m[MAT ? 2 : 1][MAT ? 4 : 1], lin[2][4], linm[MAT ? 2 : 1][MAT ? 4 : 1];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            r2[a][b] = 0.0;
+            lin[a][b] = 0.0;
+            if (MAT) r2m[MAT ? a : 0][MAT ? b : 0] = 0.0;
+            if (MAT) linm[MAT ? a : 0][MAT ? b : 0] = 0.0;
+          }
+#pragma unroll 1
+        for (int d0 = 0; d0 < D; d0 += DC) {
+          if (!one) {
+            __syncthreads();  // (every wave has read the previous chunk)
+            stage(d0);
+            __syncthreads();
+          }
+          const int nd = min(DC, D - d0);
+#pragma unroll 1
+          for (int dd = 0; dd < nd; ++dd) {
+            const int d = d0 + dd;
+            const double ua[2] = {sa[dd * T + ra], sa[dd * T + ra + 4]};
+            const bool second = MAT && (d >= dsp);
+            const bool obs = d >= dlo && d < dhi;  // (uniform)
+            double t[2] = {0.0, 0.0};
+            if (obs) {
+              const double g = sg[dd];
+#pragma unroll
+              for (int a = 0; a < 2; ++a) t[a] = okr[a] ? pa[a][1 + d - dlo] * g : 0.0;
+            }
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+              const double ub = sb[dd * T + cb + 16 * b];
+#pragma unroll
+              for (int a = 0; a < 2; ++a) {
+                const double df = ua[a] - ub;
+                if (MAT && second) r2m[MAT ? a : 0][MAT ? b : 0] = fma(df, df, r2m[MAT ? a : 0][MAT ? b : 0]);
+                else r2[a][b] = fma(df, df, r2[a][b]);
+                if (obs) {
+                  if (MAT && second) linm[MAT ? a : 0][MAT ? b : 0] = fma(t[a], df, linm[MAT ? a : 0][MAT ? b : 0]);
+                  else lin[a][b] = fma(t[a], df, lin[a][b]);
+                }
+              }
+            }
+          }
+        }
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+          const double a0s = (okr[a] ? pa[a][0] : 0.0) * sf2;
+          double s = 0.0;
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            const double ex = gpp_exp_nonpos(-r2[a][b], ec);
+            const double e1 = sf2 * ex;
+            double kv = ex, m0, m1 = 0.0;
+            if (MAT) {
+              const GppMatern m = gpp_matern(kind, r2m[MAT ? a : 0][MAT ? b : 0], ec);
+              const double hm = m.p * m.er;
+              kv = ex * hm;
+              m0 = -(e1 * hm);
+              m1 = e1 * (m.dp * m.er);
+            } else {
+              m0 = -e1;
+            }
+            double c = __builtin_fma(a0s, kv, -slab[((2 * h + a) * 4 + b) * 256 + tid]);
+            c = __builtin_fma(m0, lin[a][b], c);
+            if (MAT) c = __builtin_fma(m1, linm[MAT ? a : 0][MAT ? b : 0], c);
+            double t = c * c;
+            t = (cb + 16 * b < clim) ? t : 0.0;  // (a select: whatever a column beyond M_r holds never reaches a sum)
+            s = fma(som[cb + 16 * b], t, s);
+          }
+#pragma unroll
+          for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o);  // the 16 lanes (li) that share this row
+          if (li == 0) rs[(wave & 1) * T + ra + 4 * a] = s;
+        }
+      }
+    }
+    __syncthreads();
+    if (tid < T) rec[tid] = rs[tid] + rs[T + tid];
+  }
+};
+
+template <int VAR, bool MAT>
+__global__ __launch_bounds__(256, VAR == 2 ? 2 : 1) void gpp_post_cross_lin_f64(GemmArgs p, PostCrossLinArgs e) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int t = (int)blockIdx.x;
+  const int tm = t / p.tiles_n, tn = t - tm * p.tiles_n;
+  gemm_tile<VAR, 64, 64, 2, 16, 2, 2>(p, tm, tn, p.A, p.B, nullptr, nullptr, smem, GemmNoHook(), PostCrossLinEpilogue<MAT>{e, t, p.N});
+}
+
 // ---- Vc Vr^T with the minima of affine images of the posterior cross-covariance as its epilogue (gpp_post_cross_min in gpp.h) -----
 // The knowledge gradient's reduction: for every node k < Q, min_r (m_r + t_ck c_cr) with c = g - acc as in PostCrossEpilogue (the
 // same staging, r2 order, exponential and Matern factors) and t_ck = nodes[k] * scale[c], one rounded product per row and node.
@@ -1251,6 +1416,34 @@ hipError_t gpp_launch_post_cross(hipStream_t s, int variant, const GemmArgs& a_i
   const size_t bytes = gemm_lds_bytes(variant, 128, 128, 16, 2);
   auto* fn = variant == 2 ? (mat ? gpp_post_cross_f64<2, true> : gpp_post_cross_f64<2, false>)
                           : (mat ? gpp_post_cross_f64<0, true> : gpp_post_cross_f64<0, false>);
+  static std::atomic<bool> attr_set[4][64];  // per instantiation and device
+  int dev = 0;
+  hipError_t err = hipGetDevice(&dev);
+  if (err != hipSuccess) return err;
+  const int which = (variant == 2 ? 2 : 0) + (mat ? 1 : 0);
+  if (dev < 0 || dev >= 64 || !attr_set[which][dev]) {
+    err = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (err != hipSuccess) return err;
+    if (dev >= 0 && dev < 64) attr_set[which][dev] = true;
+  }
+  hipLaunchKernelGGL(fn, dim3((unsigned)nt), dim3(256), bytes, s, a, e);
+  return hipGetLastError();
+}
+
+// as gpp_launch_post_cross; e.dn carries the observed directions
+hipError_t gpp_launch_post_cross_lin(hipStream_t s, int variant, const GemmArgs& a_in, const PostCrossLinArgs& e) {
+  GemmArgs a = a_in;
+  const int D = e.dk & 255, dlo = e.dn & 255, dnum = e.dn >> 8;
+  if (a.M <= 0 || a.N <= 0 || a.K <= 0 || (variant != 0 && variant != 2) || dnum < 1 || dlo + dnum > D || e.lda < 1 + dnum)
+    return hipErrorInvalidValue;
+  a.tiles_m = (a.M + 127) / 128;
+  a.tiles_n = (a.N + 127) / 128;
+  const int64_t nt = (int64_t)a.tiles_m * a.tiles_n;
+  if (nt >= (int64_t)1 << 31) return hipErrorInvalidValue;
+  const bool mat = ((e.dk >> 8) & 255) != 0;
+  const size_t bytes = gemm_lds_bytes(variant, 128, 128, 16, 2);
+  auto* fn = variant == 2 ? (mat ? gpp_post_cross_lin_f64<2, true> : gpp_post_cross_lin_f64<2, false>)
+                          : (mat ? gpp_post_cross_lin_f64<0, true> : gpp_post_cross_lin_f64<0, false>);
   static std::atomic<bool> attr_set[4][64];  // per instantiation and device
   int dev = 0;
   hipError_t err = hipGetDevice(&dev);

@@ -296,6 +296,22 @@ struct PostCrossArgs {
 hipError_t gpp_launch_post_cross(hipStream_t s, int variant, const GemmArgs& p, const PostCrossArgs& e);
 size_t gpp_post_cross_ws_bytes(int64_t Mc, int64_t Mr);  // gpp_alc.hip
 
+// The same product and record scheme for rows that are LINEAR functionals of f at their point (gpp_gemm.hip; gpp_post_cross_lin_sq
+// in gpp.h): row i observes A[i][0] f + sum_j A[i][1 + j] df/du_{d0 + j} at Uf_i
+struct PostCrossLinArgs {
+  const double* Uf;     // M_f x D features, row-major
+  const double* Ur;     // M_r x D
+  const double* w;      // D weights
+  const double* sf2;
+  const double* omega;  // M_r weights, or null for all ones
+  const double* A;      // M_f x lda coefficients, row-major; the columns [1 + nd, lda) are never read
+  int64_t lda;
+  double* rec;          // [tiles_m][tiles_n][128]
+  int dk;               // D | kind << 8 | d_split << 16
+  int dn;               // d0 | nd << 8
+};
+hipError_t gpp_launch_post_cross_lin(hipStream_t s, int variant, const GemmArgs& p, const PostCrossLinArgs& e);
+
 // The same product whose epilogue is min_r (m_r + nodes_k scale_c c_cr) for Q nodes (gpp_gemm.hip; gpp_post_cross_min in gpp.h):
 // the column half `half` of tile (tm, tn) leaves the minima of its 128 rows at rec[(((tm tiles_n + tn) 2 + half) 128 + row) Q + k]
 struct PostCrossMinArgs {

@@ -10,7 +10,8 @@ from .gpcore.distributions import DenseCovariance, MultivariateNormal
 from .gpcore.module import Module
 from .utils import data_type_check
 
-__all__ = ["GRADIENT_NUGGET_REL", "GradientEnhancedPosterior", "condition_on_gradients", "check_gradient_observations"]
+__all__ = ["GRADIENT_NUGGET_REL", "GradientEnhancedPosterior", "condition_on_gradients", "check_gradient_observations",
+           "check_gradient_run", "variance_reduction_of_runs"]
 
 #: ``noise=None``: the variance given to a gradient observation, as a fraction of the prior curvature of its direction (the prior
 #: variance of that component of the gradient, ``linalg.gradient_prior_curvature``).
@@ -20,10 +21,10 @@ GRADIENT_NUGGET_REL = 1e-6
 class GradientEnhancedPosterior:
     """The posterior of a fitted model conditioned on its own training data AND on gradient observations, as returned by
     ``GP_Plus.condition_on_gradients``.  It offers ``predict`` and ``predict_gradient`` with the conventions of the model's own, and
-    the attributes ``num_function_rows`` (N), ``num_gradient_points`` (Mg), ``num_gradient_observations`` (q: Mg p, or the number of
-    observed components when an ``observed=`` mask was given) and ``observed`` (the (Mg, p) bool mask).  Nothing else: no further
-    conditioning, no sampling, no leave-one-out or cross-validation, no acquisition scores, no joint covariance, no hyperparameter
-    training on the gradient data.  It holds a detached copy of the model (parameters, training inputs, no N x N factors) for the features, prior means and
+    ``variance_reduction`` (where to run next, with or without gradients), the attributes ``num_function_rows`` (N),
+    ``num_gradient_points`` (Mg), ``num_gradient_observations`` (q: Mg p, or the number of observed components when an ``observed=``
+    mask was given) and ``observed`` (the (Mg, p) bool mask).  Nothing else: no further conditioning, no sampling, no leave-one-out or
+    cross-validation, no knowledge gradient, no joint covariance, no hyperparameter training on the gradient data.  It holds a detached copy of the model (parameters, training inputs, no N x N factors) for the features, prior means and
     noise of test rows: refitting or modifying the model it came from does not change it."""
 
     def __init__(self, model, gcache):
@@ -90,6 +91,15 @@ class GradientEnhancedPosterior:
             if return_std:
                 return mean * scale, var.clamp_min(0.0).sqrt() * scale.abs()
             return mean * scale
+
+
+    def variance_reduction(self, Xcand, Xref, weights=None, gradient=None, gradient_noise=None):
+        """``GP_Plus.variance_reduction`` from this posterior, with the same arguments, units and refusals.  ``gradient=None``: the
+        expected reduction of the weighted posterior variance over ``Xref`` from ONE noisy function value at each row of ``Xcand``
+        (M_c scores; gpp_post_cross_sq on operands of N + q coordinates).  ``gradient=True`` or a length-p bool mask: the pair
+        (scores of a run that returns y and those gradient components, scores of the value alone), by
+        ``linalg.variance_reduction_block``.  Nothing is conditioned: the posterior stays as it is."""
+        return variance_reduction_of_runs(self._model, self._cache, Xcand, Xref, weights, gradient, gradient_noise)
 
 
 def _check_observed_mask(observed, Mg: int, p: int, what: str):
@@ -199,3 +209,100 @@ def condition_on_gradients(model, X, dY, noise=None, observed=None) -> GradientE
         child = model._copy_without_factors()
         child.eval()
     return GradientEnhancedPosterior(child, gcache)
+
+
+def check_gradient_run(model, gradient, gradient_noise, Mc: int, what: str):
+    """The host-side validation of ``variance_reduction(..., gradient=, gradient_noise=)``: returns (mask, noise) with ``mask`` a host
+    bool (p) tensor of the gradient components a run returns (``gradient=True``: all p quantitative columns) and ``noise`` an fp64
+    (Mc, p) tensor in (y per input unit)^2, or None for ``GRADIENT_NUGGET_REL`` times the prior curvature.  ``ValueError`` for a model
+    without a quantitative column, ``gradient=False``, a mask that is not one, of another length or without a True, and noise that
+    does not broadcast to (Mc, p), is not finite or is negative under the mask (what lies under a False is not read)."""
+    p = int(model.quant_index.numel())
+    if p == 0:
+        raise ValueError(f"{what}: the model has no quantitative input column to differentiate")
+    if gradient is True:
+        mask = torch.ones(p, dtype=torch.bool)
+    elif gradient is False:
+        raise ValueError(f"{what}: gradient must be None (a run returns y alone), True or a bool mask of the {p} quantitative columns")
+    else:
+        g = gradient.detach().cpu() if torch.is_tensor(gradient) else torch.as_tensor(np.asarray(gradient))
+        if g.dim() != 1 or g.shape[0] != p:
+            raise ValueError(f"{what}: gradient must be True or a bool mask of length {p}, one entry per quantitative column: the same "
+                             f"directions at every candidate (got shape {tuple(g.shape)})")
+        mask = _check_observed_mask(g.reshape(1, p), 1, p, what)[0]
+    noise = gradient_noise
+    if noise is not None:
+        noise = noise.detach().cpu().to(torch.float64) if torch.is_tensor(noise) else torch.as_tensor(np.asarray(noise, dtype=np.float64))
+        try:
+            noise = torch.broadcast_to(noise, (Mc, p))
+        except RuntimeError:
+            raise ValueError(f"{what}: gradient_noise must be a scalar, a row of {p} or ({Mc}, {p}) (got {tuple(noise.shape)})") from None
+        noise = torch.where(mask, noise, torch.zeros((), dtype=noise.dtype))
+        if not bool(torch.isfinite(noise).all()) or bool((noise < 0).any()):
+            raise ValueError(f"{what}: the gradient noise variances must be finite and not negative")
+    return mask, noise
+
+
+def variance_reduction_of_runs(model, cache, Xcand, Xref, weights=None, gradient=None, gradient_noise=None):
+    """The work behind ``GP_Plus.variance_reduction(..., gradient=)`` (``cache`` None: the model's own prediction cache) and
+    ``GradientEnhancedPosterior.variance_reduction`` (``cache``: its ``GradientFactorCache``; ``model``: its copy of the model).
+    Everything is validated on the host before any device work; results in y^2 units."""
+    from . import settings as gpp_settings
+    from .backend import get_context
+    from .linalg import gradient_prior_curvature, variance_reduction_block, variance_reduction_from_gradient_cache
+
+    what = "variance_reduction"
+    Xc, Xr = model._alc_rows(Xcand, "Xcand"), model._alc_rows(Xref, "Xref")
+    Mc, Mr = Xc.shape[0], Xr.shape[0]
+    if weights is not None:
+        weights = data_type_check(weights).reshape(-1).to(torch.float64)
+        if weights.shape[0] != Mr:
+            raise ValueError(f"{what}: {weights.shape[0]} weights for {Mr} reference rows")
+        if not bool(torch.isfinite(weights).all()) or bool((weights < 0).any()):
+            raise ValueError(f"{what}: the weights must be finite and non-negative")
+        if not bool((weights > 0).any()):
+            raise ValueError(f"{what}: the weights are all zero")
+    if gradient is None:
+        if gradient_noise is not None:
+            raise ValueError(f"{what}: gradient_noise without gradient= (a run that returns y alone has no gradient noise)")
+        mask = noise = None
+    else:
+        mask, noise = check_gradient_run(model, gradient, gradient_noise, Mc, what)
+    if gpp_settings.sharded_evaluation.value() is not None:
+        raise NotImplementedError(f"{what} is not available under settings.sharded_evaluation")
+    train_x = model.train_inputs[0]
+    get_context(train_x.device)  # (raises for anything but a GPU: there is no CPU path)
+
+    Xc, Xr = Xc.to(train_x), Xr.to(train_x)
+    model.eval()
+    with torch.no_grad():
+        if cache is None:
+            cache = model._ensure_prediction_cache()
+        out_c = Module.__call__(model, Xc)
+        Uc = out_c.lazy_covariance_matrix.U1
+        Ur = Module.__call__(model, Xr).lazy_covariance_matrix.U1
+        lik = model.likelihood
+        swap = hasattr(lik, "fidel_indices")
+        if swap:  # the noise of each candidate's own source, as condition_on gives a new row
+            saved, lik.fidel_indices = lik.fidel_indices, Xc[:, -1]
+        try:
+            noisy = lik(out_c).lazy_covariance_matrix
+        finally:
+            if swap:
+                lik.fidel_indices = saved
+        tau = noisy.tau.detach().reshape(-1).to(torch.float64)
+        tau_c = tau[noisy.grp.long()] if noisy.grp is not None else tau[:1].expand(Mc)
+        dev = train_x.device
+        omega = None if weights is None else weights.to(dev)
+        scale = model.y_std.detach().to(torch.float64) ** 2
+        if mask is None:
+            return variance_reduction_from_gradient_cache(cache, Uc, tau_c, Ur, omega=omega) * scale
+        p = int(mask.numel())
+        d0 = Uc.shape[1] - p
+        dirs = [d0 + int(j) for j in mask.nonzero().reshape(-1)]
+        if noise is None:
+            gnoise = (GRADIENT_NUGGET_REL * gradient_prior_curvature(cache.spec, d0, p))[mask.to(dev)].expand(Mc, len(dirs))
+        else:
+            gnoise = noise[:, mask].to(dev) / scale
+        with_g, value = variance_reduction_block(cache, Uc, tau_c, gnoise.contiguous(), dirs, Ur, omega=omega)
+        return with_g * scale, value * scale

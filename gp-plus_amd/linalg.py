@@ -1052,8 +1052,10 @@ class GradientFactorCache:
     (``append_gradients_to_cache``): row N + a nd + j is d f / du_{d0+j} at the feature row ``Ug[a]``.  With a selection ``sel``
     (``backend.GradientSelection``: partial gradients) q = sel.q and row N + k is its observation k, the direction sel.dir[k] at the
     point that owns k.  It owns its matrices (never stale) and is deliberately NOT a ``FactorCache``: its last q rows are not
-    function values, so nothing that reads a ``FactorCache`` (prediction, appends, scores, sampling) may take it.
-    ``predict_from_gradient_cache`` is its only consumer."""
+    function values, so nothing that reads a ``FactorCache`` (prediction, appends, scores, sampling) may take it.  Its consumers
+    are ``predict_from_gradient_cache``, ``variance_reduction_from_gradient_cache`` (plain ALC from the gradient-enhanced posterior)
+    and ``variance_reduction_block`` (the score of a run that returns y and gradient components), which build their (N + q)-row
+    operands with the same helpers (``_gek_function_operand``, ``_gek_gradient_tail``)."""
 
     def __init__(self, gctx, own, n, q, z, alpha, U, Ug, d0, nd, spec, jitter, sel=None):
         self.gctx, self._own = gctx, own
@@ -1145,6 +1147,33 @@ def append_gradients_to_cache(cache: FactorCache, Ug, d0: int, nd: int, r_g, noi
         return GradientFactorCache(gctx, own, n, q, z, alpha, cache.U, Ug, d0, nd, spec, cache.jitter, sel)
 
 
+def _gek_function_tail(gcache: "GradientFactorCache", Us) -> torch.Tensor:
+    """cov(f(Us_a), gradient observation k) as an M x q matrix: gpp_cross_kernel_dx(Ua = Ug, Ub = Us), the observations of the cache's
+    selection as columns (what ``predict_from_gradient_cache`` and ``variance_reduction_block`` transpose into a function column)."""
+    spec = gcache.spec
+    return gcache.gctx.cross_kernel_dx(gcache.Ug, Us, spec.w, spec.sf2.reshape(1), gcache.d0, gcache.nd,
+                                       rows_buffer(Us.shape[0], gcache.q, Us.device), kind=spec.kind, d_split=spec.d_split,
+                                       sel=gcache.sel)
+
+
+def _gek_function_operand(gcache: "GradientFactorCache", Us) -> torch.Tensor:
+    """The (N + q) x M operand of gpp_predict_tn for the latent f at ``Us``: rows [0, N) = gpp_cross_kernel(U, Us), rows [N, N + q) =
+    ``_gek_function_tail`` transposed."""
+    spec, N = gcache.spec, gcache.U.shape[0]
+    op = rows_buffer(N + gcache.q, Us.shape[0], Us.device)
+    gcache.gctx.cross_kernel(gcache.U, Us, spec.w, spec.sf2.reshape(1), op[:N], kind=spec.kind, d_split=spec.d_split)
+    gcache.gctx.transpose(_gek_function_tail(gcache, Us), op[N:])
+    return op
+
+
+def _gek_gradient_tail(gcache: "GradientFactorCache", Us, out, sel_b=None) -> torch.Tensor:
+    """cov(gradient observation k, d f / du_{d0+l}(Us_a)) into ``out`` (q x (M nd), or with the selection ``sel_b`` of the test
+    side's (point, direction) entries q x sel_b.q): gpp_kernel_dxdx(Ug, Us) on the cache's selection of its own side."""
+    spec = gcache.spec
+    return gcache.gctx.kernel_dxdx(gcache.Ug, Us, spec.w, spec.sf2.reshape(1), gcache.d0, gcache.nd, out, kind=spec.kind,
+                                   d_split=spec.d_split, sel_a=gcache.sel, sel_b=sel_b)
+
+
 @torch.no_grad()
 def predict_from_gradient_cache(gcache: GradientFactorCache, Us, want: str = "function"):
     """Posterior at the feature rows ``Us`` (M x D) from a ``GradientFactorCache``, in the cache's scaled units, by gpp_predict_tn on
@@ -1169,16 +1198,12 @@ def predict_from_gradient_cache(gcache: GradientFactorCache, Us, want: str = "fu
         if Us.dim() != 2 or Us.shape[0] < 1 or Us.shape[1] != D:
             raise ValueError(f"the test points must be at least one row of {D} features (got {tuple(Us.shape)})")
         M, d0, nd = Us.shape[0], gcache.d0, gcache.nd
-        q, sel = gcache.q, gcache.sel  # (the test side stays dense: all nd directions at every test point)
+        q = gcache.q  # (the test side stays dense: all nd directions at every test point)
         spec = gcache.spec
         w, sf2 = spec.w, spec.sf2.reshape(1)
         if want == "function":
-            op = rows_buffer(N + q, M, dev)
             with _stage("gek_operands"):
-                gctx.cross_kernel(gcache.U, Us, w, sf2, op[:N], kind=spec.kind, d_split=spec.d_split)
-                Dsg = gctx.cross_kernel_dx(gcache.Ug, Us, w, sf2, d0, nd, rows_buffer(M, q, dev), kind=spec.kind, d_split=spec.d_split,
-                                           sel=sel)
-                gctx.transpose(Dsg, op[N:])
+                op = _gek_function_operand(gcache, Us)
             mean = torch.empty(M, dtype=torch.float64, device=dev)
             var = torch.empty(M, dtype=torch.float64, device=dev)
             with _stage("gek_predict_tn"):
@@ -1195,13 +1220,219 @@ def predict_from_gradient_cache(gcache: GradientFactorCache, Us, want: str = "fu
             v_c = torch.empty(mc * nd, dtype=torch.float64, device=dev)
             with _stage("gek_operands"):
                 gctx.cross_kernel_dx(Us[a0:a0 + mc], gcache.U, w, sf2, d0, nd, op[:N], kind=spec.kind, d_split=spec.d_split)
-                gctx.kernel_dxdx(gcache.Ug, Us[a0:a0 + mc], w, sf2, d0, nd, op[N:], kind=spec.kind, d_split=spec.d_split, sel_a=sel)
+                _gek_gradient_tail(gcache, Us[a0:a0 + mc], op[N:])
             with _stage("gek_predict_tn"):
                 gctx.predict_tn(gcache.Linv, gcache.z, op, kappa.repeat(mc), rows_buffer(mc * nd, N + q, dev), g_c, v_c)
             del op
             mean[a0:a0 + mc] = g_c.view(mc, nd)
             var[a0:a0 + mc] = v_c.view(mc, nd)
         return mean, var
+
+
+#: Most bytes each of the chunk-sized buffers of ``variance_reduction_block`` may take (the operand block, V, the whitened V and its
+#: transpose; ``GRAD_CHUNK_BYTES`` idiom): the candidates go in chunks of as many as fit, at least one.  MEASURED (tools/
+#: bench_alc_gradient.py, N = 20 000, M_c x M_r = 4096 x 4096, all 8 gradient components: b = 9): the whole score takes 1088 / 537 / 415 ms
+#: at 64 / 256 / 1024 MiB (46 / 184 / 744 candidates per chunk) — gpp_predict_tn on a chunk's columns 672 / 336 / 257 ms and the fused
+#: launch 341 / 144 / 103 ms: both want some thousands of rows per call.  At 1 GiB a call holds about 5 GiB of temporaries.
+ALC_GRADIENT_CHUNK_BYTES = 1024 << 20
+
+
+def _alc_gradient_chunk_points(K: int, b: int) -> int:
+    mc = max(1, ALC_GRADIENT_CHUNK_BYTES // (8 * b * row_stride(K)))
+    while mc > 1 and 8 * K * row_stride(mc * b) > ALC_GRADIENT_CHUNK_BYTES:
+        mc -= 1
+    return mc
+
+
+def _function_operand_V(cache, Us, transposed: bool):
+    """(V or V^T, latent variance) of the latent f at ``Us`` from a ``FactorCache`` (``_cross_operands``) or a ``GradientFactorCache``
+    (K = N + q coordinates): the operand of gpp_post_cross_sq / gpp_post_cross_lin_sq, points x K or with ``transposed`` K x points."""
+    if not isinstance(cache, GradientFactorCache):
+        return _cross_operands(cache, (Us,), cache.U.shape[0], transposed)[0]
+    dev, gctx = Us.device, cache.gctx
+    M, K = Us.shape[0], cache.U.shape[0] + cache.q
+    op = _gek_function_operand(cache, Us)
+    V = rows_buffer(M, K, dev)
+    mean = torch.empty(M, dtype=torch.float64, device=dev)
+    var = torch.empty(M, dtype=torch.float64, device=dev)
+    gctx.predict_tn(cache.Linv, cache.z, op, cache.spec.sf2.reshape(1).expand(M).contiguous(), V, mean, var)
+    if not transposed:
+        return V, var
+    del op
+    Vt = rows_buffer(K, M, dev)
+    gctx.transpose(V, Vt)
+    return Vt, var
+
+
+def _alc_common(what: str, cache, Uc, tau_c, Ur, omega):
+    """The checks ``variance_reduction_from_gradient_cache`` and ``variance_reduction_block`` share: (Uc, tau_c, Ur, omega) on the
+    cache's device, fp64 and contiguous; ``omega`` None: 1 / M_r each."""
+    dev, D = cache.U.device, cache.U.shape[1]
+    Uc, Ur = _as_f64(Uc.detach(), dev).contiguous(), _as_f64(Ur.detach(), dev).contiguous()
+    for U, name in ((Uc, "candidates"), (Ur, "reference points")):
+        if U.dim() != 2 or U.shape[0] < 1 or U.shape[1] != D:
+            raise ValueError(f"{what}: the {name} must be at least one row of {D} features (got {tuple(U.shape)})")
+    Mc, Mr = Uc.shape[0], Ur.shape[0]
+    tau_c = _as_f64(tau_c.detach().reshape(-1), dev)
+    if tau_c.numel() != Mc:
+        raise ValueError(f"{what}: {tau_c.numel()} noise levels for {Mc} candidates")
+    if omega is None:
+        omega = torch.full((Mr,), 1.0 / Mr, dtype=torch.float64, device=dev)
+    else:
+        omega = _as_f64(omega.detach().reshape(-1), dev).contiguous()
+        if omega.numel() != Mr:
+            raise ValueError(f"{what}: {omega.numel()} weights for {Mr} reference points")
+    return Uc, tau_c, Ur, omega
+
+
+@torch.no_grad()
+def variance_reduction_from_gradient_cache(gcache: GradientFactorCache, Uc, tau_c, Ur, omega=None, transposed: Optional[bool] = None):
+    """First-round scores of ``variance_reduction`` (one noisy function value per candidate) from a gradient-enhanced posterior:
+    gpp_post_cross_sq on operands of K = N + q coordinates, dV(c) = sum_r omega_r c(x_r, x_c)^2 / (c(x_c, x_c) + tau_c + jitter).
+    M_c scores in the cache's scaled units; the cache is only read.  Refused under ``settings.sharded_evaluation`` and inside a graph
+    capture."""
+    what = "variance_reduction_from_gradient_cache"
+    _gradient_cache_refusals(what)
+    dev, gctx = gcache.U.device, gcache.gctx
+    transposed = ALC_TRANSPOSED if transposed is None else bool(transposed)
+    with torch.cuda.device(dev) if dev.type == "cuda" else nullcontext():
+        _gradient_cache_refusals(what, dev)
+        Uc, tau_c, Ur, omega = _alc_common(what, gcache, Uc, tau_c, Ur, omega)
+        spec, K = gcache.spec, gcache.U.shape[0] + gcache.q
+        with _stage("alc_operands"):
+            (Vc, var_c), (Vr, _) = _function_operand_V(gcache, Uc, transposed), _function_operand_V(gcache, Ur, transposed)
+        num = torch.empty(Uc.shape[0], dtype=torch.float64, device=dev)
+        with _stage("post_cross_sq"):
+            gctx.post_cross_sq(Uc, Ur, spec.w, spec.sf2.reshape(1), Vc, Vr, K, num, omega=omega, kind=spec.kind, d_split=spec.d_split,
+                               transposed=transposed)
+        return num / (var_c.clamp_min(0.0) + tau_c + gcache.jitter)
+
+
+@torch.no_grad()
+def variance_reduction_block(cache, Uc, tau_c, gnoise, dirs, Ur, omega=None, transposed: Optional[bool] = None):
+    """Expected reduction of the omega-weighted posterior variance of the latent f over ``Ur`` (M_r x D) from ONE run at each candidate
+    ``Uc`` (M_c x D) that returns a noisy function value AND noisy gradient components: the b = 1 + p' linear functionals
+    l_0 = f(x_c), l_j = d f / du_{dirs[j-1]}(x_c).  With c_r (b) the posterior cross-covariance of f(x_r) with the functionals and S_c
+    (b x b) their posterior covariance plus the observation diagonal,
+        dV(c) = sum_r omega_r c_r^T S_c^-1 c_r = sum_{i < b} sum_r omega_r (W_c c_r)_i^2,      S_c = L_c L_c^T,  W_c = L_c^-1,
+    whatever the observed values.  Row i of W_c is itself a linear functional at x_c, so the b sums of a candidate are b rows of ONE
+    gpp_post_cross_lin_sq launch on the whitened explained part W_c V_c: the M_c b x M_r block never exists.
+
+    ``cache``: a ``FactorCache``, or a ``GradientFactorCache`` (the score from a gradient-enhanced posterior, K = N + q coordinates).
+    ``dirs``: the observed directions, a strictly increasing list of feature columns (inside the cache's differentiated range
+    [d0, d0 + nd) for a ``GradientFactorCache``); one set serves every candidate of a call.  ``tau_c`` (M_c) and ``gnoise`` (M_c x p'):
+    the noise variances of the value and of the gradient components;
+        S_c = blockdiag(sf2, diag kappa_dirs) - G_c + diag(tau_c + jitter, gnoise + jitter),        G_c = V_c V_c^T,
+    the diagonal ``append_to_cache`` and ``append_gradients_to_cache`` add: the score equals what conditioning would do.  Per chunk of
+    candidates (``ALC_GRADIENT_CHUNK_BYTES``): the raw operand block ((N or N + q) x (m_c b) columns, candidate-major: the function
+    column by ``cross_kernel``, the gradient columns by gpp_cross_kernel_dx on a selection of ``dirs``, the last q rows of a gradient
+    cache by the helpers of ``predict_from_gradient_cache``), gpp_predict_tn for V, gpp_point_gram with group size b for G_c (b <= 16;
+    ``torch.bmm`` above), a batched Cholesky and triangular inverse on the host side (N m_c b^2 flops for W_c V_c against
+    N^2 m_c b for V), the transposition under ``ALC_TRANSPOSED``, one fused launch, and the sum of each candidate's b rows.  The
+    reference operand V_r is computed once.
+
+    Returns (the M_c scores of the run with gradients, the M_c scores of the value alone: row 0 of each block, the first-round score
+    of ``variance_reduction``), in the cache's scaled units.  ``errors.NotPSDError`` when a candidate's S_c is not positive definite
+    (it names the candidate): pass more noise.  The cache is only read.  Refused under ``settings.sharded_evaluation`` and inside a
+    graph capture, like ``variance_reduction``."""
+    from .backend import GradientSelection
+    from .errors import NotPSDError
+
+    what = "variance_reduction_block"
+    _gradient_cache_refusals(what)
+    is_g = isinstance(cache, GradientFactorCache)
+    dev, gctx = cache.U.device, cache.gctx
+    on_gpu = dev.type == "cuda"  # (anything else only under a stand-in context: the library itself has no CPU path)
+    transposed = ALC_TRANSPOSED if transposed is None else bool(transposed)
+    with torch.cuda.device(dev) if on_gpu else nullcontext():
+        _gradient_cache_refusals(what, dev)
+        Uc, tau_c, Ur, omega = _alc_common(what, cache, Uc, tau_c, Ur, omega)
+        (N, D), Mc = cache.U.shape, Uc.shape[0]
+        dirs = [int(d) for d in dirs]
+        lo, hi = (cache.d0, cache.d0 + cache.nd) if is_g else (0, D)
+        if len(dirs) < 1 or any(b <= a for a, b in zip(dirs, dirs[1:])) or dirs[0] < lo or dirs[-1] >= hi:
+            raise ValueError(f"{what}: dirs must be a strictly increasing, non-empty list of feature columns in [{lo}, {hi}) "
+                             f"(got {dirs})")
+        pn = len(dirs)
+        b = 1 + pn
+        gnoise = _as_f64(gnoise.detach(), dev)
+        if gnoise.shape != (Mc, pn):
+            raise ValueError(f"{what}: gnoise must be ({Mc}, {pn}): one variance per candidate and observed direction "
+                             f"(got {tuple(gnoise.shape)})")
+        if not is_g:
+            cache.refresh()  # (a cache of the shared workspace that another model has factored into since)
+        spec = cache.spec
+        w, sf2 = spec.w, spec.sf2.reshape(1)
+        K = N + (cache.q if is_g else 0)
+        # the derivative kernels' range and the selection of dirs inside it; the fused launch's range is the span of dirs
+        dd0, dnd = (cache.d0, cache.nd) if is_g else (dirs[0], dirs[-1] - dirs[0] + 1)
+        k0, kn = dirs[0], dirs[-1] - dirs[0] + 1
+        row_mask = torch.zeros(dnd, dtype=torch.bool)
+        row_mask[[d - dd0 for d in dirs]] = True
+        acol = torch.tensor([1 + d - k0 for d in dirs], dtype=torch.int64, device=dev)
+        prior = torch.cat([sf2, gradient_prior_curvature(spec, 0, D)[torch.tensor(dirs, dtype=torch.int64, device=dev)]])
+        noise = torch.cat([tau_c.reshape(-1, 1), gnoise], 1) + cache.jitter
+        with _stage("alc_operands"):
+            Vr, _ = _function_operand_V(cache, Ur, transposed)
+        with_g = torch.empty(Mc, dtype=torch.float64, device=dev)
+        value = torch.empty(Mc, dtype=torch.float64, device=dev)
+        step = _alc_gradient_chunk_points(K, b)
+        for a0 in range(0, Mc, step):
+            mc = min(step, Mc - a0)
+            Ux = Uc[a0:a0 + mc]
+            selc = None if pn == dnd else GradientSelection(row_mask.expand(mc, dnd).contiguous(), dev)
+            with _stage("alc_gradient_operands"):
+                op = rows_buffer(K, mc * b, dev)
+                o3 = op.unflatten(1, (mc, b))  # candidate-major columns: (value, dirs) of each candidate side by side
+                o3[:N, :, 0] = cross_kernel(cache.U, Ux, spec)
+                Dk = gctx.cross_kernel_dx(Ux, cache.U, w, sf2, dd0, dnd, rows_buffer(N, mc * pn, dev), kind=spec.kind,
+                                          d_split=spec.d_split, sel=selc)
+                o3[:N, :, 1:] = Dk.unflatten(1, (mc, pn))
+                del Dk
+                if is_g:
+                    o3[N:, :, 0] = _gek_function_tail(cache, Ux).T
+                    o3[N:, :, 1:] = _gek_gradient_tail(cache, Ux, rows_buffer(cache.q, mc * pn, dev), selc).unflatten(1, (mc, pn))
+            V = rows_buffer(mc * b, K, dev)
+            mean = torch.empty(mc * b, dtype=torch.float64, device=dev)
+            var = torch.empty(mc * b, dtype=torch.float64, device=dev)
+            with _stage("alc_gradient_predict_tn"):
+                gctx.predict_tn(cache.Linv, cache.z, op, prior.repeat(mc), V, mean, var)
+            del op
+            V3 = V.unflatten(0, (mc, b))
+            with _stage("alc_gradient_whiten"):
+                if b <= 16:
+                    G = torch.empty((mc, b, b), dtype=torch.float64, device=dev)
+                    gctx.point_gram(V, b, G=G)
+                else:
+                    G = torch.bmm(V3, V3.transpose(1, 2))
+                    G = 0.5 * (G + G.transpose(1, 2))
+                S = torch.diag_embed(prior + noise[a0:a0 + mc]) - G
+                Lc, info = torch.linalg.cholesky_ex(S)
+                if bool((info != 0).any()):
+                    j = int((info != 0).to(torch.int32).argmax())
+                    raise NotPSDError(f"{what}: the covariance of the value and the {pn} gradient components at candidate {a0 + j} is "
+                                      f"not positive definite (leading minor {int(info[j])}); pass a larger gradient noise")
+                W = torch.linalg.solve_triangular(Lc, torch.eye(b, dtype=torch.float64, device=dev).expand(mc, b, b), upper=False)
+                Vw = rows_buffer(mc * b, K, dev)
+                Vw.unflatten(0, (mc, b)).copy_(torch.bmm(W, V3))
+                del V, V3
+                if transposed:
+                    Vf = rows_buffer(K, mc * b, dev)
+                    gctx.transpose(Vw, Vf)
+                    del Vw
+                else:
+                    Vf = Vw
+                A = torch.zeros((mc, b, 1 + kn), dtype=torch.float64, device=dev)
+                A[:, :, 0] = W[:, :, 0]
+                A[:, :, acol] = W[:, :, 1:]
+            num = torch.empty(mc * b, dtype=torch.float64, device=dev)
+            with _stage("post_cross_lin_sq"):
+                gctx.post_cross_lin_sq(Ux.repeat_interleave(b, 0), Ur, w, sf2, A.view(mc * b, 1 + kn), k0, kn, Vf, Vr, K, num, omega=omega,
+                                       kind=spec.kind, d_split=spec.d_split, transposed=transposed)
+            num = num.view(mc, b)
+            with_g[a0:a0 + mc] = num.sum(1)
+            value[a0:a0 + mc] = num[:, 0]
+        return with_g, value
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -640,6 +640,36 @@ class GP_Plus(GPR):
             return ActiveSubspace(matrix=matrix, eigenvalues=evals.flip(0), eigenvectors=evecs.flip(1), mean_part=mean_part,
                                   cov_part=cov_part, sensitivity=torch.diagonal(matrix).clone())
 
+    def variance_reduction(self, Xcand, Xref, weights=None, gradient=None, gradient_noise=None):
+        """Active learning by expected variance reduction (``GPR.variance_reduction``, documented there), for runs that return y
+        alone or y AND gradient components — the question an adjoint solver raises: is the gradient worth its cost here?
+
+        ``gradient=None``: the scores of one noisy function value per row of ``Xcand`` (M_c), today's path, bit for bit.
+        ``gradient=True`` (all p quantitative columns) or a length-p bool mask in ``quant_index`` order (the same components at
+        every candidate): the pair (scores of a run that returns y and those components of dy/dx, scores of the value alone),
+        M_c each, in y^2 units.  ``gradient_noise``: the variance of the gradient components in (y per input unit)^2 — a scalar, a
+        length-p row or (M_c, p); entries under a False of the mask are not read; ``None`` takes
+        ``gradient_enhanced.GRADIENT_NUGGET_REL`` times the prior curvature, as ``condition_on_gradients`` does.  The value's noise
+        is that of the candidate's own source.  The score is the reduction ``condition_on`` followed by
+        ``condition_on_gradients(..., observed=mask)`` at that row would give, whatever the observed values; nothing is conditioned
+        and nothing is factorised: ``linalg.variance_reduction_block`` whitens the 1 + p' functionals of each candidate and one
+        gpp_post_cross_lin_sq launch per chunk of candidates sums the squared posterior cross-covariances.
+        Dividing the two scores by the two costs answers the question (``bayesian_optimizations.
+        select_run_by_variance_reduction``).  No reference counterpart.
+
+        ``ValueError`` before any device work, in addition to ``GPR.variance_reduction``'s: a model without a quantitative column,
+        ``gradient=False``, a mask of another length or type or without a True, ``gradient_noise`` without ``gradient``, of a
+        shape that does not broadcast, negative or not finite.  ``errors.NotPSDError`` when a candidate's block is not positive
+        definite (it names the candidate): pass more gradient noise.  ``NotImplementedError`` for a model with calibration
+        parameters, under ``settings.sharded_evaluation`` or a graph capture."""
+        if gradient is None and gradient_noise is None:
+            return super().variance_reduction(Xcand, Xref, weights)
+        from ..gradient_enhanced import variance_reduction_of_runs
+
+        self._refuse_calibrated("variance_reduction with gradient=", "the gradient by a calibrated column has no meaning on the "
+                                "calibrated source")
+        return variance_reduction_of_runs(self, None, Xcand, Xref, weights, gradient, gradient_noise)
+
     def condition_on_gradients(self, X, dY, noise=None, observed=None):
         """Gradient-enhanced Kriging on the fitted model: a ``GradientEnhancedPosterior`` of this model's training data plus observed
         gradients, made by bordering the cached factorisation in O(N^2 q), q = Mg p, without refactorising
@@ -659,8 +689,9 @@ class GP_Plus(GPR):
         The receiver's data, parameters and cache are not modified (it is put in eval mode, as by ``predict``; without a cache it
         is factorised first).  The returned object holds a detached copy of the model without the N x N factors and offers
         ``predict(Xtest, return_std=True, include_noise=True)`` and ``predict_gradient(Xtest, return_std=True)`` in this model's
-        conventions and units, ``num_function_rows``, ``num_gradient_points``, ``num_gradient_observations`` (q) and ``observed``
-        — nothing else: no further appends, no sampling, LOO / CV, acquisition scores or ``return_cov``, no training on the gradient data.  No reference
+        conventions and units, ``variance_reduction`` (this model's, ``gradient=`` included), ``num_function_rows``,
+        ``num_gradient_points``, ``num_gradient_observations`` (q) and ``observed`` — nothing else: no further appends, no sampling,
+        LOO / CV, knowledge gradient or ``return_cov``, no training on the gradient data.  No reference
         counterpart.
 
         ``ValueError`` before any kernel runs: wrong column count or shapes, NaN / inf, Mg = 0, a categorical level or source the

@@ -58,6 +58,7 @@ typedef struct gpp_handle_s* gpp_handle_t;
 #define GPP_OP_POST_CROSS_MIN 7 /* gpp_post_cross_min: N = M_r reference points, M = M_c candidates, S = Q nodes (D is not read) */
 #define GPP_OP_POINT_GRAM 8 /* gpp_point_gram with a weighted sum: M points, D = nd rows per point (N and S are not read) */
 #define GPP_OP_GEK_GRAD 9   /* gpp_gek_grad_reduce: N function points, M = Mg gradient points, D features, S carries dU */
+#define GPP_OP_POST_CROSS_LIN 10 /* gpp_post_cross_lin_sq: N = M_r reference points, M = M_f functionals (D and S are not read) */
 
 const char* gpp_version(void);
 
@@ -625,6 +626,28 @@ int gpp_chol_append(gpp_handle_t h, double* A, int64_t ld, double* Linv, int64_t
 int gpp_post_cross_sq(gpp_handle_t h, const double* Uc, int64_t Mc, const double* Ur, int64_t Mr, int D, const double* w,
                       const double* sf2, int kind, int d_split, const double* Vc, int64_t ldc, const double* Vr, int64_t ldr,
                       int64_t K, int vt, const double* omega, double* out);
+
+/*
+ * gpp_post_cross_sq for rows that observe a LINEAR functional of f, a value plus gradient components at the row's point: the
+ * numerator of the expected variance reduction of a run that returns y and (part of) its gradient (linalg.py
+ * variance_reduction_block; no reference counterpart):
+ *   out[i] = sum_r omega_r ( g_i(r) - sum_{n < K} Vf[i,n] Vr[r,n] )^2
+ *   g_i(r) = A[i,0] sf2 k(Uf_i, Ur_r; w) + sum_{j < nd} A[i,1+j] 2 w_{d0+j} (Uf[i,d0+j] - Ur[r,d0+j]) m_{f(j)}(i, r)
+ * with the multipliers m_0 = -sf2 k and m_1 = sf2 e1 h' of gpp_cross_kernel_dx (h' without a division by r).  A: M_f x (1 + nd)
+ * row-major, lda >= 1 + nd; its columns [1 + nd, lda) are never read.  0 <= d0, nd >= 1, d0 + nd <= D <= 64.  Uf, Ur, w, sf2, kind,
+ * d_split, vt, Vf / ldf, Vr / ldr (16-byte aligned, even leading dimensions), K, omega (or NULL) and out as in gpp_post_cross_sq, and
+ * so are the tiles, the records (gpp_workspace_bytes(h, GPP_OP_POST_CROSS_LIN, M_r, M_f, 0, 0) bytes; GPP_NO_WORKSPACE with nothing
+ * enqueued when it is missing) and the second launch.  Per entry: one multiplier pair from one exponential (and one Matern factor),
+ * one fma per observed direction on the staged difference sqrt(w_d) (Uf - Ur) with the rounded coefficient A[i,1+j] 2 sqrt(w_d), then
+ * fma(A[i,0] sf2, k, -acc), fma(m_0, lin_0, .), fma(m_1, lin_1, .).  Hence: a row with A[i,:] = (1, 0, ..., 0) is bit for bit the
+ * gpp_post_cross_sq value of the same operands; a feature with w_d == 0 contributes an exact 0; a row of Uf that equals a row of Ur
+ * gives finite values for the Matern kinds and an exact 0 derivative part.  No float atomics, two calls agree bit for bit, and a
+ * row's value does not depend on its index or on the other rows.  Nothing outside the stated extents is read or written.
+ * Argument codes in the order of the arguments (-11 d0, -12 nd, -13 A, -14 lda, -15 Vf or ldf, -17 Vr or ldr, -19 K, -20 vt, -22 out).
+ */
+int gpp_post_cross_lin_sq(gpp_handle_t h, const double* Uf, int64_t Mf, const double* Ur, int64_t Mr, int D, const double* w,
+                          const double* sf2, int kind, int d_split, int d0, int nd, const double* A, int64_t lda, const double* Vf,
+                          int64_t ldf, const double* Vr, int64_t ldr, int64_t K, int vt, const double* omega, double* out);
 
 /*
  * Minima of affine images of the posterior cross-covariance, the reduction of the knowledge gradient under a Q-node quadrature:
