@@ -14,7 +14,8 @@
 // (WT=64: 64 accumulator doubles per lane, in VGPRs: __launch_bounds__(256, 2)).  K is consumed in chunks of 16;
 // both operand chunks are staged in LDS in [k][row] order (padded strides, see ldt_*), double-buffered: the global
 // loads of chunk c+1 are issued before the MFMAs of chunk c and written to the other buffer afterwards, one barrier
-// per chunk.  WT = 32 / 16 variants (64^2 / 32^2 tiles) and a 128 x 32 tile serve the small sub-problems, where the
+// per chunk (in the interior loop of the launch-per-product kernels both run UNDER the MFMAs, see PIPE).
+// WT = 32 / 16 variants (64^2 / 32^2 tiles) and a 128 x 32 tile serve the small sub-problems, where the
 // grid of 128^2 tiles would leave most of the 256 CUs idle; they stage K in chunks of 64 with one LDS buffer (template
 // parameters BK, NBUF below).  Work-groups are independent along two batch dimensions (grid.y, grid.z).
 #include "../../include/gpp.h"
@@ -26,9 +27,14 @@
 
 typedef double v2d __attribute__((ext_vector_type(2)));
 typedef double v4d __attribute__((ext_vector_type(4)));
+typedef const char __attribute__((address_space(1))) gchar;  // global address space, spelled out
+typedef const v2d __attribute__((address_space(1))) gv2d;
 
 namespace {
 
+#ifndef GPP_CLEAN_SETPRIO
+#define GPP_CLEAN_SETPRIO 1  // s_setprio pair around the big tile's pipelined loop in the TAG != 0 kernels (build-time A/B knob)
+#endif
 constexpr int BK16 = 16;  // K chunk of the big tile and of every k-contiguous ("KC") operand
 // LDS layouts.  Row-contiguous operands ("MC", stored [k][row] in memory) are staged as [k][T+16]: 16-byte aligned
 // rows for ds_write_b128, and the two k-rows a 32-lane ds_read_b64 group touches fall in different bank halves.
@@ -213,6 +219,11 @@ __device__ __forceinline__ void gemm_tile(const P& p, const int tm, const int tn
   constexpr int OPA = (WR == 2) ? OPSZ : BK * LDA, OPB = (WR == 2) ? OPSZ : BK * LDB;
   constexpr int NVA = BK * TM / (2 * NTH), NVB = BK * TN / (2 * NTH);  // 16-byte vectors per thread and chunk
   constexpr int RB = WTM / 4, CB = WTN / 16;
+  constexpr bool SPLIT = (VAR == 2 && RB == 16 && CB == 4 && BK == 16 && NBUF == 2 && WR == 2);  // the big row-contiguous tile
+  // The pipelined form of its clean loop (below) for every kernel but the DAG executor, which is the one caller with a hook: it has no
+  // VGPR to spare (256, with spills outside its MFMA blocks), and the pipelined body raised its spill count from 17 to 26
+  // (profiles/EXPERIMENTS.md) — it keeps the plain loop.
+  constexpr bool PIPE = SPLIT && __is_same(H, GemmNoHook);
 
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
@@ -271,6 +282,12 @@ __device__ __forceinline__ void gemm_tile(const P& p, const int tm, const int tn
     if constexpr (VAR == 2) {
       if (chunk_in_range<TM, BK>(row0, Mld, kb, khi)) pa = chunk_is_interior<TM, BK>(row0, Mld, kb, khi, p.a_mask) ? 1 : 2;
       if (chunk_in_range<TN, BK>(col0, Nld, kb, khi)) pb = chunk_is_interior<TN, BK>(col0, Nld, kb, khi, p.b_mask) ? 1 : 2;
+    }
+    if constexpr (PIPE) {  // keep the offsets' zero-extension beside the loads (see the clean loop below)
+#pragma unroll
+      for (int i = 0; i < NVA; ++i) asm("" : "+v"(offa[i]));
+#pragma unroll
+      for (int i = 0; i < NVB; ++i) asm("" : "+v"(offb[i]));
     }
     if (pa) {
       load_fast<NVA>(ubaseA + (int64_t)kb * stepA, offa, ra);
@@ -335,8 +352,7 @@ __device__ __forceinline__ void gemm_tile(const P& p, const int tm, const int tn
   // block, so the compiler can spread the memory instructions over the MFMAs and the wave spends no issue slots on
   // the path selection (~100 scalar instructions per chunk).
   int ca = 0, cb = 0;  // clean iterations: ca <= c < cb
-  // (big tile only: the small tiles run a handful of chunks per launch and lose more to the second loop's code)
-  constexpr bool SPLIT = (VAR == 2 && RB == 16 && CB == 4 && BK == 16);
+  // (big tile only, SPLIT above: the small tiles run a handful of chunks per launch and lose more to the second loop's code)
   if constexpr (SPLIT) {
     if (row0 + TM <= Mld && col0 + TN <= Nld && nch > 1) {
       int k_lo = klo, k_hi = khi;  // chunk [kb, kb+BK) is interior iff k_lo <= kb and kb + BK <= k_hi
@@ -370,21 +386,144 @@ __device__ __forceinline__ void gemm_tile(const P& p, const int tm, const int tn
   };
   int c = 0;
   for (; c < ca; ++c) general_iter(c);
-  if constexpr (SPLIT) {
+  if constexpr (SPLIT && !PIPE) {
     for (; c < cb; ++c) {
-      const int cur = (NBUF == 2) ? (c & 1) : 0, nxt = (NBUF == 2) ? (cur ^ 1) : 0;
+      const int cur = c & 1, nxt = cur ^ 1;
       const int kb = kpos(c + 1);
       load_fast<NVA>(ubaseA + (int64_t)kb * stepA, offa, ra);
       load_fast<NVB>(ubaseB + (int64_t)kb * stepB, offb, rb);
-      // raised wave priority around the MFMA phase: +2.3 % for LAUUM (TAG 1: 63.95 -> 65.4 TFLOP/s, same box), nothing
-      // for gpp_trtri's masked merges, -3 % for the look-ahead factorisation's concurrent streams (both TAG 0)
-      if constexpr (TAG != 0) __builtin_amdgcn_s_setprio(1);
       compute(cur);
-      if constexpr (TAG != 0) __builtin_amdgcn_s_setprio(0);
-      if (NBUF == 1) __syncthreads();
       store_mc<TM, BK, false, NTH>(smem + nxt * (OPA + OPB), tid, ra, 0);
       store_mc<TN, BK, false, NTH>(smem + nxt * (OPA + OPB) + OPA, tid, rb, 0);
       __syncthreads();
+    }
+  }
+  if constexpr (PIPE) {
+    if (c < cb) {
+      // The clean loop is software-pipelined by hand: the staging of chunk c + 1 runs UNDER the 64 MFMAs of chunk c, so that only
+      // the barrier and the first fragment reads separate two chunks' MFMAs (before, ~90 instructions, eight vmcnt waits and an
+      // LDS round trip sat in series between them, once per chunk and wave, and the four waves of a work-group meet at the
+      // barrier: profiles/EXPERIMENTS.md).  The body is ONE basic block; its order is pinned with sched_group_barrier:
+      //   k-step 0: the 8 global loads of chunk c + 1, one per MFMA
+      //   k-step 2: the 4 LDS stores of A, each behind the vmcnt that covers its own load, in the k-step's second half
+      //   k-step 3: the 4 LDS stores of B in its first half; nothing but loop control between the last MFMA and the barrier
+      //   every k-step but the last: the fragment reads of the next one.
+      // The `nxt` buffer has been free since the barrier that ended chunk c - 1, so the stores need no barrier of their own.
+      // The loads address  uniform base (two SGPR pairs, advanced by a scalar add per chunk) + the thread's 32-bit offset; the
+      // empty asm keeps the offsets' zero-extension inside the loop, where instruction selection folds it into the load's
+      // SGPR-base form (hoisted, it costs 8 more VGPRs and a 64-bit VALU add per load and chunk).
+      // MFMA order (kk, a, b) and fragment read order are those of compute(): the same bits.
+      static_assert(!SPLIT || (TM == TN && LDA == LDB && NTH % (TM / 2) == 0), "the clean loop assumes the square row-contiguous tile");
+      constexpr int RPV = NTH / (TM / 2);  // LDS rows between a thread's consecutive staging vectors: (tid + NTH i) / (T/2) = tid / (T/2) + RPV i
+      auto uniform_ptr = [](const double* q) {
+        const uint64_t u = reinterpret_cast<uint64_t>(q);  // work-group uniform by construction (tile indices, product descriptor)
+        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
+        return reinterpret_cast<gchar*>(((uint64_t)hi << 32) | lo);  // (an integer cast would yield a generic pointer: flat loads)
+      };
+      const int kb1 = kpos(c + 1);
+      gchar* ua = uniform_ptr(ubaseA + (int64_t)kb1 * stepA);
+      gchar* ub = uniform_ptr(ubaseB + (int64_t)kb1 * stepB);
+      const int64_t dk = p.k_reverse ? -(int64_t)BK : (int64_t)BK;
+      const int64_t inca = dk * stepA * 8, incb = dk * stepB * 8;  // bytes per chunk
+      // one register each for the thread's LDS positions (the asm keeps hipcc from re-deriving them from wave / lane parts per chunk)
+      int wofs = (tid / (TM / 2)) * LDA + ((tid % (TM / 2)) << 1);
+      int rofa = wm + li + lk * LDA, rofb = OPA + wn + li + lk * LDB;
+      asm("" : "+v"(wofs), "+v"(rofa), "+v"(rofb));
+      for (; c < cb; ++c) {
+        const int cur = c & 1;
+        const double* sa = smem + cur * (OPA + OPB) + rofa;
+        const double* sb = smem + cur * (OPA + OPB) + rofb;
+        int wpos = (cur ^ 1) * (OPA + OPB) + wofs;
+#pragma unroll
+        for (int i = 0; i < NVA; ++i) asm("" : "+v"(offa[i]));
+#pragma unroll
+        for (int i = 0; i < NVB; ++i) asm("" : "+v"(offb[i]));
+        // raised wave priority over the MFMA phase, now the whole body: worth 0.5 ms of C2's 125 in the TAG != 0 kernels (LAUUM, the
+        // post_cross products; profiles/r08_ab_setprio_gemm_pipeline.txt).  TAG 0 stays without: around the plain loop it was
+        // nothing for gpp_trtri's masked merges and -3 % for the look-ahead factorisation's concurrent streams.
+        if constexpr (TAG != 0 && GPP_CLEAN_SETPRIO) __builtin_amdgcn_s_setprio(1);
+        double af[BK / 4][RB / 4], bf[BK / 4][CB];
+        auto frag_b = [&](int kk) {
+#pragma unroll
+          for (int b = 0; b < CB; ++b) bf[kk][b] = sb[kk * 4 * LDB + 16 * b];
+        };
+        auto frag_a = [&](int kk, int a0) {  // rows a0, a0 + 1
+#pragma unroll
+          for (int a = a0; a < a0 + 2; ++a) af[kk][a] = sa[kk * 4 * LDA + 16 * a];
+        };
+        auto mfma_rows = [&](int kk, int a0) {
+#pragma unroll
+          for (int a = a0; a < a0 + 2; ++a)
+#pragma unroll
+            for (int b = 0; b < CB; ++b)
+              acc4[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[kk][a], bf[kk][b], acc4[a][b], 0, 0, 0);
+        };
+        // Each store goes through a position the compiler cannot see through (the asm), so it may alias the store before it and the
+        // fragment reads around it: the source order of the LDS accesses below is the order they are scheduled in.
+        auto stage = [&](int ofs, const v2d& v) {
+          asm("" : "+v"(wpos));
+          *reinterpret_cast<v2d*>(smem + wpos + ofs) = v;
+        };
+        frag_b(0);
+        frag_a(0, 0);
+        frag_a(0, 2);
+#pragma unroll
+        for (int kk = 0; kk < BK / 4; ++kk) {
+          if (kk + 1 < BK / 4) frag_b(kk + 1);
+          if (kk == BK / 4 - 1) {
+#pragma unroll
+            for (int i = 0; i < NVB; ++i) stage(OPA + i * RPV * LDB, rb[i]);
+          }
+          mfma_rows(kk, 0);
+          if (kk == 0) {
+#pragma unroll
+            for (int i = 0; i < NVA; ++i) ra[i] = *reinterpret_cast<gv2d*>(ua + offa[i]);
+#pragma unroll
+            for (int i = 0; i < NVB; ++i) rb[i] = *reinterpret_cast<gv2d*>(ub + offb[i]);
+            ua += inca;
+            ub += incb;
+          }
+          if (kk + 1 < BK / 4) frag_a(kk + 1, 0);
+          if (kk == BK / 4 - 2) {
+#pragma unroll
+            for (int i = 0; i < NVA; ++i) stage(i * RPV * LDA, ra[i]);
+          }
+          if (kk + 1 < BK / 4) frag_a(kk + 1, 2);
+          mfma_rows(kk, 2);
+        }
+        // The pinned order (masks: 0x8 MFMA, 0x20 VMEM read, 0x100 DS read, 0x200 DS write; two fragment reads are one
+        // ds_read2_b64: B pair, B pair, A pair, A pair per k-step).  The next k-step's A rows 0-1 are read once this k-step's rows
+        // 0-1 are done (MFMA 8) and its rows 2-3 at the top of the next k-step, so they take over the registers of the rows they
+        // replace: one and a half fragment sets live, not two (8 VGPRs, which gpp_dag_f64 does not have).
+        static_assert(BK == 16 && RB / 4 * CB == 16 && NVA == 4 && NVB == 4, "the schedule below is written out for 4 k-steps of 16 MFMAs");
+#define GPP_SG(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
+#define GPP_SG_NEXT_B GPP_SG(0x8, 1); GPP_SG(0x100, 1); GPP_SG(0x8, 1); GPP_SG(0x100, 1)  // 2 MFMAs, B of the next k-step
+#define GPP_SG_PAIR(mask, m) GPP_SG(mask, 1); GPP_SG(0x8, m)
+        GPP_SG(0x100, 4);  // k-step 0: its own fragments,
+        GPP_SG_NEXT_B;
+        GPP_SG_PAIR(0x20, 1); GPP_SG_PAIR(0x20, 1); GPP_SG_PAIR(0x20, 1); GPP_SG_PAIR(0x20, 1); GPP_SG_PAIR(0x20, 1); GPP_SG_PAIR(0x20, 1);
+        GPP_SG(0x100, 1);  // (A rows 0-1 of k-step 1)
+        GPP_SG_PAIR(0x20, 1); GPP_SG_PAIR(0x20, 1);  // the global loads of chunk c + 1, one per MFMA
+        GPP_SG(0x8, 6);
+        GPP_SG(0x100, 1);  // k-step 1 (its A rows 2-3)
+        GPP_SG_NEXT_B;
+        GPP_SG(0x8, 6);
+        GPP_SG(0x100, 1);
+        GPP_SG(0x8, 8);
+        GPP_SG(0x100, 1);  // k-step 2
+        GPP_SG_NEXT_B;
+        GPP_SG(0x8, 6);
+        GPP_SG(0x100, 1);
+        GPP_SG_PAIR(0x200, 2); GPP_SG_PAIR(0x200, 2); GPP_SG_PAIR(0x200, 2); GPP_SG_PAIR(0x200, 2);  // the LDS stores of A
+        GPP_SG(0x100, 1);  // k-step 3
+        GPP_SG_PAIR(0x200, 2); GPP_SG_PAIR(0x200, 2); GPP_SG_PAIR(0x200, 2); GPP_SG_PAIR(0x200, 2);  // the LDS stores of B
+        GPP_SG(0x8, 8);
+#undef GPP_SG_PAIR
+#undef GPP_SG_NEXT_B
+#undef GPP_SG
+        if constexpr (TAG != 0 && GPP_CLEAN_SETPRIO) __builtin_amdgcn_s_setprio(0);
+        __syncthreads();
+      }
     }
   }
   for (; c < nch; ++c) general_iter(c);
