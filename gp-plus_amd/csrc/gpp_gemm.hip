@@ -14,7 +14,7 @@
 // (WT=64: 64 accumulator doubles per lane, in VGPRs: __launch_bounds__(256, 2)).  K is consumed in chunks of 16;
 // both operand chunks are staged in LDS in [k][row] order (padded strides, see ldt_*), double-buffered: the global
 // loads of chunk c+1 are issued before the MFMAs of chunk c and written to the other buffer afterwards, one barrier
-// per chunk (in the interior loop of the launch-per-product kernels both run UNDER the MFMAs, see PIPE).
+// per chunk (in the big tile's interior loop both run UNDER the MFMAs, see PIPE).
 // WT = 32 / 16 variants (64^2 / 32^2 tiles) and a 128 x 32 tile serve the small sub-problems, where the
 // grid of 128^2 tiles would leave most of the 256 CUs idle; they stage K in chunks of 64 with one LDS buffer (template
 // parameters BK, NBUF below).  Work-groups are independent along two batch dimensions (grid.y, grid.z).
@@ -34,6 +34,12 @@ namespace {
 
 #ifndef GPP_CLEAN_SETPRIO
 #define GPP_CLEAN_SETPRIO 1  // s_setprio pair around the big tile's pipelined loop in the TAG != 0 kernels (build-time A/B knob)
+#endif
+#ifndef GPP_DAG_CHAIN_PRIO
+#define GPP_DAG_CHAIN_PRIO 2  // s_setprio level of the DAG executor's 64-tile (chain) tasks, 0 = none (build-time A/B knob)
+#endif
+#ifndef GPP_DAG_PIPE
+#define GPP_DAG_PIPE 1  // the pipelined clean loop in the DAG executor's big tile too (0: the plain loop there; build-time A/B knob)
 #endif
 constexpr int BK16 = 16;  // K chunk of the big tile and of every k-contiguous ("KC") operand
 // LDS layouts.  Row-contiguous operands ("MC", stored [k][row] in memory) are staged as [k][T+16]: 16-byte aligned
@@ -195,6 +201,7 @@ __device__ __forceinline__ void load_fast(const double* __restrict__ ubase, cons
 // space: scalar loads, re-materialisable like kernel arguments).  A, B, C: the batch element's operands,
 // C2: its mirrored output (or null).  Ends with a work-group barrier after the last LDS read, so the caller may stage another tile at once.
 struct GemmNoHook {
+  static constexpr bool per_task = false;
   __device__ __forceinline__ void operator()() const {}
 };
 // (`epi`: anything but GemmStoreC replaces the store of C — it is handed the wave's accumulators once the main loop's LDS is free)
@@ -220,12 +227,16 @@ __device__ __forceinline__ void gemm_tile(const P& p, const int tm, const int tn
   constexpr int NVA = BK * TM / (2 * NTH), NVB = BK * TN / (2 * NTH);  // 16-byte vectors per thread and chunk
   constexpr int RB = WTM / 4, CB = WTN / 16;
   constexpr bool SPLIT = (VAR == 2 && RB == 16 && CB == 4 && BK == 16 && NBUF == 2 && WR == 2);  // the big row-contiguous tile
-  // The pipelined form of its clean loop (below) for every kernel but the DAG executor, which is the one caller with a hook: it has no
-  // VGPR to spare (256, with spills outside its MFMA blocks), and the pipelined body raised its spill count from 17 to 26
-  // (profiles/EXPERIMENTS.md) — it keeps the plain loop.
-  constexpr bool PIPE = SPLIT && __is_same(H, GemmNoHook);
+  // The pipelined form of its clean loop (below): every caller of the big tile, the DAG executor included since it stopped carrying
+  // the per-thread state of all its bodies through the tile (H::per_task; 249 VGPRs, no spill — profiles/EXPERIMENTS.md).
+  // GPP_DAG_PIPE = 0 gives the executor, and only it, the plain loop back.
+  constexpr bool PIPE = SPLIT && !(H::per_task && !GPP_DAG_PIPE);
 
-  const int tid = threadIdx.x;
+  int tid = threadIdx.x;
+  if constexpr (H::per_task) {  // one body of several inside a task loop: nothing derived from the thread index is hoisted out of that loop
+    asm volatile("" : "+v"(tid));
+    tid &= NTH - 1;  // (gives the compiler the value range back: shifts, not signed divisions)
+  }
   const int wave = tid >> 6, lane = tid & 63;
   const int wm = (wave >> 1) * WTM, wn = (wave & 1) * WTN;
   const int li = lane & 15, lk = lane >> 4;
@@ -1322,9 +1333,27 @@ __global__ __launch_bounds__(64) void gpp_dag_bind(const GemmArgs* rel, GemmArgs
   a.C2 = a.buf[3] >= 0 ? reinterpret_cast<double*>(base(a.buf[3]) + reinterpret_cast<uintptr_t>(a.C2)) : nullptr;
   abs[g] = a;
 }
+// The executor's tile hooks.  per_task: the tile is one of many bodies inside the task loop, so gemm_tile derives its per-thread
+// positions afresh per tile (else hipcc hoists the positions of EVERY body to kernel entry and carries them through every K loop).
+struct DagPlainTile {
+  static constexpr bool per_task = true;
+  __device__ __forceinline__ void operator()() const {}
+};
+template <class T>
+struct DagAhead {  // thread 0 takes the next ticket after the last MFMA and parks it in LDS
+  static constexpr bool per_task = true;
+  const T& take;
+  int* s_pre;
+  int done_after;
+  __device__ __forceinline__ void operator()() const {
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));  // (see tid_now in gpp_dag_f64)
+    if (t == 0) *s_pre = take(done_after);
+  }
+};
 __global__ __launch_bounds__(256, 2) void gpp_dag_f64(DagLaunch e) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  __shared__ int s_idx, s_ok;
+  __shared__ int s_idx, s_ok, s_pre;
   const int tid = threadIdx.x;
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wold-style-cast"
@@ -1335,35 +1364,50 @@ __global__ __launch_bounds__(256, 2) void gpp_dag_f64(DagLaunch e) {
   // increments), so the atomic's round trip runs under the epilogue's own memory traffic.  A work-group then holds two tickets for
   // those few microseconds, its current one always the smaller: the earliest unfinished task is still some work-group's CURRENT
   // task, so progress is as before.  (Earlier than the epilogue the next task — possibly a chain task — would sit behind a whole tile.)
-  int pre = -2;  // thread 0: -2 nothing taken ahead, -1 stop, >= 0 ticket
+  // s_pre (thread 0 only, in LDS so that it costs no VGPR across the tile): -2 nothing taken ahead, -1 stop, >= 0 ticket
   auto take = [&](int done_after) -> int {  // thread 0 only
     // (main workers: no budget, no quit flag, no limit — nothing but the atomic; the abort word is seen by the waits)
-    if (e.max_tasks > 0 && done_after >= e.max_tasks) return -1;
-    if (e.quit_id >= 0 && (exec_load(e.counters) != 0 || exec_load(e.counters + e.quit_id) >= e.quit_val)) return -1;
-    if (e.ticket_limit <= 0) return __hip_atomic_fetch_add(e.counters + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // (the launch's switches pass through an asm: compared afresh per call, not as flags and addresses held from kernel entry on — six
+    //  SGPRs that were spilled around every tile)
+    int max_tasks = e.max_tasks, quit_id = e.quit_id, ticket_limit = e.ticket_limit;
+    asm volatile("" : "+s"(max_tasks), "+s"(quit_id), "+s"(ticket_limit));
+    if (max_tasks > 0 && done_after >= max_tasks) return -1;
+    if (quit_id >= 0 && (exec_load(e.counters) != 0 || exec_load(e.counters + quit_id) >= e.quit_val)) return -1;
+    if (ticket_limit <= 0) return __hip_atomic_fetch_add(e.counters + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // a filler launch in front of a panel never takes a task that needs that panel: the launch could not end (gpp_dag.hip)
     int old = exec_load(e.counters + 1);
-    while (old < e.ticket_limit &&
+    while (old < ticket_limit &&
            !__hip_atomic_compare_exchange_strong(e.counters + 1, &old, old + 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
     }
-    return old < e.ticket_limit ? old : -1;
+    return old < ticket_limit ? old : -1;
   };
+  // The thread index is read afresh at every use inside the task loop (an asm the compiler cannot merge or hoist): derived once,
+  // "thread 0" masks and per-thread positions are loop invariants, which hipcc computes at kernel entry and then holds in registers
+  // (or spill slots) through every tile's K loop.
+  auto tid_now = []() {
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    return t;
+  };
+  auto first = [&]() { return tid_now() == 0; };
+  if (tid == 0) s_pre = -2;
   for (int done = 0;; ++done) {
-    if (tid == 0) {
+    if (first()) {
+      const int pre = s_pre;
       s_idx = pre != -2 ? pre : take(done);
-      pre = -2;
+      s_pre = -2;
     }
     __syncthreads();
     const int idx = __builtin_amdgcn_readfirstlane(s_idx);
     __syncthreads();  // (thread 0 rewrites s_idx at the top of the next iteration; the copy tasks have no barrier of their own)
     if (idx < 0 || idx >= e.ntasks) break;
-    if (e.trace && tid == 0) {
+    if (e.trace && first()) {
       e.trace[4 * (size_t)idx] = wall_clock64();
       e.trace[4 * (size_t)idx + 3] = (unsigned long long)blockIdx.x | ((unsigned long long)(unsigned)e.tag << 32);
     }
     const int w0 = tasks[idx].wait_id[0], w1 = tasks[idx].wait_id[1], w2 = tasks[idx].wait_id[2];
     if (w0 >= 0 || w1 >= 0 || w2 >= 0) {
-      if (tid == 0) {
+      if (first()) {
         // (fast path: all three counters' loads in flight together; the polling loop only when one of them is not there yet)
         const int v0 = tasks[idx].wait_val[0], v1 = tasks[idx].wait_val[1], v2 = tasks[idx].wait_val[2];
         const int c0 = w0 >= 0 ? exec_load(e.counters + w0) : v0, c1 = w1 >= 0 ? exec_load(e.counters + w1) : v1,
@@ -1381,18 +1425,22 @@ __global__ __launch_bounds__(256, 2) void gpp_dag_f64(DagLaunch e) {
       __syncthreads();
       if (!ok) break;
     }
-    if (e.trace && tid == 0) e.trace[4 * (size_t)idx + 1] = wall_clock64();
+    if (e.trace && first()) e.trace[4 * (size_t)idx + 1] = wall_clock64();
     const CGemmArgs& p = groups[tasks[idx].group];
     const int tm = tasks[idx].tm, tn = tasks[idx].tn;
     if (p.op == 0) {
-      auto ahead = [&]() {
-        if (tid == 0) pre = take(done + 1);
-      };
-      if (p.etile == 64) gemm_tile<2, 32, 32, 0, 64, 1, 2>(p, tm, tn, p.A, p.B, p.C, p.C2, smem);
-      else gemm_tile<2, 64, 64, 0, 16, 2, 2>(p, tm, tn, p.A, p.B, p.C, p.C2, smem, ahead);
+      if (p.etile == 64) {
+        // The 64-tile tasks are the chain between two panels: few, short, latency-bound and on the list's critical path, and they
+        // share their SIMDs with another work-group's big tile, whose pipelined loop leaves hardly an issue slot free (beside it they
+        // ran 20 % longer and the panels started later: profiles/r19_dag_traces.txt).  They run at raised wave priority.
+        if constexpr (GPP_DAG_CHAIN_PRIO != 0) __builtin_amdgcn_s_setprio(GPP_DAG_CHAIN_PRIO);
+        gemm_tile<2, 32, 32, 0, 64, 1, 2>(p, tm, tn, p.A, p.B, p.C, p.C2, smem, DagPlainTile());
+        if constexpr (GPP_DAG_CHAIN_PRIO != 0) __builtin_amdgcn_s_setprio(0);
+      } else gemm_tile<2, 64, 64, 0, 16, 2, 2>(p, tm, tn, p.A, p.B, p.C, p.C2, smem, DagAhead<decltype(take)>{take, &s_pre, done + 1});
     } else {
       // copy the M x 128 strip tn of B into C: 64 16-byte vectors per row, 4 rows per pass, 8 passes in flight
-      const int c = tn * 128 + ((tid & 63) << 1), r4 = tid >> 6;
+      const int t = tid_now() & 255;
+      const int c = tn * 128 + ((t & 63) << 1), r4 = t >> 6;
       if (c < p.N) {
         const bool pair = c + 1 < p.N;
         for (int r0 = 0; r0 < p.M; r0 += 32) {
@@ -1420,7 +1468,7 @@ __global__ __launch_bounds__(256, 2) void gpp_dag_f64(DagLaunch e) {
     if (i0 >= 0 || i1 >= 0) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's stores have left the CU
       __syncthreads();
-      if (tid == 0) {
+      if (first()) {
         // (the explicit wait between the write-back and the increments is REQUIRED: see panel_publish in gpp_leaf.hip)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1430,7 +1478,7 @@ __global__ __launch_bounds__(256, 2) void gpp_dag_f64(DagLaunch e) {
     }
     if (e.trace) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (tid == 0) e.trace[4 * (size_t)idx + 2] = wall_clock64();
+      if (first()) e.trace[4 * (size_t)idx + 2] = wall_clock64();
     }
   }
 }
