@@ -156,6 +156,14 @@ _SIGNATURES = {
     "gpp_gek_grad_reduce_sel": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                         c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
                                         c_void_p, c_void_p]),
+    "gpp_cross_kernel_dx_batched": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
+                                            c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int]),
+    "gpp_kernel_dxdx_batched": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
+                                        c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
+                                        c_int64, c_int64, c_int]),
+    "gpp_gek_grad_reduce_batched": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
+                                            c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                            c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
 }
 
 _lib = None

@@ -1337,6 +1337,153 @@ class GppContext:
             raise GppError("gpp_gek_grad_reduce: the handle's scratch workspace is missing or too small")
         check(status, "gpp_gek_grad_reduce")
 
+    # -- the three above for B problems in one launch each (batched.BatchedGEKFunction) -------------------------------------------
+    @staticmethod
+    def _dx_rows_batched(name, t, B, D):
+        """One side's feature rows of a batched call: (M, D) shared by every element or (B, M, D), each element's block contiguous;
+        returns (M, batch stride), the stride 0 for a shared block."""
+        _need(t, torch.float64, name)
+        if t.dim() == 2:
+            if t.shape[1] != D or not t.is_contiguous():
+                raise GppError(f"{name} must be a contiguous (M, {D}) matrix or (B, M, {D}) (got {tuple(t.shape)})")
+            M, s = t.shape[0], 0
+        else:
+            if t.dim() != 3 or t.shape[0] != B or t.shape[2] != D or t.stride(2) != 1 or t.stride(1) != D:
+                raise GppError(f"{name} must be ({B}, M, {D}) with contiguous elements (got {tuple(t.shape)}, strides {t.stride()})")
+            M, s = t.shape[1], (t.stride(0) if B > 1 else t.shape[1] * D + (t.shape[1] * D & 1))
+            if s & 1:
+                raise GppError(f"{name}: the batch stride ({s}) is odd: every element must stay 16-byte aligned (pad the elements)")
+            if s < M * D:
+                raise GppError(f"{name}: the batch stride ({s}) is shorter than an element ({M * D})")
+        if M < 1:
+            raise GppError(f"{name} needs at least one row")
+        return M, s
+
+    def _dx_checks_batched(self, what, Ua, Ub, w, sf2, d0, nd, kind, d_split):
+        """The operand checks of the three batched calls, those of ``_dx_checks`` per element; returns (B, D, Ma, sUa, Mb, sUb)."""
+        for t, n in ((w, "w"), (sf2, "sf2")):
+            _need(t, torch.float64, n)
+        if w.dim() != 2 or not w.is_contiguous():
+            raise GppError(f"{what}: w must be a contiguous (B, D) matrix (got {tuple(w.shape)})")
+        B, D = w.shape
+        _check_features(D)
+        if B < 1 or B > 65535:
+            raise GppError(f"{what} takes 1..65535 elements (got {B})")
+        if sf2.dim() != 1 or sf2.numel() != B or not sf2.is_contiguous():
+            raise GppError(f"{what}: sf2 must be a contiguous vector of {B} values (got {tuple(sf2.shape)})")
+        Ma, sa = self._dx_rows_batched("Ua", Ua, B, D)
+        Mb, sb = self._dx_rows_batched("Ub", Ub, B, D)
+        if not (0 <= int(d_split) <= D) or kind not in (KIND_RBF, KIND_MATERN32, KIND_MATERN52):
+            raise GppError(f"bad kernel kind / d_split ({kind}, {d_split}) for {D} features")
+        if nd < 1 or d0 < 0 or d0 + nd > D:
+            raise GppError(f"the differentiated columns [{d0}, {d0 + nd}) must be a non-empty range of the {D} features")
+        return B, D, Ma, sa, Mb, sb
+
+    @staticmethod
+    def _dx_window_batched(name, out, B, rows, cols):
+        """The (B, rows, cols) window of a batched call, e.g. a block of ``batched_buffer``; returns (leading dimension, batch stride)."""
+        _need(out, torch.float64, name)
+        if out.dim() != 3 or out.stride(2) != 1 or tuple(out.shape) != (B, rows, cols):
+            raise GppError(f"{name} must be {B} x {rows} x {cols} with unit column stride (got {tuple(out.shape)})")
+        ld = out.stride(1) if rows > 1 else max(cols + (cols & 1), out.stride(1))
+        if ld & 1 or ld < cols:
+            raise GppError(f"{name}: the leading dimension ({ld}) must be even and at least {cols}")
+        s = out.stride(0) if B > 1 else rows * ld
+        if s & 1:
+            raise GppError(f"{name}: the batch stride ({s}) is odd: every element must stay 16-byte aligned")
+        if B > 1 and s < (rows - 1) * ld + cols:
+            raise GppError(f"{name}: the batch stride ({s}) is shorter than an element")
+        if out.data_ptr() & 15:
+            raise GppError(f"{name} must be 16-byte aligned")
+        return ld, s
+
+    @staticmethod
+    def _sel_args(sel):
+        return (None, None) if sel is None else (sel.first.data_ptr(), sel.dir.data_ptr())
+
+    @_on_own_device
+    def cross_kernel_dx_batched(self, Ua, Ub, w, sf2, d0, nd, out, *, kind=KIND_RBF, d_split=0, sel=None):
+        """``cross_kernel_dx`` for B problems in one launch (gpp_cross_kernel_dx_batched).  Ua: (M, D) shared or (B, M, D); Ub: (N, D)
+        shared or (B, N, D); w: (B, D); sf2: (B,); out: a (B, N, q) window with unit column stride, an even leading dimension and an
+        even batch stride, 16-byte aligned, q = M nd or ``sel.q`` (ONE selection serves every element).  Element b is bitwise
+        ``cross_kernel_dx`` on element b's operands.  Everything is checked before the launch."""
+        d0, nd = int(d0), int(nd)
+        B, D, M, sa, N, sb = self._dx_checks_batched("cross_kernel_dx_batched", Ua, Ub, w, sf2, d0, nd, kind, d_split)
+        if sel is not None:
+            sel._check("cross_kernel_dx_batched", M, nd, Ua.device)
+        q = M * nd if sel is None else sel.q
+        ld, so = self._dx_window_batched("Dk", out, B, N, q)
+        self._stream()
+        check(self.lib.gpp_cross_kernel_dx_batched(self.h, Ua.data_ptr(), sa, M, Ub.data_ptr(), sb, N, D, w.data_ptr(), sf2.data_ptr(),
+                                                   int(kind), int(d_split), d0, nd, *self._sel_args(sel), q, out.data_ptr(), ld, so, B),
+              "gpp_cross_kernel_dx_batched")
+        return out
+
+    @_on_own_device
+    def kernel_dxdx_batched(self, Ua, Ub, w, sf2, d0, nd, out, *, kind=KIND_RBF, d_split=0, sel_a=None, sel_b=None):
+        """``kernel_dxdx`` for B problems in one launch (gpp_kernel_dxdx_batched): the operands of ``cross_kernel_dx_batched``, out a
+        (B, qa, qb) window.  Element b is bitwise ``kernel_dxdx`` on element b's operands.  Everything is checked before the launch."""
+        d0, nd = int(d0), int(nd)
+        B, D, Ma, sa, Mb, sb = self._dx_checks_batched("kernel_dxdx_batched", Ua, Ub, w, sf2, d0, nd, kind, d_split)
+        if sel_a is not None:
+            sel_a._check("kernel_dxdx_batched (rows)", Ma, nd, Ua.device)
+        if sel_b is not None:
+            sel_b._check("kernel_dxdx_batched (columns)", Mb, nd, Ua.device)
+        qa, qb = (Ma * nd if sel_a is None else sel_a.q), (Mb * nd if sel_b is None else sel_b.q)
+        ld, so = self._dx_window_batched("H", out, B, qa, qb)
+        self._stream()
+        check(self.lib.gpp_kernel_dxdx_batched(self.h, Ua.data_ptr(), sa, Ma, Ub.data_ptr(), sb, Mb, D, w.data_ptr(), sf2.data_ptr(),
+                                               int(kind), int(d_split), d0, nd, *self._sel_args(sel_a), qa, *self._sel_args(sel_b), qb,
+                                               out.data_ptr(), ld, so, B), "gpp_kernel_dxdx_batched")
+        return out
+
+    @_on_own_device
+    def gek_grad_reduce_batched(self, U, Ug, w, sf2, d0, nd, alpha, Kinv, dU, g_w, g_sf2, g_U=None, g_Ug=None, *, kind=KIND_RBF,
+                                d_split=0, sel=None):
+        """``gek_grad_reduce`` for B problems in one launch (gpp_gek_grad_reduce_batched): ADDS to ``g_w`` (B, D), ``g_sf2`` (B) and
+        ``g_U`` (B, N, dU), WRITES ``g_Ug`` (B, Mg, dU), all contiguous.  U: (N, D) shared or (B, N, D); Ug: (Mg, D) shared or
+        (B, Mg, D); w: (B, D); sf2: (B,); alpha: a (B, n) batched vector (even row stride); Kinv: a (B, n, n) window as
+        ``lauum_batched`` leaves it.  Element b is bitwise ``gek_grad_reduce`` on element b's operands.  Everything is checked before
+        the launch."""
+        d0, nd, dU = int(d0), int(nd), int(dU)
+        B, D, Mg, sug, N, su = self._dx_checks_batched("gek_grad_reduce_batched", Ug, U, w, sf2, d0, nd, kind, d_split)
+        if sel is not None:
+            sel._check("gek_grad_reduce_batched", Mg, nd, Ug.device)
+        q = Mg * nd if sel is None else sel.q
+        n = N + q
+        if dU < 0 or dU > d0 or (kind != KIND_RBF and dU > int(d_split)):
+            raise GppError(f"gek_grad_reduce_batched: the {dU} feature columns with a gradient must lie in front of the differentiated "
+                           f"ones (d0 = {d0}) and, on a Matern kind, inside the RBF factor (d_split = {d_split})")
+        _need(alpha, torch.float64, "alpha")
+        if alpha.dim() != 2 or tuple(alpha.shape) != (B, n) or alpha.stride(1) != 1:
+            raise GppError(f"alpha must be a ({B}, {n}) batched vector (got {tuple(alpha.shape)})")
+        sv = alpha.stride(0) if B > 1 else n + (n & 1)
+        if sv & 1:
+            raise GppError(f"alpha: the batch stride ({sv}) is odd: every element must stay 16-byte aligned (use batched_vector)")
+        if sv < n:
+            raise GppError(f"alpha: the batch stride ({sv}) is shorter than an element ({n})")
+        ld, sk = self._dx_window_batched("Kinv", Kinv, B, n, n)
+        for t, name, shape in ((g_w, "g_w", (B, D)), (g_sf2, "g_sf2", (B,)), (g_U, "g_U", (B, N, dU)), (g_Ug, "g_Ug", (B, Mg, dU))):
+            if t is None:
+                if dU > 0 or name in ("g_w", "g_sf2"):
+                    raise GppError(f"gek_grad_reduce_batched: {name} is missing")
+                continue
+            _need(t, torch.float64, name)
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise GppError(f"{name} must be a contiguous {shape} tensor (got {tuple(t.shape)})")
+        need = B * int(self.lib.gpp_workspace_bytes(self.h, OP_GEK_GRAD, N, Mg, D, dU))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            check(self.lib.gpp_set_workspace(self.h, self._ws.data_ptr(), self._ws.numel()), "gpp_set_workspace")
+        self._stream()
+        status = self.lib.gpp_gek_grad_reduce_batched(self.h, U.data_ptr(), su, N, Ug.data_ptr(), sug, Mg, D, w.data_ptr(),
+                                                      sf2.data_ptr(), int(kind), int(d_split), d0, nd, *self._sel_args(sel), q,
+                                                      alpha.data_ptr(), sv, Kinv.data_ptr(), ld, sk, dU, g_w.data_ptr(),
+                                                      g_sf2.data_ptr(), _ptr(g_U) if dU else None, _ptr(g_Ug) if dU else None, B)
+        if status == NO_WORKSPACE:
+            raise GppError("gpp_gek_grad_reduce_batched: the handle's scratch workspace is missing or too small")
+        check(status, "gpp_gek_grad_reduce_batched")
+
 
 
 def post_cross_min_workspace_bytes(Mc: int, Mr: int, Q: int) -> int:

@@ -10,6 +10,8 @@ kernel of ``csrc/`` takes a batch dimension (``gpp_*_batched``), and 64 restarts
     U (N, D) shared or (B, N, D);  w (B, D);  sf2 (B,);  tau (B, S);  mean (B, N);  y (N,) or (B, N)  ->  mll (B,)
 ``BatchedLOOFunction`` is ``linalg.ExactLOOFunction`` (the leave-one-out pseudo-likelihood) in the same form; the two share the
 forward's scaffold and the backward, as the eager pair shares ``linalg._exact_forward`` / ``_eval_backward``.
+``BatchedGEKFunction`` is ``linalg.ExactGEKFunction`` (the joint density of function values and gradient observations) in the same
+form, with a forward of its own: its matrix has three blocks and its jitter goes on the gradient rows as well.
 Elements whose covariance is not positive definite after the jitter schedule (gpytorch's 1e-8 * 10^i) return NaN and
 zero gradients instead of raising: one bad restart must not stop the others (the drivers score it +inf).
 """
@@ -20,11 +22,12 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from .backend import KIND_RBF, UPLO_UPPER, GppContext, get_context
+from .backend import KIND_RBF, UPLO_UPPER, GppContext, get_context, row_stride
 from .linalg import _as_f64
 from .psd_safe import jitter_schedule
 
-__all__ = ["BatchedWorkspace", "BatchedMLLFunction", "batched_mll", "BatchedLOOFunction", "batched_loo"]
+__all__ = ["BatchedWorkspace", "BatchedMLLFunction", "batched_mll", "BatchedLOOFunction", "batched_loo", "BatchedGEKFunction",
+           "batched_gek_mll"]
 
 
 class BatchedWorkspace:
@@ -246,6 +249,193 @@ class BatchedLOOFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         return _batched_backward(ctx, grad_out)
+
+
+def _even_elements(t: torch.Tensor) -> torch.Tensor:
+    """``t`` (B, M, D) contiguous with every element 16-byte aligned: an odd M D is padded by one double per element (the batched
+    derivative kernels take even batch strides only).  A shared (M, D) block is returned as it is."""
+    if t.dim() == 2 or not (t.shape[1] * t.shape[2]) & 1:
+        return t
+    B, M, D = t.shape
+    buf = torch.empty(B, M * D + 1, dtype=t.dtype, device=t.device)
+    out = buf[:, :M * D].view(B, M, D)
+    out.copy_(t)
+    return out
+
+
+class BatchedGEKFunction(torch.autograd.Function):
+    """``linalg.ExactGEKFunction`` with a leading batch dimension: (B,) joint log-densities log N([y - mean_b; r_g] | 0, Kj_b) of N
+    function rows and q gradient observations, Kj_b built from w_b, sf2_b, tau_b (and U_b, Ug_b when the features differ per element).
+        U (N, D) shared or (B, N, D);  Ug (Mg, D) shared or (B, Mg, D);  w (B, D);  sf2 (B,);  tau (B, S);  mean (B, N) or (N,);
+        y (N,) or (B, N);  r_g (q,) shared;  nu (q,) shared or None
+    ``nu=None``: ``nugget_rel`` times the prior curvature at EACH element's w and sf2, whose derivative by w and sf2 is added on the
+    host as (B, nd) sums, as the eager function does.  The sequence is the eager one, every launch serving all elements: the three
+    blocks into the upper triangle of ``ws.A`` (the two derivative blocks by gpp_cross_kernel_dx_batched / gpp_kernel_dxdx_batched,
+    built aside and copied when N is odd: their 16-byte stores need an even first column), nu and the jitter on the gradient rows'
+    diagonal, potrf, trtri, z, alpha, LAUUM, gpp_grad_reduce_batched on the leading N x N views, gpp_gek_grad_reduce_batched.
+    The jitter loop is its own: an element that fails is retried with the schedule's next jitter on ITS whole diagonal (function and
+    gradient rows, as the eager function adds ``jit`` to both) while the others keep theirs; one that is still not positive definite
+    returns NaN and zero gradients.  The gradients are produced in ``forward``; ``backward`` only scales, with the conventions of
+    ``_batched_backward``.  Not available inside a graph capture (as the eager objective)."""
+
+    @staticmethod
+    def forward(ctx, U, Ug, w, sf2, tau, mean, y, r_g, nu, grp, kind, d_split, d0, nd, dU, nugget_rel, sel=None):
+        from .linalg import KernelSpec, _curvature_coefficients
+
+        dev = w.device
+        gctx = get_context(dev)  # raises GppError for anything but a GPU: there is no CPU path
+        with torch.cuda.device(dev):
+            if torch.cuda.is_current_stream_capturing():
+                raise NotImplementedError("the gradient-enhanced objective is not available inside a graph capture")
+            B, D = w.shape
+            N, Mg = U.shape[-2], Ug.shape[-2]
+            q = Mg * nd if sel is None else sel.q
+            n = N + q
+            Ud, Ugd = _even_elements(_as_f64(U.detach(), dev)), _even_elements(_as_f64(Ug.detach(), dev))
+            wd, sd, td = _as_f64(w.detach(), dev), _as_f64(sf2.detach().reshape(B), dev), _as_f64(tau.detach().reshape(B, -1), dev)
+            S = td.shape[1]
+            if grp is not None and grp.dtype != torch.int32:
+                grp = grp.to(torch.int32)
+            need = ctx.needs_input_grad
+            need_grad = any(need[:7])
+            need_U = (need[0] or need[1]) and dU > 0
+            dUk = dU if need_U else 0
+            # c_j of the prior curvature c_j w_j sf2 (linalg.gradient_prior_curvature): the kind and the split are shared
+            coef = float(nugget_rel) * _curvature_coefficients(KernelSpec(wd[0], sd[0], kind, d_split))[d0:d0 + nd]
+            if nu is None:
+                nu_d = coef * wd[:, d0:d0 + nd] * sd.unsqueeze(1)  # (B, nd)
+                nu_d = nu_d.repeat(1, Mg) if sel is None else nu_d[:, sel.flat % nd]
+            else:
+                nu_d = _as_f64(nu.detach().reshape(1, -1), dev)
+            ws = get_batched_workspace(gctx, B, n)
+            ws.epoch += 1
+            torch.sub(_as_f64(y.detach(), dev).expand(B, N), _as_f64(mean.detach(), dev).expand(B, N), out=ws.r[:, :N])
+            ws.r[:, N:].copy_(_as_f64(r_g.detach().reshape(1, -1), dev).expand(B, q))
+            g_w = g_s = g_t = g_Ud = g_Ugd = None
+            if need_grad:
+                g_w = torch.empty(B, D, dtype=torch.float64, device=dev)
+                g_s = torch.empty(B, dtype=torch.float64, device=dev)
+                g_t = torch.empty(B, S, dtype=torch.float64, device=dev)
+                if need_U:
+                    g_Ud = torch.empty(B, N, dU, dtype=torch.float64, device=dev)
+                    g_Ugd = torch.empty(B, Mg, dU, dtype=torch.float64, device=dev)
+            aligned = N % 2 == 0
+            Kfg_w, Kgg_w = ws.A[:, :N, N:n], ws.A[:, N:n, N:n]
+            Kfg_out = Kfg_w if aligned else torch.empty(B, N, row_stride(q), dtype=torch.float64, device=dev)[:, :, :q]
+            Kgg_out = Kgg_w if aligned else torch.empty(B, q, row_stride(q), dtype=torch.float64, device=dev)[:, :, :q]
+            gdiag = Kgg_w.diagonal(dim1=1, dim2=2)
+
+            def rest():
+                gctx.trtri_batched(ws.A, ws.Li, ws.Ki)
+                gctx.mll_reduce_batched(ws.A, ws.Li, ws.r, ws.z, ws.out3)
+                if not need_grad:
+                    return
+                gctx.alpha_batched(ws.Li, ws.z, ws.alpha)
+                gctx.lauum_batched(ws.Li, ws.Ki)
+                gctx.grad_reduce_batched(Ud, wd, sd, grp, S, ws.alpha[:, :N], ws.Ki[:, :N, :N], dUk, g_w, g_s, g_t, g_Ud, kind=kind,
+                                         d_split=d_split)
+                gctx.gek_grad_reduce_batched(Ud, Ugd, wd, sd, d0, nd, ws.alpha, ws.Ki, dUk, g_w, g_s, g_Ud, g_Ugd, kind=kind,
+                                             d_split=d_split, sel=sel)
+                if nu is None:
+                    # d nu_k / dw_j = rel c_j sf2, d nu_k / dsf2 = rel c_j w_j on the rows k = (a, j), times W_kk
+                    a_g = ws.alpha[:, N:]
+                    Wd = 0.5 * (a_g * a_g - ws.Ki[:, N:n, N:n].diagonal(dim1=1, dim2=2))
+                    if sel is not None:  # (scattered into the dense layout, zeros elsewhere: the same ordered sum, no atomics)
+                        dense = torch.zeros(B, Mg * nd, dtype=torch.float64, device=dev)
+                        dense[:, sel.flat] = Wd
+                        Wd = dense
+                    Wd = Wd.reshape(B, Mg, nd).sum(1)
+                    g_w[:, d0:d0 + nd].add_(coef * sd.unsqueeze(1) * Wd)
+                    g_s.add_((coef * wd[:, d0:d0 + nd] * Wd).sum(1))
+
+            jitters = jitter_schedule()[1:]  # (the first attempt is the unjittered one)
+            extra = torch.zeros(B, 1, dtype=torch.float64, device=dev)
+            ok = None
+            for attempt in range(len(jitters) + 1):
+                gctx.kernel_build_batched(Ud, wd, sd, td + extra, grp, ws.A[:, :N, :N], kind=kind, d_split=d_split, uplo=UPLO_UPPER)
+                gctx.cross_kernel_dx_batched(Ugd, Ud, wd, sd, d0, nd, Kfg_out, kind=kind, d_split=d_split, sel=sel)
+                gctx.kernel_dxdx_batched(Ugd, Ugd, wd, sd, d0, nd, Kgg_out, kind=kind, d_split=d_split, sel_a=sel, sel_b=sel)
+                if not aligned:
+                    Kfg_w.copy_(Kfg_out)
+                    Kgg_w.copy_(Kgg_out)
+                gdiag.add_(nu_d + extra)
+                gctx.potrf_batched(ws.A, ws.Li, ws.info)
+                ok = ws.info == 0
+                ws.info_host.copy_(ws.info, non_blocking=True)
+                ws.info_event.record()
+                rest()
+                ws.info_event.synchronize()
+                if bool((ws.info_host == 0).all()) or attempt == len(jitters):
+                    break
+                extra = torch.where(ok.unsqueeze(1), extra, torch.full_like(extra, jitters[attempt]))
+            value = ws.out3[:, 2].clone()
+            ctx.saved = (g_w, g_s, g_t, g_Ud, g_Ugd, ws.alpha[:, :N].clone() if need_grad else None, ok, (B, N, Mg, D, dU))
+            ctx.in_dtypes = (U.dtype, Ug.dtype, w.dtype, sf2.dtype, tau.dtype, mean.dtype, y.dtype)
+            ctx.shapes = (U.shape, Ug.shape, sf2.shape, tau.shape, mean.shape, y.shape)
+            return torch.where(ok, value, torch.full_like(value, float("nan")))
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        g_w, g_s, g_t, g_Ud, g_Ugd, gm_all, ok, (B, N, Mg, D, dU) = ctx.saved
+        need, dt = ctx.needs_input_grad, ctx.in_dtypes
+        U_shape, Ug_shape, sf2_shape, tau_shape, mean_shape, y_shape = ctx.shapes
+        dev = gm_all.device
+        go = torch.where(ok, grad_out.to(torch.float64), torch.zeros_like(grad_out, dtype=torch.float64))  # failed: no gradient
+        gm = go.unsqueeze(1) * torch.where(ok.unsqueeze(1), gm_all, torch.zeros_like(gm_all))
+
+        def rows(g_d, M, shape):  # the gradient of a block of feature rows: columns [:dU], summed over the batch when shared
+            full = torch.zeros(B, M, D, dtype=torch.float64, device=dev)
+            if g_d is not None:
+                full[:, :, :dU] = torch.where(ok.view(B, 1, 1), g_d, torch.zeros_like(g_d)) * go.view(B, 1, 1)
+            return full if len(shape) == 3 else full.sum(0)
+
+        def red(t, shape):  # gradient of a broadcast argument: sum over the batch
+            return t.reshape(shape) if len(shape) == t.dim() else t.sum(0).reshape(shape)
+
+        nanfree = lambda t: torch.where(torch.isfinite(t), t, torch.zeros_like(t))  # noqa: E731
+        return (rows(g_Ud, N, U_shape).to(dt[0]) if need[0] else None,
+                rows(g_Ugd, Mg, Ug_shape).to(dt[1]) if need[1] else None,
+                nanfree(go.unsqueeze(1) * g_w).to(dt[2]) if need[2] else None,
+                nanfree(go * g_s).reshape(sf2_shape).to(dt[3]) if need[3] else None,
+                nanfree(go.unsqueeze(1) * g_t).reshape(tau_shape).to(dt[4]) if need[4] else None,
+                red(gm, mean_shape).to(dt[5]) if need[5] else None,
+                red(-gm, y_shape).to(dt[6]) if need[6] else None) + (None,) * 10
+
+
+def batched_gek_mll(U: torch.Tensor, Ug: torch.Tensor, w: torch.Tensor, sf2: torch.Tensor, tau: torch.Tensor, mean: torch.Tensor,
+                    y: torch.Tensor, r_g: torch.Tensor, noise: Optional[torch.Tensor], grp: Optional[torch.Tensor], kind: int,
+                    d_split: int, d0: int, nd: int, n_grad_dims: int = 0, sel=None) -> torch.Tensor:
+    """(B,) joint log-densities log N([y - mean_b; r_g] | 0, Kj_b) of the N function rows and the q observed gradients with respect
+    to the features d0 .. d0 + nd - 1 at the rows ``Ug``, for B parameter sets in one pass: ``linalg.exact_gek_mll`` with a leading
+    batch dimension (:class:`BatchedGEKFunction` for the shapes).  ``noise``: the q variances of the gradient observations, shared,
+    or None for ``gradient_enhanced.GRADIENT_NUGGET_REL`` times the prior curvature at each element's own hyperparameters; ``sel``: a
+    ``backend.GradientSelection`` of the observed (point, direction) entries, one for every element.  Differentiable with respect to
+    U[..., :n_grad_dims], Ug[..., :n_grad_dims], w, sf2, tau, mean and y; an element that is not positive definite after the jitter
+    schedule gives NaN and zero gradients.  Refused under ``settings.sharded_evaluation`` and inside a graph capture."""
+    from .gradient_enhanced import GRADIENT_NUGGET_REL
+    from .linalg import _gradient_cache_refusals
+
+    _gradient_cache_refusals("the gradient-enhanced objective")
+    d0, nd, dU = int(d0), int(nd), int(n_grad_dims)
+    if w.dim() != 2:
+        raise ValueError(f"w must be (B, D) (got {tuple(w.shape)})")
+    B, D = w.shape
+    for t, name in ((U, "U"), (Ug, "Ug")):
+        if t.dim() not in (2, 3) or t.shape[-1] != D or t.shape[-2] < 1 or (t.dim() == 3 and t.shape[0] != B):
+            raise ValueError(f"{name} must be (rows, {D}) or ({B}, rows, {D}) with at least one row (got {tuple(t.shape)})")
+    if nd < 1 or d0 < 0 or d0 + nd > D:
+        raise ValueError(f"the differentiated features [{d0}, {d0 + nd}) must be a non-empty range of the {D} features")
+    Mg = Ug.shape[-2]
+    if sel is not None and (sel.num_points, sel.nd) != (Mg, nd):
+        raise ValueError(f"a selection of {sel.num_points} points x {sel.nd} directions for {Mg} x {nd}")
+    q = Mg * nd if sel is None else sel.q
+    if r_g.numel() != q or (noise is not None and noise.numel() != q):
+        raise ValueError(f"{r_g.numel()} gradients / {None if noise is None else noise.numel()} noise variances for {q} gradient "
+                         "observations")
+    if dU > d0:
+        raise ValueError(f"the {dU} feature columns with a gradient must lie in front of the differentiated ones (d0 = {d0})")
+    return BatchedGEKFunction.apply(U, Ug, w, sf2, tau, mean, y, r_g, noise, grp, int(kind), int(d_split), d0, nd, dU,
+                                    GRADIENT_NUGGET_REL, sel)
 
 
 def batched_loo(U: torch.Tensor, w: torch.Tensor, sf2: torch.Tensor, tau: torch.Tensor, mean: torch.Tensor, y: torch.Tensor,

@@ -82,7 +82,7 @@ __device__ __forceinline__ void dg_stage_selection(const int* __restrict__ first
 // SEL: the tile's points own the compact columns [first[a0], first[a0 + na)) and entry k of point a is the direction
 // dir[first[a] + k] (gpp_cross_kernel_dx_sel); the dense instantiation is the code it was.
 template <bool MAT, bool SEL>
-__global__ __launch_bounds__(DX_THREADS) void gpp_cross_dx_f64(DxArgs p) {
+__device__ __forceinline__ void dx_tile(const DxArgs& p) {
   extern __shared__ __attribute__((aligned(16))) double dx_lds[];
   constexpr int NF = MAT ? 2 : 1;
   const int D = p.D, nd = p.nd, Dp = D | 1, ndp = nd | 1;
@@ -224,6 +224,23 @@ __global__ __launch_bounds__(DX_THREADS) void gpp_cross_dx_f64(DxArgs p) {
   }
 }
 
+template <bool MAT, bool SEL>
+__global__ __launch_bounds__(DX_THREADS) void gpp_cross_dx_f64(DxArgs p) {
+  dx_tile<MAT, SEL>(p);
+}
+
+// gpp_cross_kernel_dx_batched: the tile of element blockIdx.y, whose operands lie b strides behind the first element's
+template <bool MAT, bool SEL>
+__global__ __launch_bounds__(DX_THREADS) void gpp_cross_dx_batched_f64(DxArgs p, int64_t sUa, int64_t sUb, int64_t sDk) {
+  const int64_t b = blockIdx.y;
+  p.Ua += b * sUa;
+  p.Ub += b * sUb;
+  p.w += b * p.D;
+  p.sf2 += b;
+  p.Dk += b * sDk;
+  dx_tile<MAT, SEL>(p);
+}
+
 // ---- gpp_point_gram -----------------------------------------------------------------------------------------------------------------
 constexpr int PG_WAVES = 4;    // waves of a point's work-group: each takes every fourth run of 64 column pairs
 constexpr int PG_GROUP = 32;   // points per partial sum of the weighted total
@@ -342,11 +359,31 @@ static int dg_check_selection(const int* first, const int* dir, int64_t q, int64
   return 0;
 }
 
+// The batch of a _batched entry point: the element count and the strides, in doubles, between the elements' feature rows and
+// outputs.  The codes of what only a batch can get wrong lie behind every single-problem code.
+constexpr int DG_ODD_STRIDE = -30;    // a stride is odd: the elements behind the first would lose their 16-byte alignment
+constexpr int DG_BAD_BATCH = -31;     // batch outside 1 .. 65535 (the elements are the grid's y dimension)
+constexpr int DG_SHORT_STRIDE = -32;  // a stride that is negative, or neither 0 (where 0 means shared) nor an element's extent
+struct DgBatch {
+  int batch;
+  int64_t sUa, sUb, sOut;
+};
+
+// sa / sb: the strides of Ua (ra rows) and Ub (rb rows), 0 = shared; so: that of the rows x cols output window
+static int dg_check_batch(const DgBatch& bt, int64_t ra, int64_t rb, int D, int64_t rows, int64_t cols, int64_t ld) {
+  if (bt.batch < 1 || bt.batch > 65535) return DG_BAD_BATCH;
+  if ((bt.sUa & 1) || (bt.sUb & 1) || (bt.sOut & 1)) return DG_ODD_STRIDE;
+  if (bt.sUa != 0 && bt.sUa < ra * D) return DG_SHORT_STRIDE;
+  if (bt.sUb != 0 && bt.sUb < rb * D) return DG_SHORT_STRIDE;
+  if (bt.batch > 1 && bt.sOut < (rows - 1) * ld + cols) return DG_SHORT_STRIDE;
+  return 0;
+}
+
 // gpp_cross_kernel_dx (first == NULL, cols = M nd) and gpp_cross_kernel_dx_sel; `shift`: how far the latter's three extra arguments
-// move the codes of Dk and ld
+// move the codes of Dk and ld.  `bt`: the batch of gpp_cross_kernel_dx_batched, NULL for the single-problem calls.
 static int dx_run(gpp_handle_t h, const double* Ua, int64_t M, const double* Ub, int64_t N, int D, const double* w, const double* sf2,
                   int kind, int d_split, int d0, int nd, const int* first, const int* dir, int64_t cols, double* Dk, int64_t ld,
-                  int shift) {
+                  int shift, const DgBatch* bt = nullptr) {
   if (int rc = dg_check_pair(h, Ua, M, Ub, N, D, w, sf2, kind, d_split, d0, nd)) return rc;
   if (M * nd > 0x7ffffff0) return -3;
   if (!Dk || !dg_aligned16(Dk)) return -13 - shift;
@@ -354,9 +391,24 @@ static int dx_run(gpp_handle_t h, const double* Ua, int64_t M, const double* Ub,
   const int64_t tiles_a = (M + DX_TA - 1) / DX_TA, tiles_n = (N + DX_TN - 1) / DX_TN;
   if (tiles_a * tiles_n >= ((int64_t)1 << 31)) return -3;
   DxArgs p{Ua, Ub, w, sf2, Dk, ld, (int)M, (int)N, D, kind, d_split, d0, nd, (int)tiles_a, first, dir};
-  const dim3 grid((unsigned)(tiles_a * tiles_n)), block(DX_THREADS);
+  const dim3 block(DX_THREADS);
   const bool mat = kind != GPP_KIND_RBF;
   const int nf = mat ? 2 : 1;
+  if (bt) {
+    if (int rc = dg_check_batch(*bt, M, N, D, N, cols, ld)) return rc;
+    const dim3 grid((unsigned)(tiles_a * tiles_n), (unsigned)bt->batch);
+    const size_t lds = (first ? dx_sel_lds_doubles(D, nd, nf) : dx_lds_doubles(D, nd, nf)) * sizeof(double);
+    const int64_t sa = bt->sUa, sb = bt->sUb, so = bt->sOut;
+    if (!first) {
+      if (!mat) hipLaunchKernelGGL((gpp_cross_dx_batched_f64<false, false>), grid, block, lds, h->stream, p, sa, sb, so);
+      else hipLaunchKernelGGL((gpp_cross_dx_batched_f64<true, false>), grid, block, lds, h->stream, p, sa, sb, so);
+    } else {
+      if (!mat) hipLaunchKernelGGL((gpp_cross_dx_batched_f64<false, true>), grid, block, lds, h->stream, p, sa, sb, so);
+      else hipLaunchKernelGGL((gpp_cross_dx_batched_f64<true, true>), grid, block, lds, h->stream, p, sa, sb, so);
+    }
+    return dg_rc(hipGetLastError());
+  }
+  const dim3 grid((unsigned)(tiles_a * tiles_n));
   if (!first) {
     const size_t lds = dx_lds_doubles(D, nd, nf) * sizeof(double);
     if (!mat) hipLaunchKernelGGL((gpp_cross_dx_f64<false, false>), grid, block, lds, h->stream, p);
@@ -381,6 +433,17 @@ extern "C" int gpp_cross_kernel_dx_sel(gpp_handle_t h, const double* Ua, int64_t
   if (M * nd > 0x7ffffff0) return -3;
   if (int rc = dg_check_selection(first_a, dir_a, qa, M, nd)) return rc == 1 ? -14 : -15;
   return dx_run(h, Ua, M, Ub, N, D, w, sf2, kind, d_split, d0, nd, first_a, dir_a, qa, Dk, ld, 3);
+}
+
+extern "C" int gpp_cross_kernel_dx_batched(gpp_handle_t h, const double* Ua, int64_t sUa, int64_t M, const double* Ub, int64_t sUb,
+                                           int64_t N, int D, const double* w, const double* sf2, int kind, int d_split, int d0, int nd,
+                                           const int* first_a, const int* dir_a, int64_t qa, double* Dk, int64_t ld, int64_t sDk,
+                                           int batch) {
+  if (int rc = dg_check_pair(h, Ua, M, Ub, N, D, w, sf2, kind, d_split, d0, nd)) return rc;
+  if (M * nd > 0x7ffffff0) return -3;
+  if (int rc = dg_check_selection(first_a, dir_a, qa, M, nd)) return rc == 1 ? -14 : -15;
+  const DgBatch bt{batch, sUa, sUb, sDk};
+  return dx_run(h, Ua, M, Ub, N, D, w, sf2, kind, d_split, d0, nd, first_a, dir_a, qa, Dk, ld, 3, &bt);
 }
 
 extern "C" int gpp_point_gram(gpp_handle_t h, const double* Q, int64_t ldq, int64_t M, int nd, int64_t N, const double* omega, double* G,
@@ -453,7 +516,7 @@ inline size_t hx_sel_lds_doubles(int D, int nd, int nf) { return hx_lds_doubles(
 // SEL: rows and columns through the selections of gpp_kernel_dxdx_sel, either side dense where its pair is NULL; the dense
 // instantiation is the code it was.
 template <bool MAT, bool SEL>
-__global__ __launch_bounds__(HX_THREADS) void gpp_kernel_dxdx_f64(HxArgs p) {
+__device__ __forceinline__ void hx_tile(const HxArgs& p) {
   extern __shared__ __attribute__((aligned(16))) double hx_lds[];
   constexpr int NF = MAT ? 3 : 1;
   constexpr int MT = HX_TA * HX_TBP;  // doubles of one multiplier tile
@@ -601,13 +664,30 @@ __global__ __launch_bounds__(HX_THREADS) void gpp_kernel_dxdx_f64(HxArgs p) {
   }
 }
 
+template <bool MAT, bool SEL>
+__global__ __launch_bounds__(HX_THREADS) void gpp_kernel_dxdx_f64(HxArgs p) {
+  hx_tile<MAT, SEL>(p);
+}
+
+// gpp_kernel_dxdx_batched: the tile of element blockIdx.y
+template <bool MAT, bool SEL>
+__global__ __launch_bounds__(HX_THREADS) void gpp_kernel_dxdx_batched_f64(HxArgs p, int64_t sUa, int64_t sUb, int64_t sH) {
+  const int64_t b = blockIdx.y;
+  p.Ua += b * sUa;
+  p.Ub += b * sUb;
+  p.w += b * p.D;
+  p.sf2 += b;
+  p.H += b * sH;
+  hx_tile<MAT, SEL>(p);
+}
+
 }  // namespace
 
 // gpp_kernel_dxdx (both pairs NULL, cols = Mb nd) and gpp_kernel_dxdx_sel; `shift`: how far the latter's six extra arguments move the
 // codes of H and ld
 static int hx_run(gpp_handle_t h, const double* Ua, int64_t Ma, const double* Ub, int64_t Mb, int D, const double* w, const double* sf2,
                   int kind, int d_split, int d0, int nd, const int* first_a, const int* dir_a, const int* first_b, const int* dir_b,
-                  int64_t cols, double* H, int64_t ld, int shift) {
+                  int64_t cols, double* H, int64_t ld, int shift, int64_t rows = 0, const DgBatch* bt = nullptr) {
   if (int rc = dg_check_pair(h, Ua, Ma, Ub, Mb, D, w, sf2, kind, d_split, d0, nd)) return rc;
   if (Ma * nd > 0x7ffffff0) return -3;
   if (Mb * nd > 0x7ffffff0) return -5;
@@ -616,9 +696,25 @@ static int hx_run(gpp_handle_t h, const double* Ua, int64_t Ma, const double* Ub
   const int64_t tiles_a = (Ma + HX_TA - 1) / HX_TA, tiles_b = (Mb + HX_TB - 1) / HX_TB;
   if (tiles_a * tiles_b >= ((int64_t)1 << 31)) return -3;
   HxArgs p{Ua, Ub, w, sf2, H, ld, (int)Ma, (int)Mb, D, kind, d_split, d0, nd, (int)tiles_b, first_a, dir_a, first_b, dir_b};
-  const dim3 grid((unsigned)(tiles_a * tiles_b)), block(HX_THREADS);
+  const dim3 block(HX_THREADS);
   const bool mat = kind != GPP_KIND_RBF;
   const int nf = mat ? 3 : 1;
+  if (bt) {
+    if (int rc = dg_check_batch(*bt, Ma, Mb, D, rows, cols, ld)) return rc;
+    const dim3 grid((unsigned)(tiles_a * tiles_b), (unsigned)bt->batch);
+    const bool sel = first_a || first_b;
+    const size_t lds = (sel ? hx_sel_lds_doubles(D, nd, nf) : hx_lds_doubles(D, nd, nf)) * sizeof(double);
+    const int64_t sa = bt->sUa, sb = bt->sUb, so = bt->sOut;
+    if (!sel) {
+      if (!mat) hipLaunchKernelGGL((gpp_kernel_dxdx_batched_f64<false, false>), grid, block, lds, h->stream, p, sa, sb, so);
+      else hipLaunchKernelGGL((gpp_kernel_dxdx_batched_f64<true, false>), grid, block, lds, h->stream, p, sa, sb, so);
+    } else {
+      if (!mat) hipLaunchKernelGGL((gpp_kernel_dxdx_batched_f64<false, true>), grid, block, lds, h->stream, p, sa, sb, so);
+      else hipLaunchKernelGGL((gpp_kernel_dxdx_batched_f64<true, true>), grid, block, lds, h->stream, p, sa, sb, so);
+    }
+    return dg_rc(hipGetLastError());
+  }
+  const dim3 grid((unsigned)(tiles_a * tiles_b));
   if (!first_a && !first_b) {
     const size_t lds = hx_lds_doubles(D, nd, nf) * sizeof(double);
     if (!mat) hipLaunchKernelGGL((gpp_kernel_dxdx_f64<false, false>), grid, block, lds, h->stream, p);
@@ -645,6 +741,19 @@ extern "C" int gpp_kernel_dxdx_sel(gpp_handle_t h, const double* Ua, int64_t Ma,
   if (int rc = dg_check_selection(first_a, dir_a, qa, Ma, nd)) return rc == 1 ? -14 : -15;
   if (int rc = dg_check_selection(first_b, dir_b, qb, Mb, nd)) return rc == 1 ? -17 : -18;
   return hx_run(h, Ua, Ma, Ub, Mb, D, w, sf2, kind, d_split, d0, nd, first_a, dir_a, first_b, dir_b, qb, H, ld, 6);
+}
+
+extern "C" int gpp_kernel_dxdx_batched(gpp_handle_t h, const double* Ua, int64_t sUa, int64_t Ma, const double* Ub, int64_t sUb,
+                                       int64_t Mb, int D, const double* w, const double* sf2, int kind, int d_split, int d0, int nd,
+                                       const int* first_a, const int* dir_a, int64_t qa, const int* first_b, const int* dir_b,
+                                       int64_t qb, double* H, int64_t ld, int64_t sH, int batch) {
+  if (int rc = dg_check_pair(h, Ua, Ma, Ub, Mb, D, w, sf2, kind, d_split, d0, nd)) return rc;
+  if (Ma * nd > 0x7ffffff0) return -3;
+  if (Mb * nd > 0x7ffffff0) return -5;
+  if (int rc = dg_check_selection(first_a, dir_a, qa, Ma, nd)) return rc == 1 ? -14 : -15;
+  if (int rc = dg_check_selection(first_b, dir_b, qb, Mb, nd)) return rc == 1 ? -17 : -18;
+  const DgBatch bt{batch, sUa, sUb, sH};
+  return hx_run(h, Ua, Ma, Ub, Mb, D, w, sf2, kind, d_split, d0, nd, first_a, dir_a, first_b, dir_b, qb, H, ld, 6, qa, &bt);
 }
 
 // ---- gpp_gek_grad_reduce ------------------------------------------------------------------------------------------------------------
@@ -728,7 +837,7 @@ inline size_t gk_sel_lds_doubles(int D, int nm, int nd) { return gk_lds_doubles(
 // or -1, staged once per tile.  What is read of alpha and Kinv, and the sums P_k, Q_m, D_k, run over the observed directions alone,
 // in the order of k; with every direction observed the operations are those of the dense instantiation, which is the code it was.
 template <bool MAT, int CH, bool SEL>
-__global__ __launch_bounds__(GK_THREADS) void gpp_gek_grad_tiles(GkArgs p) {
+__device__ __forceinline__ void gk_tile(const GkArgs& p) {
   extern __shared__ __attribute__((aligned(16))) double gk_lds[];
   constexpr int NM = MAT ? 5 : 1;
   const int D = p.D, nd = p.nd, d0 = p.d0, dU = p.dU, Dp = D | 1, nrec = D + 1;
@@ -956,9 +1065,38 @@ __global__ __launch_bounds__(GK_THREADS) void gpp_gek_grad_tiles(GkArgs p) {
   }
 }
 
+template <bool MAT, int CH, bool SEL>
+__global__ __launch_bounds__(GK_THREADS) void gpp_gek_grad_tiles(GkArgs p) {
+  gk_tile<MAT, CH, SEL>(p);
+}
+
+// The strides of gpp_gek_grad_reduce_batched, in doubles: element b reads U + b sU, Ug + b sUg, w + b D, sf2 + b, alpha + b sv and
+// Kinv + b sK, keeps its records and slots in the slice b sWs of the workspace and returns g_w + b D, g_sf2 + b, g_U + b N dU and
+// g_Ug + b Mg dU
+struct GkBatch {
+  int64_t sU, sUg, sv, sK, sWs;
+};
+
+// the tile of element blockIdx.y
+template <bool MAT, int CH, bool SEL>
+__global__ __launch_bounds__(GK_THREADS) void gpp_gek_grad_tiles_batched(GkArgs p, GkBatch s) {
+  const int64_t b = blockIdx.y;
+  p.U += b * s.sU;
+  p.Ug += b * s.sUg;
+  p.w += b * p.D;
+  p.sf2 += b;
+  p.alpha += b * s.sv;
+  p.Kinv += b * s.sK;
+  p.rec += b * s.sWs;
+  p.partA += b * s.sWs;
+  p.partI += b * s.sWs;
+  p.partG += b * s.sWs;
+  gk_tile<MAT, CH, SEL>(p);
+}
+
 // g_w[q] (q < D) or g_sf2 (q == D) += the tiles' records in index order
-__global__ __launch_bounds__(256) void gpp_gek_finish(const double* __restrict__ rec, int64_t ntiles, int D, double* __restrict__ g_w,
-                                                      double* __restrict__ g_sf2) {
+__device__ __forceinline__ void gk_finish(const double* __restrict__ rec, int64_t ntiles, int D, double* __restrict__ g_w,
+                                          double* __restrict__ g_sf2) {
   __shared__ double red[256];
   const int q = (int)blockIdx.x, nrec = D + 1, tid = (int)threadIdx.x;
   double v = 0.0;
@@ -975,10 +1113,21 @@ __global__ __launch_bounds__(256) void gpp_gek_finish(const double* __restrict__
   }
 }
 
+__global__ __launch_bounds__(256) void gpp_gek_finish(const double* __restrict__ rec, int64_t ntiles, int D, double* __restrict__ g_w,
+                                                      double* __restrict__ g_sf2) {
+  gk_finish(rec, ntiles, D, g_w, g_sf2);
+}
+
+__global__ __launch_bounds__(256) void gpp_gek_finish_batched(const double* __restrict__ rec, int64_t sWs, int64_t ntiles, int D,
+                                                              double* __restrict__ g_w, double* __restrict__ g_sf2) {
+  const int64_t b = blockIdx.y;
+  gk_finish(rec + b * sWs, ntiles, D, g_w + b * D, g_sf2 + b);
+}
+
 // g_Ug[e] = the slots of partA, then of partG, in slot order (written); g_U[e] += the slots of partI in slot order
-__global__ __launch_bounds__(256) void gpp_gek_gU_finish(const double* __restrict__ partA, int64_t tiles_i, const double* __restrict__ partG,
-                                                         const double* __restrict__ partI, int64_t tiles_a, int64_t N, int64_t Mg, int dU,
-                                                         double* __restrict__ g_U, double* __restrict__ g_Ug) {
+__device__ __forceinline__ void gk_gU_finish(const double* __restrict__ partA, int64_t tiles_i, const double* __restrict__ partG,
+                                             const double* __restrict__ partI, int64_t tiles_a, int64_t N, int64_t Mg, int dU,
+                                             double* __restrict__ g_U, double* __restrict__ g_Ug) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e < Mg * dU) {
     double s = 0.0;
@@ -993,7 +1142,38 @@ __global__ __launch_bounds__(256) void gpp_gek_gU_finish(const double* __restric
   }
 }
 
+__global__ __launch_bounds__(256) void gpp_gek_gU_finish(const double* __restrict__ partA, int64_t tiles_i, const double* __restrict__ partG,
+                                                         const double* __restrict__ partI, int64_t tiles_a, int64_t N, int64_t Mg, int dU,
+                                                         double* __restrict__ g_U, double* __restrict__ g_Ug) {
+  gk_gU_finish(partA, tiles_i, partG, partI, tiles_a, N, Mg, dU, g_U, g_Ug);
+}
+
+__global__ __launch_bounds__(256) void gpp_gek_gU_finish_batched(const double* __restrict__ partA, int64_t tiles_i,
+                                                                 const double* __restrict__ partG, const double* __restrict__ partI,
+                                                                 int64_t sWs, int64_t tiles_a, int64_t N, int64_t Mg, int dU,
+                                                                 double* __restrict__ g_U, double* __restrict__ g_Ug) {
+  const int64_t b = blockIdx.y;
+  gk_gU_finish(partA + b * sWs, tiles_i, partG + b * sWs, partI + b * sWs, tiles_a, N, Mg, dU, g_U + b * N * dU, g_Ug + b * Mg * dU);
+}
+
 inline int64_t gk_tiles(int64_t n) { return (n + GK_T - 1) / GK_T; }
+
+// one launch for every element of a batch: the same instantiations, the element on the grid's y dimension
+template <bool MAT>
+void gk_launch_batched(hipStream_t s, const GkArgs& p, int64_t ntiles, const GkBatch& bt, int batch) {
+  const dim3 grid((unsigned)ntiles, (unsigned)batch), block(GK_THREADS);
+  if (!p.first) {
+    const size_t lds = gk_lds_doubles(p.D, MAT ? 5 : 1) * sizeof(double);
+    if (p.nd <= 4) hipLaunchKernelGGL((gpp_gek_grad_tiles_batched<MAT, 4, false>), grid, block, lds, s, p, bt);
+    else if (p.nd <= 8) hipLaunchKernelGGL((gpp_gek_grad_tiles_batched<MAT, 8, false>), grid, block, lds, s, p, bt);
+    else hipLaunchKernelGGL((gpp_gek_grad_tiles_batched<MAT, 16, false>), grid, block, lds, s, p, bt);
+  } else {
+    const size_t lds = gk_sel_lds_doubles(p.D, MAT ? 5 : 1, p.nd) * sizeof(double);
+    if (p.nd <= 4) hipLaunchKernelGGL((gpp_gek_grad_tiles_batched<MAT, 4, true>), grid, block, lds, s, p, bt);
+    else if (p.nd <= 8) hipLaunchKernelGGL((gpp_gek_grad_tiles_batched<MAT, 8, true>), grid, block, lds, s, p, bt);
+    else hipLaunchKernelGGL((gpp_gek_grad_tiles_batched<MAT, 16, true>), grid, block, lds, s, p, bt);
+  }
+}
 
 template <bool MAT>
 void gk_launch(hipStream_t s, const GkArgs& p, int64_t ntiles) {
@@ -1024,7 +1204,8 @@ size_t gpp_gek_grad_ws_bytes(int64_t N, int64_t Mg, int D, int dU) {
 // the codes from alpha on
 static int gk_run(gpp_handle_t h, const double* U, int64_t N, const double* Ug, int64_t Mg, int D, const double* w, const double* sf2,
                   int kind, int d_split, int d0, int nd, const int* first, const int* dir, int64_t q, const double* alpha,
-                  const double* Kinv, int64_t ldk, int dU, double* g_w, double* g_sf2, double* g_U, double* g_Ug, int shift) {
+                  const double* Kinv, int64_t ldk, int dU, double* g_w, double* g_sf2, double* g_U, double* g_Ug, int shift,
+                  int batch = 0, const GkBatch* strides = nullptr) {
   if (int rc = dg_check_pair(h, U, N, Ug, Mg, D, w, sf2, kind, d_split, d0, nd)) return rc;
   if (Mg * nd > 0x7ffffff0) return -5;
   if (!alpha) return -13 - shift;
@@ -1039,12 +1220,37 @@ static int gk_run(gpp_handle_t h, const double* U, int64_t N, const double* Ug, 
   const int64_t ta = gk_tiles(Mg), ti = gk_tiles(N);
   const int64_t n_fg = ta * ti, ntiles = n_fg + ta * (ta + 1) / 2;
   if (ntiles >= ((int64_t)1 << 31)) return -3;
-  if (!h->ws || h->ws_bytes < gpp_gek_grad_ws_bytes(N, Mg, D, dU)) return GPP_NO_WORKSPACE;
+  const size_t ws_one = gpp_gek_grad_ws_bytes(N, Mg, D, dU);
+  if (strides) {
+    // gpp_gek_grad_reduce_batched: one slice of the workspace per element, every stride even (0: shared feature rows)
+    if (batch < 1 || batch > 65535) return DG_BAD_BATCH;
+    if ((strides->sU & 1) || (strides->sUg & 1) || (strides->sv & 1) || (strides->sK & 1)) return DG_ODD_STRIDE;
+    if ((strides->sU != 0 && strides->sU < N * D) || (strides->sUg != 0 && strides->sUg < Mg * D)) return DG_SHORT_STRIDE;
+    if (batch > 1 && (strides->sv < N + q || strides->sK < (N + q - 1) * ldk + N + q)) return DG_SHORT_STRIDE;
+    if (!h->ws || h->ws_bytes < (size_t)batch * ws_one) return GPP_NO_WORKSPACE;
+  } else if (!h->ws || h->ws_bytes < ws_one) {
+    return GPP_NO_WORKSPACE;
+  }
   double* rec = reinterpret_cast<double*>(h->ws);
   double* partA = rec + ntiles * (D + 1);
   double* partI = partA + (int64_t)dU * ti * Mg;
   double* partG = partI + (int64_t)dU * ta * N;
   GkArgs p{U, Ug, w, sf2, alpha, Kinv, ldk, N, Mg, ta, n_fg, D, kind, d_split, d0, nd, dU, rec, partA, partI, partG, first, dir};
+  if (strides) {
+    GkBatch bt = *strides;
+    bt.sWs = (int64_t)(ws_one / sizeof(double));
+    const unsigned nb = (unsigned)batch;
+    if (kind == GPP_KIND_RBF) gk_launch_batched<false>(h->stream, p, ntiles, bt, batch);
+    else gk_launch_batched<true>(h->stream, p, ntiles, bt, batch);
+    if (hipError_t r = hipGetLastError(); r != hipSuccess) return dg_rc(r);
+    hipLaunchKernelGGL(gpp_gek_finish_batched, dim3((unsigned)(D + 1), nb), dim3(256), 0, h->stream, rec, bt.sWs, ntiles, D, g_w, g_sf2);
+    if (dU > 0) {
+      const int64_t rows = (Mg > N ? Mg : N) * dU;
+      hipLaunchKernelGGL(gpp_gek_gU_finish_batched, dim3((unsigned)((rows + 255) / 256), nb), dim3(256), 0, h->stream, partA, ti, partG,
+                         partI, bt.sWs, ta, N, Mg, dU, g_U, g_Ug);
+    }
+    return dg_rc(hipGetLastError());
+  }
   if (kind == GPP_KIND_RBF) gk_launch<false>(h->stream, p, ntiles);
   else gk_launch<true>(h->stream, p, ntiles);
   if (hipError_t r = hipGetLastError(); r != hipSuccess) return dg_rc(r);
@@ -1072,4 +1278,17 @@ extern "C" int gpp_gek_grad_reduce_sel(gpp_handle_t h, const double* U, int64_t 
   if (Mg * nd > 0x7ffffff0) return -5;
   if (int rc = dg_check_selection(first, dir, q, Mg, nd)) return rc == 1 ? -14 : -15;
   return gk_run(h, U, N, Ug, Mg, D, w, sf2, kind, d_split, d0, nd, first, dir, q, alpha, Kinv, ldk, dU, g_w, g_sf2, g_U, g_Ug, 3);
+}
+
+extern "C" int gpp_gek_grad_reduce_batched(gpp_handle_t h, const double* U, int64_t sU, int64_t N, const double* Ug, int64_t sUg, int64_t Mg,
+                                           int D, const double* w, const double* sf2, int kind, int d_split, int d0, int nd,
+                                           const int* first, const int* dir, int64_t q, const double* alpha, int64_t sv,
+                                           const double* Kinv, int64_t ldk, int64_t sK, int dU, double* g_w, double* g_sf2, double* g_U,
+                                           double* g_Ug, int batch) {
+  if (int rc = dg_check_pair(h, U, N, Ug, Mg, D, w, sf2, kind, d_split, d0, nd)) return rc;
+  if (Mg * nd > 0x7ffffff0) return -5;
+  if (int rc = dg_check_selection(first, dir, q, Mg, nd)) return rc == 1 ? -14 : -15;
+  const GkBatch bt{sU, sUg, sv, sK, 0};
+  return gk_run(h, U, N, Ug, Mg, D, w, sf2, kind, d_split, d0, nd, first, dir, q, alpha, Kinv, ldk, dU, g_w, g_sf2, g_U, g_Ug, 3, batch,
+                &bt);
 }

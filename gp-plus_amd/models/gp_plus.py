@@ -404,8 +404,11 @@ class GP_Plus(GPR):
         columns of X — or a ``cv.FoldIndex``) maximises the grouped cross-validation log pseudo-likelihood: always the sequential,
         eager route.  ``objective="gek"`` with ``gradients=(Xg, dY)``, ``(Xg, dY, noise)`` or ``(Xg, dY, noise, observed)`` —
         the arguments of ``condition_on_gradients`` — trains on the joint marginal likelihood of the targets and of the observed
-        gradients (``gpcore.GradientEnhancedMarginalLogLikelihood``): sequential and eager as well; afterwards
-        ``condition_on_gradients`` on the same data gives the gradient-enhanced posterior at the fitted hyperparameters."""
+        gradients (``gpcore.GradientEnhancedMarginalLogLikelihood``).  It takes the batched route too, under the conditions above
+        evaluated at n = N + q rows (q observed gradient entries), every step an eager batched evaluation
+        (``batched.batched_gek_mll``; no replayed graph); otherwise, and under ``settings.batched_restarts(False)``, the restarts run
+        one after the other.  Afterwards ``condition_on_gradients`` on the same data gives the gradient-enhanced posterior at the
+        fitted hyperparameters."""
         from ..optim.mll_torch import check_objective_folds, check_objective_gradients
         folds = check_objective_folds(objective, folds, int(self.train_targets.shape[0]))
         gradients = check_objective_gradients(objective, gradients)
@@ -431,8 +434,17 @@ class GP_Plus(GPR):
             out = fit_model_torch(model=self, model_param_groups=None, lr_default=0.01, num_iter=100,
                                   num_restarts=restarts, break_steps=50, objective=objective, folds=folds)
         elif objective == "gek":
-            out = fit_model_torch(model=self, model_param_groups=None, lr_default=0.01, num_iter=100,
-                                  num_restarts=restarts, break_steps=50, objective=objective, gradients=gradients)
+            # the joint matrix has n = N + q rows, q the observed gradient entries: the batched route is judged at that size
+            dY = torch.as_tensor(gradients[1])
+            observed = gradients[3] if len(gradients) == 4 else None
+            q = int(dY.numel() if observed is None else torch.as_tensor(observed).expand(dY.shape).sum())
+            if self._restarts_fit_one_batch(restarts + 1, int(self.train_targets.shape[0]) + q):
+                from ..optim import fit_model_torch_batched
+                out = fit_model_torch_batched(self, lr_default=0.01, num_iter=100, num_restarts=restarts, break_steps=50,
+                                              objective=objective, gradients=gradients)
+            else:
+                out = fit_model_torch(model=self, model_param_groups=None, lr_default=0.01, num_iter=100,
+                                      num_restarts=restarts, break_steps=50, objective=objective, gradients=gradients)
         elif optim_type == 'adam_torch_batched' or self._restarts_fit_one_batch(restarts + 1):
             from ..optim import fit_model_torch_batched
             out = fit_model_torch_batched(self, lr_default=0.01, num_iter=100, num_restarts=restarts, break_steps=50,
@@ -443,16 +455,17 @@ class GP_Plus(GPR):
         print("## Learning the model's parameters is successfully finished ##")
         return out
 
-    def _restarts_fit_one_batch(self, B: int) -> bool:
+    def _restarts_fit_one_batch(self, B: int, n: Optional[int] = None) -> bool:
         """True when ``B`` restarts of this model should be evaluated together: batched restarts enabled, N within the batched
-        kernels' range, and three B x N x N fp64 buffers within a third of the device memory that is free right now."""
+        kernels' range, and three B x N x N fp64 buffers within a third of the device memory that is free right now.  ``n``: the
+        rows of the matrix that is factored where that is not N (objective="gek": N + q with q gradient observations)."""
         from .. import settings as gpp_settings
         from ..backend import row_stride
         from ..optim.mll_batched import BATCHED_MAX_N
 
         if not gpp_settings.batched_restarts.value() or len(self.calibration_id) > 0:
             return False  # (calibration parameters: the batched evaluation has no gradient by theta)
-        N = int(self.train_targets.shape[0])
+        N = int(self.train_targets.shape[0]) if n is None else int(n)
         if N > BATCHED_MAX_N:
             return False
         need = 3 * B * N * row_stride(N) * 8

@@ -1,6 +1,7 @@
 """Restart-parallel Adam fit on ONE GPU: all ``num_restarts + 1`` runs of ``optim/mll_torch.py:99-141`` advance together,
 every iteration being one batched evaluation (``batched.BatchedMLLFunction`` or, for ``objective="loo"``, the leave-one-out
-pseudo-likelihood ``batched.BatchedLOOFunction``: B problems per kernel launch).
+pseudo-likelihood ``batched.BatchedLOOFunction``, or, for ``objective="gek"``, the joint likelihood of targets and observed gradients
+``batched.BatchedGEKFunction``: B problems per kernel launch).
 
 The reference runs its restarts one after the other; for the data sizes of its examples (N = 100 ... 500) a single
 evaluation leaves an MI355X almost empty, so evaluating the 5 ... 65 parameter sets together costs about as much as
@@ -23,9 +24,9 @@ from typing import Dict, List, Tuple
 import torch
 from torch.func import functional_call
 
-from ..batched import batched_loo, batched_mll
+from ..batched import batched_gek_mll, batched_loo, batched_mll
 from ..gpcore.kernels import LazyKernelMatrix
-from ..gpcore.mlls import ExactMarginalLogLikelihood
+from ..gpcore.mlls import ExactMarginalLogLikelihood, GradientEnhancedMarginalLogLikelihood
 from .mll_torch import check_objective, check_objective_folds, check_objective_gradients
 
 __all__ = ["BatchedObjective", "fit_model_torch_batched", "BATCHED_MAX_N"]
@@ -37,13 +38,21 @@ BATCHED_MAX_N = 6144
 class BatchedObjective:
     """``loss()`` -> (B,) tensor of ``-(log p(y) + log priors) / N`` for the B stacked parameter sets ``self.theta``; with
     ``objective="loo"`` the leave-one-out log pseudo-likelihood takes the place of log p(y), in the normalisation of
-    ``gpcore.LeaveOneOutPseudoLikelihood``."""
+    ``gpcore.LeaveOneOutPseudoLikelihood``.  With ``objective="gek"`` and ``gradients=(Xg, dY[, noise[, observed]])`` it is the joint
+    log-density of the targets and of the q observed gradients, ``-(joint + priors) / (N + q)``, the normalisation of
+    ``gpcore.GradientEnhancedMarginalLogLikelihood`` — which validates the data here, once, and keeps them (``self.gek``)."""
 
-    def __init__(self, model, B: int, objective: str = "mll"):
+    def __init__(self, model, B: int, objective: str = "mll", gradients=None):
         self.objective = check_objective(objective)  # (before anything touches a device)
+        gradients = check_objective_gradients(objective, gradients)
         self.model, self.B = model, B
         model.train()
         self.mll = ExactMarginalLogLikelihood(model.likelihood, model)
+        self.gek = None
+        if objective == "gek":
+            self.gek = GradientEnhancedMarginalLogLikelihood(model.likelihood, model, *gradients)
+        #: observations the loss is normalised by: N, plus the gradient observations of "gek"
+        self.num_data = int(model.train_targets.shape[0]) + (0 if self.gek is None else int(self.gek.r_g.numel()))
         self.names = [n for n, p in model.named_parameters() if p.requires_grad]
         self.fixed = {n: p.detach() for n, p in model.named_parameters() if not p.requires_grad}
         self.buffers = {n: b for n, b in model.named_buffers()}
@@ -92,7 +101,11 @@ class BatchedObjective:
             for _, module, pr, closure, _ in m.named_priors():
                 prior = prior + pr.log_prob(closure(module)).sum().to(prior)
             static = (noisy.grp, cov.spec.kind, cov.spec.d_split)
-            return (cov.U1, cov.spec.w, cov.spec.sf2.reshape(()), noisy.tau.reshape(-1), out.mean, prior), static
+            tensors = (cov.U1, cov.spec.w, cov.spec.sf2.reshape(()), noisy.tau.reshape(-1), out.mean, prior)
+            if self.gek is not None:
+                # the gradient points through the same forward (joint_log_prob does the same): they carry each run's latent map
+                tensors += (torch.nn.Module.__call__(m, self.gek.Xg).lazy_covariance_matrix.U1,)
+            return tensors, static
 
         class _Shim(torch.nn.Module):  # functional_call needs a module whose forward does the work
             def __init__(s, inner):
@@ -109,13 +122,22 @@ class BatchedObjective:
 
     def loss(self) -> torch.Tensor:
         N = self.model.train_targets.shape[0]
-        U, w, sf2, tau, mean, prior = torch.vmap(self._pre, in_dims=(0,), randomness="error")(dict(self.theta))
+        U, w, sf2, tau, mean, prior, *Ug = torch.vmap(self._pre, in_dims=(0,), randomness="error")(dict(self.theta))
         grp, kind, d_split = self._static
         # leading feature columns produced by the (trainable) latent map of the categorical inputs: they differ from run to
         # run and receive gradients; without them every run sees the same features.  (Inside vmap ``requires_grad`` of
         # the features is not visible to the model's forward, so the count is taken from the model here.)
         dz = int(self.model._features(self.model.train_inputs[0])[1]) if hasattr(self.model, "_features") else 0
         learn_U = U.requires_grad and dz > 0
+        if self.gek is not None:
+            g, Ug = self.gek, Ug[0]
+            p = g.num_directions
+            d0 = U.shape[-1] - p  # the quantitative columns are the last features, in quant_index order
+            if not learn_U:
+                U, Ug = U[0], Ug[0]
+            joint = batched_gek_mll(U, Ug, w, sf2, tau, mean, self.model.train_targets, g.r_g, g.noise, grp, kind, d_split, d0, p,
+                                    min(dz, d0) if learn_U else 0, sel=g.selection)
+            return -(joint + prior) / self.num_data
         if not learn_U:
             U = U[0]  # identical features for every run: share them
         value = batched_loo if self.objective == "loo" else batched_mll
@@ -187,8 +209,10 @@ def fit_model_torch_batched(model, lr_default: float = 0.01, num_iter: int = 100
                             break_steps: int = 50, verbose: bool = False, objective: str = "mll",
                             folds=None, gradients=None) -> Tuple[float, List[List[float]]]:
     """Drop-in for ``fit_model_torch`` (same return value) that advances all restarts together.  ``objective="loo"`` maximises the
-    leave-one-out log pseudo-likelihood (plus the priors) in the same way: batched, and replayed as a HIP graph.  ``"cv"`` and
-    ``"gek"`` have no batched form and go to the sequential driver."""
+    leave-one-out log pseudo-likelihood (plus the priors) in the same way: batched, and replayed as a HIP graph.  ``"gek"`` with
+    ``gradients=`` is batched as well while N + q (q gradient observations) is at most ``BATCHED_MAX_N``, every step evaluated eagerly
+    (its evaluation is not captured: ``last_graph`` stays None); above that it goes to the sequential driver, where ``"cv"``, which
+    has no batched form, always goes."""
     N = int(model.train_targets.shape[0])
     folds = check_objective_folds(objective, folds, N)
     gradients = check_objective_gradients(objective, gradients)
@@ -198,17 +222,21 @@ def fit_model_torch_batched(model, lr_default: float = 0.01, num_iter: int = 100
         from .mll_torch import fit_model_torch
         return fit_model_torch(model, None, lr_default, num_iter, num_restarts, break_steps, verbose=verbose, objective=objective,
                                folds=folds)
-    if objective == "gek":  # neither has the gradient-enhanced objective
-        from .mll_torch import fit_model_torch
-        return fit_model_torch(model, None, lr_default, num_iter, num_restarts, break_steps, verbose=verbose, objective=objective,
-                               gradients=gradients)
     B = num_restarts + 1
+    obj = None
+    if objective == "gek":
+        obj = BatchedObjective(model, B, objective, gradients=gradients)  # (validates the gradient data: host work)
+        if obj.num_data > BATCHED_MAX_N:  # the joint matrix has N + q rows: the limit of gpp_potrf_batched applies to them
+            from .mll_torch import fit_model_torch
+            return fit_model_torch(model, None, lr_default, num_iter, num_restarts, break_steps, verbose=verbose, objective=objective,
+                                   gradients=gradients)
     if N > BATCHED_MAX_N:
         # gpp_potrf_batched factors each problem right-looking in leaf steps and rejects larger matrices; at these sizes
         # one evaluation fills the GPU by itself, so the sequential driver loses nothing
         from .mll_torch import fit_model_torch
         return fit_model_torch(model, None, lr_default, num_iter, num_restarts, break_steps, verbose=verbose, objective=objective)
-    obj = BatchedObjective(model, B, objective)
+    if obj is None:
+        obj = BatchedObjective(model, B, objective)
     obj.sample_restarts()
     params = list(obj.theta.values())
     opt = torch.optim.Adam(params, lr=lr_default)
@@ -219,7 +247,7 @@ def fit_model_torch_batched(model, lr_default: float = 0.01, num_iter: int = 100
     done_at = num_iter
     graphed = None
     from .. import settings
-    if settings.graphed_objective.value() and dev.type == "cuda" and num_iter > 8:
+    if settings.graphed_objective.value() and dev.type == "cuda" and num_iter > 8 and objective != "gek":
         try:
             graphed = _GraphedLossAndGrad(obj, params, active)
         except RuntimeError as exc:  # a capture the stack refuses: the eager loop below is the same computation — but say so

@@ -20,7 +20,8 @@ from ..gpcore.mlls import (CrossValidationPseudoLikelihood, ExactMarginalLogLike
 OBJECTIVES = ("mll", "loo", "cv")
 #: the objectives that train on observed gradients as well, given as ``gradients=(Xg, dY)``, ``(Xg, dY, noise)`` or, for partial
 #: gradients, ``(Xg, dY, noise, observed)``: "gek" is the joint
-#: marginal log-likelihood of the targets and of those gradients (gpcore.GradientEnhancedMarginalLogLikelihood), sequential and eager
+#: marginal log-likelihood of the targets and of those gradients (gpcore.GradientEnhancedMarginalLogLikelihood), sequential and eager in this
+#: driver and in fit_model_scipy; fit_model_torch_batched evaluates all restarts together (batched.batched_gek_mll)
 GRADIENT_OBJECTIVES = ("gek",)
 
 

@@ -783,6 +783,37 @@ int gpp_gek_grad_reduce_sel(gpp_handle_t h, const double* U, int64_t N, const do
                             const double* alpha, const double* Kinv, int64_t ldk, int dU, double* g_w, double* g_sf2, double* g_U,
                             double* g_Ug);
 
+/*
+ * The three calls above for `batch` problems of the same sizes in one launch each (batched.py batched_gek_mll: all restarts of an
+ * objective="gek" fit evaluated together; no reference counterpart).  The tile bodies, the per-entry arithmetic and every order of
+ * summation are those of the single-problem calls, the element being a further grid dimension: element b of a batched call gives
+ * the bits of the single-problem call on element b's operands.  Element b reads the feature rows at base + b*s (strides in doubles;
+ * 0 = one block of rows shared by every element, each side with a stride of its own), w + b*D and sf2 + b.  ONE selection serves every
+ * element: first / dir / q as in the _sel calls, a NULL pair for the dense layout (q is then M nd).
+ *   gpp_cross_kernel_dx_batched  writes Dk + b*sDk (N x qa, leading dimension ld);
+ *   gpp_kernel_dxdx_batched      writes H + b*sH (qa x qb, leading dimension ld);
+ *   gpp_gek_grad_reduce_batched  reads alpha + b*sv (n = N + q doubles) and Kinv + b*sK (n x n, leading dimension ldk, lower triangle),
+ *                                ADDS to g_w + b*D, g_sf2 + b and g_U + b*N*dU and WRITES g_Ug + b*Mg*dU (contiguous over the batch).
+ * A window of a larger matrix is a base, a leading dimension and the stride of that matrix: the builders write the blocks
+ * A_b[:N, N:n] and A_b[N:n, N:n] of a batched joint matrix in place when N is even.  The reduction keeps each element's tile records
+ * and slots in a slice of the handle workspace of its own, batch * gpp_workspace_bytes(h, GPP_OP_GEK_GRAD, N, Mg, D, dU) bytes in all
+ * (GPP_NO_WORKSPACE with nothing enqueued when it is smaller); no float atomics.  Argument codes: those of the _sel call of the same
+ * name for what the two share (counted in ITS argument list), and for the batch alone -30 an odd stride (every stride must be even:
+ * the elements behind the first keep the 16-byte alignment of the base), -31 batch outside 1 .. 65535, -32 a stride that is neither 0
+ * (feature rows only) nor at least an element's extent.
+ */
+int gpp_cross_kernel_dx_batched(gpp_handle_t h, const double* Ua, int64_t sUa, int64_t M, const double* Ub, int64_t sUb, int64_t N, int D,
+                                const double* w, const double* sf2, int kind, int d_split, int d0, int nd, const int* first_a,
+                                const int* dir_a, int64_t qa, double* Dk, int64_t ld, int64_t sDk, int batch);
+int gpp_kernel_dxdx_batched(gpp_handle_t h, const double* Ua, int64_t sUa, int64_t Ma, const double* Ub, int64_t sUb, int64_t Mb, int D,
+                            const double* w, const double* sf2, int kind, int d_split, int d0, int nd, const int* first_a,
+                            const int* dir_a, int64_t qa, const int* first_b, const int* dir_b, int64_t qb, double* H, int64_t ld,
+                            int64_t sH, int batch);
+int gpp_gek_grad_reduce_batched(gpp_handle_t h, const double* U, int64_t sU, int64_t N, const double* Ug, int64_t sUg, int64_t Mg, int D,
+                                const double* w, const double* sf2, int kind, int d_split, int d0, int nd, const int* first,
+                                const int* dir, int64_t q, const double* alpha, int64_t sv, const double* Kinv, int64_t ldk, int64_t sK,
+                                int dU, double* g_w, double* g_sf2, double* g_U, double* g_Ug, int batch);
+
 #ifdef __cplusplus
 }
 #endif
