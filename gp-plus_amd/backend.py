@@ -1156,42 +1156,96 @@ class GppContext:
         check(status, "gpp_post_cross_min")
         return out
 
-    # -- posterior of the gradient -----------------------------------------------------------------------------------------------
+    # -- the derivative blocks: posterior of the gradient, conditioning and training on gradient observations ---------------------
+    # (one problem per call, or B in one launch each for batched.BatchedGEKFunction: the checks below serve both)
     @staticmethod
-    def _dx_checks(what, sizes, Ua, Ub, w, sf2, d0, nd, kind, d_split):
-        """The operand checks ``cross_kernel_dx`` and ``kernel_dxdx`` share; returns the two row counts."""
-        for t, n in ((Ua, "Ua"), (Ub, "Ub"), (w, "w"), (sf2, "sf2")):
+    def _dx_rows(name, t, B, D):
+        """One side's feature rows: a contiguous (M, D) matrix or, in a batched call (``B`` not None), (B, M, D) with each element's
+        block contiguous; returns (M, batch stride), the stride 0 for a matrix (which every element of a batch then shares)."""
+        _need(t, torch.float64, name)
+        if t.dim() == 2:
+            if t.shape[1] != D or not t.is_contiguous():
+                raise GppError(f"{name} must be a contiguous (M, {D}) matrix{'' if B is None else f' or ({B}, M, {D})'} "
+                               f"(got {tuple(t.shape)})")
+            M, s = t.shape[0], 0
+        else:
+            if B is None or t.dim() != 3 or t.shape[0] != B or t.shape[2] != D or t.stride(2) != 1 or t.stride(1) != D:
+                raise GppError(f"{name} must be {'an (M' if B is None else f'({B}, M'}, {D}) matrix with contiguous rows "
+                               f"(got {tuple(t.shape)}, strides {t.stride()})")
+            M, s = t.shape[1], (t.stride(0) if B > 1 else t.shape[1] * D + (t.shape[1] * D & 1))
+            if s & 1:
+                raise GppError(f"{name}: the batch stride ({s}) is odd: every element must stay 16-byte aligned (pad the elements)")
+            if s < M * D:
+                raise GppError(f"{name}: the batch stride ({s}) is shorter than an element ({M * D})")
+        if M < 1:
+            raise GppError(f"{name} needs at least one row")
+        return M, s
+
+    def _dx_checks(self, what, Ua, Ub, w, sf2, d0, nd, kind, d_split, batched=False):
+        """The operand checks of the derivative-block calls; returns (B, D, Ma, sUa, Mb, sUb), B None and the strides 0 for one
+        problem.  One problem: w holds D weights and sf2 one value; batched: w is (B, D) and sf2 (B,)."""
+        for t, n in ((w, "w"), (sf2, "sf2")):
             _need(t, torch.float64, n)
-        if Ua.dim() != 2 or Ub.dim() != 2 or Ua.shape[1] != Ub.shape[1]:
-            raise GppError(f"Ua and Ub must be matrices with the same feature count (got {tuple(Ua.shape)}, {tuple(Ub.shape)})")
-        (Ma, D), Mb = Ua.shape, Ub.shape[0]
+        if not w.is_contiguous() or (batched and w.dim() != 2):
+            raise GppError(f"{what}: w must be a contiguous {'(B, D) matrix' if batched else 'vector of weights'} (got {tuple(w.shape)})")
+        B, D = w.shape if batched else (None, w.numel())
         _check_features(D)
-        if min(Ma, Mb) < 1:
-            raise GppError(f"{what} takes {sizes} >= 1 (got {Ma}, {Mb})")
-        if not (Ua.is_contiguous() and Ub.is_contiguous()):
-            raise GppError("Ua and Ub must be contiguous")
-        if w.numel() != D or not w.is_contiguous():
-            raise GppError(f"w must be a contiguous vector of {D} weights (got {w.numel()})")
-        if sf2.numel() < 1:
-            raise GppError("sf2 must hold one value")
+        if batched and (B < 1 or B > 65535):
+            raise GppError(f"{what} takes 1..65535 elements (got {B})")
+        if sf2.numel() < 1 or (batched and (sf2.dim() != 1 or sf2.numel() != B or not sf2.is_contiguous())):
+            raise GppError(f"{what}: sf2 must {f'be a contiguous vector of {B} values' if batched else 'hold one value'} "
+                           f"(got {tuple(sf2.shape)})")
+        Ma, sa = self._dx_rows("Ua", Ua, B, D)
+        Mb, sb = self._dx_rows("Ub", Ub, B, D)
         if not (0 <= int(d_split) <= D) or kind not in (KIND_RBF, KIND_MATERN32, KIND_MATERN52):
             raise GppError(f"bad kernel kind / d_split ({kind}, {d_split}) for {D} features")
         if nd < 1 or d0 < 0 or d0 + nd > D:
             raise GppError(f"the differentiated columns [{d0}, {d0 + nd}) must be a non-empty range of the {D} features")
-        return Ma, Mb
+        return B, D, Ma, sa, Mb, sb
 
     @staticmethod
-    def _dx_window(name, out, rows, cols):
-        """The output window's checks of the same two; returns its leading dimension."""
+    def _dx_window(name, out, rows, cols, B=None):
+        """The checks of a window the same calls write or read: rows x cols, or (B, rows, cols) in a batched call (e.g. a block of
+        ``batched_buffer``), with unit column stride, an even leading dimension and batch stride, 16-byte aligned; returns
+        (leading dimension, batch stride), the stride 0 for one problem."""
         _need(out, torch.float64, name)
-        if out.dim() != 2 or out.stride(1) != 1 or out.shape != (rows, cols):
-            raise GppError(f"{name} must be {rows} x {cols} with unit column stride (got {tuple(out.shape)})")
-        ld = _ld(out)
+        shape = (rows, cols) if B is None else (B, rows, cols)
+        if out.dim() != len(shape) or out.stride(-1) != 1 or tuple(out.shape) != shape:
+            raise GppError(f"{name} must be {' x '.join(map(str, shape))} with unit column stride (got {tuple(out.shape)})")
+        # (a single row has no stride to speak of: a batch takes the padded width, one problem the width itself)
+        ld = out.stride(-2) if rows > 1 else max(cols + (0 if B is None else cols & 1), out.stride(-2))
         if ld & 1 or ld < cols:
             raise GppError(f"{name}: the leading dimension ({ld}) must be even and at least {cols}")
+        s = 0
+        if B is not None:
+            s = out.stride(0) if B > 1 else rows * ld
+            if s & 1:
+                raise GppError(f"{name}: the batch stride ({s}) is odd: every element must stay 16-byte aligned")
+            if B > 1 and s < (rows - 1) * ld + cols:
+                raise GppError(f"{name}: the batch stride ({s}) is shorter than an element")
         if out.data_ptr() & 15:
             raise GppError(f"{name} must be 16-byte aligned")
-        return ld
+        return ld, s
+
+    @staticmethod
+    def _sel_q(what, sel, M, nd, device):
+        """The number of gradient entries of M points: all M nd, or those of the ``GradientSelection`` ``sel`` (checked)."""
+        if sel is None:
+            return M * nd
+        sel._check(what, M, nd, device)
+        return sel.q
+
+    @staticmethod
+    def _sel_args(sel, q):
+        """A side's selection as the ``_sel`` and ``_batched`` entry points take it: first, dir (NULL for every entry) and q."""
+        return (None, None, q) if sel is None else (sel.first.data_ptr(), sel.dir.data_ptr(), q)
+
+    def _dx_entry(self, name, sides):
+        """(entry point, its name, selection arguments) of a single-problem call: the plain one, which takes no selection
+        arguments, unless a side of ``sides`` = ((sel, q), ...) has a selection."""
+        if all(sel is None for sel, _ in sides):
+            return getattr(self.lib, name), name, ()
+        return getattr(self.lib, name + "_sel"), name + "_sel", tuple(a for side in sides for a in self._sel_args(*side))
 
     @_on_own_device
     def cross_kernel_dx(self, Ua, Ub, w, sf2, d0, nd, out, *, kind=KIND_RBF, d_split=0, sel=None):
@@ -1201,19 +1255,13 @@ class GppContext:
         ``sel``: a ``GradientSelection`` of the points ``Ua``: ``out`` is then N x sel.q, column k the selected entry k
         (gpp_cross_kernel_dx_sel)."""
         d0, nd = int(d0), int(nd)
-        M, N = self._dx_checks("cross_kernel_dx", "M, N", Ua, Ub, w, sf2, d0, nd, kind, d_split)
-        if sel is not None:
-            sel._check("cross_kernel_dx", M, nd, Ua.device)
-            ld, D = self._dx_window("Dk", out, N, sel.q), Ua.shape[1]
-            self._stream()
-            check(self.lib.gpp_cross_kernel_dx_sel(self.h, Ua.data_ptr(), M, Ub.data_ptr(), N, D, w.data_ptr(), sf2.data_ptr(),
-                                                   int(kind), int(d_split), d0, nd, sel.first.data_ptr(), sel.dir.data_ptr(), sel.q,
-                                                   out.data_ptr(), ld), "gpp_cross_kernel_dx_sel")
-            return out
-        ld, D = self._dx_window("Dk", out, N, M * nd), Ua.shape[1]
+        _, D, M, _, N, _ = self._dx_checks("cross_kernel_dx", Ua, Ub, w, sf2, d0, nd, kind, d_split)
+        q = self._sel_q("cross_kernel_dx", sel, M, nd, Ua.device)
+        ld, _ = self._dx_window("Dk", out, N, q)
+        fn, name, sel_args = self._dx_entry("gpp_cross_kernel_dx", ((sel, q),))
         self._stream()
-        check(self.lib.gpp_cross_kernel_dx(self.h, Ua.data_ptr(), M, Ub.data_ptr(), N, D, w.data_ptr(), sf2.data_ptr(), int(kind),
-                                           int(d_split), d0, nd, out.data_ptr(), ld), "gpp_cross_kernel_dx")
+        check(fn(self.h, Ua.data_ptr(), M, Ub.data_ptr(), N, D, w.data_ptr(), sf2.data_ptr(), int(kind), int(d_split), d0, nd,
+                 *sel_args, out.data_ptr(), ld), name)
         return out
 
     @_on_own_device
@@ -1266,30 +1314,50 @@ class GppContext:
         ``sel_a`` / ``sel_b``: a ``GradientSelection`` of the points ``Ua`` / ``Ub``: the rows / columns of ``out`` are then its
         selected entries (gpp_kernel_dxdx_sel)."""
         d0, nd = int(d0), int(nd)
-        Ma, Mb = self._dx_checks("kernel_dxdx", "Ma, Mb", Ua, Ub, w, sf2, d0, nd, kind, d_split)
-        if sel_a is not None or sel_b is not None:
-            if sel_a is not None:
-                sel_a._check("kernel_dxdx (rows)", Ma, nd, Ua.device)
-            if sel_b is not None:
-                sel_b._check("kernel_dxdx (columns)", Mb, nd, Ua.device)
-            qa, qb = (Ma * nd if sel_a is None else sel_a.q), (Mb * nd if sel_b is None else sel_b.q)
-            ld, D = self._dx_window("H", out, qa, qb), Ua.shape[1]
-            self._stream()
-            check(self.lib.gpp_kernel_dxdx_sel(self.h, Ua.data_ptr(), Ma, Ub.data_ptr(), Mb, D, w.data_ptr(), sf2.data_ptr(),
-                                               int(kind), int(d_split), d0, nd,
-                                               None if sel_a is None else sel_a.first.data_ptr(),
-                                               None if sel_a is None else sel_a.dir.data_ptr(), qa,
-                                               None if sel_b is None else sel_b.first.data_ptr(),
-                                               None if sel_b is None else sel_b.dir.data_ptr(), qb, out.data_ptr(), ld),
-                  "gpp_kernel_dxdx_sel")
-            return out
-        ld, D = self._dx_window("H", out, Ma * nd, Mb * nd), Ua.shape[1]
+        _, D, Ma, _, Mb, _ = self._dx_checks("kernel_dxdx", Ua, Ub, w, sf2, d0, nd, kind, d_split)
+        qa = self._sel_q("kernel_dxdx (rows)", sel_a, Ma, nd, Ua.device)
+        qb = self._sel_q("kernel_dxdx (columns)", sel_b, Mb, nd, Ua.device)
+        ld, _ = self._dx_window("H", out, qa, qb)
+        fn, name, sel_args = self._dx_entry("gpp_kernel_dxdx", ((sel_a, qa), (sel_b, qb)))
         self._stream()
-        check(self.lib.gpp_kernel_dxdx(self.h, Ua.data_ptr(), Ma, Ub.data_ptr(), Mb, D, w.data_ptr(), sf2.data_ptr(), int(kind),
-                                       int(d_split), d0, nd, out.data_ptr(), ld), "gpp_kernel_dxdx")
+        check(fn(self.h, Ua.data_ptr(), Ma, Ub.data_ptr(), Mb, D, w.data_ptr(), sf2.data_ptr(), int(kind), int(d_split), d0, nd,
+                 *sel_args, out.data_ptr(), ld), name)
         return out
 
     # -- training on gradient observations ---------------------------------------------------------------------------------------
+    def _gek_grad_checks(self, what, U, Ug, w, sf2, d0, nd, alpha, Kinv, dU, g_w, g_sf2, g_U, g_Ug, kind, d_split, sel, batched):
+        """The checks ``gek_grad_reduce`` and its batched form share: the operands, dU, alpha ((n,), or a (B, n) batched vector), the
+        window Kinv and the four outputs.  Returns (B, D, Mg, sUg, N, sU, q, alpha's batch stride, Kinv's leading dimension and batch
+        stride), B None and the strides 0 for one problem."""
+        B, D, Mg, sug, N, su = self._dx_checks(what, Ug, U, w, sf2, d0, nd, kind, d_split, batched)
+        q = self._sel_q(what, sel, Mg, nd, Ug.device)
+        n, lead = N + q, ((B,) if batched else ())
+        if dU < 0 or dU > d0 or (kind != KIND_RBF and dU > int(d_split)):
+            raise GppError(f"{what}: the {dU} feature columns with a gradient must lie in front of the differentiated ones "
+                           f"(d0 = {d0}) and, on a Matern kind, inside the RBF factor (d_split = {d_split})")
+        _need(alpha, torch.float64, "alpha")
+        if tuple(alpha.shape) != lead + (n,) or alpha.stride(-1) != 1:
+            raise GppError(f"alpha must be a {'(%d, %d) batched vector' % (B, n) if batched else 'contiguous vector of %d doubles' % n} "
+                           f"(got {tuple(alpha.shape)})")
+        sv = 0
+        if batched:
+            sv = alpha.stride(0) if B > 1 else n + (n & 1)
+            if sv & 1:
+                raise GppError(f"alpha: the batch stride ({sv}) is odd: every element must stay 16-byte aligned (use batched_vector)")
+            if sv < n:
+                raise GppError(f"alpha: the batch stride ({sv}) is shorter than an element ({n})")
+        ld, sk = self._dx_window("Kinv", Kinv, n, n, B)
+        for t, name, shape in ((g_w, "g_w", (D,)), (g_sf2, "g_sf2", () if batched else (1,)), (g_U, "g_U", (N, dU)),
+                               (g_Ug, "g_Ug", (Mg, dU))):
+            if t is None:
+                if dU > 0 or name in ("g_w", "g_sf2"):
+                    raise GppError(f"{what}: {name} is missing")
+                continue
+            _need(t, torch.float64, name)
+            if tuple(t.shape) != lead + shape or not t.is_contiguous():
+                raise GppError(f"{name} must be a contiguous {lead + shape} tensor (got {tuple(t.shape)})")
+        return B, D, Mg, sug, N, su, q, sv, ld, sk
+
     @_on_own_device
     def gek_grad_reduce(self, U, Ug, w, sf2, d0, nd, alpha, Kinv, dU, g_w, g_sf2, g_U=None, g_Ug=None, *, kind=KIND_RBF, d_split=0,
                         sel=None):
@@ -1300,107 +1368,19 @@ class GppContext:
         ``sel``: a ``GradientSelection`` of the points ``Ug``: n = N + sel.q, row N + k the selected entry k
         (gpp_gek_grad_reduce_sel)."""
         d0, nd, dU = int(d0), int(nd), int(dU)
-        Mg, N = self._dx_checks("gek_grad_reduce", "Mg, N", Ug, U, w, sf2, d0, nd, kind, d_split)
-        if sel is not None:
-            sel._check("gek_grad_reduce", Mg, nd, Ug.device)
-        D, n = U.shape[1], N + (Mg * nd if sel is None else sel.q)
-        if dU < 0 or dU > d0 or (kind != KIND_RBF and dU > int(d_split)):
-            raise GppError(f"gek_grad_reduce: the {dU} feature columns with a gradient must lie in front of the differentiated ones "
-                           f"(d0 = {d0}) and, on a Matern kind, inside the RBF factor (d_split = {d_split})")
-        _need(alpha, torch.float64, "alpha")
-        if alpha.dim() != 1 or alpha.numel() != n or not alpha.is_contiguous():
-            raise GppError(f"alpha must be a contiguous vector of {n} doubles (got {tuple(alpha.shape)})")
-        ld = self._dx_window("Kinv", Kinv, n, n)
-        for t, name, shape in ((g_w, "g_w", (D,)), (g_sf2, "g_sf2", (1,)), (g_U, "g_U", (N, dU)), (g_Ug, "g_Ug", (Mg, dU))):
-            if t is None:
-                if dU > 0 or name in ("g_w", "g_sf2"):
-                    raise GppError(f"gek_grad_reduce: {name} is missing")
-                continue
-            _need(t, torch.float64, name)
-            if tuple(t.shape) != shape or not t.is_contiguous():
-                raise GppError(f"{name} must be a contiguous {shape} tensor (got {tuple(t.shape)})")
+        _, D, Mg, _, N, _, q, _, ld, _ = self._gek_grad_checks("gek_grad_reduce", U, Ug, w, sf2, d0, nd, alpha, Kinv, dU, g_w, g_sf2,
+                                                               g_U, g_Ug, kind, d_split, sel, False)
+        fn, name, sel_args = self._dx_entry("gpp_gek_grad_reduce", ((sel, q),))
         self.ensure_workspace(OP_GEK_GRAD, N, Mg, D, dU)
         self._stream()
-        if sel is not None:
-            status = self.lib.gpp_gek_grad_reduce_sel(self.h, U.data_ptr(), N, Ug.data_ptr(), Mg, D, w.data_ptr(), sf2.data_ptr(),
-                                                      int(kind), int(d_split), d0, nd, sel.first.data_ptr(), sel.dir.data_ptr(), sel.q,
-                                                      alpha.data_ptr(), Kinv.data_ptr(), ld, dU, g_w.data_ptr(), g_sf2.data_ptr(),
-                                                      _ptr(g_U) if dU else None, _ptr(g_Ug) if dU else None)
-            if status == NO_WORKSPACE:
-                raise GppError("gpp_gek_grad_reduce_sel: the handle's scratch workspace is missing or too small")
-            check(status, "gpp_gek_grad_reduce_sel")
-            return
-        status = self.lib.gpp_gek_grad_reduce(self.h, U.data_ptr(), N, Ug.data_ptr(), Mg, D, w.data_ptr(), sf2.data_ptr(), int(kind),
-                                              int(d_split), d0, nd, alpha.data_ptr(), Kinv.data_ptr(), ld, dU, g_w.data_ptr(),
-                                              g_sf2.data_ptr(), _ptr(g_U) if dU else None, _ptr(g_Ug) if dU else None)
+        status = fn(self.h, U.data_ptr(), N, Ug.data_ptr(), Mg, D, w.data_ptr(), sf2.data_ptr(), int(kind), int(d_split), d0, nd,
+                    *sel_args, alpha.data_ptr(), Kinv.data_ptr(), ld, dU, g_w.data_ptr(), g_sf2.data_ptr(),
+                    _ptr(g_U) if dU else None, _ptr(g_Ug) if dU else None)
         if status == NO_WORKSPACE:
-            raise GppError("gpp_gek_grad_reduce: the handle's scratch workspace is missing or too small")
-        check(status, "gpp_gek_grad_reduce")
+            raise GppError(f"{name}: the handle's scratch workspace is missing or too small")
+        check(status, name)
 
     # -- the three above for B problems in one launch each (batched.BatchedGEKFunction) -------------------------------------------
-    @staticmethod
-    def _dx_rows_batched(name, t, B, D):
-        """One side's feature rows of a batched call: (M, D) shared by every element or (B, M, D), each element's block contiguous;
-        returns (M, batch stride), the stride 0 for a shared block."""
-        _need(t, torch.float64, name)
-        if t.dim() == 2:
-            if t.shape[1] != D or not t.is_contiguous():
-                raise GppError(f"{name} must be a contiguous (M, {D}) matrix or (B, M, {D}) (got {tuple(t.shape)})")
-            M, s = t.shape[0], 0
-        else:
-            if t.dim() != 3 or t.shape[0] != B or t.shape[2] != D or t.stride(2) != 1 or t.stride(1) != D:
-                raise GppError(f"{name} must be ({B}, M, {D}) with contiguous elements (got {tuple(t.shape)}, strides {t.stride()})")
-            M, s = t.shape[1], (t.stride(0) if B > 1 else t.shape[1] * D + (t.shape[1] * D & 1))
-            if s & 1:
-                raise GppError(f"{name}: the batch stride ({s}) is odd: every element must stay 16-byte aligned (pad the elements)")
-            if s < M * D:
-                raise GppError(f"{name}: the batch stride ({s}) is shorter than an element ({M * D})")
-        if M < 1:
-            raise GppError(f"{name} needs at least one row")
-        return M, s
-
-    def _dx_checks_batched(self, what, Ua, Ub, w, sf2, d0, nd, kind, d_split):
-        """The operand checks of the three batched calls, those of ``_dx_checks`` per element; returns (B, D, Ma, sUa, Mb, sUb)."""
-        for t, n in ((w, "w"), (sf2, "sf2")):
-            _need(t, torch.float64, n)
-        if w.dim() != 2 or not w.is_contiguous():
-            raise GppError(f"{what}: w must be a contiguous (B, D) matrix (got {tuple(w.shape)})")
-        B, D = w.shape
-        _check_features(D)
-        if B < 1 or B > 65535:
-            raise GppError(f"{what} takes 1..65535 elements (got {B})")
-        if sf2.dim() != 1 or sf2.numel() != B or not sf2.is_contiguous():
-            raise GppError(f"{what}: sf2 must be a contiguous vector of {B} values (got {tuple(sf2.shape)})")
-        Ma, sa = self._dx_rows_batched("Ua", Ua, B, D)
-        Mb, sb = self._dx_rows_batched("Ub", Ub, B, D)
-        if not (0 <= int(d_split) <= D) or kind not in (KIND_RBF, KIND_MATERN32, KIND_MATERN52):
-            raise GppError(f"bad kernel kind / d_split ({kind}, {d_split}) for {D} features")
-        if nd < 1 or d0 < 0 or d0 + nd > D:
-            raise GppError(f"the differentiated columns [{d0}, {d0 + nd}) must be a non-empty range of the {D} features")
-        return B, D, Ma, sa, Mb, sb
-
-    @staticmethod
-    def _dx_window_batched(name, out, B, rows, cols):
-        """The (B, rows, cols) window of a batched call, e.g. a block of ``batched_buffer``; returns (leading dimension, batch stride)."""
-        _need(out, torch.float64, name)
-        if out.dim() != 3 or out.stride(2) != 1 or tuple(out.shape) != (B, rows, cols):
-            raise GppError(f"{name} must be {B} x {rows} x {cols} with unit column stride (got {tuple(out.shape)})")
-        ld = out.stride(1) if rows > 1 else max(cols + (cols & 1), out.stride(1))
-        if ld & 1 or ld < cols:
-            raise GppError(f"{name}: the leading dimension ({ld}) must be even and at least {cols}")
-        s = out.stride(0) if B > 1 else rows * ld
-        if s & 1:
-            raise GppError(f"{name}: the batch stride ({s}) is odd: every element must stay 16-byte aligned")
-        if B > 1 and s < (rows - 1) * ld + cols:
-            raise GppError(f"{name}: the batch stride ({s}) is shorter than an element")
-        if out.data_ptr() & 15:
-            raise GppError(f"{name} must be 16-byte aligned")
-        return ld, s
-
-    @staticmethod
-    def _sel_args(sel):
-        return (None, None) if sel is None else (sel.first.data_ptr(), sel.dir.data_ptr())
-
     @_on_own_device
     def cross_kernel_dx_batched(self, Ua, Ub, w, sf2, d0, nd, out, *, kind=KIND_RBF, d_split=0, sel=None):
         """``cross_kernel_dx`` for B problems in one launch (gpp_cross_kernel_dx_batched).  Ua: (M, D) shared or (B, M, D); Ub: (N, D)
@@ -1408,14 +1388,12 @@ class GppContext:
         even batch stride, 16-byte aligned, q = M nd or ``sel.q`` (ONE selection serves every element).  Element b is bitwise
         ``cross_kernel_dx`` on element b's operands.  Everything is checked before the launch."""
         d0, nd = int(d0), int(nd)
-        B, D, M, sa, N, sb = self._dx_checks_batched("cross_kernel_dx_batched", Ua, Ub, w, sf2, d0, nd, kind, d_split)
-        if sel is not None:
-            sel._check("cross_kernel_dx_batched", M, nd, Ua.device)
-        q = M * nd if sel is None else sel.q
-        ld, so = self._dx_window_batched("Dk", out, B, N, q)
+        B, D, M, sa, N, sb = self._dx_checks("cross_kernel_dx_batched", Ua, Ub, w, sf2, d0, nd, kind, d_split, True)
+        q = self._sel_q("cross_kernel_dx_batched", sel, M, nd, Ua.device)
+        ld, so = self._dx_window("Dk", out, N, q, B)
         self._stream()
         check(self.lib.gpp_cross_kernel_dx_batched(self.h, Ua.data_ptr(), sa, M, Ub.data_ptr(), sb, N, D, w.data_ptr(), sf2.data_ptr(),
-                                                   int(kind), int(d_split), d0, nd, *self._sel_args(sel), q, out.data_ptr(), ld, so, B),
+                                                   int(kind), int(d_split), d0, nd, *self._sel_args(sel, q), out.data_ptr(), ld, so, B),
               "gpp_cross_kernel_dx_batched")
         return out
 
@@ -1424,16 +1402,13 @@ class GppContext:
         """``kernel_dxdx`` for B problems in one launch (gpp_kernel_dxdx_batched): the operands of ``cross_kernel_dx_batched``, out a
         (B, qa, qb) window.  Element b is bitwise ``kernel_dxdx`` on element b's operands.  Everything is checked before the launch."""
         d0, nd = int(d0), int(nd)
-        B, D, Ma, sa, Mb, sb = self._dx_checks_batched("kernel_dxdx_batched", Ua, Ub, w, sf2, d0, nd, kind, d_split)
-        if sel_a is not None:
-            sel_a._check("kernel_dxdx_batched (rows)", Ma, nd, Ua.device)
-        if sel_b is not None:
-            sel_b._check("kernel_dxdx_batched (columns)", Mb, nd, Ua.device)
-        qa, qb = (Ma * nd if sel_a is None else sel_a.q), (Mb * nd if sel_b is None else sel_b.q)
-        ld, so = self._dx_window_batched("H", out, B, qa, qb)
+        B, D, Ma, sa, Mb, sb = self._dx_checks("kernel_dxdx_batched", Ua, Ub, w, sf2, d0, nd, kind, d_split, True)
+        qa = self._sel_q("kernel_dxdx_batched (rows)", sel_a, Ma, nd, Ua.device)
+        qb = self._sel_q("kernel_dxdx_batched (columns)", sel_b, Mb, nd, Ua.device)
+        ld, so = self._dx_window("H", out, qa, qb, B)
         self._stream()
         check(self.lib.gpp_kernel_dxdx_batched(self.h, Ua.data_ptr(), sa, Ma, Ub.data_ptr(), sb, Mb, D, w.data_ptr(), sf2.data_ptr(),
-                                               int(kind), int(d_split), d0, nd, *self._sel_args(sel_a), qa, *self._sel_args(sel_b), qb,
+                                               int(kind), int(d_split), d0, nd, *self._sel_args(sel_a, qa), *self._sel_args(sel_b, qb),
                                                out.data_ptr(), ld, so, B), "gpp_kernel_dxdx_batched")
         return out
 
@@ -1446,44 +1421,20 @@ class GppContext:
         ``lauum_batched`` leaves it.  Element b is bitwise ``gek_grad_reduce`` on element b's operands.  Everything is checked before
         the launch."""
         d0, nd, dU = int(d0), int(nd), int(dU)
-        B, D, Mg, sug, N, su = self._dx_checks_batched("gek_grad_reduce_batched", Ug, U, w, sf2, d0, nd, kind, d_split)
-        if sel is not None:
-            sel._check("gek_grad_reduce_batched", Mg, nd, Ug.device)
-        q = Mg * nd if sel is None else sel.q
-        n = N + q
-        if dU < 0 or dU > d0 or (kind != KIND_RBF and dU > int(d_split)):
-            raise GppError(f"gek_grad_reduce_batched: the {dU} feature columns with a gradient must lie in front of the differentiated "
-                           f"ones (d0 = {d0}) and, on a Matern kind, inside the RBF factor (d_split = {d_split})")
-        _need(alpha, torch.float64, "alpha")
-        if alpha.dim() != 2 or tuple(alpha.shape) != (B, n) or alpha.stride(1) != 1:
-            raise GppError(f"alpha must be a ({B}, {n}) batched vector (got {tuple(alpha.shape)})")
-        sv = alpha.stride(0) if B > 1 else n + (n & 1)
-        if sv & 1:
-            raise GppError(f"alpha: the batch stride ({sv}) is odd: every element must stay 16-byte aligned (use batched_vector)")
-        if sv < n:
-            raise GppError(f"alpha: the batch stride ({sv}) is shorter than an element ({n})")
-        ld, sk = self._dx_window_batched("Kinv", Kinv, B, n, n)
-        for t, name, shape in ((g_w, "g_w", (B, D)), (g_sf2, "g_sf2", (B,)), (g_U, "g_U", (B, N, dU)), (g_Ug, "g_Ug", (B, Mg, dU))):
-            if t is None:
-                if dU > 0 or name in ("g_w", "g_sf2"):
-                    raise GppError(f"gek_grad_reduce_batched: {name} is missing")
-                continue
-            _need(t, torch.float64, name)
-            if tuple(t.shape) != shape or not t.is_contiguous():
-                raise GppError(f"{name} must be a contiguous {shape} tensor (got {tuple(t.shape)})")
+        B, D, Mg, sug, N, su, q, sv, ld, sk = self._gek_grad_checks("gek_grad_reduce_batched", U, Ug, w, sf2, d0, nd, alpha, Kinv, dU,
+                                                                    g_w, g_sf2, g_U, g_Ug, kind, d_split, sel, True)
         need = B * int(self.lib.gpp_workspace_bytes(self.h, OP_GEK_GRAD, N, Mg, D, dU))
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             check(self.lib.gpp_set_workspace(self.h, self._ws.data_ptr(), self._ws.numel()), "gpp_set_workspace")
         self._stream()
         status = self.lib.gpp_gek_grad_reduce_batched(self.h, U.data_ptr(), su, N, Ug.data_ptr(), sug, Mg, D, w.data_ptr(),
-                                                      sf2.data_ptr(), int(kind), int(d_split), d0, nd, *self._sel_args(sel), q,
+                                                      sf2.data_ptr(), int(kind), int(d_split), d0, nd, *self._sel_args(sel, q),
                                                       alpha.data_ptr(), sv, Kinv.data_ptr(), ld, sk, dU, g_w.data_ptr(),
                                                       g_sf2.data_ptr(), _ptr(g_U) if dU else None, _ptr(g_Ug) if dU else None, B)
         if status == NO_WORKSPACE:
             raise GppError("gpp_gek_grad_reduce_batched: the handle's scratch workspace is missing or too small")
         check(status, "gpp_gek_grad_reduce_batched")
-
 
 
 def post_cross_min_workspace_bytes(Mc: int, Mr: int, Q: int) -> int:

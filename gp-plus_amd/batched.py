@@ -11,7 +11,8 @@ kernel of ``csrc/`` takes a batch dimension (``gpp_*_batched``), and 64 restarts
 ``BatchedLOOFunction`` is ``linalg.ExactLOOFunction`` (the leave-one-out pseudo-likelihood) in the same form; the two share the
 forward's scaffold and the backward, as the eager pair shares ``linalg._exact_forward`` / ``_eval_backward``.
 ``BatchedGEKFunction`` is ``linalg.ExactGEKFunction`` (the joint density of function values and gradient observations) in the same
-form, with a forward of its own: its matrix has three blocks and its jitter goes on the gradient rows as well.
+form; its matrix has three blocks and its jitter goes on the gradient rows as well, so it hands ``_factor_batched`` a build of its
+own and shares the attempt, the jitter policy (``psd_safe.psd_safe_batched``) and the backward with the other two.
 Elements whose covariance is not positive definite after the jitter schedule (gpytorch's 1e-8 * 10^i) return NaN and
 zero gradients instead of raising: one bad restart must not stop the others (the drivers score it +inf).
 """
@@ -23,8 +24,8 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from .backend import KIND_RBF, UPLO_UPPER, GppContext, get_context, row_stride
-from .linalg import _as_f64
-from .psd_safe import jitter_schedule
+from .linalg import _as_f64, _grad_buffers
+from .psd_safe import psd_safe_batched
 
 __all__ = ["BatchedWorkspace", "BatchedMLLFunction", "batched_mll", "BatchedLOOFunction", "batched_loo", "BatchedGEKFunction",
            "batched_gek_mll"]
@@ -73,23 +74,24 @@ def get_batched_workspace(ctx: GppContext, B: int, N: int) -> BatchedWorkspace:
     return ws
 
 
-def _factor_batched(gctx: GppContext, ws: BatchedWorkspace, U, w, sf2, tau, grp, kind, d_split, after=None) -> torch.Tensor:
-    """Build + factor all elements; failing ones are retried with gpytorch's jitter schedule added to THEIR noise.
-    Returns the boolean mask (B,) of elements that are positive definite in the end.  ``after()`` enqueues the rest of
-    the evaluation before the host waits for the status words (one wait per attempt, covering the factorisation only)."""
+def _factor_batched(gctx: GppContext, ws: BatchedWorkspace, build, after=None) -> torch.Tensor:
+    """Build + factor all elements; failing ones are retried with gpytorch's jitter schedule added to THEIR diagonal
+    (``psd_safe.psd_safe_batched``).  ``build(extra)`` writes every element's matrix into the upper triangle of ``ws.A`` with the
+    (B, 1) jitters ``extra`` on its diagonal, or as it is for ``extra`` None.  Returns the boolean mask (B,) of elements that are
+    positive definite in the end.  ``after()`` enqueues the rest of the evaluation before the host waits for the status words (one
+    wait per attempt, covering the factorisation only)."""
     if torch.cuda.is_current_stream_capturing():
-        # inside a HIP-graph capture (optim/mll_batched.py) nothing may wait for the host: ONE attempt without jitter; the status
-        # words stay on the device and the owner of the graph re-runs the step eagerly when any of them is not zero
-        gctx.kernel_build_batched(U, w, sf2, tau, grp, ws.A, kind=kind, d_split=d_split, uplo=UPLO_UPPER)
+        # inside a HIP-graph capture (optim/mll_batched.py) nothing may wait for the host: ONE attempt without jitter (and without
+        # the launch that would add a zero one); the status words stay on the device and the owner of the graph re-runs the step
+        # eagerly when any of them is not zero
+        build(None)
         gctx.potrf_batched(ws.A, ws.Li, ws.info)
         if after is not None:
             after()
         return ws.info == 0
-    jitters = jitter_schedule()[1:]  # (the first attempt is the unjittered one)
-    extra = torch.zeros(ws.B, 1, dtype=torch.float64, device=U.device)
-    ok = None
-    for attempt in range(len(jitters) + 1):
-        gctx.kernel_build_batched(U, w, sf2, tau + extra, grp, ws.A, kind=kind, d_split=d_split, uplo=UPLO_UPPER)
+
+    def attempt(extra):
+        build(extra)
         gctx.potrf_batched(ws.A, ws.Li, ws.info)
         ok = ws.info == 0
         ws.info_host.copy_(ws.info, non_blocking=True)
@@ -97,10 +99,18 @@ def _factor_batched(gctx: GppContext, ws: BatchedWorkspace, U, w, sf2, tau, grp,
         if after is not None:
             after()
         ws.info_event.synchronize()
-        if bool((ws.info_host == 0).all()) or attempt == len(jitters):
-            break
-        extra = torch.where(ok.unsqueeze(1), extra, torch.full_like(extra, jitters[attempt]))
-    return ok
+        return ok, ws.info_host
+
+    return psd_safe_batched(ws.B, ws.A.device, attempt)[0]
+
+
+def _batched_operands(w, sf2, tau, grp):
+    """w (B, D), sf2 (B,) and tau (B, S) detached, fp64 and contiguous on w's device, ``grp`` as int32, and S."""
+    dev, B = w.device, w.shape[0]
+    td = _as_f64(tau.detach().reshape(B, -1), dev)
+    if grp is not None and grp.dtype != torch.int32:
+        grp = grp.to(torch.int32)
+    return _as_f64(w.detach(), dev), _as_f64(sf2.detach().reshape(B), dev), td, grp, td.shape[1]
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -114,24 +124,20 @@ def _batched_forward(fn, ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU):
     gctx = get_context(dev)
     B, D = w.shape
     N = U.shape[-2]
-    Ud, wd, sd, td = _as_f64(U.detach(), dev), _as_f64(w.detach(), dev), _as_f64(sf2.detach().reshape(B), dev), \
-        _as_f64(tau.detach().reshape(B, -1), dev)
-    S = td.shape[1]
-    if grp is not None and grp.dtype != torch.int32:
-        grp = grp.to(torch.int32)
+    Ud = _as_f64(U.detach(), dev)
+    wd, sd, td, grp, S = _batched_operands(w, sf2, tau, grp)
     ws = get_batched_workspace(gctx, B, N)
     ws.epoch += 1
     torch.sub(_as_f64(y.detach(), dev).expand(B, N), _as_f64(mean.detach(), dev).expand(B, N), out=ws.r)
     need = ctx.needs_input_grad
     need_grad = any(need[:6])
-    need_U = need[0] and dU > 0
-    g_w = g_s = g_t = g_Ud = None
-    if need_grad:
-        g_w = torch.empty(B, D, dtype=torch.float64, device=dev)
-        g_s = torch.empty(B, dtype=torch.float64, device=dev)
-        g_t = torch.empty(B, S, dtype=torch.float64, device=dev)
-        g_Ud = torch.empty(B, N, dU, dtype=torch.float64, device=dev) if need_U else None
-    ops, grads = (Ud, wd, sd, grp, S), (dU if need_U else 0, g_w, g_s, g_t, g_Ud)
+    dUk = dU if need[0] and dU > 0 else 0
+    g_w, g_s, g_t, g_Ud = _grad_buffers(need_grad, dev, (B,), D, S, (N, dUk))
+    ops, grads = (Ud, wd, sd, grp, S), (dUk, g_w, g_s, g_t, g_Ud)
+
+    def build(extra):
+        gctx.kernel_build_batched(Ud, wd, sd, td if extra is None else td + extra, grp, ws.A, kind=kind, d_split=d_split,
+                                  uplo=UPLO_UPPER)
 
     def rest():
         gctx.trtri_batched(ws.A, ws.Li, ws.Ki)
@@ -140,44 +146,50 @@ def _batched_forward(fn, ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU):
             gctx.alpha_batched(ws.Li, ws.z, ws.alpha)
         fn.tail(gctx, ws, need_grad, ops, grads, kind, d_split)
 
-    ok = _factor_batched(gctx, ws, Ud, wd, sd, td, grp, kind, d_split, after=rest)
+    ok = _factor_batched(gctx, ws, build, after=rest)
     value, g_mean = fn.result(ws, need_grad)
-    ctx.saved = (g_w, g_s, g_t, g_Ud, g_mean, ok, (B, N, Ud.shape[-1], dU))
-    ctx.in_dtypes = (U.dtype, w.dtype, sf2.dtype, tau.dtype, mean.dtype, y.dtype)
-    ctx.shapes = (U.shape, sf2.shape, tau.shape, mean.shape, y.shape)
+    return _batched_result(ctx, ok, value, (g_w, g_s, g_t, (g_Ud,), g_mean), (U,), w, sf2, tau, mean, y)
+
+
+def _batched_result(ctx, ok, value, grads, blocks, w, sf2, tau, mean, y):
+    """Notes on ``ctx`` what ``_batched_backward`` needs — ``grads`` = (g_w, g_s, g_t, one g_U per block of feature rows in
+    ``blocks``, g_mean), the mask, every input's dtype and shape — and returns the values, NaN where ``ok`` is false."""
+    ctx.saved = grads + (ok,)
+    ctx.in_dtypes = tuple(t.dtype for t in blocks + (w, sf2, tau, mean, y))
+    ctx.shapes = (tuple(t.shape for t in blocks), sf2.shape, tau.shape, mean.shape, y.shape)
     return torch.where(ok, value, torch.full_like(value, float("nan")))
 
 
 def _batched_backward(ctx, grad_out):
-    """The gradients of (U, w, sf2, tau, mean, y) from the fp64 ones the forward produced, scaled by ``grad_out`` (zero for an
-    element that is not positive definite), each in its input's dtype and shape.  The saved ``g_mean`` is the objective's derivative
-    by the mean (alpha for the MLL, -beta for LOO); y receives its negative."""
-    g_w, g_s, g_t, g_Ud, gm_all, ok, (B, N, Dfull, dU) = ctx.saved
-    dev = gm_all.device
-    U_shape, sf2_shape, tau_shape, mean_shape, y_shape = ctx.shapes
-    need_U = g_Ud is not None
+    """The gradients of (the leading blocks of feature rows: U, or U and Ug; w, sf2, tau, mean, y) from the fp64 ones the forward
+    produced, scaled by ``grad_out`` (zero for an element that is not positive definite), each in its input's dtype and shape; None
+    for the arguments behind them.  A block's ``g_U`` (B, M, dU; or None) fills the leading columns of its gradient, summed over the
+    batch when the block is shared.  The saved ``g_mean`` is the objective's derivative by the mean (alpha for the MLL and GEK,
+    -beta for LOO); y receives its negative."""
+    g_w, g_s, g_t, g_rows, gm_all, ok = ctx.saved
+    need, dt = ctx.needs_input_grad, ctx.in_dtypes
+    row_shapes, sf2_shape, tau_shape, mean_shape, y_shape = ctx.shapes
+    k = len(row_shapes)
+    (B, D), dev = g_w.shape, g_w.device
     go = torch.where(ok, grad_out.to(torch.float64), torch.zeros_like(grad_out, dtype=torch.float64))  # failed: no gradient
-    dt = ctx.in_dtypes
-    gm = torch.where(ok.unsqueeze(1), gm_all, torch.zeros_like(gm_all))
-    g_U = None
-    if ctx.needs_input_grad[0]:
-        full = torch.zeros(B, N, Dfull, dtype=torch.float64, device=dev)
-        if need_U:
-            full[:, :, :dU] = torch.where(ok.view(B, 1, 1), g_Ud, torch.zeros_like(g_Ud)) * go.view(B, 1, 1)
-        g_U = (full if len(U_shape) == 3 else full.sum(0)).to(dt[0])
+    gm = go.unsqueeze(1) * torch.where(ok.unsqueeze(1), gm_all, torch.zeros_like(gm_all))
+
+    def rows(g_d, shape):
+        full = torch.zeros(B, shape[-2], D, dtype=torch.float64, device=dev)
+        if g_d is not None:
+            full[:, :, :g_d.shape[2]] = torch.where(ok.view(B, 1, 1), g_d, torch.zeros_like(g_d)) * go.view(B, 1, 1)
+        return full if len(shape) == 3 else full.sum(0)
 
     def red(t, shape):  # gradient of a broadcast argument: sum over the batch
         return t.reshape(shape) if len(shape) == t.dim() else t.sum(0).reshape(shape)
 
-    g_mean = go.unsqueeze(1) * gm
-    nanfree = lambda t: torch.where(torch.isfinite(t), t, torch.zeros_like(t))
-    return (g_U,
-            nanfree(go.unsqueeze(1) * g_w).to(dt[1]) if ctx.needs_input_grad[1] else None,
-            nanfree(go * g_s).reshape(sf2_shape).to(dt[2]) if ctx.needs_input_grad[2] else None,
-            nanfree(go.unsqueeze(1) * g_t).reshape(tau_shape).to(dt[3]) if ctx.needs_input_grad[3] else None,
-            red(g_mean, mean_shape).to(dt[4]) if ctx.needs_input_grad[4] else None,
-            red(-g_mean, y_shape).to(dt[5]) if ctx.needs_input_grad[5] else None,
-            None, None, None, None)
+    nanfree = lambda t: torch.where(torch.isfinite(t), t, torch.zeros_like(t))  # noqa: E731
+    return tuple(rows(g_d, shape).to(dt[i]) if need[i] else None for i, (g_d, shape) in enumerate(zip(g_rows, row_shapes))) + (
+        nanfree(go.unsqueeze(1) * g_w).to(dt[k]) if need[k] else None,
+        nanfree(go * g_s).reshape(sf2_shape).to(dt[k + 1]) if need[k + 1] else None,
+        nanfree(go.unsqueeze(1) * g_t).reshape(tau_shape).to(dt[k + 2]) if need[k + 2] else None,
+        red(gm, mean_shape).to(dt[k + 3]) if need[k + 3] else None,
+        red(-gm, y_shape).to(dt[k + 4]) if need[k + 4] else None) + (None,) * (len(need) - k - 5)
 
 
 class BatchedMLLFunction(torch.autograd.Function):
@@ -273,10 +285,10 @@ class BatchedGEKFunction(torch.autograd.Function):
     blocks into the upper triangle of ``ws.A`` (the two derivative blocks by gpp_cross_kernel_dx_batched / gpp_kernel_dxdx_batched,
     built aside and copied when N is odd: their 16-byte stores need an even first column), nu and the jitter on the gradient rows'
     diagonal, potrf, trtri, z, alpha, LAUUM, gpp_grad_reduce_batched on the leading N x N views, gpp_gek_grad_reduce_batched.
-    The jitter loop is its own: an element that fails is retried with the schedule's next jitter on ITS whole diagonal (function and
-    gradient rows, as the eager function adds ``jit`` to both) while the others keep theirs; one that is still not positive definite
-    returns NaN and zero gradients.  The gradients are produced in ``forward``; ``backward`` only scales, with the conventions of
-    ``_batched_backward``.  Not available inside a graph capture (as the eager objective)."""
+    The attempts are ``_factor_batched``'s: an element that fails is retried with the schedule's next jitter on ITS whole diagonal
+    (function and gradient rows, as the eager function adds ``jit`` to both) while the others keep theirs; one that is still not
+    positive definite returns NaN and zero gradients.  The gradients are produced in ``forward``; ``backward`` is
+    ``_batched_backward`` with two blocks of feature rows.  Not available inside a graph capture (as the eager objective)."""
 
     @staticmethod
     def forward(ctx, U, Ug, w, sf2, tau, mean, y, r_g, nu, grp, kind, d_split, d0, nd, dU, nugget_rel, sel=None):
@@ -292,14 +304,10 @@ class BatchedGEKFunction(torch.autograd.Function):
             q = Mg * nd if sel is None else sel.q
             n = N + q
             Ud, Ugd = _even_elements(_as_f64(U.detach(), dev)), _even_elements(_as_f64(Ug.detach(), dev))
-            wd, sd, td = _as_f64(w.detach(), dev), _as_f64(sf2.detach().reshape(B), dev), _as_f64(tau.detach().reshape(B, -1), dev)
-            S = td.shape[1]
-            if grp is not None and grp.dtype != torch.int32:
-                grp = grp.to(torch.int32)
+            wd, sd, td, grp, S = _batched_operands(w, sf2, tau, grp)
             need = ctx.needs_input_grad
             need_grad = any(need[:7])
-            need_U = (need[0] or need[1]) and dU > 0
-            dUk = dU if need_U else 0
+            dUk = dU if (need[0] or need[1]) and dU > 0 else 0
             # c_j of the prior curvature c_j w_j sf2 (linalg.gradient_prior_curvature): the kind and the split are shared
             coef = float(nugget_rel) * _curvature_coefficients(KernelSpec(wd[0], sd[0], kind, d_split))[d0:d0 + nd]
             if nu is None:
@@ -311,14 +319,7 @@ class BatchedGEKFunction(torch.autograd.Function):
             ws.epoch += 1
             torch.sub(_as_f64(y.detach(), dev).expand(B, N), _as_f64(mean.detach(), dev).expand(B, N), out=ws.r[:, :N])
             ws.r[:, N:].copy_(_as_f64(r_g.detach().reshape(1, -1), dev).expand(B, q))
-            g_w = g_s = g_t = g_Ud = g_Ugd = None
-            if need_grad:
-                g_w = torch.empty(B, D, dtype=torch.float64, device=dev)
-                g_s = torch.empty(B, dtype=torch.float64, device=dev)
-                g_t = torch.empty(B, S, dtype=torch.float64, device=dev)
-                if need_U:
-                    g_Ud = torch.empty(B, N, dU, dtype=torch.float64, device=dev)
-                    g_Ugd = torch.empty(B, Mg, dU, dtype=torch.float64, device=dev)
+            g_w, g_s, g_t, g_Ud, g_Ugd = _grad_buffers(need_grad, dev, (B,), D, S, (N, dUk), (Mg, dUk))
             aligned = N % 2 == 0
             Kfg_w, Kgg_w = ws.A[:, :N, N:n], ws.A[:, N:n, N:n]
             Kfg_out = Kfg_w if aligned else torch.empty(B, N, row_stride(q), dtype=torch.float64, device=dev)[:, :, :q]
@@ -348,10 +349,7 @@ class BatchedGEKFunction(torch.autograd.Function):
                     g_w[:, d0:d0 + nd].add_(coef * sd.unsqueeze(1) * Wd)
                     g_s.add_((coef * wd[:, d0:d0 + nd] * Wd).sum(1))
 
-            jitters = jitter_schedule()[1:]  # (the first attempt is the unjittered one)
-            extra = torch.zeros(B, 1, dtype=torch.float64, device=dev)
-            ok = None
-            for attempt in range(len(jitters) + 1):
+            def build(extra):  # (never None: this objective refuses a capture)
                 gctx.kernel_build_batched(Ud, wd, sd, td + extra, grp, ws.A[:, :N, :N], kind=kind, d_split=d_split, uplo=UPLO_UPPER)
                 gctx.cross_kernel_dx_batched(Ugd, Ud, wd, sd, d0, nd, Kfg_out, kind=kind, d_split=d_split, sel=sel)
                 gctx.kernel_dxdx_batched(Ugd, Ugd, wd, sd, d0, nd, Kgg_out, kind=kind, d_split=d_split, sel_a=sel, sel_b=sel)
@@ -359,47 +357,14 @@ class BatchedGEKFunction(torch.autograd.Function):
                     Kfg_w.copy_(Kfg_out)
                     Kgg_w.copy_(Kgg_out)
                 gdiag.add_(nu_d + extra)
-                gctx.potrf_batched(ws.A, ws.Li, ws.info)
-                ok = ws.info == 0
-                ws.info_host.copy_(ws.info, non_blocking=True)
-                ws.info_event.record()
-                rest()
-                ws.info_event.synchronize()
-                if bool((ws.info_host == 0).all()) or attempt == len(jitters):
-                    break
-                extra = torch.where(ok.unsqueeze(1), extra, torch.full_like(extra, jitters[attempt]))
-            value = ws.out3[:, 2].clone()
-            ctx.saved = (g_w, g_s, g_t, g_Ud, g_Ugd, ws.alpha[:, :N].clone() if need_grad else None, ok, (B, N, Mg, D, dU))
-            ctx.in_dtypes = (U.dtype, Ug.dtype, w.dtype, sf2.dtype, tau.dtype, mean.dtype, y.dtype)
-            ctx.shapes = (U.shape, Ug.shape, sf2.shape, tau.shape, mean.shape, y.shape)
-            return torch.where(ok, value, torch.full_like(value, float("nan")))
+
+            ok = _factor_batched(gctx, ws, build, after=rest)
+            grads = (g_w, g_s, g_t, (g_Ud, g_Ugd), ws.alpha[:, :N].clone() if need_grad else None)
+            return _batched_result(ctx, ok, ws.out3[:, 2].clone(), grads, (U, Ug), w, sf2, tau, mean, y)
 
     @staticmethod
     def backward(ctx, grad_out):
-        g_w, g_s, g_t, g_Ud, g_Ugd, gm_all, ok, (B, N, Mg, D, dU) = ctx.saved
-        need, dt = ctx.needs_input_grad, ctx.in_dtypes
-        U_shape, Ug_shape, sf2_shape, tau_shape, mean_shape, y_shape = ctx.shapes
-        dev = gm_all.device
-        go = torch.where(ok, grad_out.to(torch.float64), torch.zeros_like(grad_out, dtype=torch.float64))  # failed: no gradient
-        gm = go.unsqueeze(1) * torch.where(ok.unsqueeze(1), gm_all, torch.zeros_like(gm_all))
-
-        def rows(g_d, M, shape):  # the gradient of a block of feature rows: columns [:dU], summed over the batch when shared
-            full = torch.zeros(B, M, D, dtype=torch.float64, device=dev)
-            if g_d is not None:
-                full[:, :, :dU] = torch.where(ok.view(B, 1, 1), g_d, torch.zeros_like(g_d)) * go.view(B, 1, 1)
-            return full if len(shape) == 3 else full.sum(0)
-
-        def red(t, shape):  # gradient of a broadcast argument: sum over the batch
-            return t.reshape(shape) if len(shape) == t.dim() else t.sum(0).reshape(shape)
-
-        nanfree = lambda t: torch.where(torch.isfinite(t), t, torch.zeros_like(t))  # noqa: E731
-        return (rows(g_Ud, N, U_shape).to(dt[0]) if need[0] else None,
-                rows(g_Ugd, Mg, Ug_shape).to(dt[1]) if need[1] else None,
-                nanfree(go.unsqueeze(1) * g_w).to(dt[2]) if need[2] else None,
-                nanfree(go * g_s).reshape(sf2_shape).to(dt[3]) if need[3] else None,
-                nanfree(go.unsqueeze(1) * g_t).reshape(tau_shape).to(dt[4]) if need[4] else None,
-                red(gm, mean_shape).to(dt[5]) if need[5] else None,
-                red(-gm, y_shape).to(dt[6]) if need[6] else None) + (None,) * 10
+        return _batched_backward(ctx, grad_out)
 
 
 def batched_gek_mll(U: torch.Tensor, Ug: torch.Tensor, w: torch.Tensor, sf2: torch.Tensor, tau: torch.Tensor, mean: torch.Tensor,

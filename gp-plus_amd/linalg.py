@@ -156,6 +156,25 @@ def _factor(ctx: GppContext, ws: EvalWorkspace, U, w, sf2, tau, grp, kind, d_spl
             after()
         return 0.0
 
+    def build_factor(jit):
+        # Build and factorisation are ONE call: where the ticket list runs (N >= 6912) only the first diagonal block's columns of
+        # Ky are built on this stream; the rest is written on the library's CU-masked update stream in front of the executor,
+        # beside the first panel on its own 32 CUs.  (As an UNMASKED launch beside the panel the same build had flooded every CU,
+        # the panel's included, and the first leaf waited for it anyway: 53.6 ms against 0.64 + 52.4, not adopted then.)
+        # The "kernel_build" stage stays as the mark of an evaluation's first launch (tools/c3_stages.py and config_stages.py
+        # measure the gap in front of it); the build's time is part of "potrf".
+        with _stage("kernel_build"):
+            pass
+        with _stage("potrf"):
+            ctx.build_potrf(U, w, sf2, tau, grp, ws.A, ws.Li, ws.info, ws.Ki, jitter=jit, kind=kind, d_split=d_split)
+
+    return _attempts(ctx, ws, build_factor, inputs_nan_probe(U, w, sf2, tau), after)
+
+
+def _attempts(ctx: GppContext, ws: EvalWorkspace, build_factor, nan_probe, after=None) -> float:
+    """The attempt every single-GPU factorisation of an evaluation makes, under ``psd_safe``: ``build_factor(jit)`` enqueues the
+    matrix with ``jit`` on its diagonal and its factorisation into ``ws`` (status in ``ws.info``), ``after()`` the rest of the
+    evaluation, and only then the host waits for the status word.  Returns the jitter that was needed."""
     def attempt(jit):
         # The factorisation's launches (a DAG over the library's internal streams, ~1000 launches at N = 20000) run fastest
         # when they are enqueued while the device executes them, and measurably slower when they were parked in the
@@ -168,16 +187,7 @@ def _factor(ctx: GppContext, ws: EvalWorkspace, U, w, sf2, tau, grp, kind, d_spl
         # 25.4-26.0 -> 24.3-24.8 ms.
         if ws.N >= LOOKAHEAD_MIN_N:  # (below, the factorisation is a single-stream chain and the host is the bottleneck)
             torch.cuda.current_stream(ctx.index).synchronize()
-        # Build and factorisation are ONE call: where the ticket list runs (N >= 6912) only the first diagonal block's columns of
-        # Ky are built on this stream; the rest is written on the library's CU-masked update stream in front of the executor,
-        # beside the first panel on its own 32 CUs.  (As an UNMASKED launch beside the panel the same build had flooded every CU,
-        # the panel's included, and the first leaf waited for it anyway: 53.6 ms against 0.64 + 52.4, not adopted then.)
-        # The "kernel_build" stage stays as the mark of an evaluation's first launch (tools/c3_stages.py and config_stages.py
-        # measure the gap in front of it); the build's time is part of "potrf".
-        with _stage("kernel_build"):
-            pass
-        with _stage("potrf"):
-            ctx.build_potrf(U, w, sf2, tau, grp, ws.A, ws.Li, ws.info, ws.Ki, jitter=jit, kind=kind, d_split=d_split)
+        build_factor(jit)
         # the second host wait of an evaluation (the reference syncs on loss.item() too) covers the factorisation only: the
         # status goes to pinned host memory behind an event, the rest of the evaluation is enqueued, THEN the host waits
         ws.info_host.copy_(ws.info, non_blocking=True)
@@ -187,7 +197,7 @@ def _factor(ctx: GppContext, ws: EvalWorkspace, U, w, sf2, tau, grp, kind, d_spl
         ws.info_event.synchronize()
         return int(ws.info_host[0])
 
-    return psd_safe(ctx, attempt, inputs_nan_probe(U, w, sf2, tau))
+    return psd_safe(ctx, attempt, nan_probe)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -204,35 +214,50 @@ def _operands(U, w, sf2, tau, grp):
     return Ud, wd, sd, td, grp
 
 
-def _eval_operands(ctx, U, w, sf2, tau, mean, y, grp, dU):
-    """``_operands``, the number of noise groups S, and (need_grad, need_U) from ``ctx.needs_input_grad``.  Notes on ``ctx`` what
-    ``_eval_backward`` needs to hand every gradient back in its input's dtype and shape."""
+def _eval_operands(ctx, U, w, sf2, tau, mean, y, grp, dU, Ug=None):
+    """``_operands``, the number of noise groups S, and (need_grad, need_U) from ``ctx.needs_input_grad``, whose leading entries
+    are the blocks of feature rows: U, or U and ``Ug``.  Notes on ``ctx`` what ``_eval_backward`` needs to hand every gradient back
+    in its input's dtype and shape."""
     Ud, wd, sd, td, grp = _operands(U, w, sf2, tau, grp)
-    need = ctx.needs_input_grad
-    ctx.in_dtypes = (U.dtype, w.dtype, sf2.dtype, tau.dtype, mean.dtype, y.dtype)
-    ctx.shapes = (sf2.shape, tau.shape)
-    return Ud, wd, sd, td, grp, td.numel(), any(need[:6]), need[0] and dU > 0
+    blocks = (U,) if Ug is None else (U, Ug)
+    k, need = len(blocks), ctx.needs_input_grad
+    ctx.in_dtypes = tuple(t.dtype for t in blocks + (w, sf2, tau, mean, y))
+    ctx.shapes = (tuple(t.shape[0] for t in blocks), sf2.shape, tau.shape)
+    return Ud, wd, sd, td, grp, td.numel(), any(need[:k + 5]), any(need[:k]) and dU > 0
 
 
-def _eval_backward(ctx, grad_out, g_w, g_s, g_t, g_Ud, g_mean):
-    """The gradients of (U, w, sf2, tau, mean, y) from the fp64 ones an evaluation produced, scaled by ``grad_out``, each in its
-    input's dtype (and shape): ``g_Ud`` (N x dU, or None) fills the leading columns of U's, the others are zero; ``g_mean`` is the
-    objective's derivative by the mean (alpha for the MLL, -beta for LOO) and y receives its negative."""
-    need = ctx.needs_input_grad
+def _grad_buffers(need_grad, dev, lead, D, S, *rows):
+    """The fp64 buffers the gradient reductions fill, of one problem (``lead`` = ()) or of B (``lead`` = (B,)): g_w (D), g_s (one
+    value), g_t (S) and, for each block of feature rows ``(M, dU)``, g_U (M x dU) or None for dU = 0; all None without
+    ``need_grad``."""
+    def new(*shape):
+        return torch.empty(lead + shape, dtype=torch.float64, device=dev) if need_grad else None
+
+    return (new(D), new() if lead else new(1), new(S)) + tuple(new(M, dU) if dU > 0 else None for M, dU in rows)
+
+
+def _eval_backward(ctx, grad_out, g_w, g_s, g_t, g_rows, g_mean):
+    """The gradients of (the leading blocks of feature rows: U, or U and Ug; w, sf2, tau, mean, y) from the fp64 ones an evaluation
+    produced, scaled by ``grad_out``, each in its input's dtype (and shape): a block's entry of ``g_rows`` (M x dU, or None) fills
+    the leading columns of its gradient, the others are zero; ``g_mean`` is the objective's derivative by the mean (alpha for the
+    MLL and GEK, -beta for LOO) and y receives its negative."""
+    need, dt = ctx.needs_input_grad, ctx.in_dtypes
+    row_counts, sf2_shape, tau_shape = ctx.shapes
+    k = len(row_counts)
     go = grad_out.to(torch.float64)
-    g_U = None
-    if need[0]:
-        g_U = torch.zeros(g_mean.shape[0], g_w.shape[0], dtype=torch.float64, device=g_mean.device)
-        if g_Ud is not None:
-            g_U[:, :g_Ud.shape[1]] = g_Ud
-    dt = ctx.in_dtypes
-    sf2_shape, tau_shape = ctx.shapes
-    return (None if g_U is None else (go * g_U).to(dt[0]),
-            (go * g_w).to(dt[1]) if need[1] else None,
-            (go * g_s).reshape(sf2_shape).to(dt[2]) if need[2] else None,
-            (go * g_t).reshape(tau_shape).to(dt[3]) if need[3] else None,
-            (go * g_mean).to(dt[4]) if need[4] else None,
-            (-go * g_mean).to(dt[5]) if need[5] else None)
+
+    def rows(g_d, M):
+        g = torch.zeros(M, g_w.shape[0], dtype=torch.float64, device=g_w.device)
+        if g_d is not None:
+            g[:, :g_d.shape[1]] = g_d
+        return go * g
+
+    return tuple(rows(g_d, M).to(dt[i]) if need[i] else None for i, (g_d, M) in enumerate(zip(g_rows, row_counts))) + (
+        (go * g_w).to(dt[k]) if need[k] else None,
+        (go * g_s).reshape(sf2_shape).to(dt[k + 1]) if need[k + 1] else None,
+        (go * g_t).reshape(tau_shape).to(dt[k + 2]) if need[k + 2] else None,
+        (go * g_mean).to(dt[k + 3]) if need[k + 3] else None,
+        (-go * g_mean).to(dt[k + 4]) if need[k + 4] else None)
 
 
 def _exact_forward(fn, ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slot):
@@ -249,13 +274,9 @@ def _exact_forward(fn, ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slo
         ws = get_workspace(gctx, N, slot)
         ws.epoch += 1
         torch.sub(_as_f64(y.detach(), dev), _as_f64(mean.detach(), dev), out=ws.r)
-        g_w = g_s = g_t = g_Ud = None
-        if need_grad:
-            g_w = torch.empty(D, dtype=torch.float64, device=dev)
-            g_s = torch.empty(1, dtype=torch.float64, device=dev)
-            g_t = torch.empty(S, dtype=torch.float64, device=dev)
-            g_Ud = torch.empty(N, dU, dtype=torch.float64, device=dev) if need_U else None
-        ops, grads = (Ud, wd, sd, grp, S), (dU if need_U else 0, g_w, g_s, g_t, g_Ud)
+        dUk = dU if need_U else 0
+        g_w, g_s, g_t, g_Ud = _grad_buffers(need_grad, dev, (), D, S, (N, dUk))
+        ops, grads = (Ud, wd, sd, grp, S), (dUk, g_w, g_s, g_t, g_Ud)
 
         def rest():
             with _stage("trtri"):
@@ -272,7 +293,7 @@ def _exact_forward(fn, ctx, U, w, sf2, tau, mean, y, grp, kind, d_split, dU, slo
 
         _factor(gctx, ws, Ud, wd, sd, td, grp, kind, d_split, after=rest)
         value, g_mean = fn.result(ws, need_grad)
-        ctx.saved = (g_w, g_s, g_t, g_Ud, g_mean)
+        ctx.saved = (g_w, g_s, g_t, (g_Ud,), g_mean)
         return value
 
 
@@ -1447,8 +1468,9 @@ class ExactGEKFunction(torch.autograd.Function):
     whose derivative by w and sf2 is added on the host from the diagonal of the gradient rows' block of Kj^-1 - alpha alpha^T.
 
     As in ExactMLLFunction the whole evaluation is enqueued in ``forward``: the three blocks into the triangle gpp_potrf reads
-    (nu and the jitter on the diagonal, the jitter-retry policy of ``_factor``), potrf, trtri, z, alpha, the dense LAUUM,
-    gpp_grad_reduce on the leading N x N view and gpp_gek_grad_reduce on the other two blocks; ``backward`` scales."""
+    (nu and the jitter on the diagonal, the attempts of ``_attempts`` as for ``_factor``), potrf, trtri, z, alpha, the dense LAUUM,
+    gpp_grad_reduce on the leading N x N view and gpp_gek_grad_reduce on the other two blocks; ``backward`` is ``_eval_backward``
+    with two blocks of feature rows."""
 
     @staticmethod
     def forward(ctx, U, Ug, w, sf2, tau, mean, y, r_g, nu, grp, kind, d_split, d0, nd, dU, nugget_rel, slot, sel=None):
@@ -1460,15 +1482,8 @@ class ExactGEKFunction(torch.autograd.Function):
             (N, D), Mg = U.shape, Ug.shape[0]
             q = Mg * nd if sel is None else sel.q
             n = N + q
-            Ud, wd, sd, td, grp = _operands(U, w, sf2, tau, grp)
+            Ud, wd, sd, td, grp, S, need_grad, need_U = _eval_operands(ctx, U, w, sf2, tau, mean, y, grp, dU, Ug)
             Ugd = _as_f64(Ug.detach(), dev)
-            S = td.numel()
-            need = ctx.needs_input_grad
-            ctx.in_dtypes = (U.dtype, Ug.dtype, w.dtype, sf2.dtype, tau.dtype, mean.dtype, y.dtype)
-            ctx.shapes = (sf2.shape, tau.shape)
-            ctx.n_grad_points = Mg
-            need_grad = any(need[:7])
-            need_U = (need[0] or need[1]) and dU > 0
             dUk = dU if need_U else 0
             spec = KernelSpec(wd, sd, kind, d_split)
             if nu is None:
@@ -1480,14 +1495,7 @@ class ExactGEKFunction(torch.autograd.Function):
             ws.epoch += 1
             torch.sub(_as_f64(y.detach(), dev), _as_f64(mean.detach(), dev), out=ws.r[:N])
             ws.r[N:].copy_(_as_f64(r_g.detach().reshape(-1), dev))
-            g_w = g_s = g_t = g_Ud = g_Ugd = None
-            if need_grad:
-                g_w = torch.empty(D, dtype=torch.float64, device=dev)
-                g_s = torch.empty(1, dtype=torch.float64, device=dev)
-                g_t = torch.empty(S, dtype=torch.float64, device=dev)
-                if need_U:
-                    g_Ud = torch.empty(N, dU, dtype=torch.float64, device=dev)
-                    g_Ugd = torch.empty(Mg, dU, dtype=torch.float64, device=dev)
+            g_w, g_s, g_t, g_Ud, g_Ugd = _grad_buffers(need_grad, dev, (), D, S, (N, dUk), (Mg, dUk))
             # gpp_cross_kernel_dx / gpp_kernel_dxdx write 16-byte pairs: a window that starts at an odd column N is built aside
             aligned = N % 2 == 0
             Kfg_out = ws.A[:N, N:n] if aligned else rows_buffer(N, q, dev)
@@ -1521,9 +1529,7 @@ class ExactGEKFunction(torch.autograd.Function):
                         g_w[d0:d0 + nd].add_(c * sd * Wd)
                         g_s.add_((c * wd[d0:d0 + nd] * Wd).sum())
 
-            def attempt(jit):
-                if n >= LOOKAHEAD_MIN_N:  # (as in ``_factor``: the factorisation's launches go to an idle device)
-                    torch.cuda.current_stream(gctx.index).synchronize()
+            def build_factor(jit):
                 with _stage("gek_build"):
                     gctx.kernel_build(Ud, wd, sd, td, grp, ws.A[:N, :N], jitter=jit, kind=kind, d_split=d_split, uplo=UPLO_UPPER)
                     gctx.cross_kernel_dx(Ugd, Ud, wd, sd, d0, nd, Kfg_out, kind=kind, d_split=d_split, sel=sel)
@@ -1534,38 +1540,15 @@ class ExactGEKFunction(torch.autograd.Function):
                     ws.A[N:n, N:n].diagonal().add_(nu_d + jit)
                 with _stage("potrf"):
                     gctx.potrf(ws.A, ws.Li, ws.info, ws.Ki)
-                ws.info_host.copy_(ws.info, non_blocking=True)
-                ws.info_event.record(torch.cuda.current_stream(gctx.index))
-                rest()
-                ws.info_event.synchronize()
-                return int(ws.info_host[0])
 
-            psd_safe(gctx, attempt, inputs_nan_probe(torch.cat([Ud.reshape(-1), Ugd.reshape(-1), ws.r]), wd, sd,
-                                                     torch.cat([td, nu_d])))
-            ctx.saved = (g_w, g_s, g_t, g_Ud, g_Ugd, ws.alpha[:N].clone() if need_grad else None)
+            _attempts(gctx, ws, build_factor, inputs_nan_probe(torch.cat([Ud.reshape(-1), Ugd.reshape(-1), ws.r]), wd, sd,
+                                                               torch.cat([td, nu_d])), after=rest)
+            ctx.saved = (g_w, g_s, g_t, (g_Ud, g_Ugd), ws.alpha[:N].clone() if need_grad else None)
             return ws.out3[2].clone()
 
     @staticmethod
     def backward(ctx, grad_out):
-        g_w, g_s, g_t, g_Ud, g_Ugd, g_mean = ctx.saved
-        need = ctx.needs_input_grad
-        go = grad_out.to(torch.float64)
-        dt = ctx.in_dtypes
-        sf2_shape, tau_shape = ctx.shapes
-
-        def rows(g_d, rows_n):
-            g = torch.zeros(rows_n, g_w.shape[0], dtype=torch.float64, device=g_w.device)
-            if g_d is not None:
-                g[:, :g_d.shape[1]] = g_d
-            return go * g
-
-        return (rows(g_Ud, g_mean.shape[0]).to(dt[0]) if need[0] else None,
-                rows(g_Ugd, ctx.n_grad_points).to(dt[1]) if need[1] else None,
-                (go * g_w).to(dt[2]) if need[2] else None,
-                (go * g_s).reshape(sf2_shape).to(dt[3]) if need[3] else None,
-                (go * g_t).reshape(tau_shape).to(dt[4]) if need[4] else None,
-                (go * g_mean).to(dt[5]) if need[5] else None,
-                (-go * g_mean).to(dt[6]) if need[6] else None) + (None,) * 11
+        return _eval_backward(ctx, grad_out, *ctx.saved) + (None,) * 11
 
 
 def exact_gek_mll(U: torch.Tensor, Ug: torch.Tensor, spec: KernelSpec, tau: torch.Tensor, mean: torch.Tensor, y: torch.Tensor,

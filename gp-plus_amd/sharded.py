@@ -791,7 +791,7 @@ class ShardedMLLFunction(torch.autograd.Function):
         comm.stage = "grad"
         comm.allreduce(flat)
         ws.comm_calls = comm.calls
-        return _eval_backward(ctx, grad_out, g_w, g_s, g_t, g_Ud, ws.alpha) + (None,) * 6
+        return _eval_backward(ctx, grad_out, g_w, g_s, g_t, (g_Ud,), ws.alpha) + (None,) * 6
 
 
 def sharded_mll(U: torch.Tensor, w: torch.Tensor, sf2: torch.Tensor, tau: torch.Tensor, mean: torch.Tensor, y: torch.Tensor,
