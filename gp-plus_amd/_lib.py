@@ -206,9 +206,15 @@ def exported_symbols() -> list:
     return sorted(_SIGNATURES)
 
 
+#: GPP_NO_WORKSPACE: the call found no (or too small a) scratch workspace on the handle, nothing was enqueued
+NO_WORKSPACE = 2002
+
+
 def check(status: int, what: str) -> None:
     if status == 0:
         return
     if status < 0:
         raise GppError(f"{what}: bad argument #{-status}")
+    if status == NO_WORKSPACE:
+        raise GppError(f"{what}: the handle's scratch workspace is missing or too small")
     raise GppError(f"{what}: HIP runtime error {status - 1000}")

@@ -17,7 +17,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib, settings
-from ._lib import GppError, check
+from ._lib import NO_WORKSPACE, GppError, check  # noqa: F401 (NO_WORKSPACE: re-exported, the tests read it here)
 
 KIND_RBF, KIND_MATERN32, KIND_MATERN52 = 0, 1, 2
 UPLO_FULL, UPLO_LOWER, UPLO_UPPER = 0, 1, 2
@@ -37,7 +37,6 @@ MAX_NODES = 64
 #: longest contraction gpp_kernel_apply / gpp_rff_apply run without scratch (gpp_apply.hip AP_SPLIT)
 APPLY_SPLIT = 2048
 NOT_SUPPORTED = 2001  # GPP_NOT_SUPPORTED: gpp_lauum_grad does not take these arguments, nothing was enqueued
-NO_WORKSPACE = 2002   # GPP_NO_WORKSPACE: gpp_lauum_grad found no (or too small a) scratch workspace on the handle
 #: the tile kernels stage at most this many feature columns (manifold + quantitative) per point in LDS (gpp_build.hip DMAX)
 MAX_FEATURES = 64
 
@@ -125,6 +124,50 @@ def _ld(m: torch.Tensor) -> int:
     if m.dim() != 2 or m.stride(1) != 1:
         raise GppError("matrix must be 2-D with unit column stride")
     return m.stride(0) if m.shape[0] > 1 else max(m.shape[1], m.stride(0))
+
+
+def _post_cross_checks(fn, a, named, K, kind, d_split, transposed, omega=None, own=None):
+    """What ``post_cross_sq``, ``post_cross_lin_sq`` and ``post_cross_min`` (``fn``) check alike, in the order they always did:
+    every tensor of ``named`` (name -> tensor, in the wrapper's order) is fp64 on the GPU; the feature rows ``U{a}`` (a = "c" or "f")
+    and ``Ur``, ``w``, ``sf2``, K >= 1 and kind / d_split; then the wrapper's ``own(M_a, D)`` checks, if any; the windows ``V{a}`` and
+    ``Vr`` under ``transposed``; ``omega``.  Returns (M_a, M_r, D)."""
+    for n, t in named.items():
+        _need(t, torch.float64, n)
+    Ua, Ur, w, sf2 = named["U" + a], named["Ur"], named["w"], named["sf2"]
+    if Ua.dim() != 2 or Ur.dim() != 2 or Ua.shape[1] != Ur.shape[1]:
+        raise GppError(f"U{a} and Ur must be matrices with the same feature count (got {tuple(Ua.shape)}, {tuple(Ur.shape)})")
+    (Ma, D), Mr = Ua.shape, Ur.shape[0]
+    _check_features(D)
+    if min(Ma, Mr, K) < 1:
+        raise GppError(f"{fn} takes M_{a}, M_r, K >= 1 (got {Ma}, {Mr}, {K})")
+    if not (Ua.is_contiguous() and Ur.is_contiguous()):
+        raise GppError(f"U{a} and Ur must be contiguous")
+    if w.numel() != D or not w.is_contiguous():
+        raise GppError(f"w must be a contiguous vector of {D} weights (got {w.numel()})")
+    if sf2.numel() < 1:
+        raise GppError("sf2 must hold one value")
+    if not (0 <= int(d_split) <= D) or kind not in (KIND_RBF, KIND_MATERN32, KIND_MATERN52):
+        raise GppError(f"bad kernel kind / d_split ({kind}, {d_split}) for {D} features")
+    if own is not None:
+        own(Ma, D)
+    for n, pts in (("V" + a, Ma), ("Vr", Mr)):
+        t = named[n]
+        if t.dim() != 2 or t.stride(1) != 1:
+            raise GppError(f"{n} must be 2-D with unit column stride")
+        rows, cols = (K, pts) if transposed else (pts, K)
+        if t.shape[0] < rows or t.shape[1] < cols or (t.shape[1 if transposed else 0] != pts):
+            raise GppError(f"{n} is {tuple(t.shape)}: {fn} with {pts} points and K = {K} needs "
+                           f"{'at least ' + str(K) + ' x ' + str(pts) if transposed else str(pts) + ' x at least ' + str(K)}")
+        ld = _ld(t)
+        if ld & 1 or ld < cols:
+            raise GppError(f"{n}: the leading dimension ({ld}) must be even and at least {cols}")
+        if t.data_ptr() & 15:
+            raise GppError(f"{n} must be 16-byte aligned")
+    if omega is not None:
+        _need(omega, torch.float64, "omega")
+        if omega.dim() != 1 or omega.numel() != Mr or not omega.is_contiguous():
+            raise GppError(f"omega must be a contiguous vector of {Mr} weights (got {tuple(omega.shape)})")
+    return Ma, Mr, D
 
 
 class GradientSelection:
@@ -416,8 +459,6 @@ class GppContext:
                                          g_tau.data_ptr())
         if status == NOT_SUPPORTED:
             return False
-        if status == NO_WORKSPACE:
-            raise GppError("gpp_lauum_grad: the handle's scratch workspace is missing or too small")
         check(status, "gpp_lauum_grad")
         return True
 
@@ -988,8 +1029,6 @@ class GppContext:
         self._stream()
         status = self.lib.gpp_chol_append(self.h, A.data_ptr(), _ld(A), Linv.data_ptr(), _ld(Linv), N, q, k.data_ptr(), _ld(k),
                                           C.data_ptr(), _ld(C), rq.data_ptr(), z.data_ptr(), alpha.data_ptr(), info.data_ptr())
-        if status == NO_WORKSPACE:
-            raise GppError("gpp_chol_append: the handle's scratch workspace is missing or too small")
         check(status, "gpp_chol_append")
 
     # -- expected variance reduction ---------------------------------------------------------------------------------------------
@@ -1000,38 +1039,8 @@ class GppContext:
         (>= K) x M_c and (>= K) x M_r windows of the transposed operands; what lies beyond K is not read.  ``omega``: M_r weights or
         None for all ones.  Everything is checked before any launch."""
         K = int(K)
-        for t, n in ((Uc, "Uc"), (Ur, "Ur"), (w, "w"), (sf2, "sf2"), (Vc, "Vc"), (Vr, "Vr"), (out, "out")):
-            _need(t, torch.float64, n)
-        if Uc.dim() != 2 or Ur.dim() != 2 or Uc.shape[1] != Ur.shape[1]:
-            raise GppError(f"Uc and Ur must be matrices with the same feature count (got {tuple(Uc.shape)}, {tuple(Ur.shape)})")
-        (Mc, D), Mr = Uc.shape, Ur.shape[0]
-        _check_features(D)
-        if min(Mc, Mr, K) < 1:
-            raise GppError(f"post_cross_sq takes M_c, M_r, K >= 1 (got {Mc}, {Mr}, {K})")
-        if not (Uc.is_contiguous() and Ur.is_contiguous()):
-            raise GppError("Uc and Ur must be contiguous")
-        if w.numel() != D or not w.is_contiguous():
-            raise GppError(f"w must be a contiguous vector of {D} weights (got {w.numel()})")
-        if sf2.numel() < 1:
-            raise GppError("sf2 must hold one value")
-        if not (0 <= int(d_split) <= D) or kind not in (KIND_RBF, KIND_MATERN32, KIND_MATERN52):
-            raise GppError(f"bad kernel kind / d_split ({kind}, {d_split}) for {D} features")
-        for t, n, pts in ((Vc, "Vc", Mc), (Vr, "Vr", Mr)):
-            if t.dim() != 2 or t.stride(1) != 1:
-                raise GppError(f"{n} must be 2-D with unit column stride")
-            rows, cols = (K, pts) if transposed else (pts, K)
-            if t.shape[0] < rows or t.shape[1] < cols or (t.shape[1 if transposed else 0] != pts):
-                raise GppError(f"{n} is {tuple(t.shape)}: post_cross_sq with {pts} points and K = {K} needs "
-                               f"{'at least ' + str(K) + ' x ' + str(pts) if transposed else str(pts) + ' x at least ' + str(K)}")
-            ld = _ld(t)
-            if ld & 1 or ld < cols:
-                raise GppError(f"{n}: the leading dimension ({ld}) must be even and at least {cols}")
-            if t.data_ptr() & 15:
-                raise GppError(f"{n} must be 16-byte aligned")
-        if omega is not None:
-            _need(omega, torch.float64, "omega")
-            if omega.dim() != 1 or omega.numel() != Mr or not omega.is_contiguous():
-                raise GppError(f"omega must be a contiguous vector of {Mr} weights (got {tuple(omega.shape)})")
+        Mc, Mr, D = _post_cross_checks("post_cross_sq", "c", dict(Uc=Uc, Ur=Ur, w=w, sf2=sf2, Vc=Vc, Vr=Vr, out=out), K, kind, d_split,
+                                       transposed, omega)
         if out.dim() != 1 or out.numel() < Mc or not out.is_contiguous():
             raise GppError(f"out must be a contiguous vector with room for {Mc} doubles (got {out.numel()})")
         self.ensure_workspace(OP_POST_CROSS, Mr, Mc, 0, 0)
@@ -1039,8 +1048,6 @@ class GppContext:
         status = self.lib.gpp_post_cross_sq(self.h, Uc.data_ptr(), Mc, Ur.data_ptr(), Mr, D, w.data_ptr(), sf2.data_ptr(), int(kind),
                                             int(d_split), Vc.data_ptr(), _ld(Vc), Vr.data_ptr(), _ld(Vr), K, 1 if transposed else 0,
                                             _ptr(omega), out.data_ptr())
-        if status == NO_WORKSPACE:
-            raise GppError("gpp_post_cross_sq: the handle's scratch workspace is missing or too small")
         check(status, "gpp_post_cross_sq")
         return out
 
@@ -1051,43 +1058,16 @@ class GppContext:
         - sum_{n < K} Vf[i, n] Vr[r, n])^2.  ``A``: M_f x (>= 1 + nd) window of a row-major buffer; what lies beyond 1 + nd is not
         read.  ``Vf`` / ``Vr``, ``transposed`` and ``omega`` as in ``post_cross_sq``.  Everything is checked before any launch."""
         K, d0, nd = int(K), int(d0), int(nd)
-        for t, n in ((Uf, "Uf"), (Ur, "Ur"), (w, "w"), (sf2, "sf2"), (A, "A"), (Vf, "Vf"), (Vr, "Vr"), (out, "out")):
-            _need(t, torch.float64, n)
-        if Uf.dim() != 2 or Ur.dim() != 2 or Uf.shape[1] != Ur.shape[1]:
-            raise GppError(f"Uf and Ur must be matrices with the same feature count (got {tuple(Uf.shape)}, {tuple(Ur.shape)})")
-        (Mf, D), Mr = Uf.shape, Ur.shape[0]
-        _check_features(D)
-        if min(Mf, Mr, K) < 1:
-            raise GppError(f"post_cross_lin_sq takes M_f, M_r, K >= 1 (got {Mf}, {Mr}, {K})")
-        if not (Uf.is_contiguous() and Ur.is_contiguous()):
-            raise GppError("Uf and Ur must be contiguous")
-        if w.numel() != D or not w.is_contiguous():
-            raise GppError(f"w must be a contiguous vector of {D} weights (got {w.numel()})")
-        if sf2.numel() < 1:
-            raise GppError("sf2 must hold one value")
-        if not (0 <= int(d_split) <= D) or kind not in (KIND_RBF, KIND_MATERN32, KIND_MATERN52):
-            raise GppError(f"bad kernel kind / d_split ({kind}, {d_split}) for {D} features")
-        if d0 < 0 or nd < 1 or d0 + nd > D:
-            raise GppError(f"the observed directions [{d0}, {d0 + nd}) must be a non-empty range inside the {D} features")
-        if A.dim() != 2 or A.stride(1) != 1 or A.shape[0] != Mf or A.shape[1] < 1 + nd or (Mf > 1 and _ld(A) < 1 + nd):
-            raise GppError(f"A is {tuple(A.shape)}: {Mf} functionals of {nd} directions need {Mf} x at least {1 + nd}, "
-                           "unit column stride")
-        for t, n, pts in ((Vf, "Vf", Mf), (Vr, "Vr", Mr)):
-            if t.dim() != 2 or t.stride(1) != 1:
-                raise GppError(f"{n} must be 2-D with unit column stride")
-            rows, cols = (K, pts) if transposed else (pts, K)
-            if t.shape[0] < rows or t.shape[1] < cols or (t.shape[1 if transposed else 0] != pts):
-                raise GppError(f"{n} is {tuple(t.shape)}: post_cross_lin_sq with {pts} points and K = {K} needs "
-                               f"{'at least ' + str(K) + ' x ' + str(pts) if transposed else str(pts) + ' x at least ' + str(K)}")
-            ld = _ld(t)
-            if ld & 1 or ld < cols:
-                raise GppError(f"{n}: the leading dimension ({ld}) must be even and at least {cols}")
-            if t.data_ptr() & 15:
-                raise GppError(f"{n} must be 16-byte aligned")
-        if omega is not None:
-            _need(omega, torch.float64, "omega")
-            if omega.dim() != 1 or omega.numel() != Mr or not omega.is_contiguous():
-                raise GppError(f"omega must be a contiguous vector of {Mr} weights (got {tuple(omega.shape)})")
+
+        def functionals(Mf, D):
+            if d0 < 0 or nd < 1 or d0 + nd > D:
+                raise GppError(f"the observed directions [{d0}, {d0 + nd}) must be a non-empty range inside the {D} features")
+            if A.dim() != 2 or A.stride(1) != 1 or A.shape[0] != Mf or A.shape[1] < 1 + nd or (Mf > 1 and _ld(A) < 1 + nd):
+                raise GppError(f"A is {tuple(A.shape)}: {Mf} functionals of {nd} directions need {Mf} x at least {1 + nd}, "
+                               "unit column stride")
+
+        Mf, Mr, D = _post_cross_checks("post_cross_lin_sq", "f", dict(Uf=Uf, Ur=Ur, w=w, sf2=sf2, A=A, Vf=Vf, Vr=Vr, out=out), K, kind,
+                                       d_split, transposed, omega, own=functionals)
         if out.dim() != 1 or out.numel() < Mf or not out.is_contiguous():
             raise GppError(f"out must be a contiguous vector with room for {Mf} doubles (got {out.numel()})")
         self.ensure_workspace(OP_POST_CROSS_LIN, Mr, Mf, 0, 0)
@@ -1096,8 +1076,6 @@ class GppContext:
                                                 int(kind), int(d_split), d0, nd, A.data_ptr(), max(_ld(A), 1 + nd), Vf.data_ptr(),
                                                 _ld(Vf), Vr.data_ptr(), _ld(Vr), K, 1 if transposed else 0, _ptr(omega),
                                                 out.data_ptr())
-        if status == NO_WORKSPACE:
-            raise GppError("gpp_post_cross_lin_sq: the handle's scratch workspace is missing or too small")
         check(status, "gpp_post_cross_lin_sq")
         return out
 
@@ -1109,35 +1087,8 @@ class GppContext:
         ``scale``: M_c factors, ``nodes``: 1..64 values, ``out``: a contiguous M_c x Q matrix.  Everything is checked before any
         launch."""
         K = int(K)
-        for t, n in ((Uc, "Uc"), (Ur, "Ur"), (w, "w"), (sf2, "sf2"), (Vc, "Vc"), (Vr, "Vr"), (m, "m"), (scale, "scale"),
-                     (nodes, "nodes"), (out, "out")):
-            _need(t, torch.float64, n)
-        if Uc.dim() != 2 or Ur.dim() != 2 or Uc.shape[1] != Ur.shape[1]:
-            raise GppError(f"Uc and Ur must be matrices with the same feature count (got {tuple(Uc.shape)}, {tuple(Ur.shape)})")
-        (Mc, D), Mr = Uc.shape, Ur.shape[0]
-        _check_features(D)
-        if min(Mc, Mr, K) < 1:
-            raise GppError(f"post_cross_min takes M_c, M_r, K >= 1 (got {Mc}, {Mr}, {K})")
-        if not (Uc.is_contiguous() and Ur.is_contiguous()):
-            raise GppError("Uc and Ur must be contiguous")
-        if w.numel() != D or not w.is_contiguous():
-            raise GppError(f"w must be a contiguous vector of {D} weights (got {w.numel()})")
-        if sf2.numel() < 1:
-            raise GppError("sf2 must hold one value")
-        if not (0 <= int(d_split) <= D) or kind not in (KIND_RBF, KIND_MATERN32, KIND_MATERN52):
-            raise GppError(f"bad kernel kind / d_split ({kind}, {d_split}) for {D} features")
-        for t, n, pts in ((Vc, "Vc", Mc), (Vr, "Vr", Mr)):
-            if t.dim() != 2 or t.stride(1) != 1:
-                raise GppError(f"{n} must be 2-D with unit column stride")
-            rows, cols = (K, pts) if transposed else (pts, K)
-            if t.shape[0] < rows or t.shape[1] < cols or (t.shape[1 if transposed else 0] != pts):
-                raise GppError(f"{n} is {tuple(t.shape)}: post_cross_min with {pts} points and K = {K} needs "
-                               f"{'at least ' + str(K) + ' x ' + str(pts) if transposed else str(pts) + ' x at least ' + str(K)}")
-            ld = _ld(t)
-            if ld & 1 or ld < cols:
-                raise GppError(f"{n}: the leading dimension ({ld}) must be even and at least {cols}")
-            if t.data_ptr() & 15:
-                raise GppError(f"{n} must be 16-byte aligned")
+        Mc, Mr, D = _post_cross_checks("post_cross_min", "c", dict(Uc=Uc, Ur=Ur, w=w, sf2=sf2, Vc=Vc, Vr=Vr, m=m, scale=scale, nodes=nodes,
+                                                                   out=out), K, kind, d_split, transposed)
         if nodes.dim() != 1 or not (1 <= nodes.numel() <= MAX_NODES) or not nodes.is_contiguous():
             raise GppError(f"nodes must be a contiguous vector of 1..{MAX_NODES} values (got {tuple(nodes.shape)})")
         Q = nodes.numel()
@@ -1151,8 +1102,6 @@ class GppContext:
         status = self.lib.gpp_post_cross_min(self.h, Uc.data_ptr(), Mc, Ur.data_ptr(), Mr, D, w.data_ptr(), sf2.data_ptr(), int(kind),
                                              int(d_split), Vc.data_ptr(), _ld(Vc), Vr.data_ptr(), _ld(Vr), K, 1 if transposed else 0,
                                              m.data_ptr(), scale.data_ptr(), nodes.data_ptr(), Q, out.data_ptr())
-        if status == NO_WORKSPACE:
-            raise GppError("gpp_post_cross_min: the handle's scratch workspace is missing or too small")
         check(status, "gpp_post_cross_min")
         return out
 
@@ -1300,8 +1249,6 @@ class GppContext:
             self.ensure_workspace(OP_POINT_GRAM, 0, M, nd, 0)
         self._stream()
         status = self.lib.gpp_point_gram(self.h, Q.data_ptr(), ld, M, nd, N, _ptr(omega), _ptr(G), _ptr(Gsum))
-        if status == NO_WORKSPACE:
-            raise GppError("gpp_point_gram: the handle's scratch workspace is missing or too small")
         check(status, "gpp_point_gram")
         return G, Gsum
 
@@ -1376,8 +1323,6 @@ class GppContext:
         status = fn(self.h, U.data_ptr(), N, Ug.data_ptr(), Mg, D, w.data_ptr(), sf2.data_ptr(), int(kind), int(d_split), d0, nd,
                     *sel_args, alpha.data_ptr(), Kinv.data_ptr(), ld, dU, g_w.data_ptr(), g_sf2.data_ptr(),
                     _ptr(g_U) if dU else None, _ptr(g_Ug) if dU else None)
-        if status == NO_WORKSPACE:
-            raise GppError(f"{name}: the handle's scratch workspace is missing or too small")
         check(status, name)
 
     # -- the three above for B problems in one launch each (batched.BatchedGEKFunction) -------------------------------------------
@@ -1432,8 +1377,6 @@ class GppContext:
                                                       sf2.data_ptr(), int(kind), int(d_split), d0, nd, *self._sel_args(sel, q),
                                                       alpha.data_ptr(), sv, Kinv.data_ptr(), ld, sk, dU, g_w.data_ptr(),
                                                       g_sf2.data_ptr(), _ptr(g_U) if dU else None, _ptr(g_Ug) if dU else None, B)
-        if status == NO_WORKSPACE:
-            raise GppError("gpp_gek_grad_reduce_batched: the handle's scratch workspace is missing or too small")
         check(status, "gpp_gek_grad_reduce_batched")
 
 

@@ -51,6 +51,20 @@ class ExactGP(GP):
             self.prediction_strategy = None
         return super().train(mode)
 
+    def _likelihood_of_rows(self, out, X):
+        """``likelihood(out)`` with the noise of each row's own source: a likelihood with ``fidel_indices`` reads the source column of
+        the rows ``X`` for the call — whatever a previous predict() / evaluation() left there (models/gpregression.py:136-139
+        overwrites it with the test points' sources) — and gets the caller's value back."""
+        lik = self.likelihood
+        swap = hasattr(lik, "fidel_indices")
+        if swap:
+            saved, lik.fidel_indices = lik.fidel_indices, X[:, -1]
+        try:
+            return lik(out)
+        finally:
+            if swap:
+                lik.fidel_indices = saved
+
     def _ensure_prediction_cache(self, **kwargs):
         """Factor the training covariance once per eval() phase (gpytorch's prediction strategy caches)."""
         from ..linalg import factorize
@@ -63,18 +77,7 @@ class ExactGP(GP):
                 cov = train_out.lazy_covariance_matrix
                 if not isinstance(cov, LazyKernelMatrix):
                     raise RuntimeError("exact prediction needs the model's forward to return a lazy kernel covariance")
-                # The training covariance takes its noise groups from the TRAINING inputs' source column, whatever a
-                # previous predict()/evaluation() left in likelihood.fidel_indices (models/gpregression.py:136-139
-                # overwrites it with the test points' sources): set it around the call and put the caller's value back.
-                lik = self.likelihood
-                swap = hasattr(lik, "fidel_indices")
-                if swap:
-                    saved, lik.fidel_indices = lik.fidel_indices, self.train_inputs[0][:, -1]
-                try:
-                    noisy = lik(train_out).lazy_covariance_matrix
-                finally:
-                    if swap:
-                        lik.fidel_indices = saved
+                noisy = self._likelihood_of_rows(train_out, self.train_inputs[0]).lazy_covariance_matrix
                 self.prediction_strategy = factorize(cov.U1, cov.spec, noisy.tau, noisy.grp, train_out.mean, self.train_targets)
         return self.prediction_strategy
 

@@ -247,52 +247,24 @@ def variance_reduction_of_runs(model, cache, Xcand, Xref, weights=None, gradient
     """The work behind ``GP_Plus.variance_reduction(..., gradient=)`` (``cache`` None: the model's own prediction cache) and
     ``GradientEnhancedPosterior.variance_reduction`` (``cache``: its ``GradientFactorCache``; ``model``: its copy of the model).
     Everything is validated on the host before any device work; results in y^2 units."""
-    from . import settings as gpp_settings
-    from .backend import get_context
     from .linalg import gradient_prior_curvature, variance_reduction_block, variance_reduction_from_gradient_cache
+    from .models.gpregression import _check_weights
 
     what = "variance_reduction"
     Xc, Xr = model._alc_rows(Xcand, "Xcand"), model._alc_rows(Xref, "Xref")
-    Mc, Mr = Xc.shape[0], Xr.shape[0]
-    if weights is not None:
-        weights = data_type_check(weights).reshape(-1).to(torch.float64)
-        if weights.shape[0] != Mr:
-            raise ValueError(f"{what}: {weights.shape[0]} weights for {Mr} reference rows")
-        if not bool(torch.isfinite(weights).all()) or bool((weights < 0).any()):
-            raise ValueError(f"{what}: the weights must be finite and non-negative")
-        if not bool((weights > 0).any()):
-            raise ValueError(f"{what}: the weights are all zero")
+    Mc = Xc.shape[0]
+    weights = _check_weights(what, weights, Xr.shape[0], "reference rows")
     if gradient is None:
         if gradient_noise is not None:
             raise ValueError(f"{what}: gradient_noise without gradient= (a run that returns y alone has no gradient noise)")
         mask = noise = None
     else:
         mask, noise = check_gradient_run(model, gradient, gradient_noise, Mc, what)
-    if gpp_settings.sharded_evaluation.value() is not None:
-        raise NotImplementedError(f"{what} is not available under settings.sharded_evaluation")
-    train_x = model.train_inputs[0]
-    get_context(train_x.device)  # (raises for anything but a GPU: there is no CPU path)
-
-    Xc, Xr = Xc.to(train_x), Xr.to(train_x)
-    model.eval()
+    cache, (Xc, Xr), (out_c, out_r) = model._score_preamble(what, (Xc, Xr), cache)
     with torch.no_grad():
-        if cache is None:
-            cache = model._ensure_prediction_cache()
-        out_c = Module.__call__(model, Xc)
-        Uc = out_c.lazy_covariance_matrix.U1
-        Ur = Module.__call__(model, Xr).lazy_covariance_matrix.U1
-        lik = model.likelihood
-        swap = hasattr(lik, "fidel_indices")
-        if swap:  # the noise of each candidate's own source, as condition_on gives a new row
-            saved, lik.fidel_indices = lik.fidel_indices, Xc[:, -1]
-        try:
-            noisy = lik(out_c).lazy_covariance_matrix
-        finally:
-            if swap:
-                lik.fidel_indices = saved
-        tau = noisy.tau.detach().reshape(-1).to(torch.float64)
-        tau_c = tau[noisy.grp.long()] if noisy.grp is not None else tau[:1].expand(Mc)
-        dev = train_x.device
+        Uc, Ur = out_c.lazy_covariance_matrix.U1, out_r.lazy_covariance_matrix.U1
+        tau_c = model._noise_of_rows(out_c, Xc)
+        dev = Xc.device
         omega = None if weights is None else weights.to(dev)
         scale = model.y_std.detach().to(torch.float64) ** 2
         if mask is None:

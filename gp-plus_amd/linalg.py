@@ -814,23 +814,104 @@ def predict_from_cache(cache: FactorCache, Us: torch.Tensor, need_var: bool = Tr
 ALC_TRANSPOSED = True
 
 
-def _cross_operands(cache: FactorCache, Us, Kmax: int, transposed: bool):
-    """[(V or V^T, latent variance)] of each feature set in ``Us`` for gpp_post_cross_sq / gpp_post_cross_min: V = K_*N Linv^T of
-    ``predict_from_cache`` in a buffer with room for Kmax coordinates per point (``transposed``: Kmax x points, else points x Kmax)."""
-    dev, gctx, N = cache.U.device, cache.gctx, cache.U.shape[0]
-    bufs = []
-    if transposed:
-        for U in Us:
-            _, var, V = predict_from_cache(cache, U, need_V=True)
-            Vt = rows_buffer(Kmax, U.shape[0], dev)
-            gctx.transpose(V, Vt[:N])
-            bufs.append((Vt, var))
+def _operand_V(cache, Us, transposed: bool, Kmax: Optional[int] = None):
+    """(V or V^T, latent variance) of the latent f at the feature rows ``Us``: the operand of gpp_post_cross_sq / _lin_sq / _min, in
+    a buffer with room for ``Kmax`` coordinates per point (``transposed``: Kmax x points, else points x Kmax; None: the K it holds).
+    ``cache``: a ``FactorCache`` (K = N, V = K_*N Linv^T of ``predict_from_cache``) or a ``GradientFactorCache`` (K = N + q,
+    gpp_predict_tn on ``_gek_function_operand``)."""
+    dev, gctx, M = Us.device, cache.gctx, Us.shape[0]
+    is_g = isinstance(cache, GradientFactorCache)
+    K = cache.U.shape[0] + (cache.q if is_g else 0)
+    Kmax = K if Kmax is None else Kmax
+    V = rows_buffer(M, K if transposed else Kmax, dev)
+    if is_g:
+        mean = torch.empty(M, dtype=torch.float64, device=dev)
+        var = torch.empty(M, dtype=torch.float64, device=dev)
+        gctx.predict_tn(cache.Linv, cache.z, _gek_function_operand(cache, Us), cache.spec.sf2.reshape(1).expand(M).contiguous(),
+                        V[:, :K], mean, var)
     else:
-        for U in Us:
-            Vb = rows_buffer(U.shape[0], Kmax, dev)
-            _, var, _ = predict_from_cache(cache, U, need_V=True, V=Vb[:, :N])
-            bufs.append((Vb, var))
-    return bufs
+        _, var, _ = predict_from_cache(cache, Us, need_V=True, V=V[:, :K])
+    if not transposed:
+        return V, var
+    Vt = rows_buffer(Kmax, M, dev)
+    gctx.transpose(V, Vt[:K])
+    return Vt, var
+
+
+def _per_row(what: str, t, n: int, noun: str, rows: str, dev) -> torch.Tensor:
+    """``t`` as a contiguous fp64 vector on ``dev`` with one of ``noun`` for each of the ``n`` ``rows``."""
+    t = _as_f64(t.detach().reshape(-1), dev)
+    if t.numel() != n:
+        raise ValueError(f"{what}: {t.numel()} {noun} for {n} {rows}")
+    return t
+
+
+def _score_points(what: str, cache, Uc, Ur, q: int = 1):
+    """The first input checks of the four score functions: (Uc, Ur) on the cache's device, fp64 and contiguous, each at least one
+    row of the cache's D features, and 1 <= q <= M_c."""
+    dev, D = cache.U.device, cache.U.shape[1]
+    Uc, Ur = _as_f64(Uc.detach(), dev).contiguous(), _as_f64(Ur.detach(), dev).contiguous()
+    for U, name in ((Uc, "candidates"), (Ur, "reference points")):
+        if U.dim() != 2 or U.shape[0] < 1 or U.shape[1] != D:
+            raise ValueError(f"{what}: the {name} must be at least one row of {D} features (got {tuple(U.shape)})")
+    if q < 1 or q > Uc.shape[0]:
+        raise ValueError(f"{what}: q must be between 1 and the number of candidates ({Uc.shape[0]}); got {q}")
+    return Uc, Ur
+
+
+def _alc_common(what: str, cache, Uc, tau_c, Ur, omega, q: int = 1):
+    """The input checks of the three variance-reduction scores: ``_score_points``, then (tau_c, omega) as fp64 vectors of M_c and M_r
+    on the cache's device.  ``omega`` None: 1 / M_r each."""
+    Uc, Ur = _score_points(what, cache, Uc, Ur, q)
+    dev, Mr = Uc.device, Ur.shape[0]
+    tau_c = _per_row(what, tau_c, Uc.shape[0], "noise levels", "candidates", dev)
+    if omega is None:
+        omega = torch.full((Mr,), 1.0 / Mr, dtype=torch.float64, device=dev)
+    else:
+        omega = _per_row(what, omega, Mr, "weights", "reference points", dev)
+    return Uc, tau_c, Ur, omega
+
+
+@contextmanager
+def _score_call(what: str, cache):
+    """What every score function runs under: refused under ``settings.sharded_evaluation``, the cache's GPU current, refused inside a
+    graph capture."""
+    _gradient_cache_refusals(what)
+    dev = cache.U.device  # (anything but a GPU only under a stand-in context: the library itself has no CPU path)
+    with torch.cuda.device(dev) if dev.type == "cuda" else nullcontext():
+        _gradient_cache_refusals(what, dev)
+        yield
+
+
+def _greedy_picks(stage: str, cache: FactorCache, Uc, tau_c, Ur, q: int, cost, transposed: bool, score):
+    """The greedy rounds of ``variance_reduction`` (``stage`` "alc") and ``knowledge_gradient`` ("kg"): both operands with q - 1 spare
+    coordinates, then per round the candidates' M_c scores ``score(K, s, Vc, Vr)`` — K = N + t coordinates, s the variance of an
+    observation at each candidate, Vc / Vr the K-coordinate windows of the operands —, the pick by score (by score / ``cost``) among
+    the rows not yet taken, and the coordinate the pick appends to every point.  Returns (the first round's scores, the picked rows
+    in pick order, their undivided scores)."""
+    dev, N, Mc = cache.U.device, cache.U.shape[0], Uc.shape[0]
+    with _stage(stage + "_operands"):
+        (Vc, var_c), (Vr, _) = (_operand_V(cache, U, transposed, N + q - 1) for U in (Uc, Ur))
+    Ucr = torch.cat([Uc, Ur]) if q > 1 else None
+    taken = torch.zeros(Mc, dtype=torch.bool, device=dev)
+    picks, gains, first = [], [], None
+    for t in range(q):
+        K = N + t
+        s = var_c.clamp_min(0.0) + tau_c + cache.jitter
+        dv = score(K, s, Vc[:K] if transposed else Vc[:, :K], Vr[:K] if transposed else Vr[:, :K])
+        if t == 0:
+            first = dv.clone()
+        rank = (dv if cost is None else dv / cost).masked_fill(taken, float("-inf"))
+        j = int(torch.argmax(rank))
+        picks.append(j)
+        gains.append(dv[j])
+        taken[j] = True
+        if t + 1 == q:
+            break
+        # the new coordinate of every point: c(x, x_j) / sqrt(s_j), c by the current (N + t)-long vectors
+        with _stage(stage + "_append"):
+            var_c = _append_pick_coordinate(cache, Ucr, Uc, j, s[j], Vc, Vr, K, var_c, transposed)
+    return first, torch.tensor(picks, dtype=torch.int64, device=dev), torch.stack(gains)
 
 
 def _append_pick_coordinate(cache: FactorCache, Ucr, Uc, j: int, s_j, Vc, Vr, K: int, var_c, transposed: bool):
@@ -874,66 +955,24 @@ def variance_reduction(cache: FactorCache, Uc, tau_c, Ur, omega=None, q: int = 1
     ``omega`` None: 1 / M_r each.  Returns (the M_c first-round scores, the q picked rows of ``Uc`` in pick order, their gains), in
     the cache's (scaled-target) units.  The cache is only read.  Refused under ``settings.sharded_evaluation`` and inside a graph
     capture, like ``append_to_cache``."""
-    if settings.sharded_evaluation.value() is not None:
-        raise NotImplementedError("variance_reduction is not available under settings.sharded_evaluation")
-    dev = cache.U.device
-    gctx = cache.gctx
-    on_gpu = dev.type == "cuda"  # (anything else only under a stand-in context: the library itself has no CPU path)
-    transposed = ALC_TRANSPOSED if transposed is None else bool(transposed)
-    with torch.cuda.device(dev) if on_gpu else nullcontext():
-        if on_gpu and torch.cuda.is_current_stream_capturing():
-            raise NotImplementedError("variance_reduction is not available inside a graph capture")
-        Uc, Ur = _as_f64(Uc.detach(), dev).contiguous(), _as_f64(Ur.detach(), dev).contiguous()
-        D, q = cache.U.shape[1], int(q)
-        for U, name in ((Uc, "candidates"), (Ur, "reference points")):
-            if U.dim() != 2 or U.shape[0] < 1 or U.shape[1] != D:
-                raise ValueError(f"the {name} must be at least one row of {D} features (got {tuple(U.shape)})")
-        Mc, Mr = Uc.shape[0], Ur.shape[0]
-        if q < 1 or q > Mc:
-            raise ValueError(f"q must be between 1 and the number of candidates ({Mc}); got {q}")
-        tau_c = _as_f64(tau_c.detach().reshape(-1), dev)
-        if tau_c.numel() != Mc:
-            raise ValueError(f"{tau_c.numel()} noise levels for {Mc} candidates")
-        if omega is None:
-            omega = torch.full((Mr,), 1.0 / Mr, dtype=torch.float64, device=dev)
-        else:
-            omega = _as_f64(omega.detach().reshape(-1), dev).contiguous()
-            if omega.numel() != Mr:
-                raise ValueError(f"{omega.numel()} weights for {Mr} reference points")
+    what = "variance_reduction"
+    q, transposed = int(q), ALC_TRANSPOSED if transposed is None else bool(transposed)
+    with _score_call(what, cache):
+        gctx, spec = cache.gctx, cache.spec
+        Uc, tau_c, Ur, omega = _alc_common(what, cache, Uc, tau_c, Ur, omega, q)
+        Mc, dev = Uc.shape[0], Uc.device
         if cost is not None:
-            cost = _as_f64(cost.detach().reshape(-1), dev)
-            if cost.numel() != Mc:
-                raise ValueError(f"{cost.numel()} costs for {Mc} candidates")
+            cost = _per_row(what, cost, Mc, "costs", "candidates", dev)
         cache.refresh()  # (a cache of the shared workspace that another model has factored into since)
-        N, spec = cache.U.shape[0], cache.spec
-        w, sf2 = spec.w, spec.sf2.reshape(1)
-        Kmax = N + q - 1
-        with _stage("alc_operands"):
-            (Vc, var_c), (Vr, _) = _cross_operands(cache, (Uc, Ur), Kmax, transposed)
-        Ucr = torch.cat([Uc, Ur]) if q > 1 else None
         num = torch.empty(Mc, dtype=torch.float64, device=dev)
-        taken = torch.zeros(Mc, dtype=torch.bool, device=dev)
-        picks, gains, first = [], [], None
-        for t in range(q):
-            K = N + t
-            s = var_c.clamp_min(0.0) + tau_c + cache.jitter
+
+        def score(K, s, Vc, Vr):
             with _stage("post_cross_sq"):
-                gctx.post_cross_sq(Uc, Ur, w, sf2, Vc[:K] if transposed else Vc[:, :K], Vr[:K] if transposed else Vr[:, :K], K, num,
-                                   omega=omega, kind=spec.kind, d_split=spec.d_split, transposed=transposed)
-            dv = num / s
-            if t == 0:
-                first = dv.clone()
-            rank = (dv if cost is None else dv / cost).masked_fill(taken, float("-inf"))
-            j = int(torch.argmax(rank))
-            picks.append(j)
-            gains.append(dv[j])
-            taken[j] = True
-            if t + 1 == q:
-                break
-            # the new coordinate of every point: c(x, x_j) / sqrt(s_j), c by the current (N + t)-long vectors
-            with _stage("alc_append"):
-                var_c = _append_pick_coordinate(cache, Ucr, Uc, j, s[j], Vc, Vr, K, var_c, transposed)
-        return first, torch.tensor(picks, dtype=torch.int64, device=dev), torch.stack(gains)
+                gctx.post_cross_sq(Uc, Ur, spec.w, spec.sf2.reshape(1), Vc, Vr, K, num, omega=omega, kind=spec.kind,
+                                   d_split=spec.d_split, transposed=transposed)
+            return num / s
+
+        return _greedy_picks("alc", cache, Uc, tau_c, Ur, q, cost, transposed, score)
 
 
 #: Most bytes the derivative cross block Dk and the product Q = Dk^T Linv^T of ONE chunk of ``gradient_from_cache`` may take, each:
@@ -1265,47 +1304,6 @@ def _alc_gradient_chunk_points(K: int, b: int) -> int:
     return mc
 
 
-def _function_operand_V(cache, Us, transposed: bool):
-    """(V or V^T, latent variance) of the latent f at ``Us`` from a ``FactorCache`` (``_cross_operands``) or a ``GradientFactorCache``
-    (K = N + q coordinates): the operand of gpp_post_cross_sq / gpp_post_cross_lin_sq, points x K or with ``transposed`` K x points."""
-    if not isinstance(cache, GradientFactorCache):
-        return _cross_operands(cache, (Us,), cache.U.shape[0], transposed)[0]
-    dev, gctx = Us.device, cache.gctx
-    M, K = Us.shape[0], cache.U.shape[0] + cache.q
-    op = _gek_function_operand(cache, Us)
-    V = rows_buffer(M, K, dev)
-    mean = torch.empty(M, dtype=torch.float64, device=dev)
-    var = torch.empty(M, dtype=torch.float64, device=dev)
-    gctx.predict_tn(cache.Linv, cache.z, op, cache.spec.sf2.reshape(1).expand(M).contiguous(), V, mean, var)
-    if not transposed:
-        return V, var
-    del op
-    Vt = rows_buffer(K, M, dev)
-    gctx.transpose(V, Vt)
-    return Vt, var
-
-
-def _alc_common(what: str, cache, Uc, tau_c, Ur, omega):
-    """The checks ``variance_reduction_from_gradient_cache`` and ``variance_reduction_block`` share: (Uc, tau_c, Ur, omega) on the
-    cache's device, fp64 and contiguous; ``omega`` None: 1 / M_r each."""
-    dev, D = cache.U.device, cache.U.shape[1]
-    Uc, Ur = _as_f64(Uc.detach(), dev).contiguous(), _as_f64(Ur.detach(), dev).contiguous()
-    for U, name in ((Uc, "candidates"), (Ur, "reference points")):
-        if U.dim() != 2 or U.shape[0] < 1 or U.shape[1] != D:
-            raise ValueError(f"{what}: the {name} must be at least one row of {D} features (got {tuple(U.shape)})")
-    Mc, Mr = Uc.shape[0], Ur.shape[0]
-    tau_c = _as_f64(tau_c.detach().reshape(-1), dev)
-    if tau_c.numel() != Mc:
-        raise ValueError(f"{what}: {tau_c.numel()} noise levels for {Mc} candidates")
-    if omega is None:
-        omega = torch.full((Mr,), 1.0 / Mr, dtype=torch.float64, device=dev)
-    else:
-        omega = _as_f64(omega.detach().reshape(-1), dev).contiguous()
-        if omega.numel() != Mr:
-            raise ValueError(f"{what}: {omega.numel()} weights for {Mr} reference points")
-    return Uc, tau_c, Ur, omega
-
-
 @torch.no_grad()
 def variance_reduction_from_gradient_cache(gcache: GradientFactorCache, Uc, tau_c, Ur, omega=None, transposed: Optional[bool] = None):
     """First-round scores of ``variance_reduction`` (one noisy function value per candidate) from a gradient-enhanced posterior:
@@ -1313,19 +1311,16 @@ def variance_reduction_from_gradient_cache(gcache: GradientFactorCache, Uc, tau_
     M_c scores in the cache's scaled units; the cache is only read.  Refused under ``settings.sharded_evaluation`` and inside a graph
     capture."""
     what = "variance_reduction_from_gradient_cache"
-    _gradient_cache_refusals(what)
-    dev, gctx = gcache.U.device, gcache.gctx
     transposed = ALC_TRANSPOSED if transposed is None else bool(transposed)
-    with torch.cuda.device(dev) if dev.type == "cuda" else nullcontext():
-        _gradient_cache_refusals(what, dev)
+    with _score_call(what, gcache):
         Uc, tau_c, Ur, omega = _alc_common(what, gcache, Uc, tau_c, Ur, omega)
         spec, K = gcache.spec, gcache.U.shape[0] + gcache.q
         with _stage("alc_operands"):
-            (Vc, var_c), (Vr, _) = _function_operand_V(gcache, Uc, transposed), _function_operand_V(gcache, Ur, transposed)
-        num = torch.empty(Uc.shape[0], dtype=torch.float64, device=dev)
+            (Vc, var_c), (Vr, _) = _operand_V(gcache, Uc, transposed), _operand_V(gcache, Ur, transposed)
+        num = torch.empty(Uc.shape[0], dtype=torch.float64, device=Uc.device)
         with _stage("post_cross_sq"):
-            gctx.post_cross_sq(Uc, Ur, spec.w, spec.sf2.reshape(1), Vc, Vr, K, num, omega=omega, kind=spec.kind, d_split=spec.d_split,
-                               transposed=transposed)
+            gcache.gctx.post_cross_sq(Uc, Ur, spec.w, spec.sf2.reshape(1), Vc, Vr, K, num, omega=omega, kind=spec.kind,
+                                      d_split=spec.d_split, transposed=transposed)
         return num / (var_c.clamp_min(0.0) + tau_c + gcache.jitter)
 
 
@@ -1360,13 +1355,10 @@ def variance_reduction_block(cache, Uc, tau_c, gnoise, dirs, Ur, omega=None, tra
     from .errors import NotPSDError
 
     what = "variance_reduction_block"
-    _gradient_cache_refusals(what)
-    is_g = isinstance(cache, GradientFactorCache)
-    dev, gctx = cache.U.device, cache.gctx
-    on_gpu = dev.type == "cuda"  # (anything else only under a stand-in context: the library itself has no CPU path)
     transposed = ALC_TRANSPOSED if transposed is None else bool(transposed)
-    with torch.cuda.device(dev) if on_gpu else nullcontext():
-        _gradient_cache_refusals(what, dev)
+    with _score_call(what, cache):
+        is_g = isinstance(cache, GradientFactorCache)
+        dev, gctx = cache.U.device, cache.gctx
         Uc, tau_c, Ur, omega = _alc_common(what, cache, Uc, tau_c, Ur, omega)
         (N, D), Mc = cache.U.shape, Uc.shape[0]
         dirs = [int(d) for d in dirs]
@@ -1394,7 +1386,7 @@ def variance_reduction_block(cache, Uc, tau_c, gnoise, dirs, Ur, omega=None, tra
         prior = torch.cat([sf2, gradient_prior_curvature(spec, 0, D)[torch.tensor(dirs, dtype=torch.int64, device=dev)]])
         noise = torch.cat([tau_c.reshape(-1, 1), gnoise], 1) + cache.jitter
         with _stage("alc_operands"):
-            Vr, _ = _function_operand_V(cache, Ur, transposed)
+            Vr, _ = _operand_V(cache, Ur, transposed)
         with_g = torch.empty(Mc, dtype=torch.float64, device=dev)
         value = torch.empty(Mc, dtype=torch.float64, device=dev)
         step = _alc_gradient_chunk_points(K, b)
@@ -1628,37 +1620,19 @@ def knowledge_gradient(cache: FactorCache, Uc, tau_c, Ur, mean_r, q: int = 1, co
     ``settings.sharded_evaluation`` and inside a graph capture, like ``variance_reduction``."""
     from .backend import MAX_NODES, post_cross_min_workspace_bytes
 
-    if settings.sharded_evaluation.value() is not None:
-        raise NotImplementedError("knowledge_gradient is not available under settings.sharded_evaluation")
-    dev = cache.U.device
-    gctx = cache.gctx
-    on_gpu = dev.type == "cuda"  # (anything else only under a stand-in context: the library itself has no CPU path)
-    transposed = ALC_TRANSPOSED if transposed is None else bool(transposed)
-    with torch.cuda.device(dev) if on_gpu else nullcontext():
-        if on_gpu and torch.cuda.is_current_stream_capturing():
-            raise NotImplementedError("knowledge_gradient is not available inside a graph capture")
-        Uc, Ur = _as_f64(Uc.detach(), dev).contiguous(), _as_f64(Ur.detach(), dev).contiguous()
-        D, q, Q = cache.U.shape[1], int(q), int(num_nodes)
-        for U, name in ((Uc, "candidates"), (Ur, "reference points")):
-            if U.dim() != 2 or U.shape[0] < 1 or U.shape[1] != D:
-                raise ValueError(f"the {name} must be at least one row of {D} features (got {tuple(U.shape)})")
-        Mc, Mr = Uc.shape[0], Ur.shape[0]
-        if q < 1 or q > Mc:
-            raise ValueError(f"q must be between 1 and the number of candidates ({Mc}); got {q}")
+    what = "knowledge_gradient"
+    q, Q, transposed = int(q), int(num_nodes), ALC_TRANSPOSED if transposed is None else bool(transposed)
+    with _score_call(what, cache):
+        gctx, spec = cache.gctx, cache.spec
+        Uc, Ur = _score_points(what, cache, Uc, Ur, q)
+        (Mc, dev), Mr = (Uc.shape[0], Uc.device), Ur.shape[0]
         if Q < 1 or Q > MAX_NODES:
-            raise ValueError(f"num_nodes must be between 1 and {MAX_NODES}; got {Q}")
-        tau_c = _as_f64(tau_c.detach().reshape(-1), dev)
-        if tau_c.numel() != Mc:
-            raise ValueError(f"{tau_c.numel()} noise levels for {Mc} candidates")
-        mean_r = _as_f64(mean_r.detach().reshape(-1), dev)
-        if mean_r.numel() != Mr:
-            raise ValueError(f"{mean_r.numel()} means for {Mr} reference points")
+            raise ValueError(f"{what}: num_nodes must be between 1 and {MAX_NODES}; got {Q}")
+        tau_c = _per_row(what, tau_c, Mc, "noise levels", "candidates", dev)
+        mean_r = _per_row(what, mean_r, Mr, "means", "reference points", dev)
         if cost is not None:
-            cost = _as_f64(cost.detach().reshape(-1), dev)
-            if cost.numel() != Mc:
-                raise ValueError(f"{cost.numel()} costs for {Mc} candidates")
+            cost = _per_row(what, cost, Mc, "costs", "candidates", dev)
         cache.refresh()  # (a cache of the shared workspace that another model has factored into since)
-        N, spec = cache.U.shape[0], cache.spec
         w, sf2 = spec.w, spec.sf2.reshape(1)
         z, W = gauss_hermite_rule(Q)
         nodes = torch.tensor(z, dtype=torch.float64, device=dev)
@@ -1668,39 +1642,22 @@ def knowledge_gradient(cache: FactorCache, Uc, tau_c, Ur, mean_r, q: int = 1, co
         step = Mr
         if post_cross_min_workspace_bytes(Mc, Mr, Q) > KG_WORKSPACE_CAP:
             step = 128 * max(1, int(KG_WORKSPACE_CAP // post_cross_min_workspace_bytes(Mc, 128, Q)))
-        Kmax = N + q - 1
-        with _stage("kg_operands"):
-            (Vc, var_c), (Vr, _) = _cross_operands(cache, (Uc, Ur), Kmax, transposed)
-        Ucr = torch.cat([Uc, Ur]) if q > 1 else None
         out = torch.empty(Mc, Q, dtype=torch.float64, device=dev)
         part = torch.empty(Mc, Q, dtype=torch.float64, device=dev) if step < Mr else None
-        taken = torch.zeros(Mc, dtype=torch.bool, device=dev)
-        picks, gains, first = [], [], None
-        for t in range(q):
-            K = N + t
-            s = var_c.clamp_min(0.0) + tau_c + cache.jitter
+
+        def score(K, s, Vc, Vr):
             scale = 1.0 / s.sqrt()
             with _stage("post_cross_min"):
                 for c0 in range(0, Mr, step):
                     c1 = min(Mr, c0 + step)
-                    gctx.post_cross_min(Uc, Ur[c0:c1], w, sf2, Vc[:K] if transposed else Vc[:, :K],
-                                        Vr[:K, c0:c1] if transposed else Vr[c0:c1, :K], K, m[c0:c1], scale, nodes,
-                                        out if c0 == 0 else part, kind=spec.kind, d_split=spec.d_split, transposed=transposed)
+                    gctx.post_cross_min(Uc, Ur[c0:c1], w, sf2, Vc, Vr[:, c0:c1] if transposed else Vr[c0:c1], K, m[c0:c1], scale,
+                                        nodes, out if c0 == 0 else part, kind=spec.kind, d_split=spec.d_split,
+                                        transposed=transposed)
                     if c0 > 0:
                         torch.minimum(out, part, out=out)
-            kg = (-(out * W).sum(dim=1)).clamp_min(0.0)
-            if t == 0:
-                first = kg.clone()
-            rank = (kg if cost is None else kg / cost).masked_fill(taken, float("-inf"))
-            j = int(torch.argmax(rank))
-            picks.append(j)
-            gains.append(kg[j])
-            taken[j] = True
-            if t + 1 == q:
-                break
-            with _stage("kg_append"):
-                var_c = _append_pick_coordinate(cache, Ucr, Uc, j, s[j], Vc, Vr, K, var_c, transposed)
-        return first, torch.tensor(picks, dtype=torch.int64, device=dev), torch.stack(gains)
+            return (-(out * W).sum(dim=1)).clamp_min(0.0)
+
+        return _greedy_picks("kg", cache, Uc, tau_c, Ur, q, cost, transposed, score)
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -32,6 +32,43 @@ def _named_correlation(name: str, n_features: int) -> Kernel:
     return k
 
 
+def _check_weights(what: str, weights, n: int, noun: str):
+    """``weights`` (None stays None) as fp64, one for each of the ``n`` ``noun``: finite, non-negative, not all zero."""
+    from ..utils import data_type_check
+
+    if weights is None:
+        return None
+    weights = data_type_check(weights).reshape(-1).to(torch.float64)
+    if weights.shape[0] != n:
+        raise ValueError(f"{what}: {weights.shape[0]} weights for {n} {noun}")
+    if not bool(torch.isfinite(weights).all()) or bool((weights < 0).any()):
+        raise ValueError(f"{what}: the weights must be finite and non-negative")
+    if not bool((weights > 0).any()):
+        raise ValueError(f"{what}: the weights are all zero")
+    return weights
+
+
+def _check_cost(what: str, cost, Mc: int):
+    """``cost`` (None stays None) as fp64, one for each of the ``Mc`` candidates: finite and positive."""
+    from ..utils import data_type_check
+
+    if cost is None:
+        return None
+    cost = data_type_check(cost).reshape(-1).to(torch.float64)
+    if cost.shape[0] != Mc:
+        raise ValueError(f"{what}: {cost.shape[0]} costs for {Mc} candidates")
+    if not bool(torch.isfinite(cost).all()) or bool((cost <= 0).any()):
+        raise ValueError(f"{what}: the costs must be finite and positive")
+    return cost
+
+
+def _check_q(what: str, q, Mc: int) -> int:
+    q = int(q)
+    if q < 1 or q > Mc:
+        raise ValueError(f"{what}: q must be between 1 and the number of candidates ({Mc}); got {q}")
+    return q
+
+
 class GPR(ExactGP):
     #: registered on the model in this order (state_dict keys of the reference, models/gpregression.py:73-76)
     _TARGET_BUFFERS = ('y_min', 'y_std', 'y_scaled')
@@ -174,15 +211,7 @@ class GPR(ExactGP):
             cache = self._ensure_prediction_cache()
             out_q = Module.__call__(self, Xq)
             cov_q = out_q.lazy_covariance_matrix
-            lik = self.likelihood
-            swap = hasattr(lik, "fidel_indices")
-            if swap:  # the noise groups of the new rows' own source column, as _ensure_prediction_cache does for the training rows
-                saved, lik.fidel_indices = lik.fidel_indices, Xq[:, -1]
-            try:
-                noisy = lik(out_q).lazy_covariance_matrix
-            finally:
-                if swap:
-                    lik.fidel_indices = saved
+            noisy = self._likelihood_of_rows(out_q, Xq).lazy_covariance_matrix
             new_cache = append_to_cache(cache, cov_q.U1, noisy.tau, noisy.grp, out_q.mean, yq, reserve)
 
             child = self._copy_without_factors()
@@ -215,59 +244,48 @@ class GPR(ExactGP):
         self._check_new_rows(X)
         return X
 
+    def _noise_of_rows(self, out, X) -> torch.Tensor:
+        """The noise level of each row's own source (fp64, one per row of ``X``; ``out``: the model's prior at ``X``), as
+        ``condition_on`` gives a new row."""
+        noisy = self._likelihood_of_rows(out, X).lazy_covariance_matrix
+        tau = noisy.tau.detach().reshape(-1).to(torch.float64)
+        return tau[noisy.grp.long()] if noisy.grp is not None else tau[:1].expand(X.shape[0])
+
+    def _score_preamble(self, what: str, row_sets, cache=None):
+        """What every score does once its arguments are validated: refused under ``settings.sharded_evaluation``, a GPU context or
+        none (there is no CPU path), eval mode, the prediction cache (``cache`` None) and the model's prior at each validated row
+        set.  Returns (cache, the row sets on the model's device and dtype, their priors)."""
+        from .. import settings as gpp_settings
+        from ..backend import get_context
+        from ..gpcore.module import Module
+
+        if gpp_settings.sharded_evaluation.value() is not None:
+            raise NotImplementedError(f"{what} is not available under settings.sharded_evaluation")
+        train_x = self.train_inputs[0]
+        get_context(train_x.device)  # (raises for anything but a GPU: there is no CPU path)
+        row_sets = [X.to(train_x) for X in row_sets]
+        self.eval()
+        with torch.no_grad():
+            if cache is None:
+                cache = self._ensure_prediction_cache()
+            return cache, row_sets, [Module.__call__(self, X) for X in row_sets]
+
     def _variance_reduction(self, Xcand, Xref, weights=None, q: int = 1, cost=None):
         """(first-round scores, picked rows of ``Xcand``, their gains) of ``linalg.variance_reduction``, in y^2 units: the work behind
         ``variance_reduction`` and ``bayesian_optimizations.select_by_variance_reduction``.  Everything is validated on the host
         before any device work."""
-        from .. import settings as gpp_settings
-        from ..backend import get_context
-        from ..gpcore.module import Module
         from ..linalg import variance_reduction
-        from ..utils import data_type_check
 
+        what = "variance_reduction"
         Xc, Xr = self._alc_rows(Xcand, "Xcand"), self._alc_rows(Xref, "Xref")
-        Mc, Mr = Xc.shape[0], Xr.shape[0]
-        if weights is not None:
-            weights = data_type_check(weights).reshape(-1).to(torch.float64)
-            if weights.shape[0] != Mr:
-                raise ValueError(f"variance_reduction: {weights.shape[0]} weights for {Mr} reference rows")
-            if not bool(torch.isfinite(weights).all()) or bool((weights < 0).any()):
-                raise ValueError("variance_reduction: the weights must be finite and non-negative")
-            if not bool((weights > 0).any()):
-                raise ValueError("variance_reduction: the weights are all zero")
-        if cost is not None:
-            cost = data_type_check(cost).reshape(-1).to(torch.float64)
-            if cost.shape[0] != Mc:
-                raise ValueError(f"variance_reduction: {cost.shape[0]} costs for {Mc} candidates")
-            if not bool(torch.isfinite(cost).all()) or bool((cost <= 0).any()):
-                raise ValueError("variance_reduction: the costs must be finite and positive")
-        q = int(q)
-        if q < 1 or q > Mc:
-            raise ValueError(f"variance_reduction: q must be between 1 and the number of candidates ({Mc}); got {q}")
-        if gpp_settings.sharded_evaluation.value() is not None:
-            raise NotImplementedError("variance_reduction is not available under settings.sharded_evaluation")
-        train_x = self.train_inputs[0]
-        get_context(train_x.device)  # (raises for anything but a GPU: there is no CPU path)
-
-        Xc, Xr = Xc.to(train_x), Xr.to(train_x)
-        self.eval()
+        weights = _check_weights(what, weights, Xr.shape[0], "reference rows")
+        cost = _check_cost(what, cost, Xc.shape[0])
+        q = _check_q(what, q, Xc.shape[0])
+        cache, (Xc, Xr), (out_c, out_r) = self._score_preamble(what, (Xc, Xr))
         with torch.no_grad():
-            cache = self._ensure_prediction_cache()
-            out_c = Module.__call__(self, Xc)
-            Ur = Module.__call__(self, Xr).lazy_covariance_matrix.U1
-            lik = self.likelihood
-            swap = hasattr(lik, "fidel_indices")
-            if swap:  # the noise of each candidate's own source, as condition_on gives a new row
-                saved, lik.fidel_indices = lik.fidel_indices, Xc[:, -1]
-            try:
-                noisy = lik(out_c).lazy_covariance_matrix
-            finally:
-                if swap:
-                    lik.fidel_indices = saved
-            tau = noisy.tau.detach().reshape(-1).to(torch.float64)
-            tau_c = tau[noisy.grp.long()] if noisy.grp is not None else tau[:1].expand(Mc)
-            dev = train_x.device
-            first, picks, gains = variance_reduction(cache, out_c.lazy_covariance_matrix.U1, tau_c, Ur,
+            dev = Xc.device
+            first, picks, gains = variance_reduction(cache, out_c.lazy_covariance_matrix.U1, self._noise_of_rows(out_c, Xc),
+                                                     out_r.lazy_covariance_matrix.U1,
                                                      omega=None if weights is None else weights.to(dev), q=q,
                                                      cost=None if cost is None else cost.to(dev))
             scale = self.y_std.to(torch.float64) ** 2
@@ -294,54 +312,23 @@ class GPR(ExactGP):
         """(first-round scores, picked rows of ``Xcand``, their gains) of ``linalg.knowledge_gradient``, in the units of y: the work
         behind ``knowledge_gradient`` and ``bayesian_optimizations.select_by_knowledge_gradient``.  Everything is validated on the
         host before any device work."""
-        from .. import settings as gpp_settings
-        from ..backend import MAX_NODES, get_context
-        from ..gpcore.module import Module
+        from ..backend import MAX_NODES
         from ..linalg import knowledge_gradient, predict_from_cache
-        from ..utils import data_type_check
 
-        Xc = self._alc_rows(Xcand, "Xcand", "knowledge_gradient")
-        Xr = self._alc_rows(Xref, "Xref", "knowledge_gradient")
-        Mc = Xc.shape[0]
-        if cost is not None:
-            cost = data_type_check(cost).reshape(-1).to(torch.float64)
-            if cost.shape[0] != Mc:
-                raise ValueError(f"knowledge_gradient: {cost.shape[0]} costs for {Mc} candidates")
-            if not bool(torch.isfinite(cost).all()) or bool((cost <= 0).any()):
-                raise ValueError("knowledge_gradient: the costs must be finite and positive")
-        q, num_nodes = int(q), int(num_nodes)
-        if q < 1 or q > Mc:
-            raise ValueError(f"knowledge_gradient: q must be between 1 and the number of candidates ({Mc}); got {q}")
+        what = "knowledge_gradient"
+        Xc, Xr = self._alc_rows(Xcand, "Xcand", what), self._alc_rows(Xref, "Xref", what)
+        cost = _check_cost(what, cost, Xc.shape[0])
+        q, num_nodes = _check_q(what, q, Xc.shape[0]), int(num_nodes)
         if num_nodes < 1 or num_nodes > MAX_NODES:
-            raise ValueError(f"knowledge_gradient: num_nodes must be between 1 and {MAX_NODES}; got {num_nodes}")
-        if gpp_settings.sharded_evaluation.value() is not None:
-            raise NotImplementedError("knowledge_gradient is not available under settings.sharded_evaluation")
-        train_x = self.train_inputs[0]
-        get_context(train_x.device)  # (raises for anything but a GPU: there is no CPU path)
-
-        Xc, Xr = Xc.to(train_x), Xr.to(train_x)
-        self.eval()
+            raise ValueError(f"{what}: num_nodes must be between 1 and {MAX_NODES}; got {num_nodes}")
+        cache, (Xc, Xr), (out_c, out_r) = self._score_preamble(what, (Xc, Xr))
         with torch.no_grad():
-            cache = self._ensure_prediction_cache()
-            out_c = Module.__call__(self, Xc)
-            out_r = Module.__call__(self, Xr)
             Ur = out_r.lazy_covariance_matrix.U1
-            lik = self.likelihood
-            swap = hasattr(lik, "fidel_indices")
-            if swap:  # the noise of each candidate's own source, as condition_on gives a new row
-                saved, lik.fidel_indices = lik.fidel_indices, Xc[:, -1]
-            try:
-                noisy = lik(out_c).lazy_covariance_matrix
-            finally:
-                if swap:
-                    lik.fidel_indices = saved
-            tau = noisy.tau.detach().reshape(-1).to(torch.float64)
-            tau_c = tau[noisy.grp.long()] if noisy.grp is not None else tau[:1].expand(Mc)
-            dev = train_x.device
+            tau_c = self._noise_of_rows(out_c, Xc)
             cache.refresh()
             mean_r = out_r.mean.to(torch.float64) + predict_from_cache(cache, Ur, need_var=False)[0]
             first, picks, gains = knowledge_gradient(cache, out_c.lazy_covariance_matrix.U1, tau_c, Ur, mean_r, q=q,
-                                                     cost=None if cost is None else cost.to(dev), maximize=bool(maximize),
+                                                     cost=None if cost is None else cost.to(Xc.device), maximize=bool(maximize),
                                                      num_nodes=num_nodes)
             scale = self.y_std.to(torch.float64).abs()
             return first * scale, picks, gains * scale
