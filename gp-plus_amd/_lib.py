@@ -166,7 +166,21 @@ _SIGNATURES = {
                                             c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
 }
 
+#: every symbol ``include/gpp_ensemble.h`` declares (``libgpp_ensemble_hip.so``, built by the same Makefile from csrc/gpp_ensemble.hip: a
+#: library of its own, so that ``libgpp_hip.so`` and the source signature ``gpp_version()`` reports stay what they were)
+_ENSEMBLE_LIB_PATH = _PKG_DIR / "libgpp_ensemble_hip.so"
+_ENSEMBLE_SIGNATURES = {
+    "gpp_ensemble_version": (c_char_p, []),
+    "gpp_predict_gen_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
+    "gpp_predict_gen": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                c_int64, c_void_p, c_void_p, c_void_p]),
+    "gpp_predict_gen_batched": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
+                                        c_int, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                        c_int]),
+}
+
 _lib = None
+_ensemble_lib = None
 
 
 class GppError(RuntimeError):
@@ -199,6 +213,24 @@ def load() -> ctypes.CDLL:
         fn.restype = restype
         fn.argtypes = argtypes
     _lib = lib
+    return lib
+
+
+def load_ensemble() -> ctypes.CDLL:
+    """Load ``libgpp_ensemble_hip.so`` (after ``libgpp_hip.so``) and bind its entry points; raises if it is absent (no fallback)."""
+    global _ensemble_lib
+    if _ensemble_lib is not None:
+        return _ensemble_lib
+    load()
+    if not _ENSEMBLE_LIB_PATH.exists():
+        raise GppError(f"{_ENSEMBLE_LIB_PATH} not found: the HIP extension is required (build it with `make -C {_CSRC}`); "
+                       "there is no CPU fallback.")
+    lib = ctypes.CDLL(os.fspath(_ENSEMBLE_LIB_PATH))
+    for name, (restype, argtypes) in _ENSEMBLE_SIGNATURES.items():
+        fn = getattr(lib, name)  # AttributeError if the symbol is not exported
+        fn.restype = restype
+        fn.argtypes = argtypes
+    _ensemble_lib = lib
     return lib
 
 

@@ -808,6 +808,8 @@ class GppContext:
         D = w.shape[1]
         sU = 0 if U.dim() == 2 else U.stride(0)
         S = 0 if tau is None else tau.shape[1]
+        if grp is not None and grp.numel() != N:  # (the kernels index grp[i] unchecked; the value range is _check_groups' matter)
+            raise GppError(f"noise-group index has {grp.numel()} entries for {N} points (stale fidel_indices?)")
         self._stream()
         check(self.lib.gpp_kernel_build_batched(self.h, U.data_ptr(), sU, N, D, w.data_ptr(), sf2.data_ptr(), _ptr(tau),
                                                 _ptr(grp), S, float(jitter), kind, d_split, uplo, out.data_ptr(), out.stride(1),
@@ -851,6 +853,71 @@ class GppContext:
         self._stream()
         check(self.lib.gpp_alpha_batched(self.h, Linv.data_ptr(), Linv.stride(1), Linv.stride(0), Linv.shape[1], z.data_ptr(),
                                          alpha.data_ptr(), self._sv(z, alpha), Linv.shape[0]), "gpp_alpha_batched")
+
+    def _ensemble_lib(self):
+        """``libgpp_ensemble_hip.so`` (include/gpp_ensemble.h): gpp_predict_gen and gpp_predict_gen_batched, on this context's handle."""
+        if getattr(self, "elib", None) is None:
+            self.elib = _lib.load_ensemble()
+        return self.elib
+
+    def _ensure_predict_gen_workspace(self, N: int, M: int, batch: int) -> None:
+        need = int(self._ensemble_lib().gpp_predict_gen_workspace_bytes(N, M, batch)) + 256
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            check(self.lib.gpp_set_workspace(self.h, self._ws.data_ptr(), self._ws.numel()), "gpp_set_workspace")
+
+    @_on_own_device
+    def predict_gen(self, Ua, Ub, w, sf2, Linv, z, mean_out, var_out, *, kind=KIND_RBF, d_split=0):
+        """mean = V z and var = sf2 - rowsum(V o V), V = sf2 k(Ua, Ub; w) L^-T, from the mirror in the upper triangle of ``Linv``
+        (N x N view of an even-stride buffer) and z = Linv r, without forming the cross block or V (gpp_predict_gen)."""
+        (M, D), N = Ua.shape, Ub.shape[0]
+        _check_features(D)
+        for t, n in ((Ua, "Ua"), (Ub, "Ub"), (w, "w"), (sf2, "sf2"), (Linv, "Linv"), (z, "z"), (mean_out, "mean_out"), (var_out, "var_out")):
+            _need(t, torch.float64, n)
+        if not (Ua.is_contiguous() and Ub.is_contiguous()):
+            raise GppError("Ua/Ub must be contiguous")
+        if Ub.shape[1] != D or w.numel() != D or sf2.numel() < 1 or min(M, N) < 1:
+            raise GppError(f"gpp_predict_gen takes Ua (M, D), Ub (N, D), w (D), sf2 (1) with M, N >= 1 (got {tuple(Ua.shape)}, "
+                           f"{tuple(Ub.shape)}, {w.numel()}, {sf2.numel()})")
+        if Linv.shape != (N, N) or z.numel() != N or mean_out.numel() != M or var_out.numel() != M:
+            raise GppError(f"gpp_predict_gen: Linv must be {N} x {N}, z ({N}), mean_out / var_out ({M})")
+        if not (z.is_contiguous() and mean_out.is_contiguous() and var_out.is_contiguous()):
+            raise GppError("z, mean_out and var_out must be contiguous")
+        self._ensure_predict_gen_workspace(N, M, 1)
+        self._stream()
+        check(self._ensemble_lib().gpp_predict_gen(self.h, Ua.data_ptr(), M, Ub.data_ptr(), N, D, w.data_ptr(), sf2.data_ptr(), kind, d_split,
+                                       Linv.data_ptr(), _ld(Linv), z.data_ptr(), mean_out.data_ptr(), var_out.data_ptr()),
+              "gpp_predict_gen")
+
+    @_on_own_device
+    def predict_gen_batched(self, Ua, Ub, w, sf2, Linv, z, mean_out, var_out, *, kind=KIND_RBF, d_split=0):
+        """``predict_gen`` for B parameter sets in one launch (gpp_predict_gen_batched).  Ua: (M, D) shared or (B, M, D); Ub: (N, D)
+        shared or (B, N, D); w: (B, D); sf2: (B,); Linv: (B, N, ld) view; z: (B, N) and mean_out / var_out: (B, M) views of
+        even-stride allocations (``batched_vector``)."""
+        B, D = w.shape
+        M, N = Ua.shape[-2], Ub.shape[-2]
+        _check_features(D)
+        for t, n in ((Ua, "Ua"), (Ub, "Ub"), (w, "w"), (sf2, "sf2"), (Linv, "Linv"), (z, "z"), (mean_out, "mean_out"), (var_out, "var_out")):
+            _need(t, torch.float64, n)
+        for t, rows, n in ((Ua, M, "Ua"), (Ub, N, "Ub")):
+            if t.dim() not in (2, 3) or t.shape[-1] != D or rows < 1 or (t.dim() == 3 and t.shape[0] != B):
+                raise GppError(f"{n} must be (rows, {D}) or ({B}, rows, {D}) with at least one row (got {tuple(t.shape)})")
+            if t.stride(-1) != 1 or t.stride(-2) != D:
+                raise GppError(f"the rows of {n} must be contiguous")
+        if not w.is_contiguous() or sf2.numel() != B or not sf2.is_contiguous():
+            raise GppError(f"w must be a contiguous ({B}, {D}) tensor and sf2 a contiguous ({B},) one")
+        if Linv.shape != (B, N, N) or Linv.stride(2) != 1:
+            raise GppError(f"Linv must be a ({B}, {N}, {N}) view with contiguous rows (got {tuple(Linv.shape)})")
+        if z.shape != (B, N) or mean_out.shape != (B, M) or var_out.shape != (B, M):
+            raise GppError(f"z must be ({B}, {N}), mean_out / var_out ({B}, {M})")
+        sUa = 0 if Ua.dim() == 2 else Ua.stride(0)
+        sUb = 0 if Ub.dim() == 2 else Ub.stride(0)
+        sv, so = self._sv(z), self._sv(mean_out, var_out)
+        self._ensure_predict_gen_workspace(N, M, B)
+        self._stream()
+        check(self._ensemble_lib().gpp_predict_gen_batched(self.h, Ua.data_ptr(), sUa, M, Ub.data_ptr(), sUb, N, D, w.data_ptr(), sf2.data_ptr(),
+                                               kind, d_split, Linv.data_ptr(), Linv.stride(1), Linv.stride(0), z.data_ptr(), sv,
+                                               mean_out.data_ptr(), var_out.data_ptr(), so, B), "gpp_predict_gen_batched")
 
     @_on_own_device
     def grad_reduce_batched(self, U, w, sf2, grp, S, alpha, Kinv, dU, g_w, g_sf2, g_tau, g_U, *, kind=KIND_RBF, d_split=0):

@@ -13,6 +13,10 @@ Out of scope (raise ``NotImplementedError``): probabilistic embedding / calibrat
 ensembles), neural-network and polynomial mean functions, plotting (``visualize_latent``, ``sample_y(plot=True)``), Sobol
 indices, botorch glue, gradients through the joint predictive covariance (``predict_with_grad`` differentiates the mean and
 the variance diagonal) and gradients through posterior draws (``sample_y`` returns draws without an autograd graph).
+What this build offers in the place of the multi-pass ensembles: ``fit(keep_restarts=K)`` keeps the K best restarts of a batched
+fit as ``restart_ensemble``, an ``ensemble.HyperparameterEnsemble`` whose ``predict`` mixes the members' posteriors by the same
+moment matching (law of total variance), all members in one launch (gpp_predict_gen_batched).  The probabilistic embedding itself —
+sampling the latent map per pass — stays out of scope.
 """
 import math
 import warnings
@@ -343,6 +347,9 @@ class GP_Plus(GPR):
             out[n] = theta if mean_train is None else theta * float(std_train[n]) + float(mean_train[n])
         return out
 
+    #: the restarts kept by the last ``fit(keep_restarts=K)`` as an ``ensemble.HyperparameterEnsemble``; None otherwise
+    restart_ensemble = None
+
     def forward(self, x: torch.Tensor) -> MultivariateNormal:
         """gp_plus.py:386-484 (deterministic single pass)."""
         if x.dim() > 2:
@@ -392,7 +399,7 @@ class GP_Plus(GPR):
     def fit(self, add_prior: bool = True, num_restarts: int = 64, theta0_list: Optional[List[np.ndarray]] = None,
             jac: bool = True, options: Dict = {}, n_jobs: int = -1, method='L-BFGS-B', constraint=False, bounds=False,
             regularization_parameter: List[int] = [0, 0], optim_type='scipy', objective: str = "mll", folds=None,
-            gradients=None):
+            gradients=None, keep_restarts: int = 0):
         """gp_plus.py:547-599.  On a GPU device the reference always ends in ``fit_model_torch`` (64 restarts for
         'adam_torch', otherwise a warning and 4 restarts) — reproduced here.  The CPU branches
         (scipy / continuation drivers) do not exist in this build: the exact-GP path only runs on the MI355X.
@@ -408,10 +415,30 @@ class GP_Plus(GPR):
         evaluated at n = N + q rows (q observed gradient entries), every step an eager batched evaluation
         (``batched.batched_gek_mll``; no replayed graph); otherwise, and under ``settings.batched_restarts(False)``, the restarts run
         one after the other.  Afterwards ``condition_on_gradients`` on the same data gives the gradient-enhanced posterior at the
-        fitted hyperparameters."""
+        fitted hyperparameters.
+        ``keep_restarts=K`` (batched routes only) keeps the K restarts with the smallest finite last loss instead of discarding all
+        but the winner: afterwards ``self.restart_ensemble`` is an ``ensemble.HyperparameterEnsemble`` of them with
+        ``weights="posterior"``, member 0 the winner that is loaded into the model (fewer members when fewer restarts end finite);
+        without the keyword it is None.  The fit itself — iterates, return value, loaded parameters — is the same either way.  On a
+        route that is not batched ("cv", N above the batched kernels' range or memory, ``settings.batched_restarts(False)``, a
+        calibrated model) ``keep_restarts > 0`` raises ``NotImplementedError`` before any fitting starts."""
         from ..optim.mll_torch import check_objective_folds, check_objective_gradients
         folds = check_objective_folds(objective, folds, int(self.train_targets.shape[0]))
         gradients = check_objective_gradients(objective, gradients)
+        keep_restarts = int(keep_restarts)
+        if keep_restarts < 0:
+            raise ValueError(f"keep_restarts must be 0 or a positive count (got {keep_restarts})")
+        rows = int(self.train_targets.shape[0])
+        if objective == "gek":
+            # the joint matrix has n = N + q rows, q the observed gradient entries: the batched route is judged at that size
+            dY = torch.as_tensor(gradients[1])
+            observed = gradients[3] if len(gradients) == 4 else None
+            rows += int(dY.numel() if observed is None else torch.as_tensor(observed).expand(dY.shape).sum())
+        if keep_restarts > 0:
+            why = self._restarts_not_batched(objective, rows)  # (host work only: no device is touched)
+            if why is not None:
+                raise NotImplementedError(f"keep_restarts is available on the batched restarts only: {why}")
+        self.restart_ensemble = None
         if objective != "mll":
             self._refuse_calibrated(f'objective="{objective}"', "only the exact marginal likelihood has a gradient by theta")
         if optim_type == 'adam_torch_batched':
@@ -431,29 +458,45 @@ class GP_Plus(GPR):
         # optim/mll_batched.py) while the problem is small enough for that to pay and for the B x 3 N^2 workspace to fit;
         # settings.batched_restarts(False) restores the sequential loop, 'adam_torch_batched' asks for the batched one.
         if objective == "cv":
-            out = fit_model_torch(model=self, model_param_groups=None, lr_default=0.01, num_iter=100,
-                                  num_restarts=restarts, break_steps=50, objective=objective, folds=folds)
+            batched = False
         elif objective == "gek":
-            # the joint matrix has n = N + q rows, q the observed gradient entries: the batched route is judged at that size
-            dY = torch.as_tensor(gradients[1])
-            observed = gradients[3] if len(gradients) == 4 else None
-            q = int(dY.numel() if observed is None else torch.as_tensor(observed).expand(dY.shape).sum())
-            if self._restarts_fit_one_batch(restarts + 1, int(self.train_targets.shape[0]) + q):
-                from ..optim import fit_model_torch_batched
-                out = fit_model_torch_batched(self, lr_default=0.01, num_iter=100, num_restarts=restarts, break_steps=50,
-                                              objective=objective, gradients=gradients)
-            else:
-                out = fit_model_torch(model=self, model_param_groups=None, lr_default=0.01, num_iter=100,
-                                      num_restarts=restarts, break_steps=50, objective=objective, gradients=gradients)
-        elif optim_type == 'adam_torch_batched' or self._restarts_fit_one_batch(restarts + 1):
+            batched = self._restarts_fit_one_batch(restarts + 1, rows)
+        else:
+            batched = optim_type == 'adam_torch_batched' or self._restarts_fit_one_batch(restarts + 1)
+        extra = {k: v for k, v in (("folds", folds), ("gradients", gradients)) if v is not None}
+        if batched:
             from ..optim import fit_model_torch_batched
             out = fit_model_torch_batched(self, lr_default=0.01, num_iter=100, num_restarts=restarts, break_steps=50,
-                                          objective=objective)
+                                          objective=objective, keep=keep_restarts, **extra)
+            kept = fit_model_torch_batched.last_restarts
+            if kept is not None and kept.losses.numel() > 0:
+                from ..ensemble import HyperparameterEnsemble
+                self.restart_ensemble = HyperparameterEnsemble(self, kept.states, losses=kept.losses, weights="posterior",
+                                                               num_data=kept.num_data)
         else:
+            if keep_restarts > 0:
+                raise NotImplementedError("keep_restarts is available on the batched restarts only: the restarts of this fit do "
+                                          "not fit the device's free memory as one batch")
             out = fit_model_torch(model=self, model_param_groups=None, lr_default=0.01, num_iter=100,
-                                  num_restarts=restarts, break_steps=50, objective=objective)
+                                  num_restarts=restarts, break_steps=50, objective=objective, **extra)
         print("## Learning the model's parameters is successfully finished ##")
         return out
+
+    def _restarts_not_batched(self, objective: str, n: int) -> Optional[str]:
+        """Why the restarts of a fit with ``n`` factored rows cannot take the batched route, as far as the host can tell (None: the
+        device's free memory decides, ``_restarts_fit_one_batch``)."""
+        from .. import settings as gpp_settings
+        from ..optim.mll_batched import BATCHED_MAX_N
+
+        if objective == "cv":
+            return 'objective="cv" has no batched form'
+        if len(self.calibration_id) > 0:
+            return "the batched restarts have no gradient by calibration parameters"
+        if not gpp_settings.batched_restarts.value():
+            return "settings.batched_restarts is off"
+        if n > BATCHED_MAX_N:
+            return f"{n} rows are beyond the batched kernels' range ({BATCHED_MAX_N})"
+        return None
 
     def _restarts_fit_one_batch(self, B: int, n: Optional[int] = None) -> bool:
         """True when ``B`` restarts of this model should be evaluated together: batched restarts enabled, N within the batched

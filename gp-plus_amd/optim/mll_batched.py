@@ -29,10 +29,51 @@ from ..gpcore.kernels import LazyKernelMatrix
 from ..gpcore.mlls import ExactMarginalLogLikelihood, GradientEnhancedMarginalLogLikelihood
 from .mll_torch import check_objective, check_objective_folds, check_objective_gradients
 
-__all__ = ["BatchedObjective", "fit_model_torch_batched", "BATCHED_MAX_N"]
+__all__ = ["BatchedObjective", "fit_model_torch_batched", "member_operands", "BATCHED_MAX_N"]
 
 #: largest N the batched kernels take (gpp_api.hip: blocks up to BLK_MAX = 6144 rows are factored in leaf steps)
 BATCHED_MAX_N = 6144
+
+
+def member_operands(model, full: Dict[str, torch.Tensor], rows, note_static, priors: bool = True, extra_rows=None):
+    """One parameter set (``full``: every parameter and buffer of ``model`` by name) -> what the kernels need at the input rows
+    ``rows``, through the model's own forward / likelihood / priors under ``functional_call`` (callers ``vmap`` it over stacked
+    parameters): the tensors (U, w, sf2, tau, prior mean at the rows, log priors) and, handed to ``note_static``, what does not
+    depend on the parameters, (noise group of every row, kernel kind, d_split).  ``rows=None``: the training inputs, with the
+    likelihood as it stands (the objective's evaluation); any other rows get the noise groups of their own source column
+    (``_likelihood_of_rows``).  ``priors=False`` leaves the log priors at zero.  ``extra_rows``: the features of a second set of rows
+    are appended (the gradient points of "gek", which carry each run's latent map)."""
+    x = model.train_inputs[0] if rows is None else rows
+
+    def run(m):
+        out = torch.nn.Module.__call__(m, x)            # GP_Plus.forward: features, mean, lazy covariance
+        cov = out.lazy_covariance_matrix
+        if not isinstance(cov, LazyKernelMatrix):
+            raise RuntimeError("the batched fit needs the model's forward to return a lazy kernel covariance")
+        noisy = (m.likelihood(out) if rows is None else m._likelihood_of_rows(out, x)).lazy_covariance_matrix
+        prior = out.mean.new_zeros(())
+        if priors:
+            for _, module, pr, closure, _ in m.named_priors():
+                prior = prior + pr.log_prob(closure(module)).sum().to(prior)
+        static = (noisy.grp, cov.spec.kind, cov.spec.d_split)
+        tensors = (cov.U1, cov.spec.w, cov.spec.sf2.reshape(()), noisy.tau.reshape(-1), out.mean, prior)
+        if extra_rows is not None:
+            # the gradient points through the same forward (joint_log_prob does the same): they carry each run's latent map
+            tensors += (torch.nn.Module.__call__(m, extra_rows).lazy_covariance_matrix.U1,)
+        return tensors, static
+
+    class _Shim(torch.nn.Module):  # functional_call needs a module whose forward does the work
+        def __init__(s, inner):
+            super().__init__()
+            s.inner = inner
+
+        def forward(s):
+            tensors, static = run(s.inner)
+            note_static(static)
+            return tensors
+
+    shim = _Shim(model)
+    return functional_call(shim, {"inner." + k: v for k, v in full.items()}, ())
 
 
 class BatchedObjective:
@@ -85,40 +126,14 @@ class BatchedObjective:
     # -- evaluation -------------------------------------------------------------------------------------------
     def _pre(self, params: Dict[str, torch.Tensor]):
         """One parameter set -> everything the kernels need, through the model's own forward / likelihood / priors."""
-        model = self.model
         full = dict(self.fixed)
         full.update(params)
         full.update(self.buffers)
-        x = model.train_inputs[0]
 
-        def run(m):
-            out = torch.nn.Module.__call__(m, x)            # GP_Plus.forward: features, mean, lazy covariance
-            cov = out.lazy_covariance_matrix
-            if not isinstance(cov, LazyKernelMatrix):
-                raise RuntimeError("the batched fit needs the model's forward to return a lazy kernel covariance")
-            noisy = m.likelihood(out).lazy_covariance_matrix
-            prior = out.mean.new_zeros(())
-            for _, module, pr, closure, _ in m.named_priors():
-                prior = prior + pr.log_prob(closure(module)).sum().to(prior)
-            static = (noisy.grp, cov.spec.kind, cov.spec.d_split)
-            tensors = (cov.U1, cov.spec.w, cov.spec.sf2.reshape(()), noisy.tau.reshape(-1), out.mean, prior)
-            if self.gek is not None:
-                # the gradient points through the same forward (joint_log_prob does the same): they carry each run's latent map
-                tensors += (torch.nn.Module.__call__(m, self.gek.Xg).lazy_covariance_matrix.U1,)
-            return tensors, static
+        def note(static):
+            self._static = static
 
-        class _Shim(torch.nn.Module):  # functional_call needs a module whose forward does the work
-            def __init__(s, inner):
-                super().__init__()
-                s.inner = inner
-
-            def forward(s):
-                tensors, static = run(s.inner)
-                self._static = static
-                return tensors
-
-        shim = _Shim(model)
-        return functional_call(shim, {"inner." + k: v for k, v in full.items()}, ())
+        return member_operands(self.model, full, None, note, extra_rows=None if self.gek is None else self.gek.Xg)
 
     def loss(self) -> torch.Tensor:
         N = self.model.train_targets.shape[0]
@@ -207,18 +222,34 @@ class _GraphedLossAndGrad:
 
 def fit_model_torch_batched(model, lr_default: float = 0.01, num_iter: int = 100, num_restarts: int = 0,
                             break_steps: int = 50, verbose: bool = False, objective: str = "mll",
-                            folds=None, gradients=None) -> Tuple[float, List[List[float]]]:
+                            folds=None, gradients=None, keep: int = 0) -> Tuple[float, List[List[float]]]:
     """Drop-in for ``fit_model_torch`` (same return value) that advances all restarts together.  ``objective="loo"`` maximises the
     leave-one-out log pseudo-likelihood (plus the priors) in the same way: batched, and replayed as a HIP graph.  ``"gek"`` with
     ``gradients=`` is batched as well while N + q (q gradient observations) is at most ``BATCHED_MAX_N``, every step evaluated eagerly
     (its evaluation is not captured: ``last_graph`` stays None); above that it goes to the sequential driver, where ``"cv"``, which
-    has no batched form, always goes."""
+    has no batched form, always goes.
+
+    ``keep=K > 0`` leaves in ``fit_model_torch_batched.last_restarts`` the ``keep`` runs with the smallest finite last loss, the
+    winner first and the others in ascending order (fewer when fewer runs end finite): ``.states`` (name -> (K, *shape) stacked
+    parameters), ``.losses`` (K,) and ``.num_data`` (the observations the loss is normalised by) — what
+    ``ensemble.HyperparameterEnsemble`` takes.  It is None for ``keep == 0``.  Nothing else changes: iterates, return value and the
+    winner loaded into the model are the same.  ``keep > 0`` where the fit would go to the sequential driver raises
+    ``NotImplementedError`` before any fitting starts."""
     N = int(model.train_targets.shape[0])
     folds = check_objective_folds(objective, folds, N)
     gradients = check_objective_gradients(objective, gradients)
+    keep = int(keep)
+    if keep < 0:
+        raise ValueError(f"keep must be 0 or a positive count (got {keep})")
+    fit_model_torch_batched.last_restarts = None
+
+    def sequential(why):
+        if keep > 0:
+            raise NotImplementedError(f"keep is available on the batched restarts only: {why}")
     if getattr(model, "calibration_id", None):
         raise NotImplementedError("the batched restarts have no gradient by calibration parameters: use fit_model_torch")
     if objective == "cv":  # the cross-validation objective has no batched form: the sequential, eager driver
+        sequential('objective="cv" has no batched form')
         from .mll_torch import fit_model_torch
         return fit_model_torch(model, None, lr_default, num_iter, num_restarts, break_steps, verbose=verbose, objective=objective,
                                folds=folds)
@@ -227,12 +258,14 @@ def fit_model_torch_batched(model, lr_default: float = 0.01, num_iter: int = 100
     if objective == "gek":
         obj = BatchedObjective(model, B, objective, gradients=gradients)  # (validates the gradient data: host work)
         if obj.num_data > BATCHED_MAX_N:  # the joint matrix has N + q rows: the limit of gpp_potrf_batched applies to them
+            sequential(f"{obj.num_data} rows are beyond the batched kernels' range ({BATCHED_MAX_N})")
             from .mll_torch import fit_model_torch
             return fit_model_torch(model, None, lr_default, num_iter, num_restarts, break_steps, verbose=verbose, objective=objective,
                                    gradients=gradients)
     if N > BATCHED_MAX_N:
         # gpp_potrf_batched factors each problem right-looking in leaf steps and rejects larger matrices; at these sizes
         # one evaluation fills the GPU by itself, so the sequential driver loses nothing
+        sequential(f"{N} rows are beyond the batched kernels' range ({BATCHED_MAX_N})")
         from .mll_torch import fit_model_torch
         return fit_model_torch(model, None, lr_default, num_iter, num_restarts, break_steps, verbose=verbose, objective=objective)
     if obj is None:
@@ -304,4 +337,14 @@ def fit_model_torch_batched(model, lr_default: float = 0.01, num_iter: int = 100
         state = deepcopy(model.state_dict())
         state.update(obj.row(best))
         model.load_state_dict(state)
+    if keep > 0:
+        from types import SimpleNamespace
+        lc = last.cpu()
+        # the winner first (whatever index a tie gives argmin), then the other finite runs by ascending last loss, ties by index
+        order = [best] + sorted((b_ for b_ in range(B) if b_ != best), key=lambda b_: (float(lc[b_]), b_))
+        order = [b_ for b_ in order if math.isfinite(float(lc[b_]))][:keep]
+        idx = torch.tensor(order, dtype=torch.long, device=dev)
+        fit_model_torch_batched.last_restarts = SimpleNamespace(
+            states=OrderedDict((n, obj.theta[n].detach().index_select(0, idx).clone()) for n in obj.names),
+            losses=lc[order].clone(), num_data=obj.num_data)
     return f_inc, hist
